@@ -1,8 +1,16 @@
 #!/usr/bin/env python
 """Throughput of the hot path: full G+D training steps of the semi-supervised CycleGAN on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR] [--full]
     (N > 1 without a launcher: bench.py starts its own N ranks through torch.distributed.run)
+
+A plain run sets up, runs W warm-up steps, times K steps once and prints the contract line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = wall time of one timed step, plus the configuration and the timed region's allocator
+growth).  `--full` adds every secondary figure listed below (and the re-timed pass when the first one grew device memory).
+`--dump-outputs DIR` writes what the last timed step computed, before anything else runs: the nine losses the step returns
+(`DIR/<loss>.npy`, float64) and the trained networks' parameters after its updates (`DIR/params_<net>.npy`, float32; a fixed,
+seeded sample of at most DUMP_PARAM_ELEMENTS per network).  Weights, inputs and host RNG draws are seeded: the same arguments give
+the same inputs in every run.
 
 --config 2 (default) = BASELINE.json configs[1], the configuration the metric is quoted on: VOC2012 21-class, 256x256,
     semisupervised_cycleGAN, batch 8 per GPU, fp32 tensors.  `--dtype f32` (the default of this configuration) contracts the
@@ -14,10 +22,10 @@
 --config 4 / 5 = the per-rank workloads of configs[3] (config 2 on each of 8 ranks) and configs[4] (Cityscapes 512x1024, global
     batch 32 = batch 4 per rank, bf16): meant for `--gpus 8`.
 Random-init weights (the reference's N(0,0.02) init), synthetic image/label batches already resident in HBM.
-One step = one iteration of /root/reference model.py:370-552 as written (all seven networks, both optimisers).
+One step = one iteration of the reference's model.py:370-552 as written (all seven networks, both optimisers).
 Weak scaling: every rank runs the per-GPU batch; `value` = N * batch * K / (max-over-ranks wall time of K steps).
 
-Besides the contract line this prints, in the same JSON object:
+With `--full`, besides the contract line this prints, in the same JSON object:
   roofline     - the implicit-GEMM conv kernels measured live with HIP events on the launch stream during one
                  extra (untimed) step: algorithmic FLOP / kernel time against the MFMA peak of the arithmetic
                  (exact fp32: 157.3 TFLOP/s; bf16: 2500 TFLOP/s dense; split fp32: six bf16 piece products per fp32 product,
@@ -27,7 +35,7 @@ Besides the contract line this prints, in the same JSON object:
   secondary figures, never the headline: elided_dead_work (the step without the reference's unused forwards), bf16 and f32_exact
                  (the fp32 configuration in the bf16 arithmetic / with exact fp32 MFMA contractions), host_bound_case (64x64,
                  batch 2: the host's issue cost of a step; measured by `bench.py --host-bound-only` in a process of its own),
-                 host_issue_ms_per_step.
+                 host_issue_unblocked_ms (host_issue_ms_per_step, from the timed steps themselves, is in every line).
 """
 import argparse
 import contextlib
@@ -37,6 +45,7 @@ import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -80,6 +89,8 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the configuration's)")
     ap.add_argument("--dtype", choices=["f32", "f32x", "f32s", "bf16", "bf16c"], default=None, help="default: the configuration's")
     ap.add_argument("--no-bf16", action="store_true", help="config 2: skip the secondary bf16 / exact-fp32 figures")
+    ap.add_argument("--full", action="store_true", help="also measure the secondary figures (the --no-* options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's losses and trained weights as DIR/<name>.npy")
     a = ap.parse_args()
     cfg = CONFIGS[a.config]
     dtype = a.dtype or cfg["dtype"]
@@ -88,6 +99,7 @@ def main():
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(a.gpus))          # `python bench.py --gpus N` launches its own N ranks
+    import numpy as np
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus != world:
@@ -142,7 +154,7 @@ def main():
                           "host_issue_ms_per_step": round(1e3 * th, 2), "value": round(2 / ts, 2), "unit": "img/s"}))
         return
     host_bound_case = None
-    if world == 1 and not a.no_small:
+    if a.full and world == 1 and not a.no_small:
         import subprocess
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--host-bound-only", "--config", str(a.config), "--dtype", dtype],
@@ -151,13 +163,15 @@ def main():
         except Exception as e:      # a secondary figure must not take the headline with it
             host_bound_case = {"error": "%s: %s" % (type(e).__name__, e)}
 
+    np.random.seed(0)           # the image pools' draws (utils.Sample_from_Pool): the same trajectory in every run
     with contextlib.redirect_stdout(io.StringIO()):
         model = md.semisuper_cycleGAN(args, data_parallel=dp)
 
-    # synthetic batches, resident in HBM before the clock starts (rank-offset seeds)
+    # synthetic batches, resident in HBM before the clock starts (rank-offset seeds); the two seeded streams are drawn on two host
+    # threads (torch's CPU generator fills a batch serially, and releases the GIL while it does)
     nb = a.warmup + a.steps + 1
-    lab = list(data.SyntheticLoader(bsz, C, H, W, nb, 1 + 1000 * rank, device=dev))
-    unl = list(data.SyntheticLoader(bsz, C, H, W, nb, 2 + 1000 * rank, device=dev))
+    with ThreadPoolExecutor(2) as pool:
+        lab, unl = pool.map(lambda seed: list(data.SyntheticLoader(bsz, C, H, W, nb, seed + 1000 * rank, device=dev)), (1, 2))
 
     def run(i):
         return model.step(lab[i][0], lab[i][1], unl[i][0])
@@ -190,8 +204,9 @@ def main():
         run(i)
     # device memory must not grow inside the timed region (hipMalloc serialises the device; at N > 1 it also stalls the ranks that
     # wait in the all-reduce): torch's caching allocator holds every buffer of the step (the library's workspaces are torch
-    # tensors too), so `reserved` before and after the K steps says whether the region allocated.  A region that grew is timed again
-    # (once: the allocator's pools are warm then); the line carries what happened in either pass.
+    # tensors too), so `reserved` before and after the K steps says whether the region allocated.  With --full a region that grew is
+    # timed again (once: the allocator's pools are warm then); the line carries what happened in either pass.  A plain run times the
+    # K steps once and reports the growth.
     torch.cuda.synchronize()
     reserved0 = torch.cuda.memory_reserved(dev)
     dt, losses = timed(a.warmup, a.steps)
@@ -199,7 +214,7 @@ def main():
     retimed, grew2, first_ms = False, 0, None
     if dp is not None and world > 1:
         grew = int(par.max_over_ranks(float(grew)))       # every rank takes the same branch
-    if grew > 0:
+    if grew > 0 and a.full:
         first_ms = 1e3 * dt / a.steps
         reserved0 = torch.cuda.memory_reserved(dev)
         dt, losses = timed(a.warmup, a.steps)
@@ -210,6 +225,9 @@ def main():
         if grew2 > 0 and rank == 0:
             print("bench.py: device memory still grew inside the timed region (+%d bytes reserved in the second pass of %d steps); the "
                   "figure stands, `timed_region_alloc` says so" % (grew2, a.steps), file=sys.stderr)
+    if a.dump_outputs and rank == 0:
+        model.sync_losses()
+        dump_outputs(a.dump_outputs, losses, model)
     if os.environ.get("SSCG_PHASE_EVENTS") == "1" and rank == 0:
         # diagnostic: one more step with timed events around its passes (model.py _mark) - when each pass ran on the GPU and when
         # the host issued it, without a tracer's overhead
@@ -254,7 +272,7 @@ def main():
     # The host thread's issue cost of one step with NO back-pressure from the device: the same step with every kernel launch of the
     # library turned into a no-op (sscg_set_dry_run; torch's own copies / events still run).  `host_issue_ms_per_step` above includes
     # the time the thread spends blocked on a full launch queue; the difference is the back-pressure.
-    if not a.no_unblocked:
+    if a.full and not a.no_unblocked:
         lib = importlib.import_module(PKG + "._lib").lib
         torch.cuda.synchronize()
         pools = [(list(p.items), p.cur_elements) for p in model.pools]       # a dry step stores never-written tensors in the image pools
@@ -285,7 +303,7 @@ def main():
 
     # secondary figure (BASELINE.md section 2 / SURVEY 8(d)): the same step without the forwards whose outputs the
     # reference never uses (old_Gsi(l_img) -> old_Gis, model.py:419-420,423) and without old_Di's never-applied wgrad
-    if not a.no_elided:
+    if a.full and not a.no_elided:
         model.as_written = False
         run(a.warmup + a.steps)
         dte, _ = timed(a.warmup, a.steps)
@@ -294,7 +312,7 @@ def main():
                                    "note": "not the headline: skips the forwards with unused outputs + old_Di's unused wgrad"}
 
     # secondary figure at config 2: the same as-written step in bf16 (the arithmetic of configs 3/5); never the fp32 headline
-    if dtype == "f32" and not a.no_bf16:
+    if a.full and dtype == "f32" and not a.no_bf16:
         F.set_conv_precision("bf16")
         run(a.warmup + a.steps)
         dtb, lb = timed(a.warmup, a.steps)
@@ -305,7 +323,7 @@ def main():
 
     # beside the headline: the same fp32 step with the OTHER contraction of fp32 tensors (exact fp32 MFMA when the headline runs the
     # split contraction, and the other way round)
-    if dtype == "f32" and not a.no_bf16:
+    if a.full and dtype == "f32" and not a.no_bf16:
         other = "f32x" if arith == "f32s" else "f32s"
         F.set_conv_precision(other)
         run(a.warmup + a.steps)
@@ -315,7 +333,7 @@ def main():
             "value": round(world * bsz * a.steps / dts, 4), "unit": "img/s", "ms_per_step": round(1e3 * dts / a.steps, 3),
             "losses_finite": all(bool(torch.isfinite(v)) for v in ls.values()), "note": "not the headline: " + DTYPE_TEXT[other]}
 
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # per-kernel timing needs the kernels one at a time: the side stream (concurrent weight gradients /
         # frozen generators) is switched off for this extra, untimed step only.  EVERY rank runs the step (it contains
         # the gradient all-reduces); rank 0 reports.
@@ -327,7 +345,7 @@ def main():
             run(a.warmup + a.steps)
         summ = prof.summary()
         F.SideStream.enabled = True
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         fam = "bf16" if dtype == "bf16" else ("split" if arith == "f32s" else "f32")       # kernel family that dominates this configuration
         kname = {"bf16": "conv16_kernel (implicit-GEMM conv forward + data-gradient on bf16 LDS tiles, v_mfma_f32_32x32x16_bf16)",
                  "split": "convs_kernel (implicit-GEMM conv forward + data-gradient, fp32 tensors, 3-piece split-bf16 contraction: six "
@@ -381,10 +399,32 @@ def main():
                 for ms, kind, key, n, tfl in rows:
                     f.write("%8.3f ms  %-10s %-40s x%-3d %6.1f TF/s\n" % (ms, kind, key, n, tfl))
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg)
 
     emit_line(out, rank, bool(dp))
+
+
+DUMP_PARAM_ELEMENTS = 2 ** 21     # per network: 8 MB of float32, 32 MB for the four trained networks
+DUMP_NETS = ("Gis", "Gsi", "Di", "Ds")
+
+
+def dump_outputs(path, losses, model):
+    """--dump-outputs: the losses the last timed step returned (float64 scalars, `<loss>.npy`) and the parameters of the four trained
+    networks after its updates, flattened in named_parameters() order (`params_<net>.npy`, float32).  A network with more elements
+    than DUMP_PARAM_ELEMENTS is sampled at fixed, seeded positions (sorted), the same in every run of the same configuration."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(path, "%s.npy" % k), np.asarray(float(v), dtype=np.float64))
+    with torch.no_grad():
+        for name in DUMP_NETS:
+            flat = torch.cat([p.detach().reshape(-1).float() for _, p in getattr(model, name).named_parameters()])
+            if flat.numel() > DUMP_PARAM_ELEMENTS:
+                idx = np.sort(np.random.default_rng(0).choice(flat.numel(), size=DUMP_PARAM_ELEMENTS, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            np.save(os.path.join(path, "params_%s.npy" % name), flat.cpu().numpy().astype(np.float32))
 
 
 def emit_line(out, rank, in_group):

@@ -134,34 +134,30 @@ def test_synthetic_loader_contract():
     assert torch.equal(again[0], img) and torch.equal(again[1], gt)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/arch"), reason="needs the reference checkout (build container only)")
+def _reference_checkpoint_layout():
+    """The reference modules' state_dict layout (key order, shapes, dtypes) for the five networks below: oracle/nets.py's specs,
+    which gen_golden.py loaded into the reference's own modules with strict=True for every golden under tests/golden/."""
+    from oracle import nets as onets
+    specs = {"Gis": onets.deeplab_spec(21, 3), "Gsi": onets.deeplab_spec(3, 21), "Di": onets.pixel_dis_spec(3),
+             "Ds": onets.nlayer_dis_spec(21, n_layers=3), "old": onets.resnet_gen_spec_full(21, 3, use_dropout=True)}
+    return {net: [(k, tuple(shape), torch.int64 if kind == "nbt" else torch.float32) for k, (shape, kind) in spec.items()]
+            for net, spec in specs.items()}
+
+
 def test_checkpoints_interchange_with_the_reference_modules(tmp_path):
-    """a checkpoint written by the REFERENCE (its own modules' state_dict through its utils.save_checkpoint
-    format, model.py:646-655) loads into this build's networks with strict=True, and a checkpoint written by this build loads
-    into the reference's modules - for the DeepLab generators and the pixel / PatchGAN discriminators.  Runs where
-    /root/reference exists (the build container); no tensor arithmetic, so no GPU is needed."""
-    import subprocess
-    import sys
-    code = r'''
-import sys, torch, warnings
-warnings.filterwarnings("ignore")
-sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference")
-import arch
-torch.manual_seed(7)
-nets = {"Gis": arch.define_Gen(21, 3, 64, "deeplab", "instance", True, []), "Gsi": arch.define_Gen(3, 21, 64, "deeplab", "instance", True, []),
-        "Di": arch.define_Dis(3, 64, "pixel", 3, "instance", []), "Ds": arch.define_Dis(21, 64, "n_layers", 3, "instance", []),
-        "old": arch.define_Gen(21, 3, 64, "resnet_9blocks", "instance", True, [])}
-if sys.argv[1] == "save":
-    torch.save({"epoch": 3, "best_iou": 0.5, **{k: v.state_dict() for k, v in nets.items()}}, sys.argv[2])
-else:
-    ck = torch.load(sys.argv[2], map_location="cpu")
-    for k, v in nets.items():
-        v.load_state_dict(ck[k], strict=True)
-    print("reference loaded", sorted(ck))
-'''
+    """a checkpoint in the REFERENCE's format (its modules' state_dicts in one torch.save'd dict, utils.save_checkpoint,
+    model.py:646-655) loads into this build's networks with strict=True, value for value, and a checkpoint written by this build
+    carries exactly the reference modules' keys, shapes and dtypes (what their load_state_dict(strict=True) needs) - for the DeepLab
+    generators, the pixel / PatchGAN discriminators and the frozen ResNet generator.  The reference's layout is that of the oracle's
+    specs (oracle/nets.py), the reference-format checkpoint holds keyed weights (oracle/weights.py); no tensor arithmetic, no GPU."""
+    from oracle import weights as W
+    layout = _reference_checkpoint_layout()
+    ref_sd = {}
+    for net, entries in layout.items():
+        spec = {k: (shape, "nbt" if dt == torch.int64 else "conv") for k, shape, dt in entries}
+        ref_sd[net] = W.fill_state_dict(spec, 7, prefix=net + "/")
     ref_ck, our_ck = str(tmp_path / "ref.ckpt"), str(tmp_path / "ours.ckpt")
-    subprocess.run([sys.executable, "-c", code, "save", ref_ck], check=True, capture_output=True)
+    torch.save({"epoch": 3, "best_iou": 0.5, **ref_sd}, ref_ck)
     arch = load_sub("arch")
     utils = load_sub("utils")
     import contextlib
@@ -177,8 +173,14 @@ else:
         for name, t in net.state_dict().items():
             assert torch.equal(t.cpu().contiguous(), ck[k][name].contiguous()), (k, name)
     utils.save_checkpoint({"epoch": 4, "best_iou": 0.6, **{k: v.state_dict() for k, v in ours.items()}}, our_ck)
-    out = subprocess.run([sys.executable, "-c", code, "load", our_ck], check=True, capture_output=True, text=True).stdout
-    assert "reference loaded" in out
+    back = torch.load(our_ck, map_location="cpu")                    # the reference's utils.load_checkpoint
+    assert back["epoch"] == 4 and back["best_iou"] == 0.6
+    for net, entries in layout.items():
+        got = back[net]
+        assert sorted(got) == sorted(k for k, _, _ in entries), net   # no key missing or extra for the reference's strict load
+        for k, shape, dt in entries:
+            assert tuple(got[k].shape) == shape and got[k].dtype == dt, (net, k, tuple(got[k].shape), got[k].dtype)
+            assert torch.equal(got[k], ref_sd[net][k]), (net, k)      # what was loaded is what is written back
 
 
 def test_bench_cpu_baseline_leg_runs_and_reports(monkeypatch):
