@@ -237,35 +237,32 @@ def lane_events(device):
 
 
 # Data parallelism with bucketed gradient exchange (parallel.GradBuckets): GRAD_READY[0] is called with a parameter once the LAST
-# gradient kernel of this backward pass that accumulates into its arena slice has been queued.  "Last" is known by counting: every
-# forward of a conv whose weight will receive a gradient notes one use (_note_use), every backward of one takes it back (_note_done).
+# gradient kernel of this backward pass that accumulates into its arena slice has been queued.  "Last" is known by counting: the
+# forward of a conv node whose weight will receive a gradient counts one use of its weight and bias and keeps them on ctx
+# (ctx.counted = _note_use(w, bias)); the node's backward takes back exactly those (_note_done(ctx.counted)) once their gradient
+# kernels are queued.  "Will receive a gradient" = ctx.needs_input_grad AND the grad mode of the node's caller, which the wrappers
+# below pass into apply() (inside forward() it is always off): needs_input_grad is True for a trainable weight under torch.no_grad()
+# as well, but such a forward never sees a backward - it must neither count a use nor keep pre-norm activations alive for one (the
+# unused Gis(lab_gt) pass of a step, evaluation, validation).
 GRAD_READY = [None]
-# grad mode of the CALLER of the autograd.Function being applied (inside forward() it is always off): ctx.needs_input_grad is True
-# for a trainable weight under torch.no_grad() as well, but such a forward never sees a backward - it must neither count a use nor keep
-# pre-norm activations alive for one (the unused Gis(lab_gt) pass of a step, evaluation, validation)
-_CALLER_GRAD = [True]
-
-
-def _will_backward(ctx, i=None):
-    need = any(ctx.needs_input_grad) if i is None else ctx.needs_input_grad[i]
-    return bool(need) and _CALLER_GRAD[0]
 
 
 def _note_use(*params):
-    if GRAD_READY[0] is not None:
-        for p in params:
-            if p is not None and getattr(p, "_sscg_grad", None) is not None:
-                p._sscg_uses = getattr(p, "_sscg_uses", 0) + 1
+    """Counts one use of each parameter that takes part in the exchange; returns the parameters counted."""
+    if GRAD_READY[0] is None:
+        return ()
+    counted = tuple(p for p in params if p is not None and getattr(p, "_sscg_grad", None) is not None)
+    for p in counted:
+        p._sscg_uses = getattr(p, "_sscg_uses", 0) + 1
+    return counted
 
 
-def _note_done(*params):
+def _note_done(counted):
     hook = GRAD_READY[0]
-    if hook is not None:
-        for p in params:
-            if p is not None and getattr(p, "_sscg_grad", None) is not None:
-                p._sscg_uses = getattr(p, "_sscg_uses", 0) - 1
-                if p._sscg_uses == 0:
-                    hook(p)
+    for p in counted:
+        p._sscg_uses -= 1
+        if p._sscg_uses == 0 and hook is not None:
+            hook(p)
 
 
 def d_stream(device):
@@ -1538,35 +1535,61 @@ def _acc_target(param):
     return acc
 
 
+def _running_stats(running_mean, running_var, per_sample):
+    """The running statistics that a batch-statistics pass advances: none for a layer without them or with per-sample (InstanceNorm)
+    statistics."""
+    if running_mean is not None and per_sample is not True:
+        return running_mean, running_var
+    return None, None
+
+
+def _conv_stats_fwd(x, w, bias, geom, out_f32, norm, fallback=True):
+    """(y, mean, rstd, (g, l, c)): y = conv(x, w) + bias and the batch statistics of the normalisation layer `norm` = (per_sample, eps,
+    running_mean, running_var, momentum) that follows it - from the conv's epilogue where one takes them for the geometry, else
+    (`fallback`) from a statistics pass over y; without the fallback mean / rstd are then None."""
+    stride, pad, dil, pad_mode = geom
+    per_sample, eps, rmean, rvar, momentum = norm
+    n, _, h, wd = x.shape
+    p, q = conv_out_size(h, w.shape[2], stride, pad, dil), conv_out_size(wd, w.shape[3], stride, pad, dil)
+    glc = _glc_shape((n, w.shape[0], p, q), per_sample)
+    y, mean, rstd = conv2d_fwd_norm(x, w, bias, stride, pad, dil, pad_mode, out_f32, glc, eps, rmean, rvar, momentum)
+    if mean is None and fallback:
+        mean, rstd = norm_stats(y, per_sample, eps, *_running_stats(rmean, rvar, per_sample), momentum)
+    return y, mean, rstd, glc
+
+
+def _add_into(acc, src_ptr, count):
+    check(lib.sscg_add(acc.data_ptr(), src_ptr, acc.data_ptr(), F32, count, _stream()), "sscg_add")
+
+
+def _arena_add(device, acc, src_ptr, count, ref, keep):
+    """acc += `count` fp32 sums at src_ptr (inside the tensor `keep`), queued on the side lane of the parameter `ref` that owns the
+    arena slice `acc`: every gradient of a parameter is accumulated on that parameter's lane."""
+    run_on_side_stream(device, (keep,), lambda: _add_into(acc, src_ptr, count), lane=getattr(ref, "_sscg_lane", 0), defer=True)
+
+
 class Conv2dFn(torch.autograd.Function):
     """nn.Conv2d (+ folded nn.ReflectionPad2d, + fused activation when no norm layer follows).
 
     `norm` = None, or the description of the normalisation layer that follows - (per_sample, eps, running_mean,
     running_var, momentum): the conv's epilogue then also produces that layer's batch statistics (arch/ops.py:40-57 "Conv +
     InstanceNorm / BatchNorm" blocks) and the function returns (y, mean, rstd); mean is None when the fusion does not apply
-    to the geometry (the caller falls back to a statistics pass over y)."""
+    to the geometry (the caller falls back to a statistics pass over y).
+    `grad` = the grad mode of the caller (inside forward() it is always off)."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, stride, pad, dil, pad_mode, act, slope, out_f32, norm):
+    def forward(ctx, x, w, bias, stride, pad, dil, pad_mode, act, slope, out_f32, norm, grad):
         x = to_nhwc(x)
         mean = rstd = None
-        if norm is not None:
-            per_sample, eps, rmean, rvar, momentum = norm
-            n, _, h, wd = x.shape
-            p, q = conv_out_size(h, w.shape[2], stride, pad, dil), conv_out_size(wd, w.shape[3], stride, pad, dil)
-            g, l, c = _glc_shape((n, w.shape[0], p, q), per_sample)
-            if act == ACT_NONE:
-                y, mean, rstd = conv2d_fwd_norm(x, w, bias, stride, pad, dil, pad_mode, out_f32, (g, l, c), eps, rmean, rvar, momentum)
-            else:       # (no conv epilogue takes statistics behind an activation)
-                y = conv2d_fwd(x, w, bias, stride, pad, dil, pad_mode, act, slope, out_f32)
-        else:
+        if norm is not None and act == ACT_NONE:
+            y, mean, rstd, _ = _conv_stats_fwd(x, w, bias, (stride, pad, dil, pad_mode), out_f32, norm, fallback=False)
+        else:       # (no conv epilogue takes statistics behind an activation)
             y = conv2d_fwd(x, w, bias, stride, pad, dil, pad_mode, act, slope, out_f32)
         ctx.cfg = (stride, pad, dil, pad_mode, act, slope)
         ctx.has_bias = bias is not None
         ctx.wref = w
         ctx.bref = bias
-        if _will_backward(ctx, 1):
-            _note_use(w, bias)
+        ctx.counted = _note_use(w, bias) if grad and ctx.needs_input_grad[1] else ()
         ctx.save_for_backward(x, w, y if act != ACT_NONE else None)
         # (mean, rstd) are non-differentiable outputs: left alone, autograd hands backward() two zero-filled tensors for them -
         # 850 fill launches per Cityscapes step
@@ -1581,22 +1604,23 @@ class Conv2dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, *_unused):
         if dy is None:          # nothing downstream used y
-            return (None,) * 11
+            return (None,) * 12
         x, w, y = ctx.saved_tensors
         stride, pad, dil, pad_mode, act, slope = ctx.cfg
         dy = to_nhwc(dy)
         if act != ACT_NONE:
             dy = act_bwd(dy, y, act, slope)
         dx, dw, db = _conv_backward(dy, x, w, ctx.wref, ctx.bref if ctx.has_bias else None, (stride, pad, dil, pad_mode),
-                                    ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
-        return dx, dw, db, None, None, None, None, None, None, None, None
+                                    ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], ctx.counted)
+        return dx, dw, db, None, None, None, None, None, None, None, None, None
 
 
-def _conv_backward(dy, x, w, wref, bref, geom, want_x, want_w, want_b):
+def _conv_backward(dy, x, w, wref, bref, geom, want_x, want_w, want_b, counted):
     """Backward of y = conv(x, w) + bias for the gradient dy of the PRE-activation output: (dx, dw, db).  Weight / bias gradients of
-    parameters owned by optim.FusedAdam go straight into its gradient arena on the parameter's side lane (dw, db then None)."""
+    parameters owned by optim.FusedAdam go straight into its gradient arena on the parameter's side lane (dw, db then None).
+    `counted`: the parameters whose use the forward counted (_note_use); their gradient kernels are queued when this returns."""
     stride, pad, dil, pad_mode = geom
-    dx = dw = db = None
+    dx = None
     if want_x:
         if pad_mode == PAD_REFLECT:
             raise _lib.SscgError("input gradient through a reflection-padded conv: use ReflectPadFn + pad=0 conv")
@@ -1632,33 +1656,43 @@ def _conv_backward(dy, x, w, wref, bref, geom, want_x, want_w, want_b):
             dx = conv2d_dgrad_param(dy, wref, x.shape, w.shape, stride, pad, dil, out_dtype=x.dtype)
             if join is not None:
                 join[0].deposit(join[1], dx)
+    dw, db = _param_grads(x, dy, dy, w.shape, geom, wref, bref, want_w, want_b)
+    _note_done(counted)
+    return dx, dw, db
+
+
+def _param_grads(a, b, dy, wshape, geom, wref, bref, want_w, want_b):
+    """Parameter gradients of a convolution: (dw, db) with dw = wgrad(a, b) (input and output gradient of the conv that is
+    differentiated) and db = the column sums of dy.  Gradients of parameters owned by optim.FusedAdam are accumulated straight into
+    its gradient arena instead (returned as None), always on the parameter's own side lane (fixed accumulation order)."""
+    stride, pad, dil, pad_mode = geom
+    dw = db = None
     wacc = _acc_target(wref) if want_w else None
     bacc = _acc_target(bref) if want_b else None
     n, k, p, q = dy.shape
 
-    def arena_grads():      # accumulate straight into the optimiser's gradient arena
+    def arena_grads():
         if wacc is not None:
-            conv2d_wgrad(x, dy, w.shape, stride, pad, dil, pad_mode, out=wacc, accumulate=True)
+            conv2d_wgrad(a, b, wshape, stride, pad, dil, pad_mode, out=wacc, accumulate=True)
         if bacc is not None:
             colsum(n * p * q, k, dy, out=bacc, accumulate=True)
 
     if wacc is not None or bacc is not None:
         # nothing on the backward critical path reads these: run them beside the data-gradient chain
-        run_on_side_stream(dy.device, (x, dy), arena_grads, lane=getattr(wref, "_sscg_lane", 0), defer=True)
+        run_on_side_stream(dy.device, (a, b), arena_grads, lane=getattr(wref, "_sscg_lane", 0), defer=True)
     if want_w and wacc is None:
-        dw = conv2d_wgrad(x, dy, w.shape, stride, pad, dil, pad_mode)
+        dw = conv2d_wgrad(a, b, wshape, stride, pad, dil, pad_mode)
     if want_b and bacc is None:
         db = colsum(n * p * q, k, dy)
-    if want_w:
-        _note_done(wref, bref)
-    return dx, dw, db
+    return dw, db
 
 
 class ConvTranspose2dFn(torch.autograd.Function):
     """nn.ConvTranspose2d (arch/ops.py:55-56) as the data-gradient of the mirrored convolution.
 
     `w` is the torch ConvTranspose2d weight, logical [Cin, Cout, R, S], channels-last memory
-    [Cin][R][S][Cout] - i.e. the [K][R][S][C] weight of a conv Cout->Cin."""
+    [Cin][R][S][Cout] - i.e. the [K][R][S][C] weight of a conv Cout->Cin.  Its parameters are not counted for the bucketed
+    exchange (GRAD_READY): their bucket goes out after the backward."""
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, pad, out_pad, act, slope, out_f32=False):
@@ -1686,29 +1720,13 @@ class ConvTranspose2dFn(torch.autograd.Function):
         dy = to_nhwc(dy)
         if act != ACT_NONE:
             dy = act_bwd(dy, y, act, slope)
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
             # gradient wrt x = forward of the mirrored conv applied to dy
             dx = conv2d_fwd(dy, w, None, stride, pad, 1, out_f32=(x.dtype == torch.float32))
-        want_w = ctx.needs_input_grad[1]
-        want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        wacc = _acc_target(ctx.wref) if want_w else None
-        bacc = _acc_target(ctx.bref) if want_b else None
-        n, k, p, q = dy.shape
-
-        def arena_grads():      # as Conv2dFn: a parameter's gradient kernels always run on ITS side lane (fixed accumulation order)
-            if wacc is not None:
-                # mirrored conv has input dy (as "x") and output-gradient x (as "dy")
-                conv2d_wgrad(dy, x, w.shape, stride, pad, 1, out=wacc, accumulate=True)
-            if bacc is not None:
-                colsum(n * p * q, k, dy, out=bacc, accumulate=True)
-
-        if wacc is not None or bacc is not None:
-            run_on_side_stream(dy.device, (x, dy), arena_grads, lane=getattr(ctx.wref, "_sscg_lane", 0), defer=True)
-        if want_w and wacc is None:
-            dw = conv2d_wgrad(dy, x, w.shape, stride, pad, 1)
-        if want_b and bacc is None:
-            db = colsum(n * p * q, k, dy)
+        # mirrored conv has input dy (as "x") and output-gradient x (as "dy")
+        dw, db = _param_grads(dy, x, dy, w.shape, (stride, pad, 1, PAD_ZEROS), ctx.wref, ctx.bref,
+                              ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
         return dx, dw, db, None, None, None, None, None, None
 
 
@@ -1725,8 +1743,8 @@ class NormActFn(torch.autograd.Function):
         if use_batch_stats and pre_mean is not None:
             mean, rstd = pre_mean, pre_rstd      # produced by the conv's epilogue (running statistics already advanced there)
         elif use_batch_stats:
-            upd = training and running_mean is not None and per_sample is not True
-            mean, rstd = norm_stats(x, per_sample, eps, running_mean if upd else None, running_var if upd else None, momentum)
+            rmean, rvar = _running_stats(running_mean, running_var, per_sample) if training else (None, None)
+            mean, rstd = norm_stats(x, per_sample, eps, rmean, rvar, momentum)
         else:
             per_sample = False          # running statistics: one (mean, rstd) row whatever the grouping
             mean = running_mean.view(1, -1)
@@ -1784,15 +1802,13 @@ def _norm_backward(dy, x, y, mean, rstd, gamma, beta, gref, betaref, per_sample,
         # this layer: a read-modify-write of the arena slice from two streams would lose updates).  weight and bias of a
         # norm layer are neighbours in the arena: one launch adds both.
         n_c = gacc.numel()
-        adjacent = bacc.data_ptr() == gacc.data_ptr() + 4 * n_c
-
-        def arena_grads():
-            if adjacent:
-                check(lib.sscg_add(gacc.data_ptr(), dgb.data_ptr(), gacc.data_ptr(), F32, 2 * n_c, _stream()), "sscg_add")
-            else:
-                check(lib.sscg_add(gacc.data_ptr(), dgamma.data_ptr(), gacc.data_ptr(), F32, n_c, _stream()), "sscg_add")
-                check(lib.sscg_add(bacc.data_ptr(), dbeta.data_ptr(), bacc.data_ptr(), F32, n_c, _stream()), "sscg_add")
-        run_on_side_stream(dy.device, (dgb,), arena_grads, lane=getattr(gref, "_sscg_lane", 0), defer=True)
+        if bacc.data_ptr() == gacc.data_ptr() + 4 * n_c:
+            _arena_add(dy.device, gacc, dgb.data_ptr(), 2 * n_c, gref, dgb)
+        else:       # (one deferred call on gamma's lane for the pair, as the adjacent case)
+            def both():
+                _add_into(gacc, dgamma.data_ptr(), n_c)
+                _add_into(bacc, dbeta.data_ptr(), n_c)
+            run_on_side_stream(dy.device, (dgb,), both, lane=getattr(gref, "_sscg_lane", 0), defer=True)
     return dx, ret_g, ret_b, dres
 
 
@@ -1800,52 +1816,90 @@ class ConvNormActFn(torch.autograd.Function):
     """The reference's fusion unit as ONE autograd node: conv -> InstanceNorm / BatchNorm (batch statistics, from the conv's
     epilogue where the library can fuse them) [+ residual] -> activation (arch/ops.py:40-57; Bottleneck conv+bn pairs,
     arch/generators.py:345-365).  The same kernels as Conv2dFn + NormActFn; one node instead of two halves the host's per-layer
-    autograd cost (575 such pairs per step).  cfg = (stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope)."""
+    autograd cost (575 such pairs per step).  cfg = (stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope, grad);
+    grad = the grad mode of the caller (inside forward() it is always off)."""
 
     @staticmethod
     def forward(ctx, x, w, bias, gamma, beta, residual, running_mean, running_var, cfg):
-        stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope = cfg
+        stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope, grad = cfg
         x = to_nhwc(x)
         if residual is not None:
             residual = to_nhwc(residual)
-        n, _, h, wd = x.shape
-        p, q = conv_out_size(h, w.shape[2], stride, pad, dil), conv_out_size(wd, w.shape[3], stride, pad, dil)
-        g, l, c = _glc_shape((n, w.shape[0], p, q), per_sample)
-        y, mean, rstd = conv2d_fwd_norm(x, w, bias, stride, pad, dil, pad_mode, False, (g, l, c), eps, running_mean, running_var, momentum)
-        if mean is None:
-            upd = running_mean is not None and per_sample is not True
-            mean, rstd = norm_stats(y, per_sample, eps, running_mean if upd else None, running_var if upd else None, momentum)
+        y, mean, rstd, glc = _conv_stats_fwd(x, w, bias, (stride, pad, dil, pad_mode), False,
+                                             (per_sample, eps, running_mean, running_var, momentum))
         z = norm_apply(y, mean, rstd, gamma, beta, residual, per_sample, act, slope)
         ctx.cfg = cfg
         ctx.has_bias = bias is not None
         ctx.has_res = residual is not None
         ctx.wref, ctx.bref, ctx.gref, ctx.betaref = w, bias, gamma, beta
-        if _will_backward(ctx, 1):
-            _note_use(w, bias)
+        ctx.counted = _note_use(w, bias) if grad and ctx.needs_input_grad[1] else ()
         need_z = act != ACT_NONE and (residual is not None or act not in (ACT_RELU, ACT_LRELU))
         ctx.save_for_backward(x, w, y, z if need_z else None, mean, rstd, gamma, beta)
         ctx.res_join = getattr(residual, "_sscg_join", None) if (residual is not None and FUSE_JOIN[0]) else None
         # (only for a forward that will see a backward: the attribute keeps y, mean, rstd alive as long as z lives - the frozen
         # generators, evaluation and validation would hold every pre-norm activation for nothing)
-        if (FUSE_BSUMS[0] and _will_backward(ctx) and act in (ACT_NONE, ACT_RELU, ACT_LRELU)
+        if (FUSE_BSUMS[0] and grad and any(ctx.needs_input_grad) and act in (ACT_NONE, ACT_RELU, ACT_LRELU)
                 and (residual is None or FUSE_JOIN[0])):
             # for the consumer's data gradient (_conv_backward): what this unit's backward reduction needs besides dz; last entry: the
             # mask cannot be recomputed from y (a residual joined before the activation) - it is read off z, the consumer's own input
-            z._sscg_norm = (y, mean, rstd, gamma, beta, (g, l, c), act, slope, need_z)
+            z._sscg_norm = (y, mean, rstd, gamma, beta, glc, act, slope, need_z)
         return z
 
     @staticmethod
     def backward(ctx, dz):
         x, w, y, z, mean, rstd, gamma, beta = ctx.saved_tensors
-        stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope = ctx.cfg
+        stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope, _ = ctx.cfg
         ni = ctx.needs_input_grad
         dy, ret_g, ret_b, dres = _norm_backward(to_nhwc(dz), y, z, mean, rstd, gamma, beta, ctx.gref, ctx.betaref, per_sample, act, slope,
                                                 True, gamma is not None and ni[3], ctx.has_res and ni[5])
         if ctx.res_join is not None and dres is not None:
             ctx.res_join[0].deposit(ctx.res_join[1], dres)      # the shortcut's gradient: the block's conv1 may add it in its data gradient
         dx, dw, db = _conv_backward(dy, x, w, ctx.wref, ctx.bref if ctx.has_bias else None, (stride, pad, dil, pad_mode),
-                                    ni[0], ni[1], ctx.has_bias and ni[2])
+                                    ni[0], ni[1], ctx.has_bias and ni[2], ctx.counted)
         return dx, dw, db, ret_g, ret_b, dres, None, None, None
+
+
+def _head_fwd(y, mean, rstd, gamma, beta, hw, hbias, per_sample, act, slope):
+    """(out, hw32): the fused tail norm -> activation -> Conv2d(c, 1, 1x1) over the pre-norm map y (sscg_norm_head_fwd: the head's
+    output is formed while normalising) and the head's weight as the flat fp32 vector its kernels read."""
+    hw32 = hw.detach().reshape(-1)
+    if hw32.dtype != torch.float32:
+        hw32 = hw32.float()
+    return norm_head_fwd(y, mean, rstd, gamma, beta, hw32, hbias, per_sample, act, slope), hw32
+
+
+def _head_backward(dout, y, mean, rstd, gamma, beta, hw32, gref, betaref, hwref, hbref, per_sample, act, slope, want_g, want_hw, want_hb):
+    """Backward of _head_fwd: (dy, dgamma, dbeta, dhw, dhbias) with dy the gradient of the pre-norm map (sscg_norm_head_bwd rebuilds
+    dout * hw and the activation from y in registers).  The four parameter gradients are sums produced beside dy on this stream; for
+    parameters owned by optim.FusedAdam their accumulation into its arena runs on each parameter's own side lane (returned as None)."""
+    dout = dout.contiguous()
+    if dout.dtype != torch.float32:
+        dout = dout.float()
+    c = hw32.numel()
+    dgb = torch.empty((2, c), dtype=torch.float32, device=y.device) if want_g else None
+    dwb = torch.empty(c + 1, dtype=torch.float32, device=y.device)
+    dy = norm_head_bwd(dout, hw32, y, mean, rstd, gamma, beta, per_sample, act, slope, True, dwb,
+                       dgb[0] if want_g else None, dgb[1] if want_g else None)
+    ret_hw = ret_hb = ret_g = ret_b = None
+    hwacc = _acc_target(hwref) if want_hw else None
+    hbacc = _acc_target(hbref) if want_hb else None
+    if want_hw and hwacc is None:
+        ret_hw = dwb[:c].reshape(hwref.shape).to(hwref.dtype)
+    if want_hb and hbacc is None:
+        ret_hb = dwb[c:c + 1].clone()
+    gacc = _acc_target(gref) if want_g else None
+    bacc = _acc_target(betaref) if want_g else None
+    if want_g and (gacc is None or bacc is None):
+        gacc = bacc = None
+        ret_g, ret_b = dgb[0], dgb[1]
+    if hwacc is not None:
+        _arena_add(y.device, hwacc, dwb.data_ptr(), c, hwref, dwb)
+    if hbacc is not None:
+        _arena_add(y.device, hbacc, dwb.data_ptr() + 4 * c, 1, hbref, dwb)
+    if gacc is not None:
+        _arena_add(y.device, gacc, dgb.data_ptr(), c, gref, dgb)
+        _arena_add(y.device, bacc, dgb.data_ptr() + 4 * c, c, betaref, dgb)
+    return dy, ret_g, ret_b, ret_hw, ret_hb
 
 
 class ConvNormActHeadFn(torch.autograd.Function):
@@ -1854,75 +1908,32 @@ class ConvNormActHeadFn(torch.autograd.Function):
     the conv) and read once per direction of the tail: the head's output is formed while normalising (sscg_norm_head_fwd), and the
     backward rebuilds dy = dout * w3 and the activation from x in registers (sscg_norm_head_bwd) - the normalised map, the head's
     input gradient and the head's weight-gradient pass over it never exist in HBM.
-    cfg = (stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope)."""
+    cfg = (stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope, grad); grad = the grad mode of the caller."""
 
     @staticmethod
     def forward(ctx, x, w, bias, gamma, beta, hw, hbias, running_mean, running_var, cfg):
-        stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope = cfg
+        stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope, grad = cfg
         x = to_nhwc(x)
-        n, _, h, wd = x.shape
-        p, q = conv_out_size(h, w.shape[2], stride, pad, dil), conv_out_size(wd, w.shape[3], stride, pad, dil)
-        g, l, c = _glc_shape((n, w.shape[0], p, q), per_sample)
-        y, mean, rstd = conv2d_fwd_norm(x, w, bias, stride, pad, dil, pad_mode, False, (g, l, c), eps, running_mean, running_var, momentum)
-        if mean is None:
-            upd = running_mean is not None and per_sample is not True
-            mean, rstd = norm_stats(y, per_sample, eps, running_mean if upd else None, running_var if upd else None, momentum)
-        hw32 = hw.detach().reshape(-1)
-        if hw32.dtype != torch.float32:
-            hw32 = hw32.float()
-        out = norm_head_fwd(y, mean, rstd, gamma, beta, hw32, hbias, per_sample, act, slope)
+        y, mean, rstd, _ = _conv_stats_fwd(x, w, bias, (stride, pad, dil, pad_mode), False,
+                                           (per_sample, eps, running_mean, running_var, momentum))
+        out, hw32 = _head_fwd(y, mean, rstd, gamma, beta, hw, hbias, per_sample, act, slope)
         ctx.cfg = cfg
         ctx.has_bias = bias is not None
         ctx.has_hbias = hbias is not None
         ctx.wref, ctx.bref, ctx.gref, ctx.betaref, ctx.hwref, ctx.hbref = w, bias, gamma, beta, hw, hbias
-        if _will_backward(ctx, 1):
-            _note_use(w, bias)
+        ctx.counted = _note_use(w, bias) if grad and ctx.needs_input_grad[1] else ()
         ctx.save_for_backward(x, w, y, mean, rstd, gamma, beta, hw32)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, w, y, mean, rstd, gamma, beta, hw32 = ctx.saved_tensors
-        stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope = ctx.cfg
+        stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope, _ = ctx.cfg
         ni = ctx.needs_input_grad
-        dout = dout.contiguous()
-        if dout.dtype != torch.float32:
-            dout = dout.float()
-        c = hw32.numel()
-        want_g = gamma is not None and ni[3]
-        dgb = torch.empty((2, c), dtype=torch.float32, device=y.device) if want_g else None
-        dwb = torch.empty(c + 1, dtype=torch.float32, device=y.device)
-        dy = norm_head_bwd(dout, hw32, y, mean, rstd, gamma, beta, per_sample, act, slope, True, dwb,
-                           dgb[0] if want_g else None, dgb[1] if want_g else None)
-        # head weight / bias, norm weight / bias: sums produced beside dy on this stream; their accumulation into the optimiser's
-        # arena runs on each parameter's own side lane (as _norm_backward)
-        ret_hw = ret_hb = ret_g = ret_b = None
-        want_hw, want_hb = ni[5], ctx.has_hbias and ni[6]
-        hwacc = _acc_target(ctx.hwref) if want_hw else None
-        hbacc = _acc_target(ctx.hbref) if want_hb else None
-        if want_hw and hwacc is None:
-            ret_hw = dwb[:c].reshape(ctx.hwref.shape).to(ctx.hwref.dtype)
-        if want_hb and hbacc is None:
-            ret_hb = dwb[c:c + 1].clone()
-        gacc = _acc_target(ctx.gref) if want_g else None
-        bacc = _acc_target(ctx.betaref) if want_g else None
-        if want_g and (gacc is None or bacc is None):
-            gacc = bacc = None
-            ret_g, ret_b = dgb[0], dgb[1]
-
-        def arena_add(acc, src_ptr, count, ref, keep):      # every gradient of a parameter is accumulated on that parameter's lane
-            def go():
-                check(lib.sscg_add(acc.data_ptr(), src_ptr, acc.data_ptr(), F32, count, _stream()), "sscg_add")
-            run_on_side_stream(y.device, (keep,), go, lane=getattr(ref, "_sscg_lane", 0), defer=True)
-        if hwacc is not None:
-            arena_add(hwacc, dwb.data_ptr(), c, ctx.hwref, dwb)
-        if hbacc is not None:
-            arena_add(hbacc, dwb.data_ptr() + 4 * c, 1, ctx.hbref, dwb)
-        if gacc is not None:
-            arena_add(gacc, dgb.data_ptr(), c, ctx.gref, dgb)
-            arena_add(bacc, dgb.data_ptr() + 4 * c, c, ctx.betaref, dgb)
+        dy, ret_g, ret_b, ret_hw, ret_hb = _head_backward(dout, y, mean, rstd, gamma, beta, hw32, ctx.gref, ctx.betaref, ctx.hwref, ctx.hbref,
+                                                          per_sample, act, slope, gamma is not None and ni[3], ni[5], ctx.has_hbias and ni[6])
         dx, dw, db = _conv_backward(dy, x, w, ctx.wref, ctx.bref if ctx.has_bias else None, (stride, pad, dil, pad_mode),
-                                    ni[0], ni[1], ctx.has_bias and ni[2])
+                                    ni[0], ni[1], ctx.has_bias and ni[2], ctx.counted)
         return dx, dw, db, ret_g, ret_b, ret_hw, ret_hb, None, None, None
 
 
@@ -1931,29 +1942,23 @@ class PixelDiscFn(torch.autograd.Function):
     Conv2d(64, 2 ndf, 1x1) [+ the norm layer's batch statistics] in ONE launch (sscg_conv2d_front_fwd: the 64-channel map is formed
     in LDS and written only for a backward pass), then the fused tail of ConvNormActHeadFn (norm -> LeakyReLU -> Conv2d(2 ndf, 1, 1x1)
     while normalising).  The backward is the chain of the separate nodes: head / norm, second conv, LeakyReLU mask, first conv.
-    cfg = (slope1, per_sample, eps, momentum, act, slope)."""
+    cfg = (slope1, per_sample, eps, momentum, act, slope, grad); grad = the grad mode of the caller."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w, bias, gamma, beta, hw, hbias, running_mean, running_var, cfg):
-        slope1, per_sample, eps, momentum, act, slope = cfg
+        slope1, per_sample, eps, momentum, act, slope, grad = cfg
         x = to_nhwc(x)
         n, _, h, wd = x.shape
         g, l, c = _glc_shape((n, w.shape[0], h, wd), per_sample)
-        will = _will_backward(ctx)
+        will = grad and any(ctx.needs_input_grad)
         y, h1, cs = conv2d_front_fwd(x, w1, b1, slope1, w, bias, (g, l, c), want_h1=will)
-        upd = running_mean is not None and per_sample is not True
-        mean, rstd = norm_stats_from_conv(cs, (g, l, c), eps, running_mean if upd else None, running_var if upd else None, momentum)
-        hw32 = hw.detach().reshape(-1)
-        if hw32.dtype != torch.float32:
-            hw32 = hw32.float()
-        out = norm_head_fwd(y, mean, rstd, gamma, beta, hw32, hbias, per_sample, act, slope)
+        mean, rstd = norm_stats_from_conv(cs, (g, l, c), eps, *_running_stats(running_mean, running_var, per_sample), momentum)
+        out, hw32 = _head_fwd(y, mean, rstd, gamma, beta, hw, hbias, per_sample, act, slope)
         ctx.cfg = cfg
         ctx.has_b1, ctx.has_bias, ctx.has_hbias = b1 is not None, bias is not None, hbias is not None
         ctx.w1ref, ctx.b1ref, ctx.wref, ctx.bref, ctx.gref, ctx.betaref, ctx.hwref, ctx.hbref = w1, b1, w, bias, gamma, beta, hw, hbias
-        if _will_backward(ctx, 1):
-            _note_use(w1, b1)
-        if _will_backward(ctx, 3):
-            _note_use(w, bias)
+        ctx.counted1 = _note_use(w1, b1) if grad and ctx.needs_input_grad[1] else ()
+        ctx.counted = _note_use(w, bias) if grad and ctx.needs_input_grad[3] else ()
         if will:
             ctx.save_for_backward(x, w1, h1, w, y, mean, rstd, gamma, beta, hw32)
         return out
@@ -1961,64 +1966,32 @@ class PixelDiscFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, w1, h1, w, y, mean, rstd, gamma, beta, hw32 = ctx.saved_tensors
-        slope1, per_sample, eps, momentum, act, slope = ctx.cfg
+        slope1, per_sample, eps, momentum, act, slope, _ = ctx.cfg
         ni = ctx.needs_input_grad
-        dout = dout.contiguous()
-        if dout.dtype != torch.float32:
-            dout = dout.float()
-        c = hw32.numel()
-        want_g = gamma is not None and ni[5]
-        dgb = torch.empty((2, c), dtype=torch.float32, device=y.device) if want_g else None
-        dwb = torch.empty(c + 1, dtype=torch.float32, device=y.device)
-        dy = norm_head_bwd(dout, hw32, y, mean, rstd, gamma, beta, per_sample, act, slope, True, dwb,
-                           dgb[0] if want_g else None, dgb[1] if want_g else None)
-        ret_hw = ret_hb = ret_g = ret_b = None
-        want_hw, want_hb = ni[7], ctx.has_hbias and ni[8]
-        hwacc = _acc_target(ctx.hwref) if want_hw else None
-        hbacc = _acc_target(ctx.hbref) if want_hb else None
-        if want_hw and hwacc is None:
-            ret_hw = dwb[:c].reshape(ctx.hwref.shape).to(ctx.hwref.dtype)
-        if want_hb and hbacc is None:
-            ret_hb = dwb[c:c + 1].clone()
-        gacc = _acc_target(ctx.gref) if want_g else None
-        bacc = _acc_target(ctx.betaref) if want_g else None
-        if want_g and (gacc is None or bacc is None):
-            gacc = bacc = None
-            ret_g, ret_b = dgb[0], dgb[1]
-
-        def arena_add(acc, src_ptr, count, ref, keep):      # every gradient of a parameter is accumulated on that parameter's lane
-            def go():
-                check(lib.sscg_add(acc.data_ptr(), src_ptr, acc.data_ptr(), F32, count, _stream()), "sscg_add")
-            run_on_side_stream(y.device, (keep,), go, lane=getattr(ref, "_sscg_lane", 0), defer=True)
-        if hwacc is not None:
-            arena_add(hwacc, dwb.data_ptr(), c, ctx.hwref, dwb)
-        if hbacc is not None:
-            arena_add(hbacc, dwb.data_ptr() + 4 * c, 1, ctx.hbref, dwb)
-        if gacc is not None:
-            arena_add(gacc, dgb.data_ptr(), c, ctx.gref, dgb)
-            arena_add(bacc, dgb.data_ptr() + 4 * c, c, ctx.betaref, dgb)
+        dy, ret_g, ret_b, ret_hw, ret_hb = _head_backward(dout, y, mean, rstd, gamma, beta, hw32, ctx.gref, ctx.betaref, ctx.hwref, ctx.hbref,
+                                                          per_sample, act, slope, gamma is not None and ni[5], ni[7], ctx.has_hbias and ni[8])
         geom = (1, 0, 1, PAD_ZEROS)
         front = ni[0] or ni[1] or (ctx.has_b1 and ni[2])
-        dh1, dw, db = _conv_backward(dy, h1, w, ctx.wref, ctx.bref if ctx.has_bias else None, geom, front, ni[3], ctx.has_bias and ni[4])
+        dh1, dw, db = _conv_backward(dy, h1, w, ctx.wref, ctx.bref if ctx.has_bias else None, geom, front, ni[3], ctx.has_bias and ni[4],
+                                     ctx.counted)
         dx = dw1 = db1 = None
         if front:
             dh1 = act_bwd(dh1, h1, ACT_LRELU, slope1)
-            dx, dw1, db1 = _conv_backward(dh1, x, w1, ctx.w1ref, ctx.b1ref if ctx.has_b1 else None, geom, ni[0], ni[1], ctx.has_b1 and ni[2])
+            dx, dw1, db1 = _conv_backward(dh1, x, w1, ctx.w1ref, ctx.b1ref if ctx.has_b1 else None, geom, ni[0], ni[1], ctx.has_b1 and ni[2],
+                                          ctx.counted1)
         return dx, dw1, db1, dw, db, ret_g, ret_b, ret_hw, ret_hb, None, None, None
 
 
 def pixel_disc(x, w1, b1, slope1, w, bias, gamma, beta, hw, hbias, running_mean, running_var, per_sample, eps, momentum, act, slope):
-    _CALLER_GRAD[0] = torch.is_grad_enabled()
     return PixelDiscFn.apply(x, w1, b1, w, bias, gamma, beta, hw, hbias, running_mean, running_var,
-                             (slope1, per_sample, eps, momentum, act, slope))
+                             (slope1, per_sample, eps, momentum, act, slope, torch.is_grad_enabled()))
 
 
 def conv_norm_act_head(x, w, bias, stride, pad, dil, pad_mode, gamma, beta, hw, hbias, running_mean, running_var, per_sample, eps,
                        momentum, act, slope):
     """conv -> norm (batch statistics) -> activation -> 1x1 conv to one channel, as one node (PixelDiscriminator's tail)."""
-    _CALLER_GRAD[0] = torch.is_grad_enabled()
     return ConvNormActHeadFn.apply(x, w, bias, gamma, beta, hw, hbias, running_mean, running_var,
-                                   (stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope))
+                                   (stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope, torch.is_grad_enabled()))
 
 
 class ActFn(torch.autograd.Function):
@@ -2440,8 +2413,7 @@ class WeightedSumFn(torch.autograd.Function):
 # functional spellings
 def conv2d(x, w, bias=None, stride=1, pad=0, dil=1, pad_mode=PAD_ZEROS, act=ACT_NONE, slope=0.0, out_f32=True):
     """out_f32 matters in bf16 mode only: True keeps the result fp32 (network heads), False makes it a bf16 activation."""
-    _CALLER_GRAD[0] = torch.is_grad_enabled()
-    return Conv2dFn.apply(x, w, bias, stride, pad, dil, pad_mode, act, slope, out_f32, None)
+    return Conv2dFn.apply(x, w, bias, stride, pad, dil, pad_mode, act, slope, out_f32, None, torch.is_grad_enabled())
 
 
 def backward(loss):
@@ -2460,16 +2432,14 @@ def backward(loss):
 def conv_norm_act(x, w, bias, stride, pad, dil, pad_mode, gamma, beta, residual, running_mean, running_var, per_sample, eps, momentum,
                   act=ACT_NONE, slope=0.0):
     """conv -> norm (batch statistics) [+ residual] -> activation as one autograd node (training-mode normalisation only)."""
-    _CALLER_GRAD[0] = torch.is_grad_enabled()
     return ConvNormActFn.apply(x, w, bias, gamma, beta, residual, running_mean, running_var,
-                               (stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope))
+                               (stride, pad, dil, pad_mode, per_sample, eps, momentum, act, slope, torch.is_grad_enabled()))
 
 
 def conv2d_norm_stats(x, w, bias, stride, pad, dil, pad_mode, norm):
     """Convolution whose epilogue also produces the statistics of the normalisation layer `norm` = (per_sample, eps,
     running_mean, running_var, momentum) that follows it.  Returns (y, mean, rstd); mean/rstd None = not fused."""
-    _CALLER_GRAD[0] = torch.is_grad_enabled()
-    return Conv2dFn.apply(x, w, bias, stride, pad, dil, pad_mode, ACT_NONE, 0.0, False, norm)
+    return Conv2dFn.apply(x, w, bias, stride, pad, dil, pad_mode, ACT_NONE, 0.0, False, norm, torch.is_grad_enabled())
 
 
 def conv_transpose2d(x, w, bias=None, stride=1, pad=0, out_pad=0, act=ACT_NONE, slope=0.0, out_f32=False):

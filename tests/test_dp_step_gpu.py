@@ -81,6 +81,11 @@ def _worker(rank, world, port, outdir, buckets=0):
     st = _state(m)
     gb = getattr(m.g_optimizer, "_sscg_buckets", None)
     st.update(after_attach=after_attach, losses=losses, bucket_order=None if gb is None else list(gb.order), buckets=None if gb is None else gb.n)
+    # the use count of every bucketed parameter (functional._note_use / _note_done) after the last step's backward and finish():
+    # each step also runs the unused Gis(lab_gt) forward under no_grad, which must not have counted
+    named = [("%s.%s" % (net, k), p) for net in ("Gis", "Gsi") for k, p in getattr(m, net).named_parameters()]
+    st["uses_left"] = None if gb is None else sorted(k for k, p in named if p in m.g_optimizer.slices and getattr(p, "_sscg_uses", 0) != 0)
+    st["uses_checked"] = sum(1 for _, p in named if p in m.g_optimizer.slices)
     torch.save(st, os.path.join(outdir, "rank%d.pt" % rank))
     dp.barrier()
     import torch.distributed as dist
@@ -128,6 +133,9 @@ def test_dp_step_world_size_2_shared_gpu(dev, tmp_path):
         assert r0["buckets"] == 4 and sorted(r0["bucket_order"]) == list(range(4)) and r0["bucket_order"] == r1["bucket_order"]
         assert r0["bucket_order"] != [3, 2, 1, 0], r0["bucket_order"]
         print("bucket launch order:", r0["bucket_order"])
+        # every use counted in a forward was taken back by a backward, and a forward under no_grad counted nothing
+        for r in (r0, r1):
+            assert r["uses_checked"] > 0 and r["uses_left"] == [], r["uses_left"][:8]
     sim = None
     for buckets, (r0, r1) in res.items():
         sim = _check_against_lockstep(r0, r1, dev, sim)
