@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSCG_ABI_VERSION 17
+#define SSCG_ABI_VERSION 18
 
 /* element types of activation / weight tensors */
 #define SSCG_F32 0
@@ -310,6 +310,31 @@ int sscg_upsample_head_fwd(const float* x, const int64_t* labels, float* y_soft,
                            int W, int C, int OH, int OW, void* ws, size_t ws_bytes, void* stream);
 int sscg_upsample_head_bwd(const float* x, const float* dy_soft, const float* dlogits, const float* g_ce, const float* valid, float* dx,
                            int N, int H, int W, int C, int OH, int OW, void* stream);
+/* ------------------------------------------------------------------ inference heads (ABI v18): one launch from a generator's output
+ * to what its consumer keeps.  Forward only; never launched by the training step.
+ *
+ * sscg_predict_head: label maps from the segmentation generator's low-resolution logits x [N][H][W][C] (C <= 64) - the per-epoch
+ * evaluation (model.py:555-574: interp -> Softmax2d -> .max(1)[1] -> runningScore._fast_hist), validation.py:97-120 and
+ * testing.py:43 (softmax -> argmax on the net's own output).  Per output pixel: the bilinear resize to [OH][OW] with
+ * align_corners=True (the arithmetic of sscg_upsample_bilinear_fwd), the softmax over C (sscg_softmax_fwd's), the first maximum
+ * (sscg_argmax_onehot's rule) - the same expressions in the same order, so every output equals the unfused chain's bit for bit; the
+ * resized logits and the probabilities never reach memory.  OH == H && OW == W is the identity resize: no interpolation arithmetic.
+ *   index      (nullable) int64 [N][OH][OW]: what sscg_argmax_onehot writes;
+ *   label_u8   (nullable) uint8 [N][OH][OW]: the same class ids as bytes (the paletted PNGs of the drivers);
+ *   label_true / hist (nullable together) int64 [N][OH][OW] / int64 [C][C]: hist[C*t + p] += 1 under sscg_confusion_hist's rules
+ *              (t outside [0, C) ignored; accumulated into; integer atomics, exact).
+ * At least one of index / label_u8 / hist is required.
+ *
+ * sscg_image_head: the image generator's output x [N][H][W][C] (C <= 4) as validation.py:108-114 consumes it:
+ *   y_nhwc (nullable) fp32 [N][OH][OW][C] = tanh(resize(x)) - sscg_upsample_bilinear_fwd then sscg_act_fwd(SSCG_ACT_TANH), bit for
+ *          bit: the tensor validation.py feeds back into Gsi;
+ *   rgb_u8 (nullable) uint8 [N][OH][OW][C] = uint8(clamp((t * 0.5f + 0.5f) * 255.f + 0.5f, 0, 255)) with t = y_nhwc's value and every
+ *          operation rounded to fp32 on its own: un-normalise (validation.py) + torchvision's save_image (x * 255 + 0.5, clamp,
+ *          truncate), the bytes the host wrote from the fp32 tensor.
+ * At least one of the two is required. */
+int sscg_predict_head(const float* x, int N, int H, int W, int C, int OH, int OW, int64_t* index, uint8_t* label_u8,
+                      const int64_t* label_true, int64_t* hist, void* stream);
+int sscg_image_head(const float* x, int N, int H, int W, int C, int OH, int OW, float* y_nhwc, uint8_t* rgb_u8, void* stream);
 /* nn.MSELoss against a constant target map of ones/zeros (LSGAN; model.py:445-446,452,521-528) */
 int sscg_mse_const_fwd(const float* x, int64_t n, float target, float* loss, void* ws, size_t ws_bytes, void* stream);
 int sscg_mse_const_bwd(const float* x, int64_t n, float target, const float* gscale, float w, float* dx, void* stream);

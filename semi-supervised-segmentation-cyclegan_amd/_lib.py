@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSCG_LIB") or os.path.join(_HERE, "libsscg.so")   # SSCG_LIB: kernel-ablation builds (tools/)
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 F32, BF16, BF16X3 = 0, 1, 2     # SSCG_F32 / SSCG_BF16 / SSCG_BF16X3 (split weight operand)
 
@@ -105,6 +105,8 @@ SIGNATURES = {
     "sscg_upsample_head_workspace": (_sz, [_i, _i, _i]),
     "sscg_upsample_head_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "sscg_upsample_head_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "sscg_predict_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_mse_const_fwd": (_i, [_p, _i64, _f, _p, _p, _sz, _p]),
     "sscg_mse_const_bwd": (_i, [_p, _i64, _f, _p, _f, _p, _p]),
     "sscg_mse_fwd": (_i, [_p, _p, _i64, _p, _p, _sz, _p]),

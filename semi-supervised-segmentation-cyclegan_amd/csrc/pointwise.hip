@@ -1,6 +1,7 @@
 // HBM-bound pointwise / pooling / resize / layout kernels (NHWC fp32).  Reference call sites are
 // listed per entry point in include/sscg.h.
 #include "common.h"
+#include "head_common.h"
 #include "sscg_internal.h"
 
 namespace {
@@ -219,15 +220,11 @@ __global__ void upsample_fwd_kernel(const float* __restrict__ x, float* __restri
         int ox = (int)(t % OW); t /= OW;
         int oy = (int)(t % OH);
         int n = (int)(t / OH);
-        float fy = sh * oy, fx = sw * ox;
-        int y0 = (int)fy, x0 = (int)fx;
-        int yp = y0 < H - 1 ? 1 : 0, xp = x0 < W - 1 ? 1 : 0;
-        float ly = fy - y0, lx = fx - x0;
-        float hy = 1.f - ly, hx = 1.f - lx;
+        const sscg_bilin g = sscg_bilin_at(oy, ox, H, W, sh, sw);
         const float* b = x + (size_t)n * H * W * C + c;
-        float v00 = b[((size_t)y0 * W + x0) * C], v01 = b[((size_t)y0 * W + x0 + xp) * C];
-        float v10 = b[((size_t)(y0 + yp) * W + x0) * C], v11 = b[((size_t)(y0 + yp) * W + x0 + xp) * C];
-        y[i] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+        float v00 = b[((size_t)g.y0 * W + g.x0) * C], v01 = b[((size_t)g.y0 * W + g.x0 + g.xp) * C];
+        float v10 = b[((size_t)(g.y0 + g.yp) * W + g.x0) * C], v11 = b[((size_t)(g.y0 + g.yp) * W + g.x0 + g.xp) * C];
+        y[i] = sscg_bilerp(g, v00, v01, v10, v11);
     }
 }
 

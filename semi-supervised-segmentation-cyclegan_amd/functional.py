@@ -1213,6 +1213,68 @@ def confusion_hist(label_true, label_pred, num_classes, hist=None):
     return hist
 
 
+# The inference heads (sscg_predict_head / sscg_image_head): what evaluate(), validation.py and testing.py keep of a generator's
+# output, in one launch.  SSCG_FUSE_PREDICT=0 keeps those call sites on the chain of separate passes (an A/B aid: the bits are the same).
+FUSE_PREDICT = [os.environ.get("SSCG_FUSE_PREDICT", "1") != "0"]
+
+
+def _no_grad_input(x, what):
+    if x.requires_grad and torch.is_grad_enabled():
+        raise _lib.SscgError("%s is an inference call, not an autograd node: call it under torch.no_grad() or on a detached tensor" % what)
+
+
+def predict_labels(logits, size, *, want_index=False, want_u8=True, label_true=None, hist=None, num_classes=None):
+    """interp(size, bilinear, align_corners=True) -> Softmax2d -> .max(1)[1] of fp32 logits [N,C,H,W] in one launch, bit for bit what
+    `argmax_index(softmax2d(upsample_bilinear(logits, size)))` gives (model.py:555-574, validation.py:97-120, testing.py:43).
+    Returns (label_u8 uint8 [N,OH,OW] or None, index int64 [N,OH,OW] or None, hist or None).  `label_true` (int64, N*OH*OW elements)
+    adds the batch to the confusion matrix `hist` (int64 [C,C] on the device, runningScore._fast_hist's rules; None = a new zeroed one)."""
+    _need_hip(logits, f32_only=True)
+    if logits.dim() != 4:
+        raise _lib.SscgError("predict_labels: 4-D logits expected")
+    _no_grad_input(logits, "predict_labels")
+    x = to_nhwc(logits.detach())
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    if num_classes is not None and int(num_classes) != c:
+        raise _lib.SscgError("predict_labels: %d classes asked for, the logits have %d channels" % (num_classes, c))
+    if hist is not None and label_true is None:
+        raise _lib.SscgError("predict_labels: a confusion matrix needs label_true")
+    lt = None
+    if label_true is not None:
+        if not label_true.is_cuda:
+            raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % label_true.device)
+        lt = label_true.to(torch.int64).contiguous()
+        if lt.numel() != n * oh * ow:
+            raise _lib.SscgError("predict_labels: label_true must have N*OH*OW elements")
+        if hist is None:
+            hist = torch.empty((c, c), dtype=torch.int64, device=x.device)
+            check(lib.sscg_fill(hist.data_ptr(), 2 * hist.numel(), 0.0, _stream()), "sscg_fill")   # 2 fp32 zeros per int64 zero
+        elif not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == c * c):
+            raise _lib.SscgError("predict_labels: hist must be a contiguous int64 [C, C] tensor on the device")
+    u8 = torch.empty((n, oh, ow), dtype=torch.uint8, device=x.device) if want_u8 else None
+    idx = torch.empty((n, oh, ow), dtype=torch.int64, device=x.device) if want_index else None
+    check(lib.sscg_predict_head(x.data_ptr(), n, h, w, c, oh, ow, _ptr(idx), _ptr(u8), _ptr(lt), _ptr(hist), _stream()),
+          "sscg_predict_head")
+    return u8, idx, hist
+
+
+def predict_image(x, size, *, want_float=True, want_u8=True):
+    """interp(size) -> Tanh of the image generator's fp32 output [N,C,H,W] (C <= 4) in one launch (validation.py:108-114).  Returns
+    (y, rgb_u8): y = fp32 [N,C,OH,OW] channels-last, bit for bit `act_fwd(to_nhwc(upsample_bilinear(x, size)), ACT_TANH)`; rgb_u8 =
+    uint8 [N,OH,OW,C], the pixels `save_image(y * 0.5 + 0.5)` writes (x * 255 + 0.5, clamp, truncate; every step rounded to fp32)."""
+    _need_hip(x, f32_only=True)
+    if x.dim() != 4:
+        raise _lib.SscgError("predict_image: 4-D tensor expected")
+    _no_grad_input(x, "predict_image")
+    x = to_nhwc(x.detach())
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    y = empty_nhwc(n, c, oh, ow, x.device) if want_float else None
+    u8 = torch.empty((n, oh, ow, c), dtype=torch.uint8, device=x.device) if want_u8 else None
+    check(lib.sscg_image_head(x.data_ptr(), n, h, w, c, oh, ow, _ptr(y), _ptr(u8), _stream()), "sscg_image_head")
+    return y, u8
+
+
 def image_u8_to_f32(img_u8, mean, std):
     """uint8 [B,H,W,C] (HWC pixels as PIL decoded them) -> fp32 logical [B,C,H,W], channels-last, ((u/255) - mean) / std:
     ToTensor + Normalize of data_utils/__init__.py:126-150 on the device."""

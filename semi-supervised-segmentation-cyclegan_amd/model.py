@@ -446,7 +446,11 @@ class semisuper_cycleGAN(object):
         self.running_metrics_val.reset()
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
-            outputs = F.softmax2d(self.interp(self.Gsi(val_img)))
+            logits = self.Gsi(val_img)
+            if F.FUSE_PREDICT[0]:            # interp -> Softmax2d -> max(1)[1] -> _fast_hist in one launch (:565-569)
+                self.running_metrics_val.update_logits(val_gt.squeeze(1), logits, self.crop)
+                continue
+            outputs = F.softmax2d(self.interp(logits))
             self.running_metrics_val.update_device(val_gt.squeeze(1), F.argmax_index(outputs))   # :566-569 without the host round trip
         score, class_iou = self.running_metrics_val.get_scores()
         self.Gsi.train()
@@ -558,7 +562,11 @@ class supervised_model(object):
         self.running_metrics_val.reset()
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
-            outputs = F.softmax2d(F.upsample_bilinear(self.Gsi(val_img), self.crop))
+            logits = self.Gsi(val_img)
+            if F.FUSE_PREDICT[0]:
+                self.running_metrics_val.update_logits(val_gt.squeeze(1), logits, self.crop)
+                continue
+            outputs = F.softmax2d(F.upsample_bilinear(logits, self.crop))
             self.running_metrics_val.update_device(val_gt.squeeze(1), F.argmax_index(outputs))
         score, class_iou = self.running_metrics_val.get_scores()
         self.running_metrics_val.reset()

@@ -170,6 +170,12 @@ class runningScore(object):
         device->host copy of the maps per batch (model.py:568-569 moves both to numpy)."""
         self._device_hist = F.confusion_hist(label_trues, label_preds, self.n_classes, self._device_hist)
 
+    def update_logits(self, label_trues, logits, size):
+        """update_device() from the network's low-resolution logits: resize -> softmax -> argmax -> counts in one launch
+        (F.predict_labels); neither the resized logits nor a predicted label map reach memory."""
+        self._device_hist = F.predict_labels(logits, size, want_u8=False, label_true=label_trues, hist=self._device_hist,
+                                             num_classes=self.n_classes)[2]
+
     def _fold_device(self):
         if self._device_hist is not None:
             self.confusion_matrix += self._device_hist.cpu().numpy().astype(np.float64)
@@ -237,6 +243,13 @@ def colorize_mask(mask, dataset):
     new_mask = Image.fromarray(np.asarray(mask).astype(np.uint8)).convert('P')
     new_mask.putpalette({'voc2012': palette, 'cityscapes': cityscape_palette, 'acdc': acdc_palette}[dataset])
     return new_mask
+
+
+def save_image_u8(pixels, path):
+    """save_image() for the uint8 HWC pixels F.predict_image already holds (its x * 255 + 0.5, clamp, truncate ran on the device)."""
+    from PIL import Image
+    arr = np.asarray(pixels)
+    Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(path)
 
 
 def save_image(tensor, path):

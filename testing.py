@@ -40,7 +40,11 @@ def test(args, test_loader=None):
     with torch.no_grad():
         for i, (image_test, image_name) in enumerate(test_loader):
             image_test = utils.cuda(image_test, args.gpu_ids)
-            prediction = F.argmax_index(F.softmax2d(Gsi(image_test))).cpu().numpy()
+            logits = Gsi(image_test)
+            if F.FUSE_PREDICT[0]:            # softmax -> argmax on the net's own output: one launch, a uint8 map (identity resize)
+                prediction = F.predict_labels(logits, logits.shape[2:])[0].cpu().numpy()
+            else:
+                prediction = F.argmax_index(F.softmax2d(logits)).cpu().numpy()
             for j in range(prediction.shape[0]):
                 utils.colorize_mask(prediction[j], args.dataset).save(os.path.join(out, image_name[j] + '.png'))
             print('Epoch-', str(i + 1), ' Done!')

@@ -46,30 +46,44 @@ def validation(args, val_loader=None):
     except Exception:
         print(' [*] No checkpoint!')
 
-    seg = lambda x: F.softmax2d(F.upsample_bilinear(Gsi(x), size))                 # Gsi -> interp -> Softmax2d
+    fused = F.FUSE_PREDICT[0]                     # SSCG_FUSE_PREDICT=0: the chain of separate passes (same bits)
+    soft = lambda lg: F.softmax2d(F.upsample_bilinear(lg, size))                    # interp -> Softmax2d
+    # Gsi's logits -> interp -> Softmax2d -> argmax: uint8 label maps from one launch, or the int64 maps of the separate passes
+    labels = (lambda lg: F.predict_labels(lg, size)[0].cpu().numpy()) if fused else (lambda lg: F.argmax_index(soft(lg)).cpu().numpy())
     img = lambda x: F.act_fwd(F.to_nhwc(F.upsample_bilinear(Gis(x), size)), F.ACT_TANH)   # Gis -> interp -> Tanh
     Gsi.eval()
     with torch.no_grad():
         for i, (image_test, real_segmentation, image_name) in enumerate(val_loader):
             image_test, real_segmentation = utils.cuda([image_test, real_segmentation], args.gpu_ids)
-            seg_map = seg(image_test)
-            prediction = F.argmax_index(seg_map).cpu().numpy()
+            logits = Gsi(image_test)
+            prediction = labels(logits)
             if not semi:
                 out = _mk(args.validation_dir, 'supervised')
                 for j in range(prediction.shape[0]):
                     utils.colorize_mask(prediction[j], args.dataset).save(os.path.join(out, image_name[j] + '.png'))
             else:
-                fake_img = img(seg_map)                                                                   # :108-110
-                fake_img_from_labels = img(utils.make_one_hot(real_segmentation, args.dataset, args.gpu_ids))   # :112-114
-                regenerated = F.argmax_index(seg(fake_img_from_labels)).cpu().numpy()                     # :115-120
-                fake_img = F.to_nchw(fake_img).cpu() * 0.5 + 0.5                                          # undo Normalize(.5, .5)
-                fake_img_from_labels = F.to_nchw(fake_img_from_labels).cpu() * 0.5 + 0.5
+                onehot = utils.make_one_hot(real_segmentation, args.dataset, args.gpu_ids)
                 base = os.path.join(args.validation_dir, 'unsupervised')
+                if fused:
+                    # Gis -> interp -> Tanh -> un-normalise -> save_image's uint8 pixels in one launch; the fp32 image only where it
+                    # goes back into Gsi
+                    fake_img = F.predict_image(Gis(soft(logits)), size, want_float=False)[1].cpu().numpy()             # :108-110
+                    from_labels, fake_img_from_labels = F.predict_image(Gis(onehot), size)                                # :112-114
+                    fake_img_from_labels = fake_img_from_labels.cpu().numpy()
+                    regenerated = labels(Gsi(from_labels))                                                                # :115-120
+                    save = utils.save_image_u8
+                else:
+                    fake_img = img(soft(logits))
+                    fake_img_from_labels = img(onehot)
+                    regenerated = labels(Gsi(fake_img_from_labels))
+                    fake_img = F.to_nchw(fake_img).cpu() * 0.5 + 0.5                                      # undo Normalize(.5, .5)
+                    fake_img_from_labels = F.to_nchw(fake_img_from_labels).cpu() * 0.5 + 0.5
+                    save = utils.save_image
                 for j in range(prediction.shape[0]):
                     utils.colorize_mask(prediction[j], args.dataset).save(os.path.join(_mk(base, 'generated_labels'), image_name[j] + '.png'))
                     utils.colorize_mask(regenerated[j], args.dataset).save(os.path.join(_mk(base, 'regenerated_labels'), image_name[j] + '.png'))
-                    utils.save_image(fake_img[j], os.path.join(_mk(base, 'regenerated_image'), image_name[j] + '.jpg'))
-                    utils.save_image(fake_img_from_labels[j], os.path.join(_mk(base, 'image_from_labels'), image_name[j] + '.jpg'))
+                    save(fake_img[j], os.path.join(_mk(base, 'regenerated_image'), image_name[j] + '.jpg'))
+                    save(fake_img_from_labels[j], os.path.join(_mk(base, 'image_from_labels'), image_name[j] + '.jpg'))
             print('Epoch-', str(i + 1), ' Done!')
     print('The iou of the resulting segment maps: ', str(best_iou))
     return best_iou
