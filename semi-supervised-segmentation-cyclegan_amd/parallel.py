@@ -60,6 +60,7 @@ class DataParallel:
             for t in list(net.parameters()) + list(net.buffers()):
                 if getattr(t, "_sscg_grad", None) is None:   # arena-resident parameters were broadcast above
                     dist.broadcast(t.data, 0)
+        _invalidate_loose_copies()
 
     def attach_one(self, opt, nets):
         """Single-optimiser drivers (supervised_model)."""
@@ -70,6 +71,7 @@ class DataParallel:
             for t in list(net.parameters()) + list(net.buffers()):
                 if getattr(t, "_sscg_grad", None) is None:
                     dist.broadcast(t.data, 0)
+        _invalidate_loose_copies()
 
     def sync_grads(self, opt):
         allreduce_flat(opt.grad)
@@ -271,12 +273,24 @@ def preflight(dp, batch_per_rank, shared_gpu_ok=False):
     return rows
 
 
+def _invalidate_loose_copies():
+    """The weights no arena owns (the frozen nets) were broadcast through `.data` - no `_version` moved: their cached operand
+    copies are invalidated through the global weight epoch."""
+    from . import functional as F
+    F.bump_weight_epoch()
+
+
 def _refresh_operand_copies(opt):
-    """The optimiser's operand copies of its parameters (bf16 shadow / split planes) follow a broadcast of the arena."""
+    """The optimiser's operand copies of its parameters follow a broadcast of the arena: the bf16 shadow / split planes are rebuilt
+    here; the copies cached on the weights (transposed, padded - a model that ran a pass before it was attached has them) are
+    invalidated through the optimiser's epoch, as after an update: the broadcast wrote the arena through a raw view, so no
+    parameter's `_version` moved."""
+    from . import functional as F
     if opt.arena16 is not None:
         opt.refresh_shadow()
     if getattr(opt, "arena_x3", None) is not None:
         opt.refresh_split()
+    F.bump_weight_epoch(getattr(opt, "_epoch", None))
 
 
 def allreduce_flat(flat, chunk=CHUNK_ELEMS, wait=True):
