@@ -102,6 +102,26 @@ int sscg_conv2d_fwd_stats(const sscg_conv_desc* d, const void* x, const void* w,
 int sscg_norm_stats_from_conv(const sscg_conv_desc* d, const void* stats, int G, int64_t L, float eps, float* mean, float* rstd,
                               float* running_mean, float* running_var, float momentum, void* stream);
 
+/* Eval-mode nn.Conv2d -> nn.BatchNorm2d [+ residual] -> activation as ONE launch (added to ABI v18; see below): the DeepLab units of
+ * arch/generators.py:345-365 as model.py:555-574 (evaluate()), validation.py and testing.py run them, under .eval() and
+ * torch.no_grad().  There the normalisation is a per-channel affine known before the conv starts, and the conv's store phase applies it:
+ *   y = act(((conv(x, w) + bias) - running_mean) * rstd * gamma + beta + residual),  rstd = (float)(1 / sqrt((double)running_var + eps))
+ * - bit for bit what sscg_conv2d_fwd (act NONE), sscg_rstd_from_var and sscg_norm_apply compute in three launches, without the round trip
+ * of the conv's output through memory (with bf16 tensors the conv's result is rounded to bf16 in front of the affine, as the stored map
+ * is).  d->act / d->slope is the activation BEHIND the norm (NONE / RELU / LRELU), not a conv activation.  gamma and beta: both or
+ * neither.  residual: NULL or [N][P][Q][K] in y's dtype.  ws: sscg_conv2d_fwd_workspace(d) bytes (the split-K plan is the plain
+ * forward's; the tail's reduction carries the affine).  sscg_conv2d_fwd_affine_applies: 1 for fp32 tensors with w = SSCG_BF16X3 split
+ * planes (C % 32 == 0, K % 4 == 0, K > 32) and for bf16 tensors (C % 64 == 0, K % 8 == 0, K > 32, y bf16); 0 for the exact-fp32 kernel
+ * (which also serves the 3-channel stems), the thin 1x1 kernels, the heads' 32-column tile classes and tanh - the caller then runs the
+ * separate passes.  Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, gamma without beta), SSCG_ERR_UNSUPPORTED (applies ==
+ * 0), SSCG_ERR_WORKSPACE. */
+/* (The two entries are an addition: no existing entry, struct or code changes meaning, so SSCG_ABI_VERSION stays 18 and a caller
+ * built against the v18 header keeps working; a binding that needs them finds them by name.) */
+int sscg_conv2d_fwd_affine_applies(const sscg_conv_desc* d);
+int sscg_conv2d_fwd_affine(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, const float* running_mean,
+                           const float* running_var, float eps, const float* gamma, const float* beta, const void* residual, void* y,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* PixelDiscriminator's front half as ONE launch (arch/discriminators.py:70-73: nn.Conv2d(input_nc, ndf, 1) -> nn.LeakyReLU(0.2) ->
  * nn.Conv2d(ndf, 2 ndf, 1) [-> the statistics of the InstanceNorm / BatchNorm layer at :73]).  `d` describes the SECOND conv (C = 64
  * source channels, 1x1, stride 1, no padding, fp32 tensors, w = its SSCG_BF16X3 split planes); `xf` [N*H*W][cin] fp32 is the FIRST

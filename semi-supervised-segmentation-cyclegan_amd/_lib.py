@@ -49,6 +49,8 @@ SIGNATURES = {
     "sscg_conv2d_fwd_stats_workspace": (_sz, [_dp]),
     "sscg_conv2d_fwd_stats": (_i, [_dp, _p, _p, _p, _p, _i, _i64, _p, _sz, _p, _sz, _p]),
     "sscg_norm_stats_from_conv": (_i, [_dp, _p, _i, _i64, _f, _p, _p, _p, _p, _f, _p]),
+    "sscg_conv2d_fwd_affine_applies": (_i, [_dp]),
+    "sscg_conv2d_fwd_affine": (_i, [_dp, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _sz, _p]),
     "sscg_conv2d_front_applies": (_i, [_dp, _i]),
     "sscg_conv2d_front_fwd": (_i, [_dp, _p, _i, _p, _p, _f, _p, _p, _p, _p, _i, _i64, _p, _sz, _p]),
     "sscg_conv2d_dgrad_workspace": (_sz, [_dp]),

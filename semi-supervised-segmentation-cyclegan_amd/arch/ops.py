@@ -246,6 +246,16 @@ def conv_norm_act(conv, norm, x, act=ACT_NONE, slope=0.0, residual=None, reflect
     """The reference's fusion unit (arch/ops.py:40-57; Bottleneck conv+bn pairs, arch/generators.py:345-365):
     conv -> norm [+ residual] -> activation.  The norm's batch statistics come out of the conv's epilogue when the library
     can fuse them (sscg_conv2d_fwd_stats); the output is then read once (normalise) instead of twice."""
+    if (F.FUSE_EVAL_NORM[0] and isinstance(norm, BatchNorm2d) and not norm.training and isinstance(conv, Conv2d) and x.is_cuda
+            and not (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or norm.weight.requires_grad
+                                                  or (residual is not None and residual.requires_grad)))):
+        # inference: the normalisation is a per-channel affine known before the conv starts - the conv's store phase applies it
+        # (one launch; no num_batches_tracked step in eval mode, as in BatchNorm2d.forward)
+        pad, mode = (reflect, PAD_REFLECT) if reflect else (conv.padding, PAD_ZEROS)
+        if (not (reflect and conv.padding != 0)
+                and F.conv_bn_eval_applies(x, conv.weight, conv.stride, pad, conv.dilation, mode, act, slope, conv.head)):
+            return F.conv_bn_eval_act(x, conv.weight, conv.bias, norm.running_mean, norm.running_var, norm.weight, norm.bias, residual,
+                                      conv.stride, pad, conv.dilation, mode, norm.eps, act, slope, conv.head)
     spec = norm.stat_spec() if (F.FUSE_STATS[0] and isinstance(conv, Conv2d)) else None
     if spec is None:
         y = conv(x, reflect=reflect) if isinstance(conv, Conv2d) else conv(x)

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "sscg_internal.h"
 #include "reduce_common.h"
+#include "bn_fold.h"
 #include <type_traits>
 
 namespace {
@@ -70,6 +71,14 @@ struct K16Params {
     int bn_L, bn_G, bn_chunks, bn_act;
     float bn_slope;
     FastDiv div_tn, div_hw, div_w, div_gl;   // by tiles_n, OH * OW, OW, stat_L / bn_L (launch16): tile and row decode without integer divisions (~35 VALU operations each)
+    // AFF instances only (sscg_conv2d_fwd_affine): the eval-mode BatchNorm behind this forward, applied in the store phase (bn_fold.h);
+    // `act` / `slope` are then the activation behind the norm.  Last in the struct: no other instance's argument offsets move.
+    const float* __restrict__ af_mean;   // running_mean [Ng]
+    const float* __restrict__ af_var;    // running_var [Ng]
+    const float* __restrict__ af_gamma;  // [Ng] or null
+    const float* __restrict__ af_beta;
+    const bf16* __restrict__ af_res;     // [M][Ng] added behind the affine, or null
+    float af_eps;
 };
 
 // activations of the epilogue in every class but the heads' (32 columns): none / ReLU / LeakyReLU.  tanh - the ResNet generators' 3- and
@@ -96,8 +105,12 @@ __device__ __forceinline__ void pin(bf16x8& v) { asm volatile("" : "+v"(v)); }  
 // BS: the data gradient also takes the backward sums of the normalisation layer in front, in its store phase (its own instances: the
 // sums' code and registers otherwise ride in every data-gradient launch; a BS instance carries no fan-in code - bf16 tensors never
 // ask for both)
-template <int MODE, int WM, int WN, int TM, int TN, int NSTAGE, bool BS = false>
+// AFF: the forward of an eval-mode conv -> BatchNorm [+ residual] -> activation unit with bf16 tensors (instances of their own).  The
+// separate passes round the conv's output to bf16 before the norm reads it: so does the staged tile here, and the store phase
+// widens it again in front of the affine - both paths agree bit for bit.
+template <int MODE, int WM, int WN, int TM, int TN, int NSTAGE, bool BS = false, bool AFF = false>
 __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && TM * TN == 2) ? 4 : 2) void conv16_kernel(K16Params p) {
+    static_assert(!AFF || (MODE == MODE_FWD && !BS && WN * TN * 32 >= 64), "folded BatchNorm: plain forwards of the staged tile classes");
     constexpr int NT = WM * WN * 64;          // 4 waves (256 threads) or 8 waves (512)
     constexpr int BM = WM * TM * 32;
     constexpr int BN = WN * TN * 32;
@@ -469,7 +482,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && TM * TN == 2) ? 4 : 
                     }
                     typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
                     typedef float f32x2_t __attribute__((ext_vector_type(2)));
-                    const f32x2_t pr = {PLAIN ? pre0 : k16_act(pre0, p.act, p.slope), PLAIN ? pre1 : k16_act(pre1, p.act, p.slope)};
+                    // (AFF: the launch's activation belongs behind the norm - the staged tile is the conv's output)
+                    const f32x2_t pr = {(PLAIN || AFF) ? pre0 : k16_act(pre0, p.act, p.slope), (PLAIN || AFF) ? pre1 : k16_act(pre1, p.act, p.slope)};
                     const bf16x2_t pk = __builtin_convertvector(pr, bf16x2_t);      // RNE, v_cvt_pk_bf16_f32
                     ob[(ro / 2) * OLD + j * 32] = __builtin_bit_cast(uint32_t, pk);
                 }
@@ -486,7 +500,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && TM * TN == 2) ? 4 : 
             }
         }
         };
-        if (!p.bias && p.act == SSCG_ACT_NONE) stage_tile(std::true_type{});
+        if (!p.bias && (AFF || p.act == SSCG_ACT_NONE)) stage_tile(std::true_type{});
         else stage_tile(std::false_type{});
         __syncthreads();
         if (want_stats && tid < BN && n0 + tid < p.Ng) {
@@ -599,6 +613,54 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && TM * TN == 2) ? 4 : 
                 }
             }
         }
+        // Eval-mode BatchNorm [+ residual] + activation of the staged bf16 rows (AFF): the four per-channel vectors of the thread's eight
+        // channels are hoisted, rstd is formed here (no sscg_rstd_from_var launch), the residual's 16-byte row segments of every pass
+        // are requested up front like the addend's.  Per element the operations of norm.hip's apply pass in their order (bn_fold.h).
+        constexpr int NAF = AFF ? NPS : 1;
+        static_assert(!AFF || NPS <= 2, "folded BatchNorm: the classes the plan uses (sscg_conv16_affine_applies)");
+        uint4 fr0[NAF], fr1[NAF];
+        float fmu[8], frs[8], fga[8], fbe[8];
+        const bool f_g = AFF && p.af_gamma != nullptr, f_r = AFF && p.af_res != nullptr;
+        if constexpr (AFF) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { fmu[e] = 0.f; frs[e] = 0.f; fga[e] = 1.f; fbe[e] = 0.f; }
+            if (n < p.Ng) {                     // (host: Ng % 8 == 0)
+                float fv[8];
+                ld8<float>(p.af_mean + n, fmu);
+                ld8<float>(p.af_var + n, fv);
+                if (f_g) { ld8<float>(p.af_gamma + n, fga); ld8<float>(p.af_beta + n, fbe); }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) frs[e] = sscg_bn_rstd(fv[e], p.af_eps);
+            }
+#pragma unroll
+            for (int ps = 0; ps < NAF; ++ps) {
+                const int m = m0 + 2 * (tid / TPR + ps * RPP);
+                fr0[ps] = uint4{0u, 0u, 0u, 0u}; fr1[ps] = uint4{0u, 0u, 0u, 0u};
+                if (f_r && (tid / TPR + ps * RPP) < BM / 2 && n < p.Ng) {
+                    if (m < p.M) fr0[ps] = *reinterpret_cast<const uint4*>(p.af_res + (size_t)m * p.Ng + n);
+                    if (m + 1 < p.M) fr1[ps] = *reinterpret_cast<const uint4*>(p.af_res + (size_t)(m + 1) * p.Ng + n);
+                }
+            }
+        }
+        auto fold8 = [&](const uint4& v, const uint4& r) -> uint4 {
+            typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+            typedef float f32x2_t __attribute__((ext_vector_type(2)));
+            const uint32_t vw[4] = {v.x, v.y, v.z, v.w}, rw[4] = {r.x, r.y, r.z, r.w};
+            uint32_t ow[4];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                f32x2_t o;
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    const int e = 2 * w + hh;
+                    const float xx = __uint_as_float(hh ? (vw[w] & 0xffff0000u) : (vw[w] << 16));
+                    const float rr = __uint_as_float(hh ? (rw[w] & 0xffff0000u) : (rw[w] << 16));
+                    o[hh] = k16_act(sscg_bn_fold(xx, fmu[e], frs[e], fga[e], fbe[e], f_g, rr, f_r), p.act, p.slope);
+                }
+                ow[w] = __builtin_bit_cast(uint32_t, __builtin_convertvector(o, bf16x2_t));      // RNE, as the apply pass stores
+            }
+            return uint4{ow[0], ow[1], ow[2], ow[3]};
+        };
         auto add2 = [](uint32_t v, uint32_t a) -> uint32_t {       // two bf16 sums, each rounded to nearest even (= the add kernel's)
             typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
             typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -622,6 +684,10 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && TM * TN == 2) ? 4 : 
             if (joins) {
                 lo.x = add2(lo.x, ad0[ps % NAD].x); lo.y = add2(lo.y, ad0[ps % NAD].y); lo.z = add2(lo.z, ad0[ps % NAD].z); lo.w = add2(lo.w, ad0[ps % NAD].w);
                 hi.x = add2(hi.x, ad1[ps % NAD].x); hi.y = add2(hi.y, ad1[ps % NAD].y); hi.z = add2(hi.z, ad1[ps % NAD].z); hi.w = add2(hi.w, ad1[ps % NAD].w);
+            }
+            if constexpr (AFF) {
+                lo = fold8(lo, fr0[ps % NAF]);
+                hi = fold8(hi, fr1[ps % NAF]);
             }
             if (bsp) {
                 if (m < gb) bsp_row(lo, xr0[ps % NAD]);
@@ -743,6 +809,25 @@ __global__ __launch_bounds__(256) void k16_reduce_kernel(const float* __restrict
     store_out(y, i, sscg_act(s, act, slope), out_bf16);
 }
 
+// the reduction of a folded-BatchNorm launch's tail (AFF instances, bf16 tensors): per element what k16_reduce_kernel followed by
+// sscg_norm_apply computes - the sum is rounded to bf16 (the conv's stored output) and widened again in front of the affine
+__global__ __launch_bounds__(256) void k16_reduce_affine_kernel(const float* __restrict__ part, const float* __restrict__ bias, bf16* __restrict__ y,
+                                                                 size_t n, int Ng, int splits, int act, float slope, const float* __restrict__ mean,
+                                                                 const float* __restrict__ var, float eps, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, const bf16* __restrict__ res) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < splits; ++k) s += part[(size_t)k * n + i];
+    if (bias) s += bias[(int)(i % Ng)];
+    const int c = (int)(i % Ng);
+    const float x = (float)(bf16)s;
+    const float v = sscg_bn_fold(x, mean[c], sscg_bn_rstd(var[c], eps), gamma ? gamma[c] : 1.f, gamma ? beta[c] : 0.f, gamma != nullptr,
+                                 res ? (float)res[i] : 0.f, res != nullptr);
+    y[i] = (bf16)k16_act(v, act, slope);
+}
+
 // ---- host-side plan
 // tile classes: block tile, waves, copy stages (k-tiles in LDS).  The deep classes hold 2-3 tiles in flight per workgroup.
 enum { CFG_128x128 = 0, CFG_64x64 = 1, CFG_128x32 = 2, CFG_128x64 = 3, CFG_128x128_W8 = 4, CFG_256x128_W8 = 5, NCFG16 = 6 };
@@ -826,7 +911,7 @@ size_t split16_bytes(const K16Split& sp, long M, int Ng) {
     return sp.splits > 1 ? (size_t)sp.splits * (M - sp.m_tail0) * Ng * sizeof(float) : 0;
 }
 
-template <int MODE, int WM, int WN, int TM, int TN, int NSTAGE, bool BS = false>
+template <int MODE, int WM, int WN, int TM, int TN, int NSTAGE, bool BS = false, bool AFF = false>
 int launch16(const K16Params& p0, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
     constexpr int BN = WN * TN * 32;
@@ -844,7 +929,7 @@ int launch16(const K16Params& p0, hipStream_t st) {
     if (stage > smem) smem = stage;
     const size_t stage_f = (BN >= 64 && p.splits > 1) ? (size_t)BM * (BN + 4) * sizeof(float) : 0;      // fp32 tile of a split-K tail's partial workgroups
     if (stage_f > smem) smem = stage_f;
-    auto kern = conv16_kernel<MODE, WM, WN, TM, TN, NSTAGE, BS>;
+    auto kern = conv16_kernel<MODE, WM, WN, TM, TN, NSTAGE, BS, AFF>;
     SSCG_ENSURE_SMEM((kern), smem);
     if (p.splits <= 1) { p.full_tiles = p.tiles; p.m_tail0 = p.M; }
     const int grid = p.full_tiles + (p.tiles - p.full_tiles) * p.splits;
@@ -854,6 +939,13 @@ int launch16(const K16Params& p0, hipStream_t st) {
         const size_t n = (size_t)(p.M - p.m_tail0) * p.Ng;
         const size_t esz = p.out_bf16 ? 2 : 4;
         void* yt = reinterpret_cast<char*>(p.dst) + (size_t)p.m_tail0 * p.Ng * esz;
+        if constexpr (AFF) {
+            hipLaunchKernelGGL(k16_reduce_affine_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, st, p.part, p.bias, reinterpret_cast<bf16*>(yt), n, p.Ng,
+                               p.splits, p.act, p.slope, p.af_mean, p.af_var, p.af_eps, p.af_gamma, p.af_beta,
+                               p.af_res ? p.af_res + (size_t)p.m_tail0 * p.Ng : nullptr);
+            SSCG_LAUNCH_CHECK();
+            return SSCG_OK;
+        }
         if (p.xstats)
             return launch_split_reduce_stats(p.part, p.bias, yt, p.out_bf16, p.M - p.m_tail0, p.Ng, p.splits, p.act, p.slope, p.xstats, st);
         hipLaunchKernelGGL(k16_reduce_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, st, p.part, p.bias, yt, p.out_bf16, n, p.Ng,
@@ -884,6 +976,16 @@ int dispatch16(const K16Params& p, int tuning, hipStream_t st) {
         case CFG_128x128_W8: return launch16<MODE, 2, 4, 2, 1, 2>(p, st);      // 8 waves of 64x32: 4 waves per SIMD with 2 workgroups per CU
         case CFG_256x128_W8: return launch16<MODE, 4, 2, 2, 2, 2>(p, st);      // 8 waves of 64x64: 96 KB of LDS, one workgroup per CU
         default: return SSCG_ERR_BAD_ARG;
+    }
+}
+
+// the forward with an eval-mode BatchNorm folded into the store phase: the staged classes the plan uses
+int dispatch16_affine(const K16Params& p, int tuning, hipStream_t st) {
+    switch (choose16(p.M, p.Ng, p.Ktot, tuning)) {
+        case CFG_64x64: return launch16<MODE_FWD, 2, 2, 1, 1, 2, false, true>(p, st);
+        case CFG_128x64: return launch16<MODE_FWD, 2, 2, 2, 1, 2, false, true>(p, st);
+        case CFG_128x128_W8: return launch16<MODE_FWD, 2, 4, 2, 1, 2, false, true>(p, st);
+        default: return SSCG_ERR_UNSUPPORTED;
     }
 }
 
@@ -955,6 +1057,36 @@ int sscg_conv16_fwd(const sscg_conv_desc* d, const void* x, const void* w, const
     p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
     p.part = reinterpret_cast<float*>(ws);
     return dispatch16<MODE_FWD>(p, d->tuning, st);
+}
+
+// Eval-mode conv -> BatchNorm [+ residual] -> activation as ONE launch (sscg_conv2d_fwd_affine; conv_split.hip's twin): bf16 in, bf16
+// out, whole 16-byte row segments (K % 8 == 0), the three staged classes the plan chooses.  The split-K plan is the plain forward's.
+bool sscg_conv16_affine_applies(const sscg_conv_desc* d) {
+    if (!sscg_conv16_fwd_applies(d) || d->y_dtype != SSCG_BF16 || (d->K & 7) || d->act == SSCG_ACT_TANH) return false;
+    const int cfg = choose16((long)d->N * d->P * d->Q, d->K, d->R * d->S * d->C, d->tuning);
+    return cfg == CFG_64x64 || cfg == CFG_128x64 || cfg == CFG_128x128_W8;
+}
+
+int sscg_conv16_fwd_affine(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, const sscg_bn_fold_args& bn, void* y,
+                           void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!sscg_conv16_affine_applies(d)) return SSCG_ERR_UNSUPPORTED;
+    K16Params p = {};
+    p.src = reinterpret_cast<const bf16*>(x); p.wgt = reinterpret_cast<const bf16*>(w); p.bias = bias; p.dst = y;
+    p.src_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->C * sizeof(bf16));
+    p.wgt_bytes = (unsigned)((size_t)d->K * d->R * d->S * d->C * sizeof(bf16));
+    p.out_bf16 = 1;
+    p.M = d->N * d->P * d->Q; p.Ng = d->K; p.Cs = d->C; p.Ktot = d->R * d->S * d->C;
+    p.SH = d->H; p.SW = d->W; p.OH = d->P; p.OW = d->Q;
+    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
+    p.pad_mode = d->pad_mode; p.act = d->act; p.slope = d->slope;
+    p.af_mean = bn.mean; p.af_var = bn.var; p.af_gamma = bn.gamma; p.af_beta = bn.beta; p.af_eps = bn.eps;
+    p.af_res = reinterpret_cast<const bf16*>(bn.residual);
+    dense_taps(p);
+    K16Split sp = plan16(p.M, p.Ng, p.Ktot, d->tuning, 0);
+    if (sp.splits > 1 && (!ws || ws_bytes < split16_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
+    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
+    p.part = reinterpret_cast<float*>(ws);
+    return dispatch16_affine(p, d->tuning, st);
 }
 
 // backward sums of the normalisation layer in front from this launch's epilogue (conv_split.hip sscg_convs_bsums_geometry)

@@ -25,6 +25,7 @@
 // boundaries (wave-uniform branch every Cs/BK tiles) and the per-tile loader work is a pointer bump.
 #include "common.h"
 #include "sscg_internal.h"
+#include "bn_fold.h"
 #include "reduce_common.h"
 
 namespace {
@@ -884,6 +885,30 @@ extern "C" int sscg_conv2d_fwd_stats(const sscg_conv_desc* d, const void* x, con
     // rows that went through split-K: their statistics are produced by the split reduction itself (records after the main ones)
     double* xr = sp.xrec > 0 ? reinterpret_cast<double*>(reinterpret_cast<char*>(stats) + sp.main_bytes) : nullptr;
     return conv_fwd_impl(d, x, w, bias, y, reinterpret_cast<double*>(stats), (long)L, xr, ws, ws_bytes, stream);
+}
+
+// Eval-mode conv -> BatchNorm [+ residual] -> activation as one launch (arch/generators.py:345-365 under model.py:555-574, validation.py,
+// testing.py).  Served by the split and the bf16 families' staged tile classes; the exact-fp32 kernel, the thin 1x1 kernels and the
+// heads' 32-column classes are not (the caller runs the separate passes).
+static bool fwd_affine_applies(const sscg_conv_desc* d) {
+    if (check_desc(d) != SSCG_OK || sscg_thin1x1_fwd_applies(d)) return false;
+    if (sscg_conv16_fwd_applies(d)) return sscg_conv16_affine_applies(d);
+    return sscg_convs_affine_applies(d);
+}
+
+extern "C" int sscg_conv2d_fwd_affine_applies(const sscg_conv_desc* d) { return d && fwd_affine_applies(d) ? 1 : 0; }
+
+extern "C" int sscg_conv2d_fwd_affine(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, const float* running_mean,
+                                      const float* running_var, float eps, const float* gamma, const float* beta, const void* residual,
+                                      void* y, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!x || !w || !running_mean || !running_var || !y) return SSCG_ERR_BAD_ARG;
+    if ((gamma != nullptr) != (beta != nullptr)) return SSCG_ERR_BAD_ARG;
+    if (!fwd_affine_applies(d)) return SSCG_ERR_UNSUPPORTED;
+    const sscg_bn_fold_args bn = {running_mean, running_var, gamma, beta, residual, eps};
+    if (sscg_conv16_fwd_applies(d)) return sscg_conv16_fwd_affine(d, x, w, bias, bn, y, ws, ws_bytes, (hipStream_t)stream);
+    return sscg_convs_fwd_affine(d, x, w, bias, bn, y, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // PixelDiscriminator's front half in one launch (arch/discriminators.py:70-73): y = conv2(lrelu(conv1(xf))) [+ conv2's bias] and - with

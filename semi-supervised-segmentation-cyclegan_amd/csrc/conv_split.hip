@@ -25,6 +25,7 @@
 #include "common.h"
 #include "sscg_internal.h"
 #include "reduce_common.h"
+#include "bn_fold.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -106,6 +107,14 @@ struct KsParams {
     float* __restrict__ fr_h1;           // [M][Cs] or null: the front conv's output is ALSO written (a backward pass that wants it stored)
     FastDiv div_tn, div_gl;              // by tiles_n; by stat_L / bn_L (whichever the launch uses)
     FastDiv div_hw, div_w;               // by OH * OW and by OW (launch_ks): a row's (image, y, x) without integer divisions (~30 VALU operations each)
+    // AFF instances only (sscg_conv2d_fwd_affine): the eval-mode BatchNorm behind this forward, applied in the store phase (bn_fold.h);
+    // `act` / `slope` are then the activation behind the norm.  Last in the struct: no other instance's argument offsets move.
+    const float* __restrict__ af_mean;   // running_mean [Ng]
+    const float* __restrict__ af_var;    // running_var [Ng]
+    const float* __restrict__ af_gamma;  // [Ng] or null
+    const float* __restrict__ af_beta;
+    const float* __restrict__ af_res;    // [M][Ng] added behind the affine, or null
+    float af_eps;
 };
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -120,8 +129,11 @@ __device__ __forceinline__ float ks_act(float v, int act, float slope) {
     return v > 0.f ? v : neg;
 }
 
-template <int MODE, int WM, int WN, int TM, int TN, int CIN = 0>
+// AFF: the forward of an eval-mode conv -> BatchNorm [+ residual] -> activation unit (instances of their own: the training step's
+// kernels carry none of it)
+template <int MODE, int WM, int WN, int TM, int TN, int CIN = 0, bool AFF = false>
 __global__ __launch_bounds__(WM * WN * 64, ((KS_LB4 && TM * TN == 1) ? 4 : 2)) void convs_kernel(KsParams p) {      // (HIP: the second figure is WAVES PER SIMD)
+    static_assert(!AFF || (MODE == MODE_FWD && CIN == 0 && WN * TN * 32 >= 64), "folded BatchNorm: plain forwards of the staged tile classes");
     constexpr int NT = WM * WN * 64;
     constexpr int BM = WM * TM * 32;
     constexpr int BN = WN * TN * 32;
@@ -891,6 +903,55 @@ __global__ __launch_bounds__(WM * WN * 64, ((KS_LB4 && TM * TN == 1) ? 4 : 2)) v
         const float neg_scale = ep.bn_act == SSCG_ACT_RELU ? 0.f : (ep.bn_act == SSCG_ACT_LRELU ? ep.bn_slope : 1.f);
         // (a partial tile of a split-K tail goes to its slice of the workspace, rows counted from the tail's first)
         float* const obase = partial ? ep.part + ((long)split * (ep.M - ep.m_tail0) - ep.m_tail0) * (long)ep.Ng : ep.dst;
+        if constexpr (AFF) {
+            // Eval-mode BatchNorm [+ residual] + activation of the raw staged tile: y = act(((conv + bias) - mean) * rstd * gamma + beta
+            // + residual), the operations of the separate passes in their order (bn_fold.h).  The four per-channel vectors are hoisted
+            // like the bias; rstd is formed here, once per thread for its four channels (no sscg_rstd_from_var launch).
+            if (n < ep.Ng && partial) {          // a split-K tail's partial sums: the reduction carries the affine (ks_reduce_affine_kernel)
+#pragma unroll
+                for (int ps = 0; ps < BM / RPP; ++ps) {
+                    const int r = tid / TPR + ps * RPP;
+                    const int m = m0 + r;
+                    if (m >= ep.M) break;
+                    *reinterpret_cast<f32x4*>(obase + (size_t)m * ep.Ng + n) = *reinterpret_cast<const f32x4*>(ot + r * OLD + c4);
+                }
+            } else if (n < ep.Ng) {
+                const bool has_b = ep.bias != nullptr, has_g = ep.af_gamma != nullptr, has_r = ep.af_res != nullptr;
+                f32x4 b4 = 0.f, fg = 1.f, fb = 0.f, frs;
+                if (has_b) b4 = *reinterpret_cast<const f32x4*>(ep.bias + n);
+                const f32x4 fmu = *reinterpret_cast<const f32x4*>(ep.af_mean + n);
+                const f32x4 fvar = *reinterpret_cast<const f32x4*>(ep.af_var + n);
+                if (has_g) { fg = *reinterpret_cast<const f32x4*>(ep.af_gamma + n); fb = *reinterpret_cast<const f32x4*>(ep.af_beta + n); }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) frs[e] = sscg_bn_rstd(fvar[e], ep.af_eps);
+                // the residual of FOUR rows is requested before the first is used (the `joins` loop below: taken row by row the store
+                // phase waits one memory latency per row)
+                constexpr int PSN = BM / RPP;
+                static_assert(PSN % 4 == 0, "rows per thread");
+#pragma unroll 1
+                for (int h = 0; h < PSN; h += 4) {
+                    f32x4 rv[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int m = m0 + tid / TPR + (h + q) * RPP;
+                        rv[q] = 0.f;
+                        if (has_r && m < ep.M) rv[q] = *reinterpret_cast<const f32x4*>(ep.af_res + (size_t)m * ep.Ng + n);
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int r = tid / TPR + (h + q) * RPP;
+                        const int m = m0 + r;
+                        if (m >= ep.M) break;
+                        f32x4 v = *reinterpret_cast<const f32x4*>(ot + r * OLD + c4);
+                        if (has_b) v += b4;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            v[e] = ks_act(sscg_bn_fold(v[e], fmu[e], frs[e], fg[e], fb[e], has_g, rv[q][e], has_r), ep.act, ep.slope);
+                        *reinterpret_cast<f32x4*>(ep.dst + (size_t)m * ep.Ng + n) = v;
+                    }
+                }
+            }
+        } else {
         if (n < ep.Ng && !joins) {               // (Ng % 4 == 0: a 16-byte piece is inside the row or outside it)
             // bias and activation of the raw staged tile (the heads' class applied them before staging; a partial tile carries neither)
             const bool has_b = !ANY_NG && !partial && ep.bias != nullptr;
@@ -953,6 +1014,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((KS_LB4 && TM * TN == 1) ? 4 : 2)) v
                 }
             }
         }
+        }
         if (want_bsums) {
             __syncthreads();                    // the staged tile is dead: its LDS takes the row lanes' partial sums [RPP][BN][4]
             f32x4* ps4 = reinterpret_cast<f32x4*>(smem_raw);
@@ -995,6 +1057,29 @@ __global__ __launch_bounds__(256) void ks_reduce_kernel(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = sscg_act(s[e] + (bias ? bias[c + e] : 0.f), act, slope);
     if (addend) o += *reinterpret_cast<const f32x4*>(addend + i);
+    *reinterpret_cast<f32x4*>(y + i) = o;
+}
+
+// the reduction of a folded-BatchNorm launch's tail (AFF instances): y[i] = act(bn(sum_s part[s][i] + bias) + residual), per element
+// what ks_reduce_kernel followed by sscg_norm_apply computes
+__global__ __launch_bounds__(256) void ks_reduce_affine_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ y,
+                                                                size_t n, int Ng, int splits, int act, float slope, const float* __restrict__ mean,
+                                                                const float* __restrict__ var, float eps, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, const float* __restrict__ res) {
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= n) return;
+    f32x4 s = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < splits; ++k) s += *reinterpret_cast<const f32x4*>(part + (size_t)k * n + i);
+    const int c = (int)(i % Ng);
+    f32x4 rv = 0.f, o;
+    if (res) rv = *reinterpret_cast<const f32x4*>(res + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float x = s[e] + (bias ? bias[c + e] : 0.f);
+        o[e] = ks_act(sscg_bn_fold(x, mean[c + e], sscg_bn_rstd(var[c + e], eps), gamma ? gamma[c + e] : 1.f, gamma ? beta[c + e] : 0.f,
+                                   gamma != nullptr, rv[e], res != nullptr), act, slope);
+    }
     *reinterpret_cast<f32x4*>(y + i) = o;
 }
 
@@ -1110,7 +1195,7 @@ size_t ks_split_bytes(const KsSplit& sp, long M, int Ng) {
     return sp.splits > 1 ? (size_t)sp.splits * (M - sp.m_tail0) * Ng * sizeof(float) : 0;
 }
 
-template <int MODE, int WM, int WN, int TM, int TN, int CIN = 0>
+template <int MODE, int WM, int WN, int TM, int TN, int CIN = 0, bool AFF = false>
 int launch_ks(const KsParams& p0, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
     constexpr int BN = WN * TN * 32;
@@ -1123,7 +1208,7 @@ int launch_ks(const KsParams& p0, hipStream_t st) {
     p.div_gl = make_fastdiv((MODE == MODE_DGRAD && p.bn_sums != nullptr) ? p.bn_L : (p.stat_L > 0 ? p.stat_L : 1));
     p.tiles = cdiv(p.M, BM) * p.tiles_n;
     const size_t smem = (size_t)2 * (BM * 128 + 3 * BN * 64);
-    auto kern = convs_kernel<MODE, WM, WN, TM, TN, CIN>;
+    auto kern = convs_kernel<MODE, WM, WN, TM, TN, CIN, AFF>;
     SSCG_ENSURE_SMEM((kern), smem);
     if (p.splits <= 1) { p.full_tiles = p.tiles; p.m_tail0 = p.M; }
     const int grid = p.full_tiles + (p.tiles - p.full_tiles) * p.splits;
@@ -1132,6 +1217,13 @@ int launch_ks(const KsParams& p0, hipStream_t st) {
     if (p.splits > 1) {
         const size_t n = (size_t)(p.M - p.m_tail0) * p.Ng;
         float* yt = p.dst + (size_t)p.m_tail0 * p.Ng;
+        if constexpr (AFF) {
+            hipLaunchKernelGGL(ks_reduce_affine_kernel, dim3(cdiv((long)(n / 4), 256)), dim3(256), 0, st, p.part, p.bias, yt, n, p.Ng, p.splits, p.act,
+                               p.slope, p.af_mean, p.af_var, p.af_eps, p.af_gamma, p.af_beta,
+                               p.af_res ? p.af_res + (size_t)p.m_tail0 * p.Ng : nullptr);
+            SSCG_LAUNCH_CHECK();
+            return SSCG_OK;
+        }
         if (p.xstats)
             return launch_split_reduce_stats(p.part, p.bias, yt, 0, p.M - p.m_tail0, p.Ng, p.splits, p.act, p.slope, p.xstats, st);
         if (p.Ng & 3)
@@ -1152,6 +1244,16 @@ int dispatch_ks(const KsParams& p, int tuning, hipStream_t st) {
         case KS_128x64: return launch_ks<MODE, 4, 1, 1, 2>(p, st);         // 4 waves of 32x64: every A fragment split by one wave only
         case KS_128x32: return launch_ks<MODE, 4, 1, 1, 1>(p, st);        // 4 waves of 32x32: few-channel heads
         default: return SSCG_ERR_BAD_ARG;
+    }
+}
+
+// the forward with an eval-mode BatchNorm folded into the store phase: every class that stages its tile (not the heads' 32 columns)
+int dispatch_ks_affine(const KsParams& p, int tuning, hipStream_t st) {
+    switch (ks_choose(p.M, p.Ng, p.Ktot, tuning)) {
+        case KS_128x128: return launch_ks<MODE_FWD, 4, 1, 1, 4, 0, true>(p, st);
+        case KS_64x64: return launch_ks<MODE_FWD, 2, 2, 1, 1, 0, true>(p, st);
+        case KS_128x64: return launch_ks<MODE_FWD, 4, 1, 1, 2, 0, true>(p, st);
+        default: return SSCG_ERR_UNSUPPORTED;
     }
 }
 
@@ -1278,6 +1380,36 @@ int sscg_convs_fwd(const sscg_conv_desc* d, const void* x, const void* w, const 
     p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
     p.part = reinterpret_cast<float*>(ws);
     return dispatch_ks<MODE_FWD>(p, d->tuning, st);
+}
+
+// Eval-mode conv -> BatchNorm [+ residual] -> activation as ONE launch (sscg_conv2d_fwd_affine): d->act / d->slope is the activation
+// BEHIND the norm.  Served by the classes whose tile leaves through LDS raw (Ng % 4 == 0, not the heads' 32-column class); the split-K
+// plan is the plain forward's (sscg_convs_fwd_workspace(d, 0)) - the tail's reduction carries the affine.
+bool sscg_convs_affine_applies(const sscg_conv_desc* d) {
+    if (!KS_STAGE_OUT_HOST || !sscg_convs_fwd_applies(d) || (d->K & 3) || d->act == SSCG_ACT_TANH) return false;
+    return ks_choose((long)d->N * d->P * d->Q, d->K, d->R * d->S * d->C, d->tuning) != KS_128x32;
+}
+
+int sscg_convs_fwd_affine(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, const sscg_bn_fold_args& bn, void* y,
+                          void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!sscg_convs_affine_applies(d)) return SSCG_ERR_UNSUPPORTED;
+    KsParams p = {};
+    p.src = reinterpret_cast<const float*>(x); p.wgt = reinterpret_cast<const bf16*>(w); p.wplane = ks_plane(d);
+    p.bias = bias; p.dst = reinterpret_cast<float*>(y);
+    p.M = d->N * d->P * d->Q; p.Ng = d->K; p.Cs = d->C; p.Ktot = d->R * d->S * d->C;
+    p.SH = d->H; p.SW = d->W; p.OH = d->P; p.OW = d->Q;
+    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
+    p.pad_mode = d->pad_mode; p.act = d->act; p.slope = d->slope;
+    p.src_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->C * sizeof(float));
+    p.wgt_bytes = (unsigned)(((size_t)2 * p.wplane + (size_t)d->K * d->R * d->S * d->C) * sizeof(bf16));
+    p.af_mean = bn.mean; p.af_var = bn.var; p.af_gamma = bn.gamma; p.af_beta = bn.beta; p.af_eps = bn.eps;
+    p.af_res = reinterpret_cast<const float*>(bn.residual);
+    ks_dense_taps(p);
+    KsSplit sp = ks_plan(p.M, p.Ng, p.Ktot, d->tuning, 0);
+    if (sp.splits > 1 && (!ws || ws_bytes < ks_split_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
+    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
+    p.part = reinterpret_cast<float*>(ws);
+    return dispatch_ks_affine(p, d->tuning, st);
 }
 
 // PixelDiscriminator's front half as ONE launch (arch/discriminators.py:70-73: Conv2d(cin, 64, 1x1) -> LeakyReLU -> Conv2d(64, 2 ndf, 1x1)

@@ -2478,6 +2478,65 @@ def conv2d(x, w, bias=None, stride=1, pad=0, dil=1, pad_mode=PAD_ZEROS, act=ACT_
     return Conv2dFn.apply(x, w, bias, stride, pad, dil, pad_mode, act, slope, out_f32, None, torch.is_grad_enabled())
 
 
+# Eval-mode BatchNorm folded into the conv that feeds it (sscg_conv2d_fwd_affine): under .eval() the normalisation is a per-channel affine
+# known before the conv starts, so a conv -> BatchNorm [+ residual] -> activation unit of an inference forward is ONE launch instead of
+# three (conv, sscg_rstd_from_var, sscg_norm_apply) and its map never makes the round trip through memory.  SSCG_FUSE_EVAL_NORM=0 keeps
+# the separate passes (an A/B aid: the bits are the same).
+FUSE_EVAL_NORM = [os.environ.get("SSCG_FUSE_EVAL_NORM", "1") != "0"]
+
+
+def _bn_eval_plan(x, w, stride, pad, dil, pad_mode, act, slope, out_f32):
+    """(descriptor, weight operand) of the fused launch, or (None, None) where the library does not serve the geometry: the exact-fp32
+    kernel (3-channel stems), the thin 1x1 kernels, the heads' 32-column tile classes, padded stems, tanh."""
+    if act == ACT_TANH or (x.dtype == torch.float32 and _padded_stem(x.shape, w.shape, stride, pad, dil, pad_mode, 0)):
+        return None, None
+    if x.dtype == torch.bfloat16 and x.shape[1] % 64:
+        return None, None
+    wop, wdt, wplane = _fwd_operands(x, w, (stride, pad, dil, pad_mode))       # the copies conv2d uses, obtained the same way
+    d = make_desc(x.shape, w.shape, stride, pad, dil, pad_mode, act, slope, _dt(x), wdt, _DT[_out_dtype(out_f32)], _prec(), wplane)
+    key = (id(d), "affine")
+    ok = _PLAN_SIZES.get(key)
+    if ok is None:
+        ok = _PLAN_SIZES[key] = bool(lib.sscg_conv2d_fwd_affine_applies(C.byref(d)))
+    return (d, wop) if ok else (None, None)
+
+
+def conv_bn_eval_applies(x, w, stride=1, pad=0, dil=1, pad_mode=PAD_ZEROS, act=ACT_NONE, slope=0.0, out_f32=False):
+    """Does one launch serve this conv -> eval-mode BatchNorm -> activation unit (sscg_conv2d_fwd_affine_applies)?"""
+    return _bn_eval_plan(x, w, stride, pad, dil, pad_mode, act, slope, out_f32)[0] is not None
+
+
+def conv_bn_eval_act(x, w, bias, running_mean, running_var, gamma=None, beta=None, residual=None, stride=1, pad=0, dil=1,
+                     pad_mode=PAD_ZEROS, eps=1e-5, act=ACT_NONE, slope=0.0, out_f32=False):
+    """act(batch_norm(conv2d(x, w) + bias; running statistics) [+ residual]) of an inference forward (arch/generators.py:345-365 under
+    model.py:555-574, validation.py, testing.py): bit for bit `batch_norm_act(conv2d(x, w, bias, ...), gamma, beta, running_mean,
+    running_var, training=False, ...)`, in one launch where the library serves the geometry - and by exactly those separate passes where
+    it does not.  A plain function, not an autograd node."""
+    _need_hip(x)
+    _no_grad_input(x, "conv_bn_eval_act")
+    if residual is not None:
+        _no_grad_input(residual, "conv_bn_eval_act")
+    if (gamma is None) != (beta is None):
+        raise _lib.SscgError("conv_bn_eval_act: gamma and beta come together")
+    x = to_nhwc(x.detach())
+    res = to_nhwc(residual.detach()) if residual is not None else None
+    d, wop = _bn_eval_plan(x, w, stride, pad, dil, pad_mode, act, slope, out_f32)
+    if d is not None and res is not None and res.dtype != _out_dtype(out_f32):
+        d = None
+    if d is None:
+        with torch.no_grad():
+            y = conv2d(x, w, bias, stride, pad, dil, pad_mode, ACT_NONE, 0.0, out_f32)
+            return batch_norm_act(y, gamma, beta, running_mean, running_var, False, 0.1, eps, act, slope, res)
+    y = empty_nhwc(d.N, d.K, d.P, d.Q, x.device, _out_dtype(out_f32))
+    if res is not None and tuple(res.shape) != tuple(y.shape):
+        raise _lib.SscgError("conv_bn_eval_act: residual %s does not match the output %s" % (tuple(res.shape), tuple(y.shape)))
+    ws = _WS.get(_ws_bytes(d, "fwd"), x.device)
+    _timed("fwd", d, lambda: check(lib.sscg_conv2d_fwd_affine(C.byref(d), x.data_ptr(), wop.data_ptr(), _ptr(bias), running_mean.data_ptr(),
+                                                              running_var.data_ptr(), eps, _ptr(gamma), _ptr(beta), _ptr(res), y.data_ptr(),
+                                                              ws.data_ptr(), ws.numel(), _stream()), "sscg_conv2d_fwd_affine"))
+    return y
+
+
 def backward(loss):
     """loss.backward() with the autograd engine on the CALLING thread.  Every node of these graphs launches kernels and returns
     (nothing to run in parallel on the host), while the hop to the engine's device thread costs ~10 % of a step's issue time
