@@ -166,7 +166,8 @@ def test_conv_transpose(geom, F, dev):
 
 @pytest.mark.parametrize("per_sample", [True, False])
 @pytest.mark.parametrize("act", [0, 1, 2])
-@pytest.mark.parametrize("shape", [(2, 64, 17, 19), (3, 256, 9, 9), (2, 2048, 5, 5), (2, 20, 8, 8)])
+@pytest.mark.parametrize("shape", [(2, 64, 17, 19), (3, 256, 9, 9), (2, 2048, 5, 5), (2, 20, 8, 8),
+                                   (2, 4, 16, 16)])      # C = 4: one column group per row in the reduce, cw_shift = 0 in the slab plan (256 row lanes)
 def test_norm_act(per_sample, act, shape, F, dev):
     N, C, H, W = shape
     g = torch.Generator().manual_seed(11)
