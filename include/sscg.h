@@ -302,6 +302,25 @@ int sscg_image_u8_to_f32(const uint8_t* src, float* dst, int64_t rows, int C, co
 /* ToLabel + Relabel(255, 0) (data_utils/__init__.py:34-58) / CityscapesDataset.encode_segmap (dataloader.py:260-267) as
  * one 256-entry table: dst[i] = lut[src[i]] (int64 out, the dtype of `.long()`). */
 int sscg_label_lut(const uint8_t* src, int64_t* dst, int64_t n, const int64_t* lut256, void* stream);
+/* Batched affine augmentation fused into the two passes above: one launch warps every sample of a uint8 batch by its own integer
+ * affine map and finishes it.  img uint8 [N][H][W][C] (C in 1..4), gt (nullable) uint8 [N][H][W], mats int32 [N][6] on the device,
+ * out_img fp32 [N][OH][OW][C], out_gt (with gt) int64 [N][OH][OW].  For output pixel (ox, oy) of sample n, m = mats[n], in int64:
+ *     sx = m0*ox + m1*oy + m2        sy = m3*ox + m4*oy + m5          Q16 source INDEX coordinates (the pixel-centre offsets of
+ *                                                                     both grids are folded into m2 / m5 by the host)
+ *   label: ix = (sx + 0x8000) >> 16, iy = (sy + 0x8000) >> 16 (arithmetic shifts); id = gt[n][iy][ix], or label_fill outside
+ *     [0, W) x [0, H); out_gt = lut256[id] (label_fill is a raw id: it goes through the table like a source pixel).
+ *   image: x0 = sx >> 16, y0 = sy >> 16, fx = (sx & 0xFFFF) >> 8, fy = (sy & 0xFFFF) >> 8; the four taps (y0 | y0+1, x0 | x0+1), a
+ *     tap outside the image = image_fill; per channel top = a*(256-fx) + b*fx, bot likewise for the lower row,
+ *     v = top*(256-fy) + bot*fy (an exact integer < 2^24); t = ((float)v * 2^-16) / 255; out = (t - mean[c]) / stdev[c], every
+ *     operation rounded to nearest on its own - the last two are sscg_image_u8_to_f32's, so with the identity map (m0 = m4 = 65536,
+ *     the rest 0, OH = H, OW = W) both outputs equal sscg_image_u8_to_f32's and sscg_label_lut's bit for bit.
+ * Bilinear without antialiasing (a minifying map samples, it does not average).  Errors before any HIP call: SSCG_ERR_BAD_ARG (null
+ * tensors, C outside 1..4, non-positive sizes, a fill outside 0..255, gt without lut256 or out_gt, out_gt without gt),
+ * SSCG_ERR_UNSUPPORTED (N*OH*OW >= 2^31, H or W above 32767).
+ * (An addition: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18, as for the inference heads below.) */
+int sscg_augment_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H, int W, int C,
+                    int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill, int label_fill,
+                    void* stream);
 
 /* ------------------------------------------------------------------ losses (K10, K11), mean reduction
  * Each forward writes one fp32 scalar to `loss` (device).  Each backward takes the upstream gradient as

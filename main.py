@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
---as_written.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--as_written, --augment.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -52,6 +52,9 @@ def get_args(argv=None):
                              "perceptual (weights --lamda_perceptual / --lab_perceptual_weight)")
     parser.add_argument("--vgg_weights", type=str, default=None,
                         help="torchvision VGG16 state dict for --variants perceptual (the reference downloads vgg16(pretrained=True))")
+    parser.add_argument("--augment", type=str, default="",
+                        help="comma list of geometric augmentations of the labelled and unlabelled training batches, applied in one "
+                             "launch inside the device-side batch finish: hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop (default: none)")
     parser.add_argument("--testing_gen", type=str, default="resnet_9blocks_softmax",
                         help="generator testing.py builds (the reference hard-codes resnet_9blocks_softmax, testing.py:40)")
     return parser.parse_args(argv)

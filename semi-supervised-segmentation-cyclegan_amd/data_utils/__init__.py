@@ -9,11 +9,18 @@ Two modes of `get_transformation`:
     ToLabel + Relabel / Cityscapes encode_segmap run batched on the MI355X (`sscg_image_u8_to_f32`,
     `sscg_label_lut`): a quarter of the host->device bytes and no per-sample float work on the host cores.
 torchvision is not a dependency: Resize / CenterCrop / ToTensor / Normalize are restated below on PIL + numpy.
-The reference's `augmentations.py` is never used (`augmentation=None` at every call site) and is not restated."""
+
+Augmentation (`augmentations.py`; the reference has the module and never uses it) is opt-in - `main.py --augment`,
+`build_loaders` reading `args.augment` - and only for the 'label' and 'unlabel' sets.  Its ops are affine maps, not pixel
+code: in `device_finish` mode `DeviceLoader(..., augmentation=)` draws one map per sample on the host, uploads the int32
+matrices with the batch and finishes the batch with ONE `sscg_augment_u8` launch (warp + ToTensor + Normalize + label table)
+instead of the two passes above; in host mode the same maps go through PIL as the datasets' `augmentation=`.  Without an
+augmentation nothing changes: the same two launches as before."""
 import numpy as np
 import torch
 from PIL import Image
 
+from . import augmentations
 from .dataloader import VOCDataset, CityscapesDataset, ACDCDataset   # noqa: F401  (reference: `from data_utils import ...`)
 
 BILINEAR, NEAREST = 2, 0     # PIL.Image filter ids (torchvision's `interpolation=` ints)
@@ -169,12 +176,16 @@ def get_transformation(size, resize=False, dataset='voc2012', device_finish=Fals
 class DeviceLoader:
     """Wraps a torch DataLoader over a dataset built with `device_finish=True` transforms and yields what the step
     consumes - (img f32 [B,C,H,W] channels-last on the MI355X, gt int64 [B,1,H,W], names) - or (img, names) for the
-    'test' split.  Batches cross PCIe as uint8 from pinned memory; the float conversion is one HIP launch per batch."""
+    'test' split.  Batches cross PCIe as uint8 from pinned memory; the float conversion is one HIP launch per batch.
+    `augmentation` (an `augmentations.Compose`, default None = nothing changes): every sample is warped by an affine map of its own
+    inside the finish - the maps of a batch are drawn on the host from `RandomState(seed)`, in batch order, uploaded with the batch
+    and applied by one `functional.augment_batch` launch that replaces the two passes."""
 
-    def __init__(self, loader, transformation, device):
+    def __init__(self, loader, transformation, device, augmentation=None, seed=0):
         if not transformation.get('device_finish'):
             raise ValueError("DeviceLoader needs get_transformation(..., device_finish=True)")
         self.loader, self.device = loader, device
+        self.augmentation, self.rng = augmentation, np.random.RandomState(seed)
         self.lut = transformation['lut'].to(device)
         self.mean = torch.tensor(transformation['mean'], dtype=torch.float32, device=device)
         self.std = torch.tensor(transformation['std'], dtype=torch.float32, device=device)
@@ -189,6 +200,9 @@ class DeviceLoader:
     def __iter__(self):
         from .. import functional as F
         for batch in self.loader:
+            if self.augmentation is not None:
+                yield self._augmented(F, batch)
+                continue
             img = F.image_u8_to_f32(self._up(batch[0]), self.mean, self.std)
             if len(batch) == 2:
                 yield img, batch[1]
@@ -196,18 +210,39 @@ class DeviceLoader:
                 yield img, F.label_lut(self._up(batch[1]), self.lut), batch[2]
 
 
+    def _augmented(self, F, batch):
+        aug = self.augmentation
+        b, h, w, _ = batch[0].shape
+        mats = self._up(torch.from_numpy(aug.matrices(self.rng, b, w, h)))
+        gt = self._up(batch[1]) if len(batch) == 3 else None
+        img, gt = F.augment_batch(self._up(batch[0]), gt, mats, aug.out_size or (h, w), self.mean, self.std, self.lut,
+                                  image_fill=aug.image_fill, label_fill=aug.label_fill)
+        return (img, batch[1]) if gt is None else (img, gt, batch[2])
+
+
+LABEL_FILL = {'voc2012': 255, 'cityscapes': 250, 'acdc': 0}   # raw ids: the tables map 255 -> 0 (as boundaries), 250 -> 19 (void)
+AUGMENT_SEED = 20261017
+
+
 def build_loaders(args, roots=None, device=None, sets=('label', 'unlabel', 'val'), rank=0):
     """The datasets and DataLoaders of model.py:315-348 (ratios 0.1/0.1/0.5 for VOC, 0.5 otherwise; batch_size, shuffle and
-    drop_last on all three, as written there), finished on `device` when one is given."""
+    drop_last on all three, as written there), finished on `device` when one is given.  `args.augment` (absent or "" = none; the
+    comma list of augmentations.from_spec) augments the 'label' and 'unlabel' sets, never 'val' or 'test': inside the device finish
+    when there is a device, through the datasets' `augmentation=` (PIL, before Resize / CenterCrop) otherwise; rank r draws from
+    `RandomState(AUGMENT_SEED + 1000 * r + <index of the set>)`."""
     roots = roots or {'voc2012': './data/VOC2012', 'cityscapes': './data/Cityscape', 'acdc': './data/ACDC'}
     from torch.utils.data import DataLoader
     tr = get_transformation((args.crop_height, args.crop_width), resize=True, dataset=args.dataset, device_finish=device is not None)
     cls = {'voc2012': VOCDataset, 'cityscapes': CityscapesDataset, 'acdc': ACDCDataset}[args.dataset]
     out = []
+    size = (args.crop_height, args.crop_width)
     for name in sets:
         ratio = 0.5 if (args.dataset != 'voc2012' or name in ('val', 'test')) else 0.1
-        ds = cls(root_path=roots[args.dataset], name=name, ratio=ratio, transformation=tr, augmentation=None)
+        seed = AUGMENT_SEED + 1000 * rank + len(out)
+        aug = augmentations.from_spec(getattr(args, 'augment', ''), size, label_fill=LABEL_FILL[args.dataset], seed=seed,
+                                      out_size=size if device is not None else None) if name in ('label', 'unlabel') else None
+        ds = cls(root_path=roots[args.dataset], name=name, ratio=ratio, transformation=tr, augmentation=aug if device is None else None)
         gen = torch.Generator().manual_seed(20260928 + 1000 * rank + len(out)) if rank else None   # ranks draw different batches
         ld = DataLoader(ds, batch_size=args.batch_size, shuffle=True, drop_last=True, generator=gen)
-        out.append(DeviceLoader(ld, tr, device) if device is not None else ld)
+        out.append(DeviceLoader(ld, tr, device, augmentation=aug, seed=seed) if device is not None else ld)
     return out

@@ -1298,6 +1298,31 @@ def label_lut(gt_u8, lut):
     return dst.unsqueeze(1)
 
 
+def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, label_fill=0):
+    """Batched affine augmentation fused into the batch finish (sscg_augment_u8, one launch): uint8 [N,H,W,C] pixels, uint8 [N,H,W]
+    label ids (or None) and one int32 Q16 map per sample (`mats` [N,6], data_utils.augmentations.to_q16) -> what image_u8_to_f32 and
+    label_lut return for the warped batch: fp32 logical [N,C,OH,OW] channels-last, int64 [N,1,OH,OW] (or None).  Outside the source:
+    `image_fill` per tap, the raw id `label_fill` through the table.  Identity maps reproduce the two passes bit for bit."""
+    if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or img_u8.dim() != 4:
+        raise _lib.SscgError("augment_batch: uint8 [N,H,W,C] tensor on the MI355X expected")
+    n, h, w, c = img_u8.shape
+    if not mats.is_cuda or mats.dtype != torch.int32 or tuple(mats.shape) != (n, 6):
+        raise _lib.SscgError("augment_batch: int32 [N,6] matrices on the MI355X expected")
+    if gt_u8 is not None and (not gt_u8.is_cuda or gt_u8.dtype != torch.uint8 or tuple(gt_u8.shape) != (n, h, w)
+                              or lut is None or lut.dtype != torch.int64 or lut.numel() != 256):
+        raise _lib.SscgError("augment_batch: uint8 [N,H,W] labels on the MI355X and an int64 table of 256 entries expected")
+    oh, ow = int(out_size[0]), int(out_size[1])
+    src, m = img_u8.contiguous(), mats.contiguous()
+    dst = torch.empty((n, oh, ow, c), dtype=torch.float32, device=src.device)
+    gsrc = gt_u8.contiguous() if gt_u8 is not None else None
+    gdst = torch.empty((n, oh, ow), dtype=torch.int64, device=src.device) if gt_u8 is not None else None
+    check(lib.sscg_augment_u8(src.data_ptr(), gsrc.data_ptr() if gsrc is not None else None, m.data_ptr(), dst.data_ptr(),
+                              gdst.data_ptr() if gdst is not None else None, n, h, w, c, oh, ow, mean.data_ptr(), std.data_ptr(),
+                              lut.data_ptr() if gsrc is not None else None, int(image_fill), int(label_fill), _stream()),
+          "sscg_augment_u8")
+    return dst.permute(0, 3, 1, 2), (gdst.unsqueeze(1) if gdst is not None else None)
+
+
 def label_onehot(labels, num_classes):
     """utils.make_one_hot (utils.py:314-350): labels int64 [N,1,H,W] -> fp32 one-hot [N,C,H,W] (NHWC memory)."""
     if not labels.is_cuda or labels.dtype != torch.int64:
