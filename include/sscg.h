@@ -374,6 +374,51 @@ int sscg_upsample_head_bwd(const float* x, const float* dy_soft, const float* dl
 int sscg_predict_head(const float* x, int N, int H, int W, int C, int OH, int OW, int64_t* index, uint8_t* label_u8,
                       const int64_t* label_true, int64_t* hist, void* stream);
 int sscg_image_head(const float* x, int N, int H, int W, int C, int OH, int OW, float* y_nhwc, uint8_t* rgb_u8, void* stream);
+/* ------------------------------------------------------------------ per-epoch image panels: the image grids the reference sends to
+ * TensorBoard at the end of every epoch (model.py:576-638; supervised_model: model.py:164-186), without the host round trip of
+ * full-resolution maps, the per-pixel Python loop of utils.PIL_to_tensor (utils.py:59-94) and make_grid on the host.  Forward only;
+ * never launched by the training step.  (An addition: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.)
+ *
+ * sscg_panel_labels (model.py:580-585, :593-597: interp -> Softmax2d -> .max(1)[1] -> make_one_hot): x = low-resolution logits
+ * [N][H][W][C], C <= 64.  Per output pixel the resize, softmax and first maximum of sscg_predict_head - the same functions, so every
+ * id equals that head's label_u8 bit for bit; OH == H && OW == W is the identity resize.
+ *   label_u8 (required) uint8 [N][OH][OW]: the class ids;
+ *   onehot   (nullable) fp32 [N][OH][OW][C]: 1.0f at the id, 0.0f elsewhere, every element written - what sscg_label_onehot makes of
+ *            the same ids: the input of the image generator (model.py:586).
+ * Neither the resized logits, the probabilities nor an int64 map reach memory.
+ *
+ * A panel is one of three kinds of source, each with a pre-normalisation value v per pixel and channel:
+ *   SSCG_PANEL_IMAGE   src fp32 [pixels][C], C in {1, 3}: v = x * scale + shift, a multiply then an add, each rounded to fp32 on its
+ *                      own - the un-normalise of model.py:603-615 (scale = std, shift = mean);
+ *   SSCG_PANEL_COLOUR  src uint8 ids [pixels] (C = 1): v_c = (float)palette[3 * id + c], palette uint8 [256][3] on the device -
+ *                      utils.colorize_mask + utils.PIL_to_tensor (model.py:622-625, :629-632);
+ *   SSCG_PANEL_GREY    src int64 [pixels] (C = 1): v = (float)id - display_tensor_gt[i] = val_gt[i] (model.py:627).
+ *
+ * sscg_panel_range: range[0] / range[1] (device) = the minimum / maximum of v over all pixels and channels, what make_grid(normalize=
+ * True) takes over the whole batch (model.py:634-638).  Exact and independent of order; inputs are finite by contract.  The result
+ * stays on the device.  ws: sscg_panel_range_workspace bytes (one pair per workgroup; 0 for small panels).
+ *
+ * sscg_panel_grid: torchvision.utils.make_grid(t, nrow, padding, normalize=True) followed by the image writer's float -> byte
+ * conversion, in one launch.  src [N][H][W](C) as above; with xmaps = min(nrow, N) and ymaps = ceil(N / xmaps), grid is uint8
+ * [3][ymaps * (H + padding) + padding][xmaps * (W + padding) + padding], CHW; tile k starts at row (k / xmaps) * (H + padding) +
+ * padding, column (k % xmaps) * (W + padding) + padding.  N == 1 is torchvision's special case: the image itself, [3][H][W], no
+ * border.  A one-channel source fills all three channels.  Every byte outside a tile is 0, unused cells included; every byte of grid
+ * is written.  Inside a tile, with lo = range[0], hi = range[1]:
+ *     d = (float)max((double)hi - (double)lo, 1e-5);  u = (v - lo) / d;  byte = (uint8_t)min(max(u * 255.f, 0.f), 255.f)
+ * every operation rounded to fp32 on its own, the division IEEE, the conversion truncating.
+ *
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, an unknown kind, C outside the kind's set, non-positive sizes or nrow,
+ * negative padding, COLOUR without a palette), SSCG_ERR_UNSUPPORTED (C > 64 in the labels head, an output of >= 2^31 elements),
+ * SSCG_ERR_WORKSPACE. */
+#define SSCG_PANEL_IMAGE 0
+#define SSCG_PANEL_COLOUR 1
+#define SSCG_PANEL_GREY 2
+int sscg_panel_labels(const float* x, int N, int H, int W, int C, int OH, int OW, uint8_t* label_u8, float* onehot, void* stream);
+size_t sscg_panel_range_workspace(int64_t pixels, int C);
+int sscg_panel_range(const void* src, int kind, int64_t pixels, int C, float scale, float shift, const uint8_t* palette, float* range,
+                     void* ws, size_t ws_bytes, void* stream);
+int sscg_panel_grid(const void* src, int kind, int N, int H, int W, int C, float scale, float shift, const uint8_t* palette,
+                    const float* range, int nrow, int padding, uint8_t* grid, void* stream);
 /* nn.MSELoss against a constant target map of ones/zeros (LSGAN; model.py:445-446,452,521-528) */
 int sscg_mse_const_fwd(const float* x, int64_t n, float target, float* loss, void* ws, size_t ws_bytes, void* stream);
 int sscg_mse_const_bwd(const float* x, int64_t n, float target, const float* gscale, float w, float* dx, void* stream);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
---as_written, --augment.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--as_written, --augment, --panels.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -55,6 +55,9 @@ def get_args(argv=None):
     parser.add_argument("--augment", type=str, default="",
                         help="comma list of geometric augmentations of the labelled and unlabelled training batches, applied in one "
                              "launch inside the device-side batch finish: hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop (default: none)")
+    parser.add_argument("--panels", type=str, default=None, metavar="DIR",
+                        help="write the reference's per-epoch image panels (model.py:576-638) to DIR/epoch%%03d_<n>.png, and to a "
+                             "tensorboardX.SummaryWriter(DIR) when that module is installed (default: off)")
     parser.add_argument("--testing_gen", type=str, default="resnet_9blocks_softmax",
                         help="generator testing.py builds (the reference hard-codes resnet_9blocks_softmax, testing.py:40)")
     return parser.parse_args(argv)
@@ -87,12 +90,19 @@ def main(argv=None):
                                        rank=dp.rank if dp is not None else 0)
         else:
             print("no dataset under %s: training on synthetic batches (--synthetic_steps per epoch)" % root)
+        writer = None
+        if args.panels:
+            try:
+                from tensorboardX import SummaryWriter
+                writer = SummaryWriter(args.panels)
+            except ImportError:
+                print("tensorboardX is not installed: the panels go to %s as PNG files only" % args.panels)
         if args.model == "semisupervised_cycleGAN":
             print("Training semi-supervised cycleGAN")
-            md.semisuper_cycleGAN(args, data_parallel=dp).train(args, loaders=loaders)
+            md.semisuper_cycleGAN(args, data_parallel=dp).train(args, loaders=loaders, writer=writer, panel_dir=args.panels)
         if args.model == "supervised_model":
             print("Training base model")
-            md.supervised_model(args, data_parallel=dp).train(args, loaders=loaders)
+            md.supervised_model(args, data_parallel=dp).train(args, loaders=loaders, writer=writer, panel_dir=args.panels)
     if args.testing:                                        # main.py:69-71
         print("Testing")
         import testing

@@ -15,6 +15,7 @@ F32, BF16, BF16X3 = 0, 1, 2     # SSCG_F32 / SSCG_BF16 / SSCG_BF16X3 (split weig
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 PAD_ZEROS, PAD_REFLECT = 0, 1
+PANEL_IMAGE, PANEL_COLOUR, PANEL_GREY = 0, 1, 2     # SSCG_PANEL_*: the source kinds of sscg_panel_range / sscg_panel_grid
 
 
 class ConvDesc(C.Structure):
@@ -110,6 +111,10 @@ SIGNATURES = {
     "sscg_upsample_head_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "sscg_predict_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sscg_panel_labels": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sscg_panel_range_workspace": (_sz, [_i64, _i]),
+    "sscg_panel_range": (_i, [_p, _i, _i64, _i, _f, _f, _p, _p, _p, _sz, _p]),
+    "sscg_panel_grid": (_i, [_p, _i, _i, _i, _i, _i, _f, _f, _p, _p, _i, _i, _p, _p]),
     "sscg_mse_const_fwd": (_i, [_p, _i64, _f, _p, _p, _sz, _p]),
     "sscg_mse_const_bwd": (_i, [_p, _i64, _f, _p, _f, _p, _p]),
     "sscg_mse_fwd": (_i, [_p, _p, _i64, _p, _p, _sz, _p]),

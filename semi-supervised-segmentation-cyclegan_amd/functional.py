@@ -1275,6 +1275,91 @@ def predict_image(x, size, *, want_float=True, want_u8=True):
     return y, u8
 
 
+# The per-epoch image panels (sscg_panel_labels / sscg_panel_range / sscg_panel_grid): the grids train() hands to the image writer,
+# built on the device.  SSCG_FUSE_PANELS=0 keeps model.panels() on the chain of separate passes and the host (an A/B aid: the bytes
+# are the same).
+FUSE_PANELS = [os.environ.get("SSCG_FUSE_PANELS", "1") != "0"]
+PANEL_IMAGE, PANEL_COLOUR, PANEL_GREY = _lib.PANEL_IMAGE, _lib.PANEL_COLOUR, _lib.PANEL_GREY
+
+
+def panel_labels(logits, size, want_onehot=True):
+    """interp(size) -> Softmax2d -> .max(1)[1] -> make_one_hot of fp32 logits [N,C,H,W] in one launch (model.py:580-585, :593-597).
+    Returns (label_u8 uint8 [N,OH,OW], onehot fp32 [N,C,OH,OW] channels-last or None): the ids predict_labels gives, and what
+    label_onehot makes of them - neither the resized logits, the probabilities nor an int64 map are written."""
+    _need_hip(logits, f32_only=True)
+    if logits.dim() != 4:
+        raise _lib.SscgError("panel_labels: 4-D logits expected")
+    _no_grad_input(logits, "panel_labels")
+    x = to_nhwc(logits.detach())
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    u8 = torch.empty((n, oh, ow), dtype=torch.uint8, device=x.device)
+    onehot = empty_nhwc(n, c, oh, ow, x.device) if want_onehot else None
+    check(lib.sscg_panel_labels(x.data_ptr(), n, h, w, c, oh, ow, u8.data_ptr(), _ptr(onehot), _stream()), "sscg_panel_labels")
+    return u8, onehot
+
+
+def _panel_source(src, kind, palette, what):
+    """(contiguous source, N, H, W, C) of a panel: IMAGE fp32 [N,C,H,W] (C in {1, 3}; NHWC memory), COLOUR uint8 ids [N,H,W], GREY
+    int64 ids [N,H,W] or [N,1,H,W]."""
+    if not src.is_cuda:
+        raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % src.device)
+    if kind == PANEL_IMAGE:
+        _need_hip(src, f32_only=True)
+        if src.dim() != 4 or src.shape[1] not in (1, 3):
+            raise _lib.SscgError("%s: an image panel is fp32 [N,C,H,W] with C in {1, 3}" % what)
+        _no_grad_input(src, what)
+        x = to_nhwc(src.detach())
+        n, c, h, w = x.shape
+        return x, n, h, w, c
+    if kind not in (PANEL_COLOUR, PANEL_GREY):
+        raise _lib.SscgError("%s: unknown panel kind %r" % (what, kind))
+    want = torch.uint8 if kind == PANEL_COLOUR else torch.int64
+    if src.dtype != want:
+        raise _lib.SscgError("%s: %s ids expected, got %s" % (what, want, src.dtype))
+    if src.dim() == 4 and src.shape[1] == 1:
+        src = src.reshape(src.shape[0], src.shape[2], src.shape[3])
+    if src.dim() != 3:
+        raise _lib.SscgError("%s: ids of shape [N,H,W] expected" % what)
+    if kind == PANEL_COLOUR and (palette is None or not palette.is_cuda or palette.dtype != torch.uint8 or palette.numel() != 768
+                                 or not palette.is_contiguous()):
+        raise _lib.SscgError("%s: a colour panel needs a contiguous uint8 [256,3] palette on the MI355X" % what)
+    n, h, w = src.shape
+    return src.contiguous(), n, h, w, 1
+
+
+def panel_range(src, kind, scale=1.0, shift=0.0, palette=None):
+    """fp32 [2] on the device: the minimum and maximum of a panel's values (IMAGE: x * scale + shift; COLOUR: the palette's channels
+    of every id; GREY: the ids), over the whole batch - make_grid(normalize=True)'s range (model.py:634-638).  No host sync."""
+    x, n, h, w, c = _panel_source(src, kind, palette, "panel_range")
+    rng = torch.empty(2, dtype=torch.float32, device=x.device)
+    ws = _WS.get(lib.sscg_panel_range_workspace(n * h * w, c), x.device)
+    check(lib.sscg_panel_range(x.data_ptr(), kind, n * h * w, c, float(scale), float(shift), _ptr(palette), rng.data_ptr(),
+                               ws.data_ptr(), ws.numel(), _stream()), "sscg_panel_range")
+    return rng
+
+
+def panel_grid_shape(n, h, w, nrow, padding):
+    """[3, GH, GW] of torchvision.utils.make_grid for n tiles of h x w"""
+    if n == 1:
+        return (3, h, w)
+    xmaps = min(nrow, n)
+    ymaps = -(-n // xmaps)
+    return (3, ymaps * (h + padding) + padding, xmaps * (w + padding) + padding)
+
+
+def panel_grid(src, kind, rng, nrow=8, padding=2, scale=1.0, shift=0.0, palette=None):
+    """torchvision.utils.make_grid(t, nrow, padding, normalize=True) + the image writer's (t * 255).astype(uint8) in one launch:
+    uint8 [3,GH,GW] on the device.  `rng`: panel_range's result for the same source, scale and shift."""
+    x, n, h, w, c = _panel_source(src, kind, palette, "panel_grid")
+    if not (rng.is_cuda and rng.dtype == torch.float32 and rng.numel() == 2 and rng.is_contiguous()):
+        raise _lib.SscgError("panel_grid: the range is a contiguous fp32 [2] tensor on the MI355X (panel_range)")
+    grid = torch.empty(panel_grid_shape(n, h, w, int(nrow), int(padding)), dtype=torch.uint8, device=x.device)
+    check(lib.sscg_panel_grid(x.data_ptr(), kind, n, h, w, c, float(scale), float(shift), _ptr(palette), rng.data_ptr(), int(nrow),
+                              int(padding), grid.data_ptr(), _stream()), "sscg_panel_grid")
+    return grid
+
+
 def image_u8_to_f32(img_u8, mean, std):
     """uint8 [B,H,W,C] (HWC pixels as PIL decoded them) -> fp32 logical [B,C,H,W], channels-last, ((u/255) - mean) / std:
     ToTensor + Normalize of data_utils/__init__.py:126-150 on the device."""

@@ -56,6 +56,64 @@ LOSS_KEYS = ("img_dis_loss", "gt_dis_loss", "cycle_img_dis_loss", "img_gen_loss"
              "gt_cycle_loss", "lab_loss_CE", "lab_loss_MSE")
 
 
+# ---- per-epoch image panels (model.py:576-638, :164-186 of the reference)
+PANEL_TAGS = ('Generated segmented image: ', 'Generated image back from segmentation: ', 'Ground truth for the image: ',
+              'Image generated from val labels: ', 'Labels generated back from the cycle: ')      # model.py:634-638, as written
+SUPERVISED_PANEL_TAGS = ('Generated segmented image', 'Ground truth for the image')               # model.py:185-186
+PANEL_NROW = 2                      # make_grid(..., nrow=2, normalize=True) at every call site
+PANEL_SCALE = PANEL_SHIFT = 0.5     # trans_std / trans_mean of model.py:603-615: 0.5 for all three datasets
+
+
+def _panel_ids(logits, size, num_classes, want_onehot):
+    """interp -> Softmax2d -> max(1)[1] [-> make_one_hot] of model.py:580-585.  Returns (ids [N,OH,OW], one-hot or None): one launch
+    and uint8 ids by default; with SSCG_FUSE_PANELS=0 the inference head's int64 map, then label_onehot.
+    (At batch size 1 the reference's `.squeeze_(1).squeeze_(0)` also drops the batch axis and make_one_hot then fails on a 3-D
+    tensor: what was meant - the one-hot map of the single prediction - is served here.)"""
+    if F.FUSE_PANELS[0]:
+        return F.panel_labels(logits, size, want_onehot=want_onehot)
+    index = F.predict_labels(logits, size, want_index=True, want_u8=False)[1]
+    return index, (F.label_onehot(index.unsqueeze(1), num_classes) if want_onehot else None)
+
+
+def _panel_arrays(dataset, entries):
+    """entries: (tag, kind, source) with kind / source as F.panel_range takes them (COLOUR ids may also be the separate path's int64
+    map).  Returns an ordered dict tag -> uint8 [3,GH,GW] numpy array: make_grid(nrow=2, normalize=True) and the image writer's byte
+    conversion of every panel.  Default: range + grid per panel on the device, then five small copies; SSCG_FUSE_PANELS=0: the maps
+    go to the host and through colorize_mask, PIL_to_tensor, make_grid and grid_to_u8, as in the reference."""
+    from collections import OrderedDict
+    out = OrderedDict()
+    if F.FUSE_PANELS[0]:
+        for tag, kind, src in entries:
+            pal = utils.palette_tensor(dataset, src.device) if kind == F.PANEL_COLOUR else None
+            sc, sh = (PANEL_SCALE, PANEL_SHIFT) if kind == F.PANEL_IMAGE else (1.0, 0.0)
+            rng = F.panel_range(src, kind, sc, sh, pal)
+            out[tag] = F.panel_grid(src, kind, rng, PANEL_NROW, 2, sc, sh, pal)
+        for tag in out:
+            out[tag] = out[tag].cpu().numpy()
+        return out
+    for tag, kind, src in entries:
+        host = src.detach().cpu()
+        if kind == F.PANEL_IMAGE:
+            t = host.contiguous() * PANEL_SCALE + PANEL_SHIFT                                   # model.py:603-615
+        elif kind == F.PANEL_COLOUR:
+            maps = host.numpy()
+            t = torch.stack([utils.PIL_to_tensor(utils.colorize_mask(maps[i], dataset), dataset) for i in range(maps.shape[0])])
+        else:
+            t = host.reshape(host.shape[0], 1, host.shape[-2], host.shape[-1]).float().expand(-1, 3, -1, -1)     # :627
+        out[tag] = utils.grid_to_u8(utils.make_grid(t, nrow=PANEL_NROW, normalize=True))
+    return out
+
+
+def write_panels(panels, epoch, writer=None, panel_dir=None):
+    """writer.add_image(tag, array, epoch) for every panel (model.py:634-638) and / or panel_dir/epoch%03d_<1..n>.png"""
+    for i, (tag, arr) in enumerate(panels.items()):
+        if writer is not None:
+            writer.add_image(tag, arr, epoch)
+        if panel_dir is not None:
+            os.makedirs(panel_dir, exist_ok=True)
+            utils.save_panel_png(arr, os.path.join(panel_dir, "epoch%03d_%d.png" % (epoch, i + 1)))
+
+
 class semisuper_cycleGAN(object):
     def __init__(self, args, data_parallel=None):
         self.args = args
@@ -440,12 +498,16 @@ class semisuper_cycleGAN(object):
 
     # ------------------------------------------------------------------------------------------ evaluation (model.py:555-574)
     @torch.no_grad()
-    def evaluate(self, val_loader):
+    def evaluate(self, val_loader, first_batch=None):
+        """`first_batch`: a list that receives the first batch's (val_img, val_gt) as they went through the network - the batch the
+        panels are drawn from, without a second iterator on the loader."""
         self.Gsi.eval()
         self.Gis.eval()
         self.running_metrics_val.reset()
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
+            if first_batch is not None and not first_batch:
+                first_batch.extend((val_img, val_gt))
             logits = self.Gsi(val_img)
             if F.FUSE_PREDICT[0]:            # interp -> Softmax2d -> max(1)[1] -> _fast_hist in one launch (:565-569)
                 self.running_metrics_val.update_logits(val_gt.squeeze(1), logits, self.crop)
@@ -457,11 +519,35 @@ class semisuper_cycleGAN(object):
         self.Gis.train()
         return score["Mean IoU : \t"], class_iou
 
+    # ------------------------------------------------------------------------------------------ image panels (model.py:576-638)
+    @torch.no_grad()
+    def panels(self, val_img, val_gt):
+        """The five image grids the reference sends to TensorBoard after every epoch, from one validation batch on the device:
+        an ordered dict tag -> uint8 [3,GH,GW] numpy array (the reference's tags, make_grid(nrow=2, normalize=True), the image
+        writer's bytes).  Both generators run in eval mode (folded BatchNorm) and return to the mode they were in; no parameter,
+        buffer or optimiser state changes.  SSCG_FUSE_PANELS=0 builds the same bytes by the separate passes and the host."""
+        a, C = self.args, self.n_channels
+        modes = (self.Gsi.training, self.Gis.training)
+        self.Gsi.eval()
+        self.Gis.eval()
+        try:
+            fake_ids, fake_onehot = _panel_ids(self.Gsi(val_img), self.crop, C, True)           # :580-585
+            fake_img = self.interp(self.Gis(fake_onehot))                                       # :586-587 (no tanh: :588)
+            from_labels = self.interp(self.Gis(make_one_hot(val_gt, a.dataset, a.gpu_ids)))     # :590-591
+            regen_ids, _ = _panel_ids(self.Gsi(from_labels), self.crop, C, False)               # :593-597
+            return _panel_arrays(a.dataset, list(zip(PANEL_TAGS, (F.PANEL_COLOUR, F.PANEL_IMAGE, F.PANEL_GREY, F.PANEL_IMAGE, F.PANEL_COLOUR),
+                                                     (fake_ids, fake_img, val_gt.long(), from_labels, regen_ids))))
+        finally:
+            self.Gsi.train(modes[0])
+            self.Gis.train(modes[1])
+
     # ------------------------------------------------------------------------------------------ epoch loop
-    def train(self, args, loaders=None, max_steps=None, log_every=1, writer=None):
+    def train(self, args, loaders=None, max_steps=None, log_every=1, writer=None, panel_dir=None):
         """Epoch loop of model.py:359-660.  `loaders` = (labeled, unlabeled, val) iterables yielding the
         reference's dataset tuples (img f32[B,3,H,W], gt i64[B,1,H,W], name); None builds synthetic ones
-        (the real datasets / transforms of data_utils are outside this build's scope)."""
+        (the real datasets / transforms of data_utils are outside this build's scope).
+        `writer` (add_scalars / add_image, e.g. tensorboardX.SummaryWriter) and `panel_dir` (PNG files) receive the epoch's image
+        panels on rank 0; neither changes what is trained."""
         if loaders is None:
             from .data import synthetic_loaders
             loaders = synthetic_loaders(args, self.n_channels, rank=self.dp.rank if self.dp is not None else 0)
@@ -497,9 +583,13 @@ class semisuper_cycleGAN(object):
                     return history
             self.sync_losses()                       # the last discriminator update is visible to what follows on this stream
             if val_loader is not None:
-                miou, class_iou = self.evaluate(val_loader)
+                want_panels = rank0 and (writer is not None or panel_dir is not None)
+                first = [] if want_panels else None
+                miou, class_iou = self.evaluate(val_loader, first_batch=first)
                 if rank0:
                     print("The mIoU for the epoch is: ", miou)
+                if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
+                    write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank0:                                 # model.py:641-655
                     self.best_iou = miou
                     utils.save_checkpoint({'epoch': epoch + 1, 'Di': self.Di.state_dict(), 'Ds': self.Ds.state_dict(),
@@ -555,13 +645,16 @@ class supervised_model(object):
         return loss.detach()
 
     @torch.no_grad()
-    def evaluate(self, val_loader):
+    def evaluate(self, val_loader, first_batch=None):
         """model.py:145-162.  The reference interpolates to a hard-coded 512x512 (`interp_val`, model.py:63,152), which only
-        works for a 512x512 crop; the crop size is used here, as the semi-supervised driver does."""
+        works for a 512x512 crop; the crop size is used here, as the semi-supervised driver does.
+        `first_batch`: a list that receives the first batch's (val_img, val_gt) on the device (the batch of the panels)."""
         self.Gsi.eval()
         self.running_metrics_val.reset()
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
+            if first_batch is not None and not first_batch:
+                first_batch.extend((val_img, val_gt))
             logits = self.Gsi(val_img)
             if F.FUSE_PREDICT[0]:
                 self.running_metrics_val.update_logits(val_gt.squeeze(1), logits, self.crop)
@@ -573,7 +666,19 @@ class supervised_model(object):
         self.Gsi.train()
         return score["Mean IoU : \t"], class_iou
 
-    def train(self, args, loaders=None, max_steps=None):
+    @torch.no_grad()
+    def panels(self, val_img, val_gt):
+        """The two image grids of model.py:164-186 (prediction, ground truth) from one validation batch: tag -> uint8 [3,GH,GW]
+        numpy array.  Gsi runs in eval mode and returns to the mode it was in; nothing else changes."""
+        mode = self.Gsi.training
+        self.Gsi.eval()
+        try:
+            ids, _ = _panel_ids(self.Gsi(val_img), self.crop, self.n_channels, False)           # :168-171
+            return _panel_arrays(self.args.dataset, list(zip(SUPERVISED_PANEL_TAGS, (F.PANEL_COLOUR, F.PANEL_GREY), (ids, val_gt.long()))))
+        finally:
+            self.Gsi.train(mode)
+
+    def train(self, args, loaders=None, max_steps=None, writer=None, panel_dir=None):
         rank = self.dp.rank if self.dp is not None else 0
         if loaders is None:
             from .data import synthetic_loaders
@@ -589,13 +694,18 @@ class supervised_model(object):
                 history.append(loss)
                 if rank == 0:
                     print("Epoch: (%3d) (%5d/%5d) | Crossentropy Loss:%.2e" % (epoch, i + 1, len(labeled_loader), loss))
+                    if writer is not None:                                          # model.py:143
+                        writer.add_scalars('Supervised Loss', {'CE Loss ': loss}, len(labeled_loader) * epoch + i)
                 done += 1
                 if max_steps is not None and done >= max_steps:
                     return history
             if val_loader is not None:                                              # model.py:145-197
-                miou, class_iou = self.evaluate(val_loader)
+                first = [] if rank == 0 and (writer is not None or panel_dir is not None) else None
+                miou, class_iou = self.evaluate(val_loader, first_batch=first)
                 if rank == 0:
                     print("The mIoU for the epoch is: ", miou)
+                if first:                                                           # model.py:164-186
+                    write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank == 0:
                     self.best_iou = miou
                     utils.save_checkpoint({'epoch': epoch + 1, 'Gsi': self.Gsi.state_dict(),

@@ -241,8 +241,72 @@ def colorize_mask(mask, dataset):
     from PIL import Image
     assert dataset in ('voc2012', 'cityscapes', 'acdc')
     new_mask = Image.fromarray(np.asarray(mask).astype(np.uint8)).convert('P')
-    new_mask.putpalette({'voc2012': palette, 'cityscapes': cityscape_palette, 'acdc': acdc_palette}[dataset])
+    new_mask.putpalette(PALETTES[dataset])
     return new_mask
+
+
+PALETTES = {'voc2012': palette, 'cityscapes': cityscape_palette, 'acdc': acdc_palette}
+_PALETTE_TENSORS = {}
+
+
+def palette_tensor(dataset, device):
+    """The dataset's palette as the uint8 [256,3] device table of F.panel_range / F.panel_grid (uploaded once per device)."""
+    key = (dataset, str(device))
+    t = _PALETTE_TENSORS.get(key)
+    if t is None:
+        t = _PALETTE_TENSORS[key] = torch.tensor(PALETTES[dataset], dtype=torch.uint8).reshape(256, 3).to(device)
+    return t
+
+
+# ---- the per-epoch image panels on the host (model.py:617-638 of the reference): the separate-passes path of model.panels()
+def PIL_to_tensor(img, dataset):
+    """Paletted PIL image -> fp32 [3,H,W] of its palette colours, 0..255 (utils.py:59-94): the reference's per-pixel double loop
+    (`index = int(img_arr[i, j] * 3)`, three palette reads) as three gathers."""
+    assert dataset in ('voc2012', 'cityscapes', 'acdc')
+    img_arr = np.array(img, dtype='float32')
+    index = (img_arr * 3).astype(np.int64)
+    pal = np.asarray(PALETTES[dataset], dtype='float32')
+    return torch.tensor(np.stack([pal[index], pal[index + 1], pal[index + 2]]))
+
+
+def make_grid(tensor, nrow=8, padding=2, normalize=False):
+    """torchvision.utils.make_grid for a [N,C,H,W] batch (C in {1, 3}; pad_value 0, no value range, scale_each off): one-channel
+    images are replicated to three; normalize=True shifts the whole batch to [0, 1] by its own min / max - (x - lo) / max(hi - lo,
+    1e-5), the difference taken in double as torchvision's Python floats do, the rest in fp32; a single image is returned as it is;
+    otherwise min(nrow, N) tiles per row, `padding` pixels of 0 around every tile.  Returns an fp32 [3,GH,GW] tensor."""
+    t = torch.as_tensor(tensor)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+    if a.shape[1] == 1:
+        a = np.concatenate((a, a, a), 1)
+    if normalize:
+        lo, hi = float(a.min()), float(a.max())
+        a = (np.clip(a, np.float32(lo), np.float32(hi)) - np.float32(lo)) / np.float32(max(hi - lo, 1e-5))
+    n, c, h, w = a.shape
+    if n == 1:
+        return torch.from_numpy(a[0].copy())
+    xmaps = min(nrow, n)
+    ymaps = -(-n // xmaps)
+    grid = np.zeros((c, ymaps * (h + padding) + padding, xmaps * (w + padding) + padding), dtype=np.float32)
+    for k in range(n):
+        y0, x0 = (k // xmaps) * (h + padding) + padding, (k % xmaps) * (w + padding) + padding
+        grid[:, y0:y0 + h, x0:x0 + w] = a[k]
+    return torch.from_numpy(grid)
+
+
+def grid_to_u8(t):
+    """The image writer's float -> byte conversion of a [0, 1] CHW grid (tensorboardX: `(t * 255.0).astype(np.uint8)`)."""
+    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    return (a * 255.0).astype(np.uint8)
+
+
+def save_panel_png(grid_u8, path):
+    """One panel (uint8 CHW, as model.panels() returns it) as a PNG."""
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(np.asarray(grid_u8).transpose(1, 2, 0))).save(path)
 
 
 def save_image_u8(pixels, path):
