@@ -20,6 +20,7 @@
 #include "sscg_internal.h"
 #include "reduce_common.h"
 #include "bn_fold.h"
+#include "conv_plan.h"
 #include <type_traits>
 
 namespace {
@@ -852,63 +853,16 @@ int choose16(long M, int Ng, int Ktot, int tuning) {
     return CFG_64x64;
 }
 
-struct K16Split { int splits, ksplit, full_tiles, m_tail0; };
-
-// Which tiles are cut along K (same policy as conv_igemm.hip): few-channel heads on few rows split every tile; 64x64
-// launches split only the tail beyond the last whole round of 256 workgroups.
-K16Split plan16_raw(long M, int Ng, int Ktot, int tuning);
-
-// stat_L > 0: the launch also produces normalisation statistics; the rows of split tiles are summed separately as ONE
-// extra group of records, so they must lie in one normalisation group (else the launch is not split).
-K16Split plan16(long M, int Ng, int Ktot, int tuning, long stat_L = 0) {
-    K16Split r = plan16_raw(M, Ng, Ktot, tuning);
-    if (stat_L > 0 && r.splits > 1 && (r.full_tiles == 0 || r.m_tail0 / stat_L != (M - 1) / stat_L)) {
-        const int cfg = choose16(M, Ng, Ktot, tuning);
-        r.splits = 1; r.ksplit = Ktot / BK;
-        r.full_tiles = cdiv(M, C16_BM[cfg]) * cdiv(Ng, C16_BN[cfg]); r.m_tail0 = (int)M;
-    }
-    return r;
-}
-
-K16Split plan16_raw(long M, int Ng, int Ktot, int tuning) {
-    const int nk = Ktot / BK;
+// The bf16 family's split policy (rules in conv_plan.h): k-tiles = Ktot / BK, whole ones (Cs % BK == 0); the forced-split bits of
+// `tuning` do NOT count; few-channel heads split every tile (reductions of >= 16 k-tiles, pieces of >= 4); the 128x32 and 128x64
+// classes take no tail split.  `fused`: the launch takes backward sums or joins an addend in its store phase.
+ConvSplit plan16(long M, int Ng, int Ktot, int tuning, long stat_L = 0, bool fused = false) {
     const int cfg = choose16(M, Ng, Ktot, tuning);
-    const int bm = C16_BM[cfg], bn = C16_BN[cfg];
-    const int tiles_m = cdiv(M, bm), tiles_n = cdiv(Ng, bn);
-    const int tiles = tiles_m * tiles_n;
-    K16Split r = {1, nk, tiles, (int)M};
-    if (Ng <= 32) {
-        if (tiles >= 256 || nk < 16) return r;
-        int s = cdiv(512, tiles);
-        if (s > nk / 4) s = nk / 4;
-        if (s > 32) s = 32;
-        if (s < 2) return r;
-        r.ksplit = cdiv(nk, s);
-        r.splits = cdiv(nk, r.ksplit);
-        r.full_tiles = 0; r.m_tail0 = 0;
-        return r;
-    }
-    // 64x64 and 128x128 launches: only the TAIL beyond the last whole round of 256 workgroups is cut along K (8712 rows x 256
-    // channels = 548 tiles of 64x64; 34320 rows = 538 tiles of 128x128: 512 run whole, two per CU side by side, the other
-    // 26 would keep a tenth of the chip busy for a whole tile time)
-    if (cfg == CFG_128x32 || cfg == CFG_128x64 || nk < 8 || tiles > 2300) return r;
-    const int q = tiles / 256;
-    const int full_m = (q * 256) / tiles_n;
-    const int tail = tiles - full_m * tiles_n;
-    if (tail <= 0 || tail > 208) return r;
-    int s = 256 / tail;
-    if (s > 8) s = 8;
-    if (s > nk / 4) s = nk / 4;
-    if (s < 2) return r;
-    r.ksplit = cdiv(nk, s);
-    r.splits = cdiv(nk, r.ksplit);
-    r.full_tiles = full_m * tiles_n;
-    r.m_tail0 = full_m * bm;
-    return r;
-}
-
-size_t split16_bytes(const K16Split& sp, long M, int Ng) {
-    return sp.splits > 1 ? (size_t)sp.splits * (M - sp.m_tail0) * Ng * sizeof(float) : 0;
+    const ConvTiles t = conv_tiles(M, Ng, Ktot / BK, C16_BM[cfg], C16_BN[cfg]);
+    ConvSplit sp = unsplit(t);
+    if (Ng <= 32) sp = split_heads(t, 16, 4);
+    else if (cfg != CFG_128x32 && cfg != CFG_128x64) sp = split_tail(t);
+    return no_split_with_fused_epilogue(keep_split_rows_in_one_group(sp, t, stat_L), t, fused);
 }
 
 template <int MODE, int WM, int WN, int TM, int TN, int NSTAGE, bool BS = false, bool AFF = false>
@@ -917,13 +871,7 @@ int launch16(const K16Params& p0, hipStream_t st) {
     constexpr int BN = WN * TN * 32;
     constexpr int NT = WM * WN * 64;
     K16Params p = p0;
-    p.tiles_n = cdiv(p.Ng, BN);
-    const int tiles_m = cdiv(p.M, BM);
-    p.tiles = tiles_m * p.tiles_n;
-    p.div_tn = make_fastdiv(p.tiles_n);
-    p.div_hw = make_fastdiv(p.OH * p.OW);
-    p.div_w = make_fastdiv(p.OW);
-    p.div_gl = make_fastdiv((BS && MODE == MODE_DGRAD && p.bn_sums != nullptr) ? p.bn_L : (p.stat_L > 0 ? p.stat_L : 1));
+    const int grid = launch_prologue(p, BM, BN);
     size_t smem = (size_t)NSTAGE * (BM + BN) * BK * sizeof(bf16);
     const size_t stage = BN >= 64 ? (size_t)(BM / 2) * (BN + 4) * sizeof(uint32_t) + (size_t)WM * BN * 4 * sizeof(double) : 0;      // output tile of the staged epilogue (bf16 row pairs) + the wave rows' statistics behind it
     if (stage > smem) smem = stage;
@@ -931,8 +879,6 @@ int launch16(const K16Params& p0, hipStream_t st) {
     if (stage_f > smem) smem = stage_f;
     auto kern = conv16_kernel<MODE, WM, WN, TM, TN, NSTAGE, BS, AFF>;
     SSCG_ENSURE_SMEM((kern), smem);
-    if (p.splits <= 1) { p.full_tiles = p.tiles; p.m_tail0 = p.M; }
-    const int grid = p.full_tiles + (p.tiles - p.full_tiles) * p.splits;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), smem, st, p);
     SSCG_LAUNCH_CHECK();
     if (p.splits > 1) {
@@ -989,21 +935,27 @@ int dispatch16_affine(const K16Params& p, int tuning, hipStream_t st) {
     }
 }
 
-void dense_taps(K16Params& p) {
-    p.pad_x = p.pad; p.wKtot = p.Ktot;
-    p.wt_ky0 = 0; p.wt_kx0 = 0; p.wt_step = 1; p.wt_S = p.S;
-    p.o_step = 1; p.o_a = 0; p.o_b = 0; p.o_W = 0; p.o_HW = 0;
-}
-
 bool dgrad16_by_parity(const sscg_conv_desc* d) { return d->stride == 2 && d->dil == 1 && d->pad_mode == 0; }
 
 }  // namespace
 
 // ---- entry points used by conv_igemm.hip's dispatch (same argument meaning as the public sscg_conv2d_* functions)
 // (the copies address both operands through 32-bit buffer offsets; a masked row's offset, 2 GB, must lie outside the tensor)
+static size_t k16_src_bytes(const sscg_conv_desc* d, bool dgrad) {
+    return (dgrad ? (size_t)d->N * d->P * d->Q * d->K : (size_t)d->N * d->H * d->W * d->C) * sizeof(bf16);
+}
+static size_t k16_wgt_bytes(const sscg_conv_desc* d) { return (size_t)d->K * d->R * d->S * d->C * sizeof(bf16); }
+
 static bool k16_extents_ok(const sscg_conv_desc* d, bool dgrad) {
-    const size_t src = (dgrad ? (size_t)d->N * d->P * d->Q * d->K : (size_t)d->N * d->H * d->W * d->C) * sizeof(bf16);
-    return src < ((size_t)1 << 31) && (size_t)d->K * d->R * d->S * d->C * sizeof(bf16) < ((size_t)1 << 31);
+    return k16_src_bytes(d, dgrad) < ((size_t)1 << 31) && k16_wgt_bytes(d) < ((size_t)1 << 31);
+}
+
+// the two operands with their buffer extents, bias and destination; src = x of a forward, dy of a data gradient
+static void k16_operands(K16Params& p, const sscg_conv_desc* d, bool dgrad, const void* src, const void* w, const float* bias, void* dst) {
+    p.src = reinterpret_cast<const bf16*>(src); p.wgt = reinterpret_cast<const bf16*>(w); p.bias = bias; p.dst = dst;
+    p.src_bytes = (unsigned)k16_src_bytes(d, dgrad);
+    p.wgt_bytes = (unsigned)k16_wgt_bytes(d);
+    p.out_bf16 = (dgrad ? d->x_dtype : d->y_dtype) == SSCG_BF16;
 }
 
 bool sscg_conv16_fwd_applies(const sscg_conv_desc* d) {
@@ -1016,50 +968,40 @@ bool sscg_conv16_dgrad_applies(const sscg_conv_desc* d) {
 }
 
 // geometry of the statistics records of a forward launch (records = [tiles_m * wm][2 groups][K][2] doubles)
-bool sscg_conv16_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, int* splits, int* full_tiles, int* m_tail0) {
+bool sscg_conv16_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, ConvSplit* sp) {
     const long M = (long)d->N * d->P * d->Q;
     const int cfg = choose16(M, d->K, d->R * d->S * d->C, d->tuning);
     if (cfg == CFG_128x32 || L < C16_BM[cfg]) return false;
     *bm = C16_BM[cfg];
     *wm = d->y_dtype == SSCG_BF16 ? 1 : C16_WM[cfg];       // bf16 results leave through a staged tile: its wave rows' sums meet in LDS (one record per tile)
     *tiles_n = cdiv(d->K, C16_BN[cfg]);
-    K16Split sp = plan16(M, d->K, d->R * d->S * d->C, d->tuning, L);
-    *splits = sp.splits; *full_tiles = sp.full_tiles; *m_tail0 = sp.m_tail0;
+    *sp = plan16(M, d->K, d->R * d->S * d->C, d->tuning, L);
     return true;
 }
 
 size_t sscg_conv16_fwd_workspace(const sscg_conv_desc* d, long stat_L) {
     const long M = (long)d->N * d->P * d->Q;
-    return split16_bytes(plan16(M, d->K, d->R * d->S * d->C, d->tuning, stat_L), M, d->K);
+    return split_bytes(plan16(M, d->K, d->R * d->S * d->C, d->tuning, stat_L), M, d->K);
 }
 
 size_t sscg_conv16_dgrad_workspace(const sscg_conv_desc* d) {
     if (dgrad16_by_parity(d)) return 0;
     const long M = (long)d->N * d->H * d->W;
-    return split16_bytes(plan16(M, d->C, d->R * d->S * d->K, d->tuning), M, d->C);
+    return split_bytes(plan16(M, d->C, d->R * d->S * d->K, d->tuning), M, d->C);
 }
 
 int sscg_conv16_fwd(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, double* stats, long stat_L,
                     double* xstats, void* ws, size_t ws_bytes, hipStream_t st) {
     K16Params p = {};
-    p.src = reinterpret_cast<const bf16*>(x); p.wgt = reinterpret_cast<const bf16*>(w); p.bias = bias; p.dst = y;
-    p.src_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->C * sizeof(bf16));
-    p.wgt_bytes = (unsigned)((size_t)d->K * d->R * d->S * d->C * sizeof(bf16));
-    p.out_bf16 = d->y_dtype == SSCG_BF16;
-    p.M = d->N * d->P * d->Q; p.Ng = d->K; p.Cs = d->C; p.Ktot = d->R * d->S * d->C;
-    p.SH = d->H; p.SW = d->W; p.OH = d->P; p.OW = d->Q;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.pad_mode = d->pad_mode; p.act = d->act; p.slope = d->slope;
+    k16_operands(p, d, false, x, w, bias, y);
+    set_fwd_geometry(p, d);
     p.stats = stats; p.stat_L = (int)stat_L; p.xstats = xstats;
-    dense_taps(p);
-    K16Split sp = plan16(p.M, p.Ng, p.Ktot, d->tuning, stats ? stat_L : 0);
-    if (sp.splits > 1 && (!ws || ws_bytes < split16_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
-    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
-    p.part = reinterpret_cast<float*>(ws);
+    const int rc = apply_split(p, plan16(p.M, p.Ng, p.Ktot, d->tuning, stats ? stat_L : 0), ws, ws_bytes);
+    if (rc) return rc;
     return dispatch16<MODE_FWD>(p, d->tuning, st);
 }
 
-// Eval-mode conv -> BatchNorm [+ residual] -> activation as ONE launch (sscg_conv2d_fwd_affine; conv_split.hip's twin): bf16 in, bf16
+// Eval-mode conv -> BatchNorm [+ residual] -> activation as ONE launch (sscg_conv2d_fwd_affine, as in conv_split.hip): bf16 in, bf16
 // out, whole 16-byte row segments (K % 8 == 0), the three staged classes the plan chooses.  The split-K plan is the plain forward's.
 bool sscg_conv16_affine_applies(const sscg_conv_desc* d) {
     if (!sscg_conv16_fwd_applies(d) || d->y_dtype != SSCG_BF16 || (d->K & 7) || d->act == SSCG_ACT_TANH) return false;
@@ -1071,21 +1013,12 @@ int sscg_conv16_fwd_affine(const sscg_conv_desc* d, const void* x, const void* w
                            void* ws, size_t ws_bytes, hipStream_t st) {
     if (!sscg_conv16_affine_applies(d)) return SSCG_ERR_UNSUPPORTED;
     K16Params p = {};
-    p.src = reinterpret_cast<const bf16*>(x); p.wgt = reinterpret_cast<const bf16*>(w); p.bias = bias; p.dst = y;
-    p.src_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->C * sizeof(bf16));
-    p.wgt_bytes = (unsigned)((size_t)d->K * d->R * d->S * d->C * sizeof(bf16));
-    p.out_bf16 = 1;
-    p.M = d->N * d->P * d->Q; p.Ng = d->K; p.Cs = d->C; p.Ktot = d->R * d->S * d->C;
-    p.SH = d->H; p.SW = d->W; p.OH = d->P; p.OW = d->Q;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.pad_mode = d->pad_mode; p.act = d->act; p.slope = d->slope;
+    k16_operands(p, d, false, x, w, bias, y);       // (sscg_conv16_affine_applies: bf16 out)
+    set_fwd_geometry(p, d);
     p.af_mean = bn.mean; p.af_var = bn.var; p.af_gamma = bn.gamma; p.af_beta = bn.beta; p.af_eps = bn.eps;
     p.af_res = reinterpret_cast<const bf16*>(bn.residual);
-    dense_taps(p);
-    K16Split sp = plan16(p.M, p.Ng, p.Ktot, d->tuning, 0);
-    if (sp.splits > 1 && (!ws || ws_bytes < split16_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
-    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
-    p.part = reinterpret_cast<float*>(ws);
+    const int rc = apply_split(p, plan16(p.M, p.Ng, p.Ktot, d->tuning), ws, ws_bytes);
+    if (rc) return rc;
     return dispatch16_affine(p, d->tuning, st);
 }
 
@@ -1093,13 +1026,9 @@ int sscg_conv16_fwd_affine(const sscg_conv_desc* d, const void* x, const void* w
 bool sscg_conv16_bsums_geometry(const sscg_conv_desc* d, int G, long L, int* bm, int* wm, int* chunks) {
     if (!sscg_conv16_dgrad_applies(d) || d->x_dtype != SSCG_BF16 || dgrad16_by_parity(d) || d->stride != 1) return false;
     const long M = (long)d->N * d->H * d->W;
-    if (G <= 0 || L <= 0 || (long)G * L != M) return false;
     const int cfg = choose16(M, d->C, d->R * d->S * d->K, d->tuning);
-    if (!(cfg == CFG_64x64 || cfg == CFG_128x64 || cfg == CFG_128x128_W8) || L < C16_BM[cfg] || d->C % 8 != 0) return false;   // (the store phase's classes, whole 16-byte segments)
-    *bm = C16_BM[cfg];
-    *wm = 1;                                // one record per tile and group (the sums are taken in the store phase, per workgroup)
-    *chunks = (int)(cdiv(L, (long)C16_BM[cfg]) + 1);
-    return true;
+    if (!(cfg == CFG_64x64 || cfg == CFG_128x64 || cfg == CFG_128x128_W8) || d->C % 8 != 0) return false;   // (the store phase's classes, whole 16-byte segments)
+    return bsums_record_geometry(M, G, L, C16_BM[cfg], bm, wm, chunks);
 }
 
 // dx = dgrad + addend in the bf16 store phase: bf16 result tiles of at least 64 columns, whole 16-byte row segments
@@ -1114,11 +1043,9 @@ int sscg_conv16_dgrad(const sscg_conv_desc* d, const void* dy, const void* wt, c
                       void* ws, size_t ws_bytes, hipStream_t st, const sscg_bsums* bs, const void* addend) {
     if (act == SSCG_ACT_TANH && d->C > 32) return SSCG_ERR_UNSUPPORTED;      // (tanh lives in the 32-column class only)
     K16Params p = {};
-    bool fused = false;
     if (addend) {
         if (bs || bias || act != SSCG_ACT_NONE || !sscg_conv16_dgrad_add_applies(d)) return SSCG_ERR_UNSUPPORTED;
         p.addend = reinterpret_cast<const bf16*>(addend);
-        fused = true;           // (never split: the partial tiles' reduction does not know the addend)
     }
     if (bs) {
         int bm, wm, chunks;
@@ -1126,53 +1053,14 @@ int sscg_conv16_dgrad(const sscg_conv_desc* d, const void* dy, const void* wt, c
         p.bn_x = reinterpret_cast<const bf16*>(bs->nx); p.bn_mean = bs->mean; p.bn_rstd = bs->rstd; p.bn_gamma = bs->gamma; p.bn_beta = bs->beta;
         p.bn_sums = reinterpret_cast<double*>(bs->sums); p.bn_L = (int)bs->L; p.bn_G = bs->G; p.bn_chunks = chunks;
         p.bn_act = bs->act; p.bn_slope = bs->slope;
-        fused = true;
     }
-    p.src = reinterpret_cast<const bf16*>(dy); p.wgt = reinterpret_cast<const bf16*>(wt); p.bias = bias; p.dst = dx;
-    p.src_bytes = (unsigned)((size_t)d->N * d->P * d->Q * d->K * sizeof(bf16));
-    p.wgt_bytes = (unsigned)((size_t)d->K * d->R * d->S * d->C * sizeof(bf16));
-    p.out_bf16 = d->x_dtype == SSCG_BF16;
-    p.M = d->N * d->H * d->W; p.Ng = d->C; p.Cs = d->K; p.Ktot = d->R * d->S * d->K;
-    p.SH = d->P; p.SW = d->Q; p.OH = d->H; p.OW = d->W;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.pad_mode = 0; p.act = act; p.slope = slope;
-    dense_taps(p);
-    if (dgrad16_by_parity(d)) {
-        // stride 2: four parity classes, each a stride-1 data gradient over its sub-lattice of taps (conv_igemm.hip)
-        p.splits = 1; p.ksplit = 0; p.part = nullptr;
-        p.stride = 1; p.wt_step = 2; p.wt_S = d->S;
-        p.o_step = 2; p.o_W = d->W; p.o_HW = d->H * d->W;
-        for (int a = 0; a < 2; ++a) {
-            for (int b = 0; b < 2; ++b) {
-                const int Ha = (d->H - a + 1) / 2, Wb = (d->W - b + 1) / 2;
-                if (Ha <= 0 || Wb <= 0) continue;
-                const int ky0 = (a + d->pad) & 1, kx0 = (b + d->pad) & 1;
-                K16Params q = p;
-                q.R = ky0 < d->R ? (d->R - ky0 + 1) / 2 : 0;
-                q.S = kx0 < d->S ? (d->S - kx0 + 1) / 2 : 0;
-                if (q.R == 0 || q.S == 0) { q.R = 0; q.S = 0; }
-                q.pad = (a + d->pad - ky0) / 2;
-                q.pad_x = (b + d->pad - kx0) / 2;
-                q.wt_ky0 = ky0; q.wt_kx0 = kx0;
-                q.o_a = a; q.o_b = b;
-                q.OH = Ha; q.OW = Wb;
-                q.M = d->N * Ha * Wb;
-                q.Ktot = q.R * q.S * q.Cs;
-                int rc = dispatch16<MODE_DGRAD>(q, d->tuning, st);
-                if (rc) return rc;
-            }
-        }
-        return SSCG_OK;
-    }
-    K16Split sp = plan16(p.M, p.Ng, p.Ktot, d->tuning);
-    if (fused && sp.splits > 1) {          // fused sums: the launch is not split (its partial tiles would need the sums in the reduction)
-        const int cfg = choose16(p.M, p.Ng, p.Ktot, d->tuning);
-        sp.splits = 1; sp.ksplit = p.Ktot / BK;
-        sp.full_tiles = cdiv(p.M, C16_BM[cfg]) * cdiv(p.Ng, C16_BN[cfg]); sp.m_tail0 = p.M;
-    }
-    if (sp.splits > 1 && (!ws || ws_bytes < split16_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
-    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
-    p.part = reinterpret_cast<float*>(ws);
+    k16_operands(p, d, true, dy, wt, bias, dx);
+    set_dgrad_geometry(p, d, act, slope);
+    if (dgrad16_by_parity(d))
+        return for_each_dgrad_parity_class(p, d, [&](const K16Params& q) { return dispatch16<MODE_DGRAD>(q, d->tuning, st); });
+    // fused sums or an addend: the launch is not split (its partial tiles' reduction knows neither)
+    const int rc = apply_split(p, plan16(p.M, p.Ng, p.Ktot, d->tuning, 0, bs || addend), ws, ws_bytes);
+    if (rc) return rc;
     return dispatch16<MODE_DGRAD>(p, d->tuning, st);
 }
 

@@ -27,6 +27,7 @@
 #include "sscg_internal.h"
 #include "bn_fold.h"
 #include "reduce_common.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -618,71 +619,17 @@ static int kc_choose_cfg(int M, int Ng, int Ktot, int Cs, int tuning) {
     return fast ? 6 : 3;
 }
 
-struct KcSplit { int splits, ksplit, full_tiles, m_tail0; };
-
-// Which tiles are cut along K, and how often.
-//  * few-channel heads (Ng <= 32) on few rows: every tile (one 128x32 tile column gives only M/128 workgroups);
-//  * 64x64-tile launches: only the TAIL - the tiles beyond the last whole round of 256 workgroups.  The DeepLab
-//    stride-8 maps give 8712 rows -> 548 tiles: 512 whole tiles (2 per CU) + 36 tail tiles cut in 7, so every CU gets
-//    2 1/7 tiles of work instead of 2 or 3 (71 % balance), and only 6.5 % of the output goes through partial sums.
-static KcSplit plan_kc_split_raw(int M, int Ng, int Ktot, int Cs, int tuning);
-
-// stat_L > 0: the launch also produces normalisation statistics.  Split tiles write partial sums, not results, so their
-// rows are summed separately (one extra group of records): they must all lie in ONE normalisation group.
-static KcSplit plan_kc_split(int M, int Ng, int Ktot, int Cs, int tuning, long stat_L = 0) {
-    KcSplit r = plan_kc_split_raw(M, Ng, Ktot, Cs, tuning);
-    if (stat_L > 0 && r.splits > 1 && (r.full_tiles == 0 || r.m_tail0 / stat_L != (M - 1) / stat_L)) {
-        const int cfg = kc_choose_cfg(M, Ng, Ktot, Cs, tuning);
-        r.splits = 1; r.ksplit = (Ktot + BK - 1) / BK;
-        r.full_tiles = cdiv(M, KC_BM[cfg]) * cdiv(Ng, KC_BN[cfg]); r.m_tail0 = M;
-    }
-    return r;
-}
-
-static KcSplit plan_kc_split_raw(int M, int Ng, int Ktot, int Cs, int tuning) {
-    const int nk = (Ktot + BK - 1) / BK;
+// The exact family's split policy (rules in conv_plan.h): k-tiles = ceil(Ktot / BK), the last one may be partial; the forced-split
+// bits of `tuning` count; few-channel heads split every tile (reductions of >= 32 k-tiles, pieces of >= 8); of the other classes only
+// the 64x64 tiles take the tail split.
+static ConvSplit plan_kc_split(int M, int Ng, int Ktot, int Cs, int tuning, long stat_L = 0) {
     const int cfg = kc_choose_cfg(M, Ng, Ktot, Cs, tuning);
-    const int force_split = (tuning >> 8) & 0xff;
-    const int bm = KC_BM[cfg], bn = KC_BN[cfg];
-    const int tiles_m = cdiv(M, bm), tiles_n = cdiv(Ng, bn);
-    const int tiles = tiles_m * tiles_n;
-    KcSplit r = {1, nk, tiles, M};
-    if (force_split == 1) return r;   // tuning: never split
-    if (force_split > 1) {            // tuning: split every tile
-        r.ksplit = cdiv(nk, force_split);
-        r.splits = cdiv(nk, r.ksplit);
-        r.full_tiles = 0; r.m_tail0 = 0;
-        return r;
-    }
-    if (Ng <= 32) {
-        if (tiles >= 256 || nk < 32) return r;
-        int s = cdiv(512, tiles);
-        if (s > nk / 8) s = nk / 8;
-        if (s > 32) s = 32;
-        if (s < 2) return r;
-        r.ksplit = cdiv(nk, s);
-        r.splits = cdiv(nk, r.ksplit);
-        r.full_tiles = 0; r.m_tail0 = 0;
-        return r;
-    }
-    if (bm != 64 || bn != 64 || nk < 8 || tiles > 2300) return r;
-    const int q = tiles / 256;
-    const int full_m = (q * 256) / tiles_n;          // whole tile rows handled unsplit
-    const int tail = tiles - full_m * tiles_n;
-    if (tail <= 0 || tail > 208) return r;             // an almost complete round is left alone
-    int s = 256 / tail;
-    if (s > 8) s = 8;
-    if (s > nk / 4) s = nk / 4;
-    if (s < 2) return r;
-    r.ksplit = cdiv(nk, s);
-    r.splits = cdiv(nk, r.ksplit);
-    r.full_tiles = full_m * tiles_n;
-    r.m_tail0 = full_m * bm;
-    return r;
-}
-
-static size_t kc_split_bytes(const KcSplit& sp, int M, int Ng) {
-    return sp.splits > 1 ? (size_t)sp.splits * (M - sp.m_tail0) * Ng * sizeof(float) : 0;
+    const ConvTiles t = conv_tiles(M, Ng, cdiv(Ktot, BK), KC_BM[cfg], KC_BN[cfg]);
+    ConvSplit sp = unsplit(t);
+    if (forced_split(t, tuning, &sp)) {}
+    else if (Ng <= 32) sp = split_heads(t, 32, 8);
+    else if (KC_BM[cfg] == 64 && KC_BN[cfg] == 64) sp = split_tail(t);
+    return keep_split_rows_in_one_group(sp, t, stat_L);
 }
 
 template <int MODE, int WM, int WN, int TM, int TN, int VEC, bool FAST, int NBUF = 2, bool DMA = false, int BF16 = 0, bool N4 = false>
@@ -690,15 +637,11 @@ int launch_kc(const KcParams& p0, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
     constexpr int BN = WN * TN * 32;
     KcParams p = p0;
-    p.tiles_n = cdiv(p.Ng, BN);
-    int tiles_m = cdiv(p.M, BM);
-    p.tiles = tiles_m * p.tiles_n;
+    const int grid = launch_prologue(p, BM, BN);
     constexpr int LDR = DMA ? BK : LDK;
     size_t smem = (size_t)(NBUF * BM * LDR + NBUF * BN * LDR) * sizeof(float) + (size_t)(p.R * p.S > 0 ? p.R * p.S : 1) * 8;
     auto kern = conv_kc_kernel<MODE, WM, WN, TM, TN, VEC, FAST, NBUF, DMA, BF16, N4>;
     SSCG_ENSURE_SMEM((kern), smem);
-    if (p.splits <= 1) { p.full_tiles = p.tiles; p.m_tail0 = p.M; }
-    const int grid = p.full_tiles + (p.tiles - p.full_tiles) * p.splits;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, p);
     SSCG_LAUNCH_CHECK();
     if (p.splits > 1) {
@@ -747,13 +690,6 @@ int dispatch_mode(const KcParams& p, hipStream_t st) {
 
 }  // namespace
 
-// launch walks every tap of a dense [R][S] weight and writes rows in order
-static void kc_dense_taps(KcParams& p) {
-    p.pad_x = p.pad; p.wKtot = p.Ktot;
-    p.wt_ky0 = 0; p.wt_kx0 = 0; p.wt_step = 1; p.wt_S = p.S;
-    p.o_step = 1; p.o_a = 0; p.o_b = 0; p.o_W = 0; p.o_HW = 0;
-}
-
 // stride-2 data gradients are decomposed into parity classes when the vectorised tap walk applies (K % BK == 0)
 static bool dgrad_by_parity(const sscg_conv_desc* d) {
     return (d->tuning & 0xff) == 0 && d->stride == 2 && d->dil == 1 && d->pad_mode == 0 && d->K % BK == 0;
@@ -782,7 +718,7 @@ extern "C" size_t sscg_conv2d_fwd_workspace(const sscg_conv_desc* d) {
     if (!d) return 0;
     if (sscg_conv16_fwd_applies(d)) return sscg_conv16_fwd_workspace(d, 0);
     if (sscg_convs_fwd_applies(d)) return sscg_convs_fwd_workspace(d, 0);
-    return kc_split_bytes(plan_kc_split(d->N * d->P * d->Q, d->K, d->R * d->S * d->C, d->C, d->tuning), d->N * d->P * d->Q, d->K);
+    return split_bytes(plan_kc_split(d->N * d->P * d->Q, d->K, d->R * d->S * d->C, d->C, d->tuning), d->N * d->P * d->Q, d->K);
 }
 
 extern "C" size_t sscg_conv2d_dgrad_workspace(const sscg_conv_desc* d) {
@@ -790,44 +726,38 @@ extern "C" size_t sscg_conv2d_dgrad_workspace(const sscg_conv_desc* d) {
     if (sscg_conv16_dgrad_applies(d)) return sscg_conv16_dgrad_workspace(d);
     if (sscg_convs_dgrad_applies(d)) return sscg_convs_dgrad_workspace(d);
     if (dgrad_by_parity(d)) return 0;
-    return kc_split_bytes(plan_kc_split(d->N * d->H * d->W, d->C, d->R * d->S * d->K, d->K, d->tuning), d->N * d->H * d->W, d->C);
+    return split_bytes(plan_kc_split(d->N * d->H * d->W, d->C, d->R * d->S * d->K, d->K, d->tuning), d->N * d->H * d->W, d->C);
 }
 
 // ---- fused normalisation statistics: layout of the `stats` buffer = [tiles_m * WM records][2][K][2] doubles, then the
 // records of the split-K rows [xrec][K][2]
-struct StatPlan { int tiles_m, bm, wm, valid_tiles, xrec, xgroup; long m_tail0; size_t main_bytes, bytes; };
+struct StatPlan { int tiles_m, bm, wm, valid_tiles, xrec, xgroup; size_t main_bytes, bytes; };
+
+// the exact family's records: fp32 operands, one record per wave row (4 in the 128x32 class, else 2); not the 4-column MFMA class
+static bool kc_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, ConvSplit* sp) {
+    if (d->x_dtype != SSCG_F32 || d->w_dtype != SSCG_F32) return false;
+    const int M = d->N * d->P * d->Q, Ktot = d->R * d->S * d->C;
+    const int cfg = kc_choose_cfg(M, d->K, Ktot, d->C, d->tuning);
+    if (cfg == 8 || L < KC_BM[cfg]) return false;
+    *bm = KC_BM[cfg];
+    *wm = (cfg == 4) ? 4 : 2;
+    *tiles_n = cdiv(d->K, KC_BN[cfg]);
+    *sp = plan_kc_split(M, d->K, Ktot, d->C, d->tuning, L);
+    return true;
+}
 
 static bool fwd_stats_plan(const sscg_conv_desc* d, int G, long L, StatPlan* sp) {
     const long M = (long)d->N * d->P * d->Q;
     if (G <= 0 || L <= 0 || (long)G * L != M || d->act != SSCG_ACT_NONE || d->K <= 32) return false;   // (thin 1x1 shapes keep the matrix-core path when statistics are asked for)
-    int splits;
-    if (sscg_conv16_fwd_applies(d) || sscg_convs_fwd_applies(d)) {
-        int full_tiles, m_tail0, tiles_n;
-        if (sscg_conv16_fwd_applies(d)) {
-            if (!sscg_conv16_stats_geometry(d, L, &sp->bm, &sp->wm, &tiles_n, &splits, &full_tiles, &m_tail0)) return false;
-        } else if (!sscg_convs_stats_geometry(d, L, &sp->bm, &sp->wm, &tiles_n, &splits, &full_tiles, &m_tail0)) {
-            return false;
-        }
-        sp->tiles_m = cdiv(M, sp->bm);
-        sp->valid_tiles = splits > 1 ? full_tiles / tiles_n : sp->tiles_m;
-        sp->m_tail0 = splits > 1 ? m_tail0 : M;
-    } else {
-        if (d->x_dtype != SSCG_F32 || d->w_dtype != SSCG_F32) return false;
-        const int Ktot = d->R * d->S * d->C;
-        const int cfg = kc_choose_cfg((int)M, d->K, Ktot, d->C, d->tuning);
-        if (cfg == 8) return false;
-        sp->bm = KC_BM[cfg];
-        sp->wm = (cfg == 4) ? 4 : 2;
-        if (L < sp->bm) return false;
-        KcSplit ks = plan_kc_split((int)M, d->K, Ktot, d->C, d->tuning, L);
-        sp->tiles_m = cdiv(M, sp->bm);
-        const int tiles_n = cdiv(d->K, KC_BN[cfg]);
-        splits = ks.splits;
-        sp->valid_tiles = splits > 1 ? ks.full_tiles / tiles_n : sp->tiles_m;
-        sp->m_tail0 = splits > 1 ? ks.m_tail0 : M;
-    }
-    sp->xrec = sp->m_tail0 < M ? split_stats_records(M - sp->m_tail0, d->K) : 0;
-    sp->xgroup = sp->m_tail0 < M ? (int)(sp->m_tail0 / L) : -1;
+    const auto geometry = sscg_conv16_fwd_applies(d) ? sscg_conv16_stats_geometry : sscg_convs_fwd_applies(d) ? sscg_convs_stats_geometry : kc_stats_geometry;
+    int tiles_n;
+    ConvSplit ks;
+    if (!geometry(d, L, &sp->bm, &sp->wm, &tiles_n, &ks)) return false;
+    sp->tiles_m = cdiv(M, sp->bm);
+    sp->valid_tiles = ks.splits > 1 ? ks.full_tiles / tiles_n : sp->tiles_m;
+    const long tail0 = ks.splits > 1 ? ks.m_tail0 : M;        // first row whose statistics come out of the split reduction
+    sp->xrec = tail0 < M ? split_stats_records(M - tail0, d->K) : 0;
+    sp->xgroup = tail0 < M ? (int)(tail0 / L) : -1;
     sp->main_bytes = (size_t)sp->tiles_m * sp->wm * 2 * d->K * 2 * sizeof(double);
     sp->bytes = sp->main_bytes + (size_t)sp->xrec * d->K * 2 * sizeof(double);
     return true;
@@ -857,16 +787,10 @@ static int conv_fwd_impl(const sscg_conv_desc* d, const void* x, const void* w, 
     KcParams p = {};
     p.src = reinterpret_cast<const float*>(x); p.wgt = reinterpret_cast<const float*>(w); p.bias = bias; p.dst = y;
     p.out_bf16 = d->y_dtype == SSCG_BF16; p.precision = d->precision; p.tuning = d->tuning;
-    p.M = d->N * d->P * d->Q; p.Ng = d->K; p.Cs = d->C; p.Ktot = d->R * d->S * d->C;
-    p.SH = d->H; p.SW = d->W; p.OH = d->P; p.OW = d->Q;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.pad_mode = d->pad_mode; p.act = d->act; p.slope = d->slope; p.tiles_n = 0; p.tiles = 0;
+    set_fwd_geometry(p, d);
     p.stats = stats; p.stat_L = (int)stat_L; p.xstats = xstats;
-    kc_dense_taps(p);
-    KcSplit sp = plan_kc_split(p.M, p.Ng, p.Ktot, p.Cs, p.tuning, stats ? stat_L : 0);
-    if (sp.splits > 1 && (!ws || ws_bytes < kc_split_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
-    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
-    p.part = reinterpret_cast<float*>(ws);
+    rc = apply_split(p, plan_kc_split(p.M, p.Ng, p.Ktot, p.Cs, p.tuning, stats ? stat_L : 0), ws, ws_bytes);
+    if (rc) return rc;
     return dispatch_mode<MODE_FWD>(p, (hipStream_t)stream);
 }
 
@@ -967,44 +891,11 @@ extern "C" int sscg_conv2d_dgrad(const sscg_conv_desc* d, const void* dy, const 
     KcParams p = {};
     p.src = reinterpret_cast<const float*>(dy); p.wgt = reinterpret_cast<const float*>(wt); p.bias = bias; p.dst = dx;
     p.out_bf16 = d->x_dtype == SSCG_BF16; p.precision = d->precision; p.tuning = d->tuning;
-    p.M = d->N * d->H * d->W; p.Ng = d->C; p.Cs = d->K; p.Ktot = d->R * d->S * d->K;
-    p.SH = d->P; p.SW = d->Q; p.OH = d->H; p.OW = d->W;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.pad_mode = 0; p.act = act; p.slope = slope; p.tiles_n = 0; p.tiles = 0;
-    kc_dense_taps(p);
-    if (dgrad_by_parity(d)) {
-        // Stride 2: an output pixel (2i+a, 2j+b) only meets the taps with ky = a+pad, kx = b+pad (mod 2).  Each of the
-        // four parity classes is a stride-1 data gradient over its own sub-lattice of taps, written interleaved into
-        // dx: a quarter of the multiply-adds of walking all R*S taps with three quarters of them masked.
-        p.splits = 1; p.ksplit = 0; p.part = nullptr;
-        p.stride = 1; p.wt_step = 2; p.wt_S = d->S;
-        p.o_step = 2; p.o_W = d->W; p.o_HW = d->H * d->W;
-        for (int a = 0; a < 2; ++a) {
-            for (int b = 0; b < 2; ++b) {
-                const int Ha = (d->H - a + 1) / 2, Wb = (d->W - b + 1) / 2;
-                if (Ha <= 0 || Wb <= 0) continue;
-                const int ky0 = (a + d->pad) & 1, kx0 = (b + d->pad) & 1;
-                KcParams q = p;
-                q.R = ky0 < d->R ? (d->R - ky0 + 1) / 2 : 0;
-                q.S = kx0 < d->S ? (d->S - kx0 + 1) / 2 : 0;
-                if (q.R == 0 || q.S == 0) { q.R = 0; q.S = 0; }     // no tap meets this class: dx = act(bias)
-                q.pad = (a + d->pad - ky0) / 2;
-                q.pad_x = (b + d->pad - kx0) / 2;
-                q.wt_ky0 = ky0; q.wt_kx0 = kx0;
-                q.o_a = a; q.o_b = b;
-                q.OH = Ha; q.OW = Wb;
-                q.M = d->N * Ha * Wb;
-                q.Ktot = q.R * q.S * q.Cs;
-                rc = dispatch_mode<MODE_DGRAD>(q, (hipStream_t)stream);
-                if (rc) return rc;
-            }
-        }
-        return SSCG_OK;
-    }
-    KcSplit sp = plan_kc_split(p.M, p.Ng, p.Ktot, p.Cs, p.tuning);
-    if (sp.splits > 1 && (!ws || ws_bytes < kc_split_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
-    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
-    p.part = reinterpret_cast<float*>(ws);
+    set_dgrad_geometry(p, d, act, slope);
+    if (dgrad_by_parity(d))
+        return for_each_dgrad_parity_class(p, d, [&](const KcParams& q) { return dispatch_mode<MODE_DGRAD>(q, (hipStream_t)stream); });
+    rc = apply_split(p, plan_kc_split(p.M, p.Ng, p.Ktot, p.Cs, p.tuning), ws, ws_bytes);
+    if (rc) return rc;
     return dispatch_mode<MODE_DGRAD>(p, (hipStream_t)stream);
 }
 

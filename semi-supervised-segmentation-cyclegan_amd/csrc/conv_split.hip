@@ -26,6 +26,7 @@
 #include "sscg_internal.h"
 #include "reduce_common.h"
 #include "bn_fold.h"
+#include "conv_plan.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1094,13 +1095,9 @@ __global__ __launch_bounds__(256) void ks_reduce1_kernel(const float* __restrict
     y[i] = sscg_act(s + (bias ? bias[(int)(i % Ng)] : 0.f), act, slope);
 }
 
-
-#ifndef KS_STAGE_OUT
-#define KS_STAGE_OUT 1
-#endif
 constexpr bool KS_STAGE_OUT_HOST = KS_STAGE_OUT != 0;      // the addend joins in the staged store phase
 
-// ---- host side: tile classes and the split-K plan of the tail (same policy as conv_igemm.hip)
+// ---- host side: tile classes and the split-K plan (conv_plan.h)
 enum { KS_128x128 = 0, KS_64x64 = 1, KS_128x64 = 2, KS_128x32 = 3, KS_NCFG = 4 };
 const int KS_BM[KS_NCFG] = {128, 64, 128, 128};
 const int KS_BN[KS_NCFG] = {128, 64, 64, 32};
@@ -1146,53 +1143,15 @@ int ks_choose(long M, int Ng, int Ktot, int tuning) {
     if (Ktot >= K12864 && tm * cdiv(Ng, 64) >= T12864) return KS_128x64;
     return KS_64x64;
 }
-struct KsSplit { int splits, ksplit, full_tiles, m_tail0; };
 
-KsSplit ks_plan_raw(long M, int Ng, int Ktot, int tuning) {
-    const int nk = Ktot / BKS;
+// The split family's split policy (rules in conv_plan.h): k-tiles = Ktot / BKS, whole ones (Cs % BKS == 0); the forced-split bits of
+// `tuning` count; no heads rule; every class takes the tail split.  `fused`: the launch takes backward sums in its store phase.
+ConvSplit ks_plan(long M, int Ng, int Ktot, int tuning, long stat_L = 0, bool fused = false) {
     const int cfg = ks_choose(M, Ng, Ktot, tuning);
-    const int bm = KS_BM[cfg], bn = KS_BN[cfg];
-    const int tiles_m = cdiv(M, bm), tiles_n = cdiv(Ng, bn);
-    const int tiles = tiles_m * tiles_n;
-    KsSplit r = {1, nk, tiles, (int)M};
-    const int force = (tuning >> 8) & 0xff;         // 1 = never split, n > 1 = every tile cut in n
-    if (force == 1) return r;
-    if (force > 1) {
-        r.ksplit = cdiv(nk, force);
-        r.splits = cdiv(nk, r.ksplit);
-        r.full_tiles = 0; r.m_tail0 = 0;
-        return r;
-    }
-    if (nk < 8 || tiles > 2300) return r;
-    const int q = tiles / 256;
-    const int full_m = (q * 256) / tiles_n;
-    const int tail = tiles - full_m * tiles_n;
-    if (tail <= 0 || tail > 208) return r;
-    int s = 256 / tail;
-    if (s > 8) s = 8;
-    if (s > nk / 4) s = nk / 4;
-    if (s < 2) return r;
-    r.ksplit = cdiv(nk, s);
-    r.splits = cdiv(nk, r.ksplit);
-    r.full_tiles = full_m * tiles_n;
-    r.m_tail0 = full_m * bm;
-    return r;
-}
-
-// stat_L > 0: the launch also produces normalisation statistics; the rows of split tiles are summed separately as ONE extra group of
-// records, so they must lie in one normalisation group (else the launch is not split).
-KsSplit ks_plan(long M, int Ng, int Ktot, int tuning, long stat_L = 0) {
-    KsSplit r = ks_plan_raw(M, Ng, Ktot, tuning);
-    if (stat_L > 0 && r.splits > 1 && (r.full_tiles == 0 || r.m_tail0 / stat_L != (M - 1) / stat_L)) {
-        const int cfg = ks_choose(M, Ng, Ktot, tuning);
-        r.splits = 1; r.ksplit = Ktot / BKS;
-        r.full_tiles = cdiv(M, KS_BM[cfg]) * cdiv(Ng, KS_BN[cfg]); r.m_tail0 = (int)M;
-    }
-    return r;
-}
-
-size_t ks_split_bytes(const KsSplit& sp, long M, int Ng) {
-    return sp.splits > 1 ? (size_t)sp.splits * (M - sp.m_tail0) * Ng * sizeof(float) : 0;
+    const ConvTiles t = conv_tiles(M, Ng, Ktot / BKS, KS_BM[cfg], KS_BN[cfg]);
+    ConvSplit sp;
+    if (!forced_split(t, tuning, &sp)) sp = split_tail(t);
+    return no_split_with_fused_epilogue(keep_split_rows_in_one_group(sp, t, stat_L), t, fused);
 }
 
 template <int MODE, int WM, int WN, int TM, int TN, int CIN = 0, bool AFF = false>
@@ -1201,17 +1160,10 @@ int launch_ks(const KsParams& p0, hipStream_t st) {
     constexpr int BN = WN * TN * 32;
     constexpr int NT = WM * WN * 64;
     KsParams p = p0;
-    p.div_hw = make_fastdiv(p.OH * p.OW);
-    p.div_w = make_fastdiv(p.OW);
-    p.tiles_n = cdiv(p.Ng, BN);
-    p.div_tn = make_fastdiv(p.tiles_n);
-    p.div_gl = make_fastdiv((MODE == MODE_DGRAD && p.bn_sums != nullptr) ? p.bn_L : (p.stat_L > 0 ? p.stat_L : 1));
-    p.tiles = cdiv(p.M, BM) * p.tiles_n;
+    const int grid = launch_prologue(p, BM, BN);
     const size_t smem = (size_t)2 * (BM * 128 + 3 * BN * 64);
     auto kern = convs_kernel<MODE, WM, WN, TM, TN, CIN, AFF>;
     SSCG_ENSURE_SMEM((kern), smem);
-    if (p.splits <= 1) { p.full_tiles = p.tiles; p.m_tail0 = p.M; }
-    const int grid = p.full_tiles + (p.tiles - p.full_tiles) * p.splits;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), smem, st, p);
     SSCG_LAUNCH_CHECK();
     if (p.splits > 1) {
@@ -1267,12 +1219,6 @@ int dispatch_ks_front(const KsParams& p, int tuning, hipStream_t st) {
     }
 }
 
-void ks_dense_taps(KsParams& p) {
-    p.pad_x = p.pad; p.wKtot = p.Ktot;
-    p.wt_ky0 = 0; p.wt_kx0 = 0; p.wt_step = 1; p.wt_S = p.S;
-    p.o_step = 1; p.o_a = 0; p.o_b = 0; p.o_W = 0; p.o_HW = 0;
-}
-
 bool ks_dgrad_by_parity(const sscg_conv_desc* d) { return d->stride == 2 && d->dil == 1 && d->pad_mode == 0; }
 
 long ks_plane(const sscg_conv_desc* d) { return d->w_plane > 0 ? (long)d->w_plane : (long)d->K * d->R * d->S * d->C; }
@@ -1321,10 +1267,21 @@ __global__ void krsc_to_crsk_split_kernel(const float* __restrict__ w, bf16* __r
 
 // ---- entry points used by conv_igemm.hip's dispatch
 // the copies address both operands through 32-bit buffer offsets, a masked row's offset (2 GB) must lie outside the tensor
+static size_t ks_src_bytes(const sscg_conv_desc* d, bool dgrad) {
+    return (dgrad ? (size_t)d->N * d->P * d->Q * d->K : (size_t)d->N * d->H * d->W * d->C) * sizeof(float);
+}
+static size_t ks_wgt_bytes(const sscg_conv_desc* d) { return ((size_t)2 * ks_plane(d) + (size_t)d->K * d->R * d->S * d->C) * sizeof(bf16); }
+
 static bool ks_extents_ok(const sscg_conv_desc* d, bool dgrad) {
-    const size_t src = (dgrad ? (size_t)d->N * d->P * d->Q * d->K : (size_t)d->N * d->H * d->W * d->C) * sizeof(float);
-    const size_t wgt = ((size_t)2 * ks_plane(d) + (size_t)d->K * d->R * d->S * d->C) * sizeof(bf16);
-    return src < ((size_t)1 << 31) && wgt < ((size_t)1 << 31);
+    return ks_src_bytes(d, dgrad) < ((size_t)1 << 31) && ks_wgt_bytes(d) < ((size_t)1 << 31);
+}
+
+// the two operands with their buffer extents, bias and destination; src = x of a forward, dy of a data gradient
+static void ks_operands(KsParams& p, const sscg_conv_desc* d, bool dgrad, const void* src, const void* w, const float* bias, void* dst) {
+    p.src = reinterpret_cast<const float*>(src); p.wgt = reinterpret_cast<const bf16*>(w); p.wplane = ks_plane(d);
+    p.bias = bias; p.dst = reinterpret_cast<float*>(dst);
+    p.src_bytes = (unsigned)ks_src_bytes(d, dgrad);
+    p.wgt_bytes = (unsigned)ks_wgt_bytes(d);
 }
 
 bool sscg_convs_fwd_applies(const sscg_conv_desc* d) {
@@ -1339,46 +1296,36 @@ bool sscg_convs_dgrad_applies(const sscg_conv_desc* d) {
            d->pad_mode == 0 && d->stride <= 2 && ks_extents_ok(d, true);
 }
 
-bool sscg_convs_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, int* splits, int* full_tiles, int* m_tail0) {
+bool sscg_convs_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, ConvSplit* sp) {
     const long M = (long)d->N * d->P * d->Q;
     const int cfg = ks_choose(M, d->K, d->R * d->S * d->C, d->tuning);
     if (L < KS_BM[cfg] || (d->K & 3)) return false;       // (the epilogue's statistics ride on the staged tile: Ng % 4 == 0)
     *bm = KS_BM[cfg];
     *wm = 1;                                // one record per tile (round 6: the wave rows meet in LDS)
     *tiles_n = cdiv(d->K, KS_BN[cfg]);
-    KsSplit sp = ks_plan(M, d->K, d->R * d->S * d->C, d->tuning, L);
-    *splits = sp.splits; *full_tiles = sp.full_tiles; *m_tail0 = sp.m_tail0;
+    *sp = ks_plan(M, d->K, d->R * d->S * d->C, d->tuning, L);
     return true;
 }
 
 size_t sscg_convs_fwd_workspace(const sscg_conv_desc* d, long stat_L) {
     const long M = (long)d->N * d->P * d->Q;
-    return ks_split_bytes(ks_plan(M, d->K, d->R * d->S * d->C, d->tuning, stat_L), M, d->K);
+    return split_bytes(ks_plan(M, d->K, d->R * d->S * d->C, d->tuning, stat_L), M, d->K);
 }
 
 size_t sscg_convs_dgrad_workspace(const sscg_conv_desc* d) {
     if (ks_dgrad_by_parity(d)) return 0;
     const long M = (long)d->N * d->H * d->W;
-    return ks_split_bytes(ks_plan(M, d->C, d->R * d->S * d->K, d->tuning), M, d->C);
+    return split_bytes(ks_plan(M, d->C, d->R * d->S * d->K, d->tuning), M, d->C);
 }
 
 int sscg_convs_fwd(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, double* stats, long stat_L,
                    double* xstats, void* ws, size_t ws_bytes, hipStream_t st) {
     KsParams p = {};
-    p.src = reinterpret_cast<const float*>(x); p.wgt = reinterpret_cast<const bf16*>(w); p.wplane = ks_plane(d);
-    p.bias = bias; p.dst = reinterpret_cast<float*>(y);
-    p.M = d->N * d->P * d->Q; p.Ng = d->K; p.Cs = d->C; p.Ktot = d->R * d->S * d->C;
-    p.SH = d->H; p.SW = d->W; p.OH = d->P; p.OW = d->Q;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.pad_mode = d->pad_mode; p.act = d->act; p.slope = d->slope;
+    ks_operands(p, d, false, x, w, bias, y);
+    set_fwd_geometry(p, d);
     p.stats = stats; p.stat_L = (int)stat_L; p.xstats = xstats;
-    p.src_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->C * sizeof(float));
-    p.wgt_bytes = (unsigned)(((size_t)2 * p.wplane + (size_t)d->K * d->R * d->S * d->C) * sizeof(bf16));
-    ks_dense_taps(p);
-    KsSplit sp = ks_plan(p.M, p.Ng, p.Ktot, d->tuning, stats ? stat_L : 0);
-    if (sp.splits > 1 && (!ws || ws_bytes < ks_split_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
-    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
-    p.part = reinterpret_cast<float*>(ws);
+    const int rc = apply_split(p, ks_plan(p.M, p.Ng, p.Ktot, d->tuning, stats ? stat_L : 0), ws, ws_bytes);
+    if (rc) return rc;
     return dispatch_ks<MODE_FWD>(p, d->tuning, st);
 }
 
@@ -1394,21 +1341,12 @@ int sscg_convs_fwd_affine(const sscg_conv_desc* d, const void* x, const void* w,
                           void* ws, size_t ws_bytes, hipStream_t st) {
     if (!sscg_convs_affine_applies(d)) return SSCG_ERR_UNSUPPORTED;
     KsParams p = {};
-    p.src = reinterpret_cast<const float*>(x); p.wgt = reinterpret_cast<const bf16*>(w); p.wplane = ks_plane(d);
-    p.bias = bias; p.dst = reinterpret_cast<float*>(y);
-    p.M = d->N * d->P * d->Q; p.Ng = d->K; p.Cs = d->C; p.Ktot = d->R * d->S * d->C;
-    p.SH = d->H; p.SW = d->W; p.OH = d->P; p.OW = d->Q;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.pad_mode = d->pad_mode; p.act = d->act; p.slope = d->slope;
-    p.src_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->C * sizeof(float));
-    p.wgt_bytes = (unsigned)(((size_t)2 * p.wplane + (size_t)d->K * d->R * d->S * d->C) * sizeof(bf16));
+    ks_operands(p, d, false, x, w, bias, y);
+    set_fwd_geometry(p, d);
     p.af_mean = bn.mean; p.af_var = bn.var; p.af_gamma = bn.gamma; p.af_beta = bn.beta; p.af_eps = bn.eps;
     p.af_res = reinterpret_cast<const float*>(bn.residual);
-    ks_dense_taps(p);
-    KsSplit sp = ks_plan(p.M, p.Ng, p.Ktot, d->tuning, 0);
-    if (sp.splits > 1 && (!ws || ws_bytes < ks_split_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
-    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
-    p.part = reinterpret_cast<float*>(ws);
+    const int rc = apply_split(p, ks_plan(p.M, p.Ng, p.Ktot, d->tuning), ws, ws_bytes);
+    if (rc) return rc;
     return dispatch_ks_affine(p, d->tuning, st);
 }
 
@@ -1431,18 +1369,13 @@ int sscg_convs_fwd_front(const sscg_conv_desc* d, const void* xf, int cin, const
     if (!sscg_convs_front_applies(d, cin)) return SSCG_ERR_UNSUPPORTED;
     KsParams p = {};
     p.fr_x = reinterpret_cast<const float*>(xf); p.fr_w1 = w1; p.fr_b1 = b1; p.fr_slope = slope1; p.fr_h1 = reinterpret_cast<float*>(h1);
-    p.src = nullptr; p.wgt = reinterpret_cast<const bf16*>(w); p.wplane = ks_plane(d);
-    p.bias = bias; p.dst = reinterpret_cast<float*>(y);
-    p.M = d->N * d->P * d->Q; p.Ng = d->K; p.Cs = d->C; p.Ktot = d->C;
-    p.SH = d->H; p.SW = d->W; p.OH = d->P; p.OW = d->Q;
-    p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.dil = 1;
-    p.pad_mode = 0; p.act = d->act; p.slope = d->slope;
-    p.stats = stats; p.stat_L = (int)stat_L; p.xstats = nullptr;
-    p.src_bytes = 0;
-    p.wgt_bytes = (unsigned)(((size_t)2 * p.wplane + (size_t)d->K * d->C) * sizeof(bf16));
-    ks_dense_taps(p);
-    p.splits = 1; p.ksplit = p.Ktot / BKS; p.full_tiles = 0; p.m_tail0 = p.M;      // (launch_ks sets full_tiles / m_tail0 of an unsplit launch)
-    p.part = nullptr;
+    ks_operands(p, d, false, nullptr, w, bias, y);
+    p.src_bytes = 0;            // the A operand is formed in the prologue, not read
+    set_fwd_geometry(p, d);     // (sscg_convs_front_applies: 1x1, stride 1, no padding, unsplit)
+    p.dil = 1;
+    p.stats = stats; p.stat_L = (int)stat_L;
+    const int rc = apply_split(p, ks_plan(p.M, p.Ng, p.Ktot, d->tuning), nullptr, 0);
+    if (rc) return rc;
     switch (cin) {
         case 3: return dispatch_ks_front<3>(p, d->tuning, st);
         case 4: return dispatch_ks_front<4>(p, d->tuning, st);
@@ -1458,13 +1391,7 @@ int sscg_convs_fwd_front(const sscg_conv_desc* d, const void* xf, int cin, const
 bool sscg_convs_bsums_geometry(const sscg_conv_desc* d, int G, long L, int* bm, int* wm, int* chunks) {
     if (!sscg_convs_dgrad_applies(d) || ks_dgrad_by_parity(d) || d->stride != 1) return false;
     const long M = (long)d->N * d->H * d->W;
-    if (G <= 0 || L <= 0 || (long)G * L != M) return false;
-    const int cfg = ks_choose(M, d->C, d->R * d->S * d->K, d->tuning);
-    if (L < KS_BM[cfg]) return false;
-    *bm = KS_BM[cfg];
-    *wm = 1;                                // one record per tile and group (the sums are taken in the store phase, per workgroup)
-    *chunks = (int)(cdiv(L, (long)KS_BM[cfg]) + 1);
-    return true;
+    return bsums_record_geometry(M, G, L, KS_BM[ks_choose(M, d->C, d->R * d->S * d->K, d->tuning)], bm, wm, chunks);
 }
 
 int sscg_convs_dgrad(const sscg_conv_desc* d, const void* dy, const void* wt, const float* bias, void* dx, int act, float slope,
@@ -1482,49 +1409,16 @@ int sscg_convs_dgrad(const sscg_conv_desc* d, const void* dy, const void* wt, co
         p.bn_act = bs->act; p.bn_slope = bs->slope;
         p.bn_z = reinterpret_cast<const float*>(bs->nz);
     }
-    p.src = reinterpret_cast<const float*>(dy); p.wgt = reinterpret_cast<const bf16*>(wt); p.wplane = ks_plane(d);
-    p.bias = bias; p.dst = reinterpret_cast<float*>(dx);
-    p.M = d->N * d->H * d->W; p.Ng = d->C; p.Cs = d->K; p.Ktot = d->R * d->S * d->K;
-    p.SH = d->P; p.SW = d->Q; p.OH = d->H; p.OW = d->W;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.pad_mode = 0; p.act = act; p.slope = slope;
-    p.src_bytes = (unsigned)((size_t)d->N * d->P * d->Q * d->K * sizeof(float));
-    p.wgt_bytes = (unsigned)(((size_t)2 * p.wplane + (size_t)d->K * d->R * d->S * d->C) * sizeof(bf16));
-    ks_dense_taps(p);
-    if (ks_dgrad_by_parity(d)) {
-        // stride 2: four parity classes, each a stride-1 data gradient over its sub-lattice of taps (conv_igemm.hip)
-        p.splits = 1; p.ksplit = 0; p.part = nullptr;
-        p.stride = 1; p.wt_step = 2; p.wt_S = d->S;
-        p.o_step = 2; p.o_W = d->W; p.o_HW = d->H * d->W;
-        for (int a = 0; a < 2; ++a) {
-            for (int b = 0; b < 2; ++b) {
-                const int Ha = (d->H - a + 1) / 2, Wb = (d->W - b + 1) / 2;
-                if (Ha <= 0 || Wb <= 0) continue;
-                const int ky0 = (a + d->pad) & 1, kx0 = (b + d->pad) & 1;
-                KsParams q = p;
-                q.R = ky0 < d->R ? (d->R - ky0 + 1) / 2 : 0;
-                q.S = kx0 < d->S ? (d->S - kx0 + 1) / 2 : 0;
-                if (q.R == 0 || q.S == 0) { q.R = 0; q.S = 0; }
-                q.pad = (a + d->pad - ky0) / 2;
-                q.pad_x = (b + d->pad - kx0) / 2;
-                q.wt_ky0 = ky0; q.wt_kx0 = kx0;
-                q.o_a = a; q.o_b = b;
-                q.OH = Ha; q.OW = Wb;
-                q.M = d->N * Ha * Wb;
-                q.Ktot = q.R * q.S * q.Cs;
-                int rc = dispatch_ks<MODE_DGRAD>(q, d->tuning & ~0xff00, st);
-                if (rc) return rc;
-            }
-        }
-        return SSCG_OK;
-    }
+    ks_operands(p, d, true, dy, wt, bias, dx);
+    set_dgrad_geometry(p, d, act, slope);
+    if (ks_dgrad_by_parity(d))      // (the classes are planned unsplit: the forced-split bits do not reach them)
+        return for_each_dgrad_parity_class(p, d, [&](const KsParams& q) { return dispatch_ks<MODE_DGRAD>(q, d->tuning & ~0xff00, st); });
     // Launches with fused sums are never split: the idle second round of a 276-tile launch costs ~16 us ALONE, but in the step the other
     // lanes' kernels fill it - a tail split whose reduction took the sums for its rows (built in round 6, bit-reproducible, 3x3 256 d2
     // 148 -> 121 us alone) left the step where it was (127.9 / 128.1 against 127.4 / 127.4 ms; profiles/r06_experiments.txt item 2).
-    KsSplit sp = ks_plan(p.M, p.Ng, p.Ktot, bs ? ((d->tuning & 0xff) | 0x100) : d->tuning);
-    if (sp.splits > 1 && (!ws || ws_bytes < ks_split_bytes(sp, p.M, p.Ng))) return SSCG_ERR_WORKSPACE;
-    p.splits = sp.splits; p.ksplit = sp.ksplit; p.full_tiles = sp.full_tiles; p.m_tail0 = sp.m_tail0;
-    p.part = reinterpret_cast<float*>(ws);
+    // A launch with an addend may split: its reduction adds the addend.
+    const int rc = apply_split(p, ks_plan(p.M, p.Ng, p.Ktot, d->tuning, 0, bs != nullptr), ws, ws_bytes);
+    if (rc) return rc;
     return dispatch_ks<MODE_DGRAD>(p, d->tuning, st);
 }
 

@@ -5,10 +5,11 @@
 #include "../../include/sscg.h"
 
 struct sscg_bsums;
+struct ConvSplit;      // conv_plan.h: the split-K plan of a launch
 // conv_bf16.hip: bf16 MFMA kernels behind sscg_conv2d_{fwd,dgrad,wgrad} (dispatch lives in conv_igemm.hip / conv_wgrad.hip)
 bool sscg_conv16_fwd_applies(const sscg_conv_desc* d);
 bool sscg_conv16_dgrad_applies(const sscg_conv_desc* d);
-bool sscg_conv16_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, int* splits, int* full_tiles, int* m_tail0);
+bool sscg_conv16_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, ConvSplit* sp);
 size_t sscg_conv16_fwd_workspace(const sscg_conv_desc* d, long stat_L);
 size_t sscg_conv16_dgrad_workspace(const sscg_conv_desc* d);
 int sscg_conv16_fwd(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, double* stats, long stat_L,
@@ -23,7 +24,7 @@ int sscg_wgrad16(const sscg_conv_desc* d, const void* x, const void* dy, float* 
 // conv_split.hip: fp32-accurate "split" contraction on the bf16 matrix cores (fp32 activations, w_dtype == SSCG_BF16X3)
 bool sscg_convs_fwd_applies(const sscg_conv_desc* d);
 bool sscg_convs_dgrad_applies(const sscg_conv_desc* d);
-bool sscg_convs_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, int* splits, int* full_tiles, int* m_tail0);
+bool sscg_convs_stats_geometry(const sscg_conv_desc* d, long L, int* bm, int* wm, int* tiles_n, ConvSplit* sp);
 size_t sscg_convs_fwd_workspace(const sscg_conv_desc* d, long stat_L);
 size_t sscg_convs_dgrad_workspace(const sscg_conv_desc* d);
 int sscg_convs_fwd(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, double* stats, long stat_L,

@@ -65,6 +65,8 @@ CONV16 = [
     (2, 256, 33, 33, 512, 1, 2, 0, 1),      # stride-2 1x1 downsample: three of the four dgrad parity classes meet no tap
     (2, 64, 64, 64, 128, 3, 2, 1, 1),       # ResnetGenerator down-conv: dgrad by parity class
     (2, 128, 32, 32, 256, 4, 2, 1, 1),      # PatchGAN 4x4 stride 2
+    (2, 64, 17, 15, 64, 3, 2, 1, 1),        # stride 2 on an odd map: the four dgrad parity classes differ per axis, one meets a single tap
+    (2, 64, 16, 16, 128, 4, 2, 1, 1),       # 4x4 stride 2 on a small map
     (4, 512, 33, 33, 512, 3, 1, 4, 4),      # layer4 conv2, dilation 4
     (16, 256, 33, 65, 256, 3, 1, 2, 2),     # config-3 geometry (Cityscapes 256x512, batch 16): 128x128 tiles
     (2, 64, 128, 256, 64, 3, 1, 1, 1),      # 128x64 tiles (64 output channels on many rows)

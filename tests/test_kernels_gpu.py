@@ -45,6 +45,8 @@ CONV_CASES = [
     (2, 128, 16, 16, 256, 4, 2, 1, 1, 0, 1, 0),    # PatchGAN conv3
     (2, 256, 9, 9, 512, 4, 1, 1, 1, 0, 1, 0),      # PatchGAN conv4 (stride 1)
     (1, 20, 17, 19, 36, 3, 1, 1, 1, 0, 1, 1),      # ragged everything + relu
+    (2, 64, 17, 15, 64, 3, 2, 1, 1, 0, 1, 0),      # stride 2 on an odd map: the four dgrad parity classes differ per axis, one meets a single tap
+    (2, 64, 16, 16, 128, 4, 2, 1, 1, 0, 1, 0),     # 4x4 stride 2: every parity class walks 2x2 taps
     # bench-size maps: whole rounds of tiles unsplit + a K-split tail (plan_kc_split), cost-model wgrad plans
     (8, 256, 33, 33, 256, 3, 1, 2, 2, 0, 1, 0),    # 548 tiles = 512 whole + 36 split; bias in the tail reduce (no ReLU: 2.2 M
                                                    # outputs always hold a few within fp32 rounding of 0, whose mask flips vs fp64)
