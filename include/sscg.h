@@ -374,6 +374,34 @@ int sscg_upsample_head_bwd(const float* x, const float* dy_soft, const float* dl
 int sscg_predict_head(const float* x, int N, int H, int W, int C, int OH, int OW, int64_t* index, uint8_t* label_u8,
                       const int64_t* label_true, int64_t* hist, void* stream);
 int sscg_image_head(const float* x, int N, int H, int W, int C, int OH, int OW, float* y_nhwc, uint8_t* rgb_u8, void* stream);
+/* ------------------------------------------------------------------ multi-scale / mirrored inference: several views of one batch
+ * (the network run on resized and / or horizontally mirrored copies of the images) fused into one label map, the way DeepLab-v2 nets
+ * are conventionally evaluated.  The reference evaluates one view only, so there is no call site to name; opt-in (`--tta`), forward
+ * only, never launched by the training step.  (An addition: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.)
+ *
+ * sscg_predict_head_ms: xs / Hs / Ws are HOST arrays of length S (1 <= S <= 8), read during the call and copied into the kernel's
+ * arguments (no pointer table on the device, no host sync): xs[s] = device pointer to view s's logits [N][Hs[s]][Ws[s]][C] fp32,
+ * C <= 64.  Bit s of flip_mask: view s was computed from the horizontally mirrored image, its map is in mirrored coordinates.
+ * Per output pixel (n, oy, ox), for s = 0 .. S-1 in that order: the source column ox_s = flip ? OW-1-ox : ox; the bilinear resize of
+ * view s at (oy, ox_s) with align_corners=True (sscg_upsample_bilinear_fwd's arithmetic; Hs[s] == OH && Ws[s] == OW is the identity
+ * resize, no interpolation arithmetic); the softmax over C (sscg_softmax_fwd's); acc[c] = s == 0 ? p[c] : acc[c] + p[c], the
+ * probability rounded to fp32 before the add.  Then the first maximum of acc[] (sscg_argmax_onehot's rule).  No division by S.
+ * Every output equals the separate passes' bit for bit - per view sscg_upsample_bilinear_fwd, a mirror of the W axis where flagged,
+ * sscg_softmax_fwd, an fp32 add into the accumulator; then sscg_argmax_onehot's index and sscg_confusion_hist - and with S = 1,
+ * flip_mask = 0 it equals sscg_predict_head's.  Neither the resized logits nor a view's probabilities reach memory.
+ *   prob_sum   (nullable) fp32 [N][OH][OW][C]: the SUM of the views' probabilities;
+ *   index / label_u8 / label_true + hist: exactly as in sscg_predict_head (hist accumulated into, t outside [0, C) ignored).
+ * At least one output is required.  Errors before any HIP call: SSCG_ERR_BAD_ARG (null xs / Hs / Ws or a null xs[s]; S outside 1..8;
+ * flip bits at or above S; non-positive sizes; C outside 1..64; no output; label_true without hist or the reverse),
+ * SSCG_ERR_UNSUPPORTED (N*OH*OW, or N*OH*OW*C with prob_sum, >= 2^31).
+ *
+ * sscg_resize_flip: the network input of one view from the batch, x [N][H][W][C] -> y [N][OH][OW][C]: sscg_upsample_bilinear_fwd's
+ * arithmetic (bilinear, align_corners=True, no antialiasing: a minifying resize samples) with the output columns mirrored when flip
+ * != 0 - y[n][oy][ox] = resized[n][oy][OW-1-ox], bit for bit sscg_upsample_bilinear_fwd followed by a flip of the W axis.
+ * OH == H && OW == W with flip is a pure mirror copy. */
+int sscg_predict_head_ms(const float* const* xs, const int* Hs, const int* Ws, int S, uint32_t flip_mask, int N, int C, int OH, int OW,
+                         float* prob_sum, int64_t* index, uint8_t* label_u8, const int64_t* label_true, int64_t* hist, void* stream);
+int sscg_resize_flip(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, int flip, void* stream);
 /* ------------------------------------------------------------------ per-epoch image panels: the image grids the reference sends to
  * TensorBoard at the end of every epoch (model.py:576-638; supervised_model: model.py:164-186), without the host round trip of
  * full-resolution maps, the per-pixel Python loop of utils.PIL_to_tensor (utils.py:59-94) and make_grid on the host.  Forward only;

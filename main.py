@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
---as_written, --augment, --panels.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--as_written, --augment, --panels, --tta.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -58,6 +58,10 @@ def get_args(argv=None):
     parser.add_argument("--panels", type=str, default=None, metavar="DIR",
                         help="write the reference's per-epoch image panels (model.py:576-638) to DIR/epoch%%03d_<n>.png, and to a "
                              "tensorboardX.SummaryWriter(DIR) when that module is installed (default: off)")
+    parser.add_argument("--tta", type=str, default="", metavar="SPEC",
+                        help="multi-scale / mirrored inference in the per-epoch evaluation, --validation and --testing: a comma list "
+                             "of input scales, ':flip' adds the mirrored twin of each (e.g. 0.5,0.75,1.0:flip; at most 8 views); the "
+                             "views' probabilities are summed (default: one forward at the crop size, as the reference)")
     parser.add_argument("--testing_gen", type=str, default="resnet_9blocks_softmax",
                         help="generator testing.py builds (the reference hard-codes resnet_9blocks_softmax, testing.py:40)")
     return parser.parse_args(argv)

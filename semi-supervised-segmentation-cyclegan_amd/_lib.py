@@ -111,6 +111,8 @@ SIGNATURES = {
     "sscg_upsample_head_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "sscg_predict_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "sscg_predict_head_ms": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.c_uint32, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "sscg_resize_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "sscg_panel_labels": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_panel_range_workspace": (_sz, [_i64, _i]),
     "sscg_panel_range": (_i, [_p, _i, _i64, _i, _f, _f, _p, _p, _p, _sz, _p]),

@@ -7,6 +7,8 @@
 //   * The softmax and first-maximum over the class axis as the inference heads hold them in registers: the operations of
 //     softmax_fwd_kernel / argmax_onehot_kernel in their order (max, exp(v - max), running sum, one reciprocal, one multiply per class,
 //     strict > from class 0 up).  No multiply feeds an add there, so nothing can contract.
+//   * The sum of several views' probabilities (tta.hip): there a multiply does feed an add - the probability v[c] * inv, which the
+//     separate passes store as an fp32 value, into the accumulator - so that function is pinned as well.
 #pragma once
 #include "common.h"
 
@@ -64,6 +66,33 @@ __device__ __forceinline__ int sscg_first_max_scaled(const float* v, float inv, 
         if (CT || c < C) {
             const float p = v[c] * inv;
             if (p > best) { best = p; bi = c; }
+        }
+    return bi;
+}
+
+// acc[c] <- (first ? 0 : acc[c]) + v[c] * inv: one view's probabilities (what softmax_fwd_kernel stores) added to the running sum of the
+// views before it by a plain fp32 add.  The product is rounded to fp32 before the add - the stored value of the separate passes - so
+// nothing here may contract into an FMA.
+template <int CT>
+__device__ __forceinline__ void sscg_prob_accumulate(float* acc, const float* v, float inv, int C, bool first) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
+        if (CT || c < C) {
+            const float p = v[c] * inv;
+            acc[c] = first ? p : acc[c] + p;
+        }
+}
+
+// argmax over c of a[c], first maximum wins (argmax_onehot_kernel's strict > from class 0 up)
+template <int CT>
+__device__ __forceinline__ int sscg_first_max(const float* a, int C) {
+    float best = a[0];
+    int bi = 0;
+#pragma unroll
+    for (int c = 1; c < (CT ? CT : SSCG_MAXC); ++c)
+        if (CT || c < C) {
+            if (a[c] > best) { best = a[c]; bi = c; }
         }
     return bi;
 }

@@ -1275,6 +1275,94 @@ def predict_image(x, size, *, want_float=True, want_u8=True):
     return y, u8
 
 
+# Multi-scale / mirrored inference (sscg_predict_head_ms / sscg_resize_flip): the logit maps of several views of one batch fused into
+# one label map in one launch.  SSCG_FUSE_TTA=0 keeps predict_labels_ms on the chain of separate passes (an A/B aid: the bits are the
+# same).
+FUSE_TTA = [os.environ.get("SSCG_FUSE_TTA", "1") != "0"]
+MAX_VIEWS = 8
+
+
+def resize_flip(x, size, flip):
+    """The network input of one view: `upsample_bilinear(x, size)` (bilinear, align_corners=True; a smaller size samples), then
+    `torch.flip` of the W axis when `flip` - one launch, the same bits.  fp32 [N,C,H,W] in, channels-last out; the batch itself when
+    there is nothing to do."""
+    _need_hip(x, f32_only=True)
+    if x.dim() != 4:
+        raise _lib.SscgError("resize_flip: 4-D tensor expected")
+    _no_grad_input(x, "resize_flip")
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    if not flip and (oh, ow) == (h, w):
+        return x
+    x = to_nhwc(x.detach())
+    y = empty_nhwc(n, c, oh, ow, x.device)
+    check(lib.sscg_resize_flip(x.data_ptr(), y.data_ptr(), n, h, w, c, oh, ow, 1 if flip else 0, _stream()), "sscg_resize_flip")
+    return y
+
+
+def predict_labels_ms(logits_list, flips, size, *, want_prob=False, want_index=False, want_u8=True, label_true=None, hist=None,
+                      num_classes=None):
+    """Label maps from the logits of up to 8 views of one batch: per view, in order, interp(size, bilinear, align_corners=True) ->
+    mirror of the W axis where `flips[s]` (the view was computed from the mirrored image) -> Softmax2d, the views' probabilities
+    summed in fp32 (no division by their number), then .max(1)[1] - one launch, bit for bit what the separate passes give.
+    Returns (label_u8 uint8 [N,OH,OW] or None, index int64 [N,OH,OW] or None, hist or None, prob_sum fp32 [N,C,OH,OW] channels-last
+    or None); `label_true` / `hist` as in predict_labels."""
+    S = len(logits_list)
+    if not 1 <= S <= MAX_VIEWS or len(flips) != S:
+        raise _lib.SscgError("predict_labels_ms: 1..%d views with one flip flag each expected" % MAX_VIEWS)
+    xs = []
+    for lg in logits_list:
+        _need_hip(lg, f32_only=True)
+        if lg.dim() != 4 or lg.shape[:2] != logits_list[0].shape[:2]:
+            raise _lib.SscgError("predict_labels_ms: 4-D logits of one batch size and class count expected")
+        _no_grad_input(lg, "predict_labels_ms")
+        xs.append(to_nhwc(lg.detach()))
+    n, c = xs[0].shape[:2]
+    oh, ow = int(size[0]), int(size[1])
+    if num_classes is not None and int(num_classes) != c:
+        raise _lib.SscgError("predict_labels_ms: %d classes asked for, the logits have %d channels" % (num_classes, c))
+    if hist is not None and label_true is None:
+        raise _lib.SscgError("predict_labels_ms: a confusion matrix needs label_true")
+    if not (want_prob or want_index or want_u8 or label_true is not None):
+        raise _lib.SscgError("predict_labels_ms: no output asked for")
+    lt = None
+    if label_true is not None:
+        if not label_true.is_cuda:
+            raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % label_true.device)
+        lt = label_true.to(torch.int64).contiguous()
+        if lt.numel() != n * oh * ow:
+            raise _lib.SscgError("predict_labels_ms: label_true must have N*OH*OW elements")
+        if hist is None:
+            hist = torch.empty((c, c), dtype=torch.int64, device=xs[0].device)
+            check(lib.sscg_fill(hist.data_ptr(), 2 * hist.numel(), 0.0, _stream()), "sscg_fill")   # 2 fp32 zeros per int64 zero
+        elif not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == c * c):
+            raise _lib.SscgError("predict_labels_ms: hist must be a contiguous int64 [C, C] tensor on the device")
+    if not FUSE_TTA[0]:
+        acc = None
+        for x, flip in zip(xs, flips):
+            p = softmax_fwd(x if tuple(x.shape[2:]) == (oh, ow) else upsample_fwd(x, oh, ow))      # a fresh tensor per view
+            if flip:
+                p = torch.flip(p, dims=(3,))
+            acc = p if acc is None else acc.add_(p)
+        idx = argmax_index(acc) if (want_index or want_u8 or lt is not None) else None
+        if lt is not None:
+            confusion_hist(lt, idx, c, hist)
+        return (idx.to(torch.uint8) if want_u8 else None, idx if want_index else None, hist,
+                acc.contiguous(memory_format=CL) if want_prob else None)
+    u8 = torch.empty((n, oh, ow), dtype=torch.uint8, device=xs[0].device) if want_u8 else None
+    idx = torch.empty((n, oh, ow), dtype=torch.int64, device=xs[0].device) if want_index else None
+    prob = empty_nhwc(n, c, oh, ow, xs[0].device) if want_prob else None
+    mask = 0
+    for s, flip in enumerate(flips):
+        mask |= (1 if flip else 0) << s
+    ptrs = (C.c_void_p * S)(*[x.data_ptr() for x in xs])
+    hs = (C.c_int * S)(*[int(x.shape[2]) for x in xs])
+    ws = (C.c_int * S)(*[int(x.shape[3]) for x in xs])
+    check(lib.sscg_predict_head_ms(ptrs, hs, ws, S, mask, n, c, oh, ow, _ptr(prob), _ptr(idx), _ptr(u8), _ptr(lt), _ptr(hist), _stream()),
+          "sscg_predict_head_ms")
+    return u8, idx, hist, prob
+
+
 # The per-epoch image panels (sscg_panel_labels / sscg_panel_range / sscg_panel_grid): the grids train() hands to the image writer,
 # built on the device.  SSCG_FUSE_PANELS=0 keeps model.panels() on the chain of separate passes and the host (an A/B aid: the bytes
 # are the same).

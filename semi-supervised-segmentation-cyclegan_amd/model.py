@@ -498,9 +498,11 @@ class semisuper_cycleGAN(object):
 
     # ------------------------------------------------------------------------------------------ evaluation (model.py:555-574)
     @torch.no_grad()
-    def evaluate(self, val_loader, first_batch=None):
+    def evaluate(self, val_loader, first_batch=None, tta=None):
         """`first_batch`: a list that receives the first batch's (val_img, val_gt) as they went through the network - the batch the
-        panels are drawn from, without a second iterator on the loader."""
+        panels are drawn from, without a second iterator on the loader.  `tta`: a view list of utils.parse_tta - Gsi runs once per
+        view on the resized / mirrored batch and the views' probabilities are summed (multi-scale / mirrored inference; the
+        reference evaluates one view only).  None = the single forward of the reference."""
         self.Gsi.eval()
         self.Gis.eval()
         self.running_metrics_val.reset()
@@ -508,6 +510,9 @@ class semisuper_cycleGAN(object):
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
                 first_batch.extend((val_img, val_gt))
+            if tta:
+                self.running_metrics_val.update_logits_ms(val_gt.squeeze(1), *utils.tta_logits(self.Gsi, val_img, tta), self.crop)
+                continue
             logits = self.Gsi(val_img)
             if F.FUSE_PREDICT[0]:            # interp -> Softmax2d -> max(1)[1] -> _fast_hist in one launch (:565-569)
                 self.running_metrics_val.update_logits(val_gt.squeeze(1), logits, self.crop)
@@ -585,7 +590,7 @@ class semisuper_cycleGAN(object):
             if val_loader is not None:
                 want_panels = rank0 and (writer is not None or panel_dir is not None)
                 first = [] if want_panels else None
-                miou, class_iou = self.evaluate(val_loader, first_batch=first)
+                miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
                 if rank0:
                     print("The mIoU for the epoch is: ", miou)
                 if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
@@ -645,16 +650,20 @@ class supervised_model(object):
         return loss.detach()
 
     @torch.no_grad()
-    def evaluate(self, val_loader, first_batch=None):
+    def evaluate(self, val_loader, first_batch=None, tta=None):
         """model.py:145-162.  The reference interpolates to a hard-coded 512x512 (`interp_val`, model.py:63,152), which only
         works for a 512x512 crop; the crop size is used here, as the semi-supervised driver does.
-        `first_batch`: a list that receives the first batch's (val_img, val_gt) on the device (the batch of the panels)."""
+        `first_batch`: a list that receives the first batch's (val_img, val_gt) on the device (the batch of the panels).
+        `tta`: a view list of utils.parse_tta, as in semisuper_cycleGAN.evaluate; None = the single forward of the reference."""
         self.Gsi.eval()
         self.running_metrics_val.reset()
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
                 first_batch.extend((val_img, val_gt))
+            if tta:
+                self.running_metrics_val.update_logits_ms(val_gt.squeeze(1), *utils.tta_logits(self.Gsi, val_img, tta), self.crop)
+                continue
             logits = self.Gsi(val_img)
             if F.FUSE_PREDICT[0]:
                 self.running_metrics_val.update_logits(val_gt.squeeze(1), logits, self.crop)
@@ -701,7 +710,7 @@ class supervised_model(object):
                     return history
             if val_loader is not None:                                              # model.py:145-197
                 first = [] if rank == 0 and (writer is not None or panel_dir is not None) else None
-                miou, class_iou = self.evaluate(val_loader, first_batch=first)
+                miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
                 if rank == 0:
                     print("The mIoU for the epoch is: ", miou)
                 if first:                                                           # model.py:164-186

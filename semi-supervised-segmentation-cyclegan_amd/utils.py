@@ -176,6 +176,12 @@ class runningScore(object):
         self._device_hist = F.predict_labels(logits, size, want_u8=False, label_true=label_trues, hist=self._device_hist,
                                              num_classes=self.n_classes)[2]
 
+    def update_logits_ms(self, label_trues, logits_list, flips, size):
+        """update_logits() over several views of the batch (multi-scale / mirrored inference): the views' probabilities are summed
+        and the counts taken in one launch (F.predict_labels_ms)."""
+        self._device_hist = F.predict_labels_ms(logits_list, flips, size, want_u8=False, label_true=label_trues,
+                                                hist=self._device_hist, num_classes=self.n_classes)[2]
+
     def _fold_device(self):
         if self._device_hist is not None:
             self.confusion_matrix += self._device_hist.cpu().numpy().astype(np.float64)
@@ -202,6 +208,45 @@ class runningScore(object):
     def reset(self):
         self.confusion_matrix = np.zeros((self.n_classes, self.n_classes))
         self._device_hist = None
+
+
+MAX_TTA_VIEWS = 8
+
+
+def parse_tta(spec):
+    """`--tta`: the views of multi-scale / mirrored inference.  "0.5,0.75,1.0" = one view per scale; a trailing ":flip" adds the
+    horizontally mirrored twin of every scale directly after it.  Returns a list of (scale, flip) in view order, None for ""."""
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    scales, sep, mode = spec.partition(":")
+    if sep and mode != "flip":
+        raise ValueError("--tta: %r after ':' (only 'flip' is known)" % mode)
+    views = []
+    for tok in scales.split(","):
+        try:
+            scale = float(tok)
+        except ValueError:
+            raise ValueError("--tta: %r is not a scale" % tok)
+        if not (scale > 0 and scale != float("inf")):
+            raise ValueError("--tta: scale %r is not positive" % tok)
+        views.append((scale, False))
+        if sep:
+            views.append((scale, True))
+    if len(views) > MAX_TTA_VIEWS:
+        raise ValueError("--tta: %d views, at most %d" % (len(views), MAX_TTA_VIEWS))
+    return views
+
+
+def tta_size(h, w, scale):
+    """The network input size of a view: the crop scaled and rounded half up, never below one pixel."""
+    return max(1, int(h * scale + 0.5)), max(1, int(w * scale + 0.5))
+
+
+def tta_logits(net, images, views):
+    """One forward of `net` per view on F.resize_flip of the batch: (logit maps, flip flags) for F.predict_labels_ms."""
+    h, w = images.shape[2:]
+    return [net(F.resize_flip(images, tta_size(h, w, scale), flip)) for scale, flip in views], [flip for _, flip in views]
 
 
 def save_checkpoint(state, save_path):

@@ -36,12 +36,15 @@ def test(args, test_loader=None):
         print(' [*] No checkpoint!')
     out = os.path.join(args.results_dir, 'unsupervised' if semi else 'supervised')
     os.makedirs(out, exist_ok=True)
+    tta = utils.parse_tta(getattr(args, 'tta', ''))
     Gsi.eval()
     with torch.no_grad():
         for i, (image_test, image_name) in enumerate(test_loader):
             image_test = utils.cuda(image_test, args.gpu_ids)
-            logits = Gsi(image_test)
-            if F.FUSE_PREDICT[0]:            # softmax -> argmax on the net's own output: one launch, a uint8 map (identity resize)
+            logits = None if tta else Gsi(image_test)
+            if tta:             # --tta: Gsi once per view, the views fused into one uint8 map at the images' size
+                prediction = F.predict_labels_ms(*utils.tta_logits(Gsi, image_test, tta), image_test.shape[2:])[0].cpu().numpy()
+            elif F.FUSE_PREDICT[0]:          # softmax -> argmax on the net's own output: one launch, a uint8 map (identity resize)
                 prediction = F.predict_labels(logits, logits.shape[2:])[0].cpu().numpy()
             else:
                 prediction = F.argmax_index(F.softmax2d(logits)).cpu().numpy()

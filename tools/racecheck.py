@@ -366,6 +366,13 @@ class _Checked(object):
                                 core.access(v, s, int(p), 4, False, where + ".terms")
                         if arg in ("terms", "w"):
                             continue
+                    if name == "sscg_predict_head_ms" and arg == "xs":     # a host array of device pointers: the views' logits
+                        for p in val:
+                            if where is None:
+                                where = "%s(%s)" % (name, _where())
+                            al = core._alloc_of(int(p))
+                            core.access(v, s, int(p), ext.get(int(p), (al.base + al.nbytes - int(p)) if al is not None else 4), False, where + ".xs")
+                        continue
                     if not isinstance(val, int):
                         continue
                     if where is None:

@@ -50,13 +50,16 @@ def validation(args, val_loader=None):
     soft = lambda lg: F.softmax2d(F.upsample_bilinear(lg, size))                    # interp -> Softmax2d
     # Gsi's logits -> interp -> Softmax2d -> argmax: uint8 label maps from one launch, or the int64 maps of the separate passes
     labels = (lambda lg: F.predict_labels(lg, size)[0].cpu().numpy()) if fused else (lambda lg: F.argmax_index(soft(lg)).cpu().numpy())
+    tta = utils.parse_tta(getattr(args, 'tta', ''))
+    # --tta: Gsi once per view of the images, the views fused into one uint8 map (F.FUSE_TTA: in one launch)
+    labels_ms = lambda x: F.predict_labels_ms(*utils.tta_logits(Gsi, x, tta), size)[0].cpu().numpy()
     img = lambda x: F.act_fwd(F.to_nhwc(F.upsample_bilinear(Gis(x), size)), F.ACT_TANH)   # Gis -> interp -> Tanh
     Gsi.eval()
     with torch.no_grad():
         for i, (image_test, real_segmentation, image_name) in enumerate(val_loader):
             image_test, real_segmentation = utils.cuda([image_test, real_segmentation], args.gpu_ids)
-            logits = Gsi(image_test)
-            prediction = labels(logits)
+            logits = Gsi(image_test) if semi or not tta else None     # the image-regeneration branches stay single-view
+            prediction = labels_ms(image_test) if tta else labels(logits)
             if not semi:
                 out = _mk(args.validation_dir, 'supervised')
                 for j in range(prediction.shape[0]):
