@@ -292,6 +292,10 @@ int sscg_label_onehot(const int64_t* labels, float* onehot, int64_t rows, int C,
  * hist[C*t + p] += 1 for every pixel with 0 <= t < C (others, e.g. the 255 "void" label, are ignored).
  * `hist` is int64 [C][C] on the device and is accumulated into; C <= 64. */
 int sscg_confusion_hist(const int64_t* label_true, const int64_t* label_pred, int64_t n, int C, int64_t* hist, void* stream);
+/* Class frequencies of a label map, the input of the class-weight rules of the weighted cross entropy (median-frequency balancing,
+ * ENet's 1 / ln(k + f)): counts[c] += #{labels == c}; ids outside [0, C) are ignored.  `counts` is int64 [C] on the device and is
+ * accumulated into; C <= 64.  Per-block LDS histogram, then integer atomics: exact, as sscg_confusion_hist.  n == 0 is a no-op. */
+int sscg_label_hist(const int64_t* labels, int64_t n, int C, int64_t* counts, void* stream);
 
 /* ------------------------------------------------------------------ input pipeline
  * The tail of the reference's per-sample transforms, batched on the device: images travel to HBM as the uint8
@@ -334,6 +338,23 @@ int sscg_ce_fwd(const float* logits, const int64_t* labels, int64_t rows, int C,
                 size_t ws_bytes, void* stream);
 int sscg_ce_bwd(const float* logits, const int64_t* labels, int64_t rows, int C, const float* gscale, float w,
                 const float* valid, float* dx, void* stream);
+/* Class-weighted, label-smoothed cross entropy: F.cross_entropy(logits, labels, weight=class_w, label_smoothing=smoothing) once
+ * every label outside [0, C) is mapped to the ignore index - sscg_ce_fwd / _bwd plus two arguments.  class_w: device pointer to [C]
+ * fp32, NULL = all ones; smoothing (eps) in [0, 1).  With p = softmax(z) of a pixel, y its label, W = sum_c class_w[c], and a pixel
+ * COUNTED when 0 <= y < C:
+ *     term    = (1-eps) * w[y] * (-log p[y]) + (eps/C) * sum_c w[c] * (-log p[c])
+ *     loss    = sum over the counted pixels of term / D,      D = sum over the counted pixels of w[y]
+ *     d loss / d z[c] = ((1-eps) * w[y] * (p[c] - [c==y]) + (eps/C) * (p[c] * W - w[c])) / D        (0 for a pixel not counted)
+ * The smoothing part of a counted pixel is NOT multiplied by w[y]: a pixel of a weight-0 class still adds it.  `valid` receives D (a
+ * float rounded from the fp64 sum); the backward divides by it (NULL = rows).  D == 0 - no counted pixel, or every counted pixel in a
+ * weight-0 class: the loss is NaN, the gradient zero (sscg_ce_fwd's rule for "no counted pixel").  class_w == NULL && smoothing == 0
+ * runs sscg_ce_fwd / _bwd themselves: the same kernels, the same bits.  The weights are not checked here (the host checks them once,
+ * when it makes them: finite, >= 0).  Errors before any HIP call: SSCG_ERR_BAD_ARG (smoothing outside [0, 1) or NaN; then the rules of
+ * sscg_ce_fwd / _bwd), SSCG_ERR_WORKSPACE.  (An addition: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+int sscg_ce_fwd_w(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing, float* loss,
+                  float* valid, void* ws, size_t ws_bytes, void* stream);
+int sscg_ce_bwd_w(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing,
+                  const float* gscale, float w, const float* valid, float* dx, void* stream);
 /* The head of the segmentation generator without the resized logits in memory (ABI v12): x = low-resolution logits [N][H][W][C]
  * (C <= 64), resized to [OH][OW] by bilinear interpolation with align_corners=True (model.py:390-392, the arithmetic of
  * sscg_upsample_bilinear_fwd), then
@@ -343,10 +364,20 @@ int sscg_ce_bwd(const float* logits, const int64_t* labels, int64_t rows, int C,
  *   y_soft != NULL ([N][OH][OW][C]): softmax over C of the resized logits (model.py:401-402).
  * sscg_upsample_head_bwd: dx = adjoint of the resize applied to softmax_bwd(dy_soft, y_soft) (dy_soft NULL: that branch is unused)
  * + dlogits * g_ce / valid (dlogits NULL: no cross-entropy branch; g_ce NULL = 1).  Gather form, fixed summation order.
- * ws: sscg_upsample_head_workspace bytes (cross-entropy branch only). */
+ * It serves sscg_upsample_head_fwd_w unchanged: that forward leaves dlogits = sum over the counted pixels of d(their weighted,
+ * smoothed term) / dx and valid = D, and the gradient is again dlogits * g_ce / valid.
+ * ws: sscg_upsample_head_workspace bytes (cross-entropy branch only).
+ * sscg_upsample_head_fwd_w: sscg_upsample_head_fwd with the cross entropy of sscg_ce_fwd_w (class_w NULL = all ones, smoothing in
+ * [0, 1); the formulas above, on the resized logits): `loss`, `valid` (= D) and `dlogits` follow them, the forward still leaves the
+ * gradient, the y_soft branch is untouched (the same bits).  The weighted form is its own kernel instantiation; labels == NULL, or
+ * class_w == NULL && smoothing == 0, runs sscg_upsample_head_fwd itself.  Errors before any HIP call: SSCG_ERR_BAD_ARG for a smoothing
+ * outside [0, 1), then sscg_upsample_head_fwd's rules. */
 size_t sscg_upsample_head_workspace(int N, int H, int W);
 int sscg_upsample_head_fwd(const float* x, const int64_t* labels, float* y_soft, float* loss, float* valid, float* dlogits, int N, int H,
                            int W, int C, int OH, int OW, void* ws, size_t ws_bytes, void* stream);
+int sscg_upsample_head_fwd_w(const float* x, const int64_t* labels, const float* class_w, float smoothing, float* y_soft, float* loss,
+                             float* valid, float* dlogits, int N, int H, int W, int C, int OH, int OW, void* ws, size_t ws_bytes,
+                             void* stream);
 int sscg_upsample_head_bwd(const float* x, const float* dy_soft, const float* dlogits, const float* g_ce, const float* valid, float* dx,
                            int N, int H, int W, int C, int OH, int OW, void* stream);
 /* ------------------------------------------------------------------ inference heads (ABI v18): one launch from a generator's output

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
---as_written, --augment, --panels, --tta.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
 import sys
-from argparse import ArgumentParser
+from argparse import SUPPRESS, ArgumentParser, Namespace
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 PKG = "semi-supervised-segmentation-cyclegan_amd"
@@ -26,6 +26,14 @@ DEFAULT_CROP = {"voc2012": (320, 320), "acdc": (256, 256), "cityscapes": (512, 1
 
 
 DATA_ROOTS = {'voc2012': './data/VOC2012', 'cityscapes': './data/Cityscape', 'acdc': './data/ACDC'}   # model.py:21-23
+
+
+class _Args(Namespace):
+    """Defaults of the opt-in loss flags as CLASS attributes (their parser default is SUPPRESS: argparse stores nothing for a flag
+    that is not given), so a run that names neither flag parses to the namespace it always did - `vars(args)` lists what the earlier
+    flags put there and nothing else - while `args.ce_weights` / `args.label_smoothing` read "" / 0.0."""
+    ce_weights = ""
+    label_smoothing = 0.0
 
 
 def get_args(argv=None):
@@ -64,7 +72,14 @@ def get_args(argv=None):
                              "views' probabilities are summed (default: one forward at the crop size, as the reference)")
     parser.add_argument("--testing_gen", type=str, default="resnet_9blocks_softmax",
                         help="generator testing.py builds (the reference hard-codes resnet_9blocks_softmax, testing.py:40)")
-    return parser.parse_args(argv)
+    parser.add_argument("--ce_weights", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="class weights of the ground-truth cross entropies (lab_loss_CE, gt_cycle_loss, the supervised loss): a "
+                             "comma list of one weight per class, or a rule computed from the labelled set's class frequencies in one "
+                             "pass at start - median (median-frequency balancing) or invlog[:k] (1 / ln(k + f), k = 1.02) "
+                             "(default: none, the reference's nn.CrossEntropyLoss())")
+    parser.add_argument("--label_smoothing", type=float, default=SUPPRESS, metavar="F",
+                        help="label smoothing of the same cross entropies, in [0, 1) (default: 0.0)")
+    return parser.parse_args(argv, namespace=_Args())
 
 
 def main(argv=None):

@@ -100,14 +100,18 @@ SIGNATURES = {
     "sscg_argmax_onehot": (_i, [_p, _p, _p, _i64, _i, _p]),
     "sscg_label_onehot": (_i, [_p, _p, _i64, _i, _p]),
     "sscg_confusion_hist": (_i, [_p, _p, _i64, _i, _p, _p]),
+    "sscg_label_hist": (_i, [_p, _i64, _i, _p, _p]),
     "sscg_image_u8_to_f32": (_i, [_p, _p, _i64, _i, _p, _p, _p]),
     "sscg_label_lut": (_i, [_p, _p, _i64, _p, _p]),
     "sscg_augment_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p]),
     "sscg_loss_workspace": (_sz, [_i64]),
     "sscg_ce_fwd": (_i, [_p, _p, _i64, _i, _p, _p, _p, _sz, _p]),
     "sscg_ce_bwd": (_i, [_p, _p, _i64, _i, _p, _f, _p, _p, _p]),
+    "sscg_ce_fwd_w": (_i, [_p, _p, _i64, _i, _p, _f, _p, _p, _p, _sz, _p]),
+    "sscg_ce_bwd_w": (_i, [_p, _p, _i64, _i, _p, _f, _p, _f, _p, _p, _p]),
     "sscg_upsample_head_workspace": (_sz, [_i, _i, _i]),
     "sscg_upsample_head_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
+    "sscg_upsample_head_fwd_w": (_i, [_p, _p, _p, _f, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "sscg_upsample_head_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "sscg_predict_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),

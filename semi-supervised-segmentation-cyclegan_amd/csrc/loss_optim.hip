@@ -95,9 +95,23 @@ __global__ void label_onehot_kernel(const int64_t* __restrict__ lab, float* __re
 // Pixels whose label lies outside [0, C) take no part in the loss (nn.CrossEntropyLoss's ignore_index semantics,
 // extended to every out-of-range id: the 255 "void" of an un-relabelled VOC map, a raw Cityscapes id, -100): they add
 // nothing to the sum, are not counted in the mean and get a zero gradient - never an out-of-bounds read.
+//
+// WT (class weights w and / or label smoothing eps; sscg_ce_fwd_w / _bwd_w / sscg_upsample_head_fwd_w) is a separate instantiation of
+// each kernel - the plain ones keep their instruction stream.  With p = softmax(z), W = sum_c w[c], a counted pixel adds
+//     term = (1-eps) * w[y] * (-log p[y]) + (eps/C) * sum_c w[c] * (-log p[c])          to the loss sum,
+//     w[y]                                                                              to the divisor D (`valid`),
+//     d term / d z[c] = (1-eps) * w[y] * (p[c] - [c==y]) + (eps/C) * (p[c] * W - w[c])  to the gradient (times g / D in the backward)
+// - F.cross_entropy(weight=w, label_smoothing=eps).  sum_c w[c] * (-log p[c]) = W * log(s) - sum_c w[c] * (z[c] - m) with m = max z,
+// s = sum exp(z - m): one FMA per class in the loop that forms the exponentials.  class_w == NULL: all ones.
+__device__ __forceinline__ float class_weight(const float* __restrict__ class_w, int c) { return class_w ? class_w[c] : 1.f; }
+
+template <bool WT>
 __global__ void ce_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab, size_t rows, int C,
-                              double* __restrict__ part, int nparts) {
+                              double* __restrict__ part, int nparts, const float* __restrict__ class_w, float smoothing) {
     double acc = 0.0, cnt = 0.0;
+    float wsum = 0.f;
+    if (WT)
+        for (int c = 0; c < C; ++c) wsum += class_weight(class_w, c);
     for (size_t r = (size_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (size_t)gridDim.x * 256) {
         const int64_t l = lab[r];
         if (l < 0 || l >= C) continue;
@@ -105,6 +119,18 @@ __global__ void ce_fwd_kernel(const float* __restrict__ x, const int64_t* __rest
         float m = -INFINITY;
         for (int c = 0; c < C; ++c) m = fmaxf(m, xr[c]);
         float s = 0.f;
+        if (WT) {
+            float swd = 0.f;
+            for (int c = 0; c < C; ++c) {
+                const float d = xr[c] - m;
+                swd += class_weight(class_w, c) * d;
+                s += expf(d);
+            }
+            const float wl = class_weight(class_w, (int)l), ls = logf(s);
+            acc += (double)((1.f - smoothing) * wl * (ls + m - xr[l]) + smoothing / (float)C * (ls * wsum - swd));
+            cnt += (double)wl;
+            continue;
+        }
         for (int c = 0; c < C; ++c) s += expf(xr[c] - m);
         acc += (double)(logf(s) + m - xr[l]);
         cnt += 1.0;
@@ -130,11 +156,15 @@ __global__ void finish_ce_kernel(const double* __restrict__ part, int nparts, fl
     }
 }
 
+template <bool WT>
 __global__ void ce_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab, size_t rows, int C,
                               const float* __restrict__ gscale, float w, const float* __restrict__ valid,
-                              float* __restrict__ dx) {
+                              float* __restrict__ dx, const float* __restrict__ class_w, float smoothing) {
     const float n = valid ? *valid : (float)rows;
     const float g = (gscale ? *gscale : 1.f) * (n > 0.f ? w / n : 0.f);
+    float wsum = 0.f;
+    if (WT)
+        for (int c = 0; c < C; ++c) wsum += class_weight(class_w, c);
     for (size_t r = (size_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (size_t)gridDim.x * 256) {
         const float* xr = x + r * C;
         const int64_t l64 = lab[r];
@@ -151,6 +181,12 @@ __global__ void ce_bwd_kernel(const float* __restrict__ x, const int64_t* __rest
         float inv = 1.f / s;
         const int l = (int)l64;
         float* dr = dx + r * C;
+        if (WT) {
+            const float a = (1.f - smoothing) * class_weight(class_w, l), bs = smoothing / (float)C;
+            const float k = a + bs * wsum;
+            for (int c = 0; c < C; ++c) dr[c] = (v[c] * inv * k - (c == l ? a : 0.f) - bs * class_weight(class_w, c)) * g;
+            continue;
+        }
         for (int c = 0; c < C; ++c) dr[c] = (v[c] * inv - (c == l ? 1.f : 0.f)) * g;
     }
 }
@@ -200,12 +236,14 @@ __device__ __forceinline__ float head_weight(float scale, int o, int i, int n_sr
 }
 
 // MODE 0: forward (labels and / or softmax output); MODE 1: backward of the softmax output (dy_soft), plus the scaled
-// cross-entropy gradient the forward left
-template <int CT, int MODE>
+// cross-entropy gradient the forward left.  WT (MODE 0 only): the class-weighted / label-smoothed cross entropy - see ce_fwd_kernel;
+// `cnt` then sums w[y], and what is left in dlo is still the gradient up to g / valid, so MODE 1 and head_scale_kernel serve it as is.
+template <int CT, int MODE, bool WT>
 __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab, float* __restrict__ y_soft,
                                                    const float* __restrict__ dy_soft, float* __restrict__ dlo, const float* __restrict__ dl_ce,
                                                    const float* __restrict__ g_ce, const float* __restrict__ valid,
-                                                   double* __restrict__ part, int nparts, HeadGeom g) {
+                                                   double* __restrict__ part, int nparts, HeadGeom g,
+                                                   const float* __restrict__ class_w, float smoothing) {
     __shared__ float red[4][MAXC];
     const int C = CT ? CT : g.C;
     const int b = blockIdx.x;
@@ -220,6 +258,16 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
 #pragma unroll
     for (int c = 0; c < (CT ? CT : MAXC); ++c) acc[c] = 0.f;
     double loss = 0.0, cnt = 0.0;
+    float wr[WT ? (CT ? CT : MAXC) : 1];      // WT: the class weights (block-uniform loads) and their sum, once per block
+    float wsum = 0.f;
+    if (WT) {
+#pragma unroll
+        for (int c = 0; c < (CT ? CT : MAXC); ++c) {
+            if (CT == 0 && c >= C) break;
+            wr[c] = class_weight(class_w, c);
+            wsum += wr[c];
+        }
+    }
     for (int t = threadIdx.x; t < cand; t += 256) {
         const int oy = oy_lo + t / nx, ox = ox_lo + t % nx;
         const float wy = head_weight(g.sh, oy, iy, g.H);
@@ -241,16 +289,38 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
             const int64_t l64 = lab[o];
             l = (l64 < 0 || l64 >= C) ? -1 : (int)l64;
         }
-        float s = 0.f;
+        float s = 0.f, swd = 0.f;
 #pragma unroll
         for (int c = 0; c < (CT ? CT : MAXC); ++c) {
             if (CT == 0 && c >= C) break;
             if (c == l) vl = v[c];
+            if (WT) swd += wr[c] * (v[c] - m);
             v[c] = expf(v[c] - m);
             s += v[c];
         }
         const float inv = 1.f / s;
-        if (MODE == 0) {
+        if (MODE == 0 && WT) {
+            if (owner && y_soft) {
+                float* yr = y_soft + o * C;
+#pragma unroll
+                for (int c = 0; c < (CT ? CT : MAXC); ++c) { if (CT == 0 && c >= C) break; yr[c] = v[c] * inv; }
+            }
+            if (l >= 0) {
+                const float wl = class_weight(class_w, l);
+                const float a = (1.f - smoothing) * wl, bs = smoothing / (float)C;
+                if (owner) {
+                    const float ls = logf(s);
+                    loss += (double)(a * (ls + m - vl) + bs * (ls * wsum - swd));
+                    cnt += (double)wl;
+                }
+                const float k = a + bs * wsum;
+#pragma unroll
+                for (int c = 0; c < (CT ? CT : MAXC); ++c) {
+                    if (CT == 0 && c >= C) break;
+                    acc[c] += w * (v[c] * inv * k - (c == l ? a : 0.f) - bs * wr[c]);
+                }
+            }
+        } else if (MODE == 0) {
             if (owner && l >= 0) { loss += (double)(logf(s) + m - vl); cnt += 1.0; }
             if (owner && y_soft) {
                 float* yr = y_soft + o * C;
@@ -458,6 +528,31 @@ extern "C" int sscg_confusion_hist(const int64_t* label_true, const int64_t* lab
     return SSCG_OK;
 }
 
+// Class frequencies of a label map (the input of the class-weight rules): the same scheme with C bins.
+__global__ __launch_bounds__(256) void label_hist_kernel(const int64_t* __restrict__ lab, int64_t n, int C,
+                                                          unsigned long long* __restrict__ counts) {
+    __shared__ unsigned int bins[64];
+    if (threadIdx.x < 64) bins[threadIdx.x] = 0u;
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t l = lab[i];
+        if (l >= 0 && l < C) atomicAdd(&bins[(int)l], 1u);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < C && bins[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)bins[threadIdx.x]);
+}
+
+extern "C" int sscg_label_hist(const int64_t* labels, int64_t n, int C, int64_t* counts, void* stream) {
+    if (!labels || !counts || n < 0 || C <= 0 || C > 64) return SSCG_ERR_BAD_ARG;
+    if (n == 0) return SSCG_OK;
+    int64_t blocks = (n + 256 * 16 - 1) / (256 * 16);   // as sscg_confusion_hist: a block's int32 bins hold at most n / blocks < 2^32 counts
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(label_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, labels, n, C,
+                       reinterpret_cast<unsigned long long*>(counts));
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
 extern "C" size_t sscg_loss_workspace(int64_t n) {
     (void)n;
     return (size_t)2 * LOSS_BLOCKS * sizeof(double);   // cross entropy keeps (sum, count) partials
@@ -470,7 +565,24 @@ extern "C" int sscg_ce_fwd(const float* logits, const int64_t* labels, int64_t r
     hipStream_t st = (hipStream_t)stream;
     int nb = ew_blocks(rows, LOSS_BLOCKS);
     double* part = reinterpret_cast<double*>(ws);
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(nb), dim3(256), 0, st, logits, labels, (size_t)rows, C, part, nb);
+    hipLaunchKernelGGL(ce_fwd_kernel<false>, dim3(nb), dim3(256), 0, st, logits, labels, (size_t)rows, C, part, nb, (const float*)nullptr, 0.f);
+    hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nb, loss, valid);
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
+static bool smoothing_ok(float smoothing) { return smoothing >= 0.f && smoothing < 1.f; }     // (false for a NaN)
+
+extern "C" int sscg_ce_fwd_w(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing,
+                             float* loss, float* valid, void* ws, size_t ws_bytes, void* stream) {
+    if (!smoothing_ok(smoothing)) return SSCG_ERR_BAD_ARG;
+    if (!class_w && smoothing == 0.f) return sscg_ce_fwd(logits, labels, rows, C, loss, valid, ws, ws_bytes, stream);
+    if (!logits || !labels || !loss || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
+    if (!ws || ws_bytes < sscg_loss_workspace(rows)) return SSCG_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    int nb = ew_blocks(rows, LOSS_BLOCKS);
+    double* part = reinterpret_cast<double*>(ws);
+    hipLaunchKernelGGL(ce_fwd_kernel<true>, dim3(nb), dim3(256), 0, st, logits, labels, (size_t)rows, C, part, nb, class_w, smoothing);
     hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nb, loss, valid);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
@@ -487,14 +599,15 @@ static bool head_geom(HeadGeom* g, int N, int H, int W, int C, int OH, int OW) {
     return true;
 }
 
-template <int MODE>
+template <int MODE, bool WT = false>
 static void launch_head(const HeadGeom& g, hipStream_t st, const float* x, const int64_t* lab, float* y_soft, const float* dy_soft,
-                        float* dlo, const float* dl_ce, const float* g_ce, const float* valid, double* part, int nparts) {
+                        float* dlo, const float* dl_ce, const float* g_ce, const float* valid, double* part, int nparts,
+                        const float* class_w = nullptr, float smoothing = 0.f) {
     const dim3 grid(nparts), blk(256);
-    if (g.C == 21) hipLaunchKernelGGL((head_kernel<21, MODE>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g);
-    else if (g.C == 20) hipLaunchKernelGGL((head_kernel<20, MODE>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g);
-    else if (g.C == 4) hipLaunchKernelGGL((head_kernel<4, MODE>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g);
-    else hipLaunchKernelGGL((head_kernel<0, MODE>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g);
+    if (g.C == 21) hipLaunchKernelGGL((head_kernel<21, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
+    else if (g.C == 20) hipLaunchKernelGGL((head_kernel<20, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
+    else if (g.C == 4) hipLaunchKernelGGL((head_kernel<4, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
+    else hipLaunchKernelGGL((head_kernel<0, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
 }
 
 extern "C" size_t sscg_upsample_head_workspace(int N, int H, int W) {
@@ -512,6 +625,25 @@ extern "C" int sscg_upsample_head_fwd(const float* x, const int64_t* labels, flo
     double* part = labels ? reinterpret_cast<double*>(ws) : nullptr;
     launch_head<0>(g, st, x, labels, y_soft, nullptr, labels ? dlogits : nullptr, nullptr, nullptr, nullptr, part, nparts);
     if (labels) hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nparts, loss, valid);
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
+extern "C" int sscg_upsample_head_fwd_w(const float* x, const int64_t* labels, const float* class_w, float smoothing, float* y_soft,
+                                        float* loss, float* valid, float* dlogits, int N, int H, int W, int C, int OH, int OW, void* ws,
+                                        size_t ws_bytes, void* stream) {
+    if (!smoothing_ok(smoothing)) return SSCG_ERR_BAD_ARG;
+    if (!labels || (!class_w && smoothing == 0.f))      // nothing weighted to compute: the plain instantiations
+        return sscg_upsample_head_fwd(x, labels, y_soft, loss, valid, dlogits, N, H, W, C, OH, OW, ws, ws_bytes, stream);
+    HeadGeom g;
+    if (!x || !head_geom(&g, N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
+    if (!loss || !valid || !dlogits) return SSCG_ERR_BAD_ARG;
+    if (!ws || ws_bytes < sscg_upsample_head_workspace(N, H, W)) return SSCG_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int nparts = N * H * W;
+    double* part = reinterpret_cast<double*>(ws);
+    launch_head<0, true>(g, st, x, labels, y_soft, nullptr, dlogits, nullptr, nullptr, nullptr, part, nparts, class_w, smoothing);
+    hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nparts, loss, valid);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }
@@ -536,8 +668,19 @@ extern "C" int sscg_upsample_head_bwd(const float* x, const float* dy_soft, cons
 extern "C" int sscg_ce_bwd(const float* logits, const int64_t* labels, int64_t rows, int C, const float* gscale, float w,
                            const float* valid, float* dx, void* stream) {
     if (!logits || !labels || !dx || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, logits, labels, (size_t)rows,
-                       C, gscale, w, valid, dx);
+    hipLaunchKernelGGL(ce_bwd_kernel<false>, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, logits, labels, (size_t)rows,
+                       C, gscale, w, valid, dx, (const float*)nullptr, 0.f);
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
+extern "C" int sscg_ce_bwd_w(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing,
+                             const float* gscale, float w, const float* valid, float* dx, void* stream) {
+    if (!smoothing_ok(smoothing)) return SSCG_ERR_BAD_ARG;
+    if (!class_w && smoothing == 0.f) return sscg_ce_bwd(logits, labels, rows, C, gscale, w, valid, dx, stream);
+    if (!logits || !labels || !dx || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
+    hipLaunchKernelGGL(ce_bwd_kernel<true>, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, logits, labels, (size_t)rows,
+                       C, gscale, w, valid, dx, class_w, smoothing);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

@@ -1213,6 +1213,19 @@ def confusion_hist(label_true, label_pred, num_classes, hist=None):
     return hist
 
 
+def label_hist(labels, num_classes, counts=None):
+    """counts[c] += #{labels == c}; ids outside [0, C) are ignored.  `counts` int64 [C] on the device (exact: integer atomics) - the
+    class frequencies the weight rules of the class-weighted cross entropy start from (utils.ce_weights_from_counts)."""
+    if not labels.is_cuda:
+        raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % labels.device)
+    lab = labels.to(torch.int64).contiguous()
+    if counts is None:
+        counts = torch.empty((num_classes,), dtype=torch.int64, device=lab.device)
+        check(lib.sscg_fill(counts.data_ptr(), 2 * counts.numel(), 0.0, _stream()), "sscg_fill")   # 2 fp32 zeros per int64 zero
+    check(lib.sscg_label_hist(lab.data_ptr(), lab.numel(), num_classes, counts.data_ptr(), _stream()), "sscg_label_hist")
+    return counts
+
+
 # The inference heads (sscg_predict_head / sscg_image_head): what evaluate(), validation.py and testing.py keep of a generator's
 # output, in one launch.  SSCG_FUSE_PREDICT=0 keeps those call sites on the chain of separate passes (an A/B aid: the bits are the same).
 FUSE_PREDICT = [os.environ.get("SSCG_FUSE_PREDICT", "1") != "0"]
@@ -2477,33 +2490,71 @@ class SoftmaxFn(torch.autograd.Function):
         return softmax_bwd(to_nhwc(dy), y)
 
 
+def ce_weight(values, num_classes, device):
+    """The class-weight operand of the weighted cross entropy: `values` (a sequence of C numbers) checked on the host - length C, every
+    entry finite and >= 0 - and sent to `device` as fp32 [C].  The check is made here, once; the loss calls only look at the tensor's
+    dtype, device and length (no host sync per step)."""
+    import math
+    vals = [float(v) for v in values]
+    if len(vals) != int(num_classes):
+        raise ValueError("class weights: %d entries for %d classes" % (len(vals), num_classes))
+    for i, v in enumerate(vals):
+        if not math.isfinite(v) or v < 0:
+            raise ValueError("class weights: entry %d (%r) is not a finite number >= 0" % (i, v))
+    return torch.tensor(vals, dtype=torch.float32).to(device)
+
+
+def _ce_options(weight, label_smoothing, c, device):
+    """(weight tensor or None, smoothing as a float, whether the weighted entries are needed) of a cross-entropy call."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError("label_smoothing %r is outside [0, 1)" % (label_smoothing,))
+    if weight is not None:
+        if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and weight.device == device
+                and weight.dim() == 1 and weight.numel() == c and weight.is_contiguous()):
+            raise _lib.SscgError("class weights must be a contiguous fp32 [%d] tensor on %s (functional.ce_weight makes one)" % (c, device))
+    return weight, eps, weight is not None or eps != 0.0
+
+
 class CrossEntropyFn(torch.autograd.Function):
-    """nn.CrossEntropyLoss()(logits [N,C,H,W], labels [N,H,W]) - mean over N*H*W."""
+    """nn.CrossEntropyLoss(weight, label_smoothing)(logits [N,C,H,W], labels [N,H,W]) - mean over the counted pixels (the sum of their
+    class weights when weighted).  Optional trailing inputs: weight (fp32 [C] on the device, or None), label_smoothing."""
 
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, *opt):
         _need_hip(logits, f32_only=True)
         logits = to_nhwc(logits)
         labels = labels.contiguous()
         n, c, h, w = logits.shape
         if labels.numel() != n * h * w or labels.dtype != torch.int64:
             raise _lib.SscgError("labels must be int64 with N*H*W elements")
+        weight, eps, weighted = _ce_options(opt[0] if opt else None, opt[1] if len(opt) > 1 else 0.0, c, logits.device)
         loss = _scalar(logits.device)
         valid = _scalar(logits.device)      # pixels with a label in [0, C): the divisor of the mean (all of them in the reference)
         ws = _loss_ws(logits.device)
-        check(lib.sscg_ce_fwd(logits.data_ptr(), labels.data_ptr(), n * h * w, c, loss.data_ptr(), valid.data_ptr(), ws.data_ptr(),
-                              ws.numel(), _stream()), "sscg_ce_fwd")
+        if weighted:
+            check(lib.sscg_ce_fwd_w(logits.data_ptr(), labels.data_ptr(), n * h * w, c, _ptr(weight), eps, loss.data_ptr(),
+                                    valid.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sscg_ce_fwd_w")
+        else:
+            check(lib.sscg_ce_fwd(logits.data_ptr(), labels.data_ptr(), n * h * w, c, loss.data_ptr(), valid.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _stream()), "sscg_ce_fwd")
+        ctx.ce = (weight, eps, weighted, len(opt))
         ctx.save_for_backward(logits, labels, valid)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         logits, labels, valid = ctx.saved_tensors
+        weight, eps, weighted, n_opt = ctx.ce
         n, c, h, w = logits.shape
         dx = torch.empty_like(logits, memory_format=CL)
-        check(lib.sscg_ce_bwd(logits.data_ptr(), labels.data_ptr(), n * h * w, c, g.data_ptr(), 1.0, valid.data_ptr(),
-                              dx.data_ptr(), _stream()), "sscg_ce_bwd")
-        return dx, None
+        if weighted:
+            check(lib.sscg_ce_bwd_w(logits.data_ptr(), labels.data_ptr(), n * h * w, c, _ptr(weight), eps, g.data_ptr(), 1.0,
+                                    valid.data_ptr(), dx.data_ptr(), _stream()), "sscg_ce_bwd_w")
+        else:
+            check(lib.sscg_ce_bwd(logits.data_ptr(), labels.data_ptr(), n * h * w, c, g.data_ptr(), 1.0, valid.data_ptr(),
+                                  dx.data_ptr(), _stream()), "sscg_ce_bwd")
+        return (dx, None) + (None,) * n_opt
 
 
 FUSE_HEAD = [os.environ.get("SSCG_FUSE_HEAD", "1") != "0"]      # interp -> {softmax, cross entropy} without the resized logits in memory
@@ -2518,10 +2569,12 @@ def _head_applies(x, oh, ow):
 class UpsampleHeadFn(torch.autograd.Function):
     """interp (bilinear, align_corners=True) -> softmax2d and / or nn.CrossEntropyLoss, from the LOW-resolution logits (model.py:390-392,
     398, 401-402, 455).  Returns (softmax map or None, loss or None).  The forward of the cross-entropy branch already leaves the
-    gradient with respect to the low-resolution logits (it depends on logits and labels only); the backward scales it."""
+    gradient with respect to the low-resolution logits (it depends on logits and labels only); the backward scales it.  Optional
+    trailing inputs: weight (fp32 [C] on the device, or None), label_smoothing - the class-weighted, smoothed cross entropy, for which
+    all of the above still holds (`valid` is then the sum of the counted pixels' class weights)."""
 
     @staticmethod
-    def forward(ctx, x, oh, ow, labels, want_soft):
+    def forward(ctx, x, oh, ow, labels, want_soft, *opt):
         _need_hip(x, f32_only=True)
         x = to_nhwc(x)
         n, c, h, w = x.shape
@@ -2534,8 +2587,14 @@ class UpsampleHeadFn(torch.autograd.Function):
             loss, valid = _scalar(x.device), _scalar(x.device)
             dl = empty_nhwc(n, c, h, w, x.device)
             ws = torch.empty(lib.sscg_upsample_head_workspace(n, h, w), dtype=torch.uint8, device=x.device)
-        check(lib.sscg_upsample_head_fwd(x.data_ptr(), _ptr(labels), _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl), n, h, w, c, oh, ow,
-                                         _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "sscg_upsample_head_fwd")
+        weight, eps, weighted = _ce_options(opt[0] if opt else None, opt[1] if len(opt) > 1 else 0.0, c, x.device)
+        if weighted and labels is not None:
+            check(lib.sscg_upsample_head_fwd_w(x.data_ptr(), _ptr(labels), _ptr(weight), eps, _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl),
+                                               n, h, w, c, oh, ow, _ptr(ws), ws.numel(), _stream()), "sscg_upsample_head_fwd_w")
+        else:
+            check(lib.sscg_upsample_head_fwd(x.data_ptr(), _ptr(labels), _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl), n, h, w, c, oh, ow,
+                                             _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "sscg_upsample_head_fwd")
+        ctx.n_opt = len(opt)
         ctx.geom = (oh, ow)
         ctx.save_for_backward(x, dl, valid)
         # an output nothing differentiates (the step reads lab_gt's softmax through .detach() only): backward gets None, not a
@@ -2549,7 +2608,7 @@ class UpsampleHeadFn(torch.autograd.Function):
         oh, ow = ctx.geom
         n, c, h, w = x.shape
         if dy is None and (g is None or dl is None):
-            return None, None, None, None, None
+            return (None,) * (5 + ctx.n_opt)
         if dy is not None:
             dy = to_nhwc(dy)
         use_ce = g is not None and dl is not None
@@ -2557,17 +2616,20 @@ class UpsampleHeadFn(torch.autograd.Function):
         check(lib.sscg_upsample_head_bwd(x.data_ptr(), _ptr(dy), _ptr(dl if use_ce else None), _ptr(g if use_ce else None),
                                          _ptr(valid if use_ce else None), dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
               "sscg_upsample_head_bwd")
-        return dx, None, None, None, None
+        return (dx, None, None, None, None) + (None,) * ctx.n_opt
 
 
-def upsample_softmax_ce(x, size, labels=None, want_soft=True):
+def upsample_softmax_ce(x, size, labels=None, want_soft=True, weight=None, label_smoothing=0.0):
     """(softmax2d(interp(x)) or None, CrossEntropyLoss(interp(x), labels) or None) - fused when the resize grows the map, else the
-    three separate passes."""
+    three separate passes.  weight (functional.ce_weight's tensor) / label_smoothing: nn.CrossEntropyLoss's, on either path."""
     oh, ow = int(size[0]), int(size[1])
+    plain = weight is None and label_smoothing == 0.0
     if _head_applies(x, oh, ow):
-        return UpsampleHeadFn.apply(x, oh, ow, labels, want_soft)
+        if plain:
+            return UpsampleHeadFn.apply(x, oh, ow, labels, want_soft)
+        return UpsampleHeadFn.apply(x, oh, ow, labels, want_soft, weight, label_smoothing)
     up = upsample_bilinear(x, size)
-    return (softmax2d(up) if want_soft else None), (cross_entropy(up, labels) if labels is not None else None)
+    return (softmax2d(up) if want_soft else None), (cross_entropy(up, labels, weight, label_smoothing) if labels is not None else None)
 
 
 class MSEConstFn(torch.autograd.Function):
@@ -2819,8 +2881,10 @@ def softmax2d(x):
     return SoftmaxFn.apply(x)
 
 
-def cross_entropy(logits, labels):
-    return CrossEntropyFn.apply(logits, labels)
+def cross_entropy(logits, labels, weight=None, label_smoothing=0.0):
+    if weight is None and label_smoothing == 0.0:
+        return CrossEntropyFn.apply(logits, labels)
+    return CrossEntropyFn.apply(logits, labels, weight, label_smoothing)
 
 
 def mse_const(x, target):

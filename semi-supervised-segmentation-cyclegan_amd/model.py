@@ -114,7 +114,61 @@ def write_panels(panels, epoch, writer=None, panel_dir=None):
             utils.save_panel_png(arr, os.path.join(panel_dir, "epoch%03d_%d.png" % (epoch, i + 1)))
 
 
-class semisuper_cycleGAN(object):
+class _WeightedCE(object):
+    """--ce_weights / --label_smoothing (opt-in; the reference has neither): the class weights and the smoothing of the ground-truth
+    cross entropies of both drivers.  A list of weights is final at construction; a rule (median, invlog) needs the labelled set's
+    class frequencies: resolve_ce_weights(labeled_loader), which train() calls before its first step."""
+    ce_weight = None        # fp32 [C] on the device, or None = unweighted
+    ce_smoothing = 0.0
+    _ce_rule = None         # a rule of utils.parse_ce_weights still to be resolved
+
+    def _init_ce(self, args, C):
+        self.ce_smoothing = float(getattr(args, "label_smoothing", 0.0) or 0.0)
+        if not 0.0 <= self.ce_smoothing < 1.0:
+            raise ValueError("--label_smoothing %r is outside [0, 1)" % (args.label_smoothing,))
+        spec = utils.parse_ce_weights(getattr(args, "ce_weights", ""), C)
+        if isinstance(spec, list):
+            self._set_ce_weight(spec, "--ce_weights")
+        else:
+            self._ce_rule = spec
+
+    def _ce_device(self):
+        ids = getattr(self.args, "gpu_ids", None)
+        return torch.device("cuda", int(ids[0])) if ids else torch.device("cpu")
+
+    def _set_ce_weight(self, values, origin):
+        self.ce_weight = F.ce_weight(values, self.n_channels, self._ce_device())
+        self._ce_rule = None
+        if self.dp is None or self.dp.rank == 0:
+            print("cross-entropy class weights (%s): %s" % (origin, ", ".join("%.6g" % v for v in values)))
+
+    def resolve_ce_weights(self, labeled_loader):
+        """One pass over the labelled loader's label maps (F.label_hist on the device; the counts are summed over the ranks of a
+        process group, so every rank trains with the same weights) -> the weights of the rule --ce_weights names.  A no-op otherwise."""
+        if self._ce_rule is None:
+            return self.ce_weight
+        rule, counts = self._ce_rule, None
+        for _, l_gt, _ in labeled_loader:
+            counts = F.label_hist(utils.cuda(l_gt, self.args.gpu_ids), self.n_channels, counts)
+        if counts is None:
+            raise ValueError("--ce_weights %s: the labelled loader is empty" % rule[0])
+        if self.dp is not None:
+            from .parallel import allreduce_flat
+            allreduce_flat(counts)
+        self._set_ce_weight(utils.ce_weights_from_counts(rule, counts.cpu().tolist()),
+                            "%s of the labelled set's class frequencies" % ":".join(str(r) for r in rule))
+        return self.ce_weight
+
+    def _ce_kwargs(self):
+        if self._ce_rule is not None:
+            raise RuntimeError("--ce_weights %s needs the labelled set's class frequencies: call resolve_ce_weights(labeled_loader) "
+                               "before the first step (train() does)" % self._ce_rule[0])
+        if self.ce_weight is None and self.ce_smoothing == 0.0:
+            return {}
+        return {"weight": self.ce_weight, "label_smoothing": self.ce_smoothing}
+
+
+class semisuper_cycleGAN(_WeightedCE):
     def __init__(self, args, data_parallel=None):
         self.args = args
         _select_device(args)
@@ -163,6 +217,7 @@ class semisuper_cycleGAN(object):
         # stream: callers read them after `sync_losses()` (train() and bench.py do).
         self.overlap_d = bool(getattr(args, "overlap_d", False))
         self.dp = data_parallel
+        self._init_ce(args, C)
 
         self.g_optimizer = FusedAdam(itertools.chain(self.Gis.parameters(), self.Gsi.parameters()), lr=args.lr, betas=(0.5, 0.999))
         self.d_optimizer = FusedAdam(itertools.chain(self.Di.parameters(), self.Ds.parameters()), lr=args.lr, betas=(0.5, 0.999))
@@ -277,7 +332,8 @@ class semisuper_cycleGAN(object):
             gsi_second.record(main)
         # :391-392 (interp), :398 (CE of the resized logits), :401-402 (their softmax) from the low-resolution logits in one pass each:
         # the resized [B, C, crop] logits are never written (functional.UpsampleHeadFn)
-        lab_gt, lab_loss_CE = F.upsample_softmax_ce(lab_logits, self.crop, labels)
+        ce = self._ce_kwargs()      # {} by default: the reference's plain nn.CrossEntropyLoss()
+        lab_gt, lab_loss_CE = F.upsample_softmax_ce(lab_logits, self.crop, labels, **ce)
         fake_gt, _ = F.upsample_softmax_ce(fake_logits, self.crop)
         if fork:
             main.wait_event(gis_first)
@@ -346,7 +402,7 @@ class semisuper_cycleGAN(object):
         img_gen_loss = F.mse_const(fake_img_dis, 1.0)                                # :445
         gt_gen_loss = F.mse_const(fake_gt_dis, 1.0)                                  # :446
         img_cycle_loss = F.mse_const(resnet_fake_img_dis, 1.0)                       # :452
-        _, gt_cycle_loss = F.upsample_softmax_ce(recon_logits, self.crop, labels, want_soft=False)    # :415 (interp), :455
+        _, gt_cycle_loss = F.upsample_softmax_ce(recon_logits, self.crop, labels, want_soft=False, **ce)    # :415 (interp), :455
         lab_loss_MSE = F.l1_loss(fake_img_l1, l_img)                                 # :461
         # :464-468  gen_loss = CE_w*CE + MSE_w*L1 + adv_w*(img_gen + gt_gen) + img_cycle + lamda_gt*gt_cycle
         gen_loss = F.weighted_sum(
@@ -426,7 +482,7 @@ class semisuper_cycleGAN(object):
         x_img = fake_img.detach().clone().requires_grad_(True)
         recon_img = self.interp(self.Gis(x_gt))                                          # :408,413
         img_cycle_loss = F.mse_const(self.old_Di(recon_img), 1.0)                        # :432,452
-        _, gt_cycle_loss = F.upsample_softmax_ce(self.Gsi(x_img), self.crop, labels, want_soft=False)    # :410,415,455
+        _, gt_cycle_loss = F.upsample_softmax_ce(self.Gsi(x_img), self.crop, labels, want_soft=False, **self._ce_kwargs())    # :410,415,455
         F.backward(F.weighted_sum([img_cycle_loss, gt_cycle_loss], [1.0, 1.0]))          # (each term reaches one of the two inputs only)
         F.SideStream.join(l_gt.device)
         with torch.no_grad():
@@ -557,6 +613,7 @@ class semisuper_cycleGAN(object):
             from .data import synthetic_loaders
             loaders = synthetic_loaders(args, self.n_channels, rank=self.dp.rank if self.dp is not None else 0)
         labeled_loader, unlabeled_loader, val_loader = loaders
+        self.resolve_ce_weights(labeled_loader)
         rank0 = self.dp is None or self.dp.rank == 0
         done = 0
         history = []
@@ -607,7 +664,7 @@ class semisuper_cycleGAN(object):
         return history
 
 
-class supervised_model(object):
+class supervised_model(_WeightedCE):
     """DeepLab Gsi + CrossEntropy + Adam(0.9, 0.999) (model.py:33-199; BASELINE config 1)."""
 
     def __init__(self, args, data_parallel=None):
@@ -623,6 +680,7 @@ class supervised_model(object):
         self.dp = data_parallel
         if self.dp is not None:
             self.dp.attach_one(self.gsi_optimizer, [self.Gsi])
+        self._init_ce(args, self.n_channels)
         self.running_metrics_val = utils.runningScore(self.n_channels, args.dataset)
         if not os.path.isdir(args.checkpoint_dir):
             os.makedirs(args.checkpoint_dir, exist_ok=True)
@@ -641,7 +699,7 @@ class supervised_model(object):
         """model.py:120-143."""
         self.gsi_optimizer.zero_grad()
         _, loss = F.upsample_softmax_ce(self.Gsi(l_img), self.crop, l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3]),
-                                        want_soft=False)
+                                        want_soft=False, **self._ce_kwargs())
         F.backward(loss)
         if self.dp is not None:
             F.SideStream.join(l_img.device)
@@ -693,6 +751,7 @@ class supervised_model(object):
             from .data import synthetic_loaders
             loaders = synthetic_loaders(args, self.n_channels, rank=rank)
         labeled_loader = loaders[0]
+        self.resolve_ce_weights(labeled_loader)
         val_loader = loaders[2] if len(loaders) > 2 else None
         history, done = [], 0
         for epoch in range(self.start_epoch, args.epochs):

@@ -249,6 +249,63 @@ def tta_logits(net, images, views):
     return [net(F.resize_flip(images, tta_size(h, w, scale), flip)) for scale, flip in views], [flip for _, flip in views]
 
 
+CE_INVLOG_K = 1.02      # ENet's constant in w = 1 / ln(k + f)
+
+
+def parse_ce_weights(spec, n_classes):
+    """`--ce_weights`: the class weights of the ground-truth cross entropies.  "" -> None (the reference's unweighted loss); a comma
+    list of exactly n_classes numbers (finite, >= 0) -> that list of floats; a rule computed from the labelled set's class frequencies
+    (ce_weights_from_counts): "median" -> ("median",), "invlog" / "invlog:<k>" -> ("invlog", k) with k > 1, default 1.02."""
+    import math
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    if spec == "median":
+        return ("median",)
+    name, sep, arg = spec.partition(":")
+    if name == "invlog":
+        if not sep:
+            return ("invlog", CE_INVLOG_K)
+        try:
+            k = float(arg)
+        except ValueError:
+            raise ValueError("--ce_weights: %r is not a number (invlog:<k>)" % arg)
+        if not (math.isfinite(k) and k > 1.0):
+            raise ValueError("--ce_weights: invlog needs k > 1 (1 / ln(k + f) with f in (0, 1]), got %r" % arg)
+        return ("invlog", k)
+    vals = []
+    for tok in spec.split(","):
+        try:
+            v = float(tok)
+        except ValueError:
+            raise ValueError("--ce_weights: %r is neither a number nor a rule (median, invlog[:k])" % tok)
+        if not math.isfinite(v) or v < 0:
+            raise ValueError("--ce_weights: %r is not a finite weight >= 0" % tok)
+        vals.append(v)
+    if len(vals) != int(n_classes):
+        raise ValueError("--ce_weights: %r has %d entries, the dataset has %d classes" % (spec, len(vals), n_classes))
+    return vals
+
+
+def ce_weights_from_counts(rule, counts):
+    """Class weights from per-class pixel counts (a pure host function).  f[c] = counts[c] / sum(counts);
+    ("median",): median-frequency balancing, w[c] = median(f over the classes present) / f[c];
+    ("invlog", k): w[c] = 1 / ln(k + f[c]) (ENet's rule).  A class with no pixel gets weight 0."""
+    import math
+    counts = [int(c) for c in counts]
+    total = sum(counts)
+    if total <= 0 or min(counts) < 0:
+        raise ValueError("class weights: the label maps hold no pixel of any class (counts %r)" % (counts,))
+    f = [c / total for c in counts]
+    if rule[0] == "median":
+        med = float(np.median([x for x in f if x > 0]))
+        return [med / x if x > 0 else 0.0 for x in f]
+    if rule[0] == "invlog":
+        k = float(rule[1])
+        return [1.0 / math.log(k + x) if x > 0 else 0.0 for x in f]
+    raise ValueError("unknown class-weight rule %r" % (rule,))
+
+
 def save_checkpoint(state, save_path):
     torch.save(state, save_path)
 
