@@ -491,13 +491,32 @@ int sscg_l1_bwd(const float* a, const float* b, int64_t n, const float* gscale, 
 int sscg_weighted_sum(const float* const* terms, const float* w, int n, float* out, void* stream);
 
 /* ------------------------------------------------------------------ optimiser (K14)
- * torch.optim.Adam (model.py:286-287; steps :474,:542): eps 1e-8, no weight decay, no amsgrad.
+ * torch.optim.Adam (model.py:286-287; steps :474,:542): eps 1e-8, no amsgrad.  sscg_adam_step is that optimiser and nothing else;
+ * gradient-norm clipping, weight decay and an EMA of the parameters are the opt-in sscg_grad_norm / sscg_adam_step_ex below.
  * One launch over a flat arena; grad is multiplied by grad_scale first (1/world_size under data parallel).
  * `shadow` (nullable): an operand copy of the parameter arena rewritten in the same pass - the copy the convolutions read (the
  * fp32 arena stays the master copy): shadow_dtype SSCG_BF16 = a bfloat16 arena of n elements; SSCG_BF16X3 = the three planes
  * of the split contraction (sscg_split3), n elements apart. */
 int sscg_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow, int shadow_dtype, int64_t n,
                    double lr, double beta1, double beta2, double eps, int step, float grad_scale, void* stream);
+/* Global L2 norm of grad * grad_scale over the arena and torch.nn.utils.clip_grad_norm_'s coefficient, both left on the device:
+ * t = fp32(grad[i] * grad_scale) - the value the Adam kernel sees -, sum of (double)t * t in two fixed-order fp64 stages (no atomics:
+ * equal bits from call to call), *norm = (float)sqrt(sum), *clip = min(1.0f, max_norm / (*norm + 1e-6f)) in fp32; a non-finite norm
+ * propagates as in torch (a NaN coefficient stays NaN).  norm or clip may be null, not both.  Any n >= 1 and any 4-byte-aligned grad.
+ * ws: sscg_grad_norm_workspace(n) bytes. */
+size_t sscg_grad_norm_workspace(int64_t n);
+int sscg_grad_norm(const float* grad, int64_t n, float grad_scale, float max_norm, float* norm, float* clip, void* ws, size_t ws_bytes,
+                   void* stream);
+/* sscg_adam_step with options, still one launch.  Per element: g = grad * grad_scale (* *clip when `clip`, a device scalar, is given:
+ * the two factors are multiplied first, so *clip == 1.0f changes no bit); weight_decay > 0 with decoupled == 0: g = fma(wd, param, g)
+ * (torch.optim.Adam(weight_decay=): after the clip, and not part of the norm); with decoupled != 0: param *= (float)(1 - lr * wd)
+ * first (torch.optim.AdamW); then sscg_adam_step's update and shadow write; `ema` (nullable, n floats): ema += (param_new - ema) *
+ * (float)(1 - ema_decay), ema_decay in [0, 1).  With no clip, no decay and no ema this IS sscg_adam_step; with *clip == 1.0f and / or
+ * an ema and no decay, param, both moments and shadow get sscg_adam_step's bits.  Zero param with zero grad (arena padding) stays zero
+ * in param and ema under every option. */
+int sscg_adam_step_ex(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow, int shadow_dtype, float* ema,
+                      int64_t n, double lr, double beta1, double beta2, double eps, int step, float grad_scale, const float* clip,
+                      double weight_decay, int decoupled, double ema_decay, void* stream);
 int sscg_fill(float* x, int64_t n, float v, void* stream);
 
 #ifdef __cplusplus

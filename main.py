@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
---as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
+--ema_decay.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -29,11 +30,16 @@ DATA_ROOTS = {'voc2012': './data/VOC2012', 'cityscapes': './data/Cityscape', 'ac
 
 
 class _Args(Namespace):
-    """Defaults of the opt-in loss flags as CLASS attributes (their parser default is SUPPRESS: argparse stores nothing for a flag
+    """Defaults of the opt-in loss and optimiser flags as CLASS attributes (their parser default is SUPPRESS: argparse stores nothing for a flag
     that is not given), so a run that names neither flag parses to the namespace it always did - `vars(args)` lists what the earlier
-    flags put there and nothing else - while `args.ce_weights` / `args.label_smoothing` read "" / 0.0."""
+    flags put there and nothing else - while `args.ce_weights` / `args.label_smoothing` read "" / 0.0 and the optimiser options read
+    FusedAdam's own defaults (off)."""
     ce_weights = ""
     label_smoothing = 0.0
+    clip_grad_norm = None
+    weight_decay = 0.0
+    adamw = False
+    ema_decay = None
 
 
 def get_args(argv=None):
@@ -79,7 +85,27 @@ def get_args(argv=None):
                              "(default: none, the reference's nn.CrossEntropyLoss())")
     parser.add_argument("--label_smoothing", type=float, default=SUPPRESS, metavar="F",
                         help="label smoothing of the same cross entropies, in [0, 1) (default: 0.0)")
-    return parser.parse_args(argv, namespace=_Args())
+    parser.add_argument("--clip_grad_norm", type=float, default=SUPPRESS, metavar="F",
+                        help="clip the global gradient norm to F before every update, as torch.nn.utils.clip_grad_norm_; every "
+                             "optimiser clips its own parameters - generators, discriminators, the supervised Gsi (default: off)")
+    parser.add_argument("--weight_decay", type=float, default=SUPPRESS, metavar="F",
+                        help="weight decay of every optimiser, as torch.optim.Adam(weight_decay=F) (default: 0.0)")
+    parser.add_argument("--adamw", action="store_true", default=SUPPRESS,
+                        help="apply --weight_decay decoupled from the gradient, as torch.optim.AdamW")
+    parser.add_argument("--ema_decay", type=float, default=SUPPRESS, metavar="F",
+                        help="keep an exponential moving average of the generators' (the supervised Gsi's) weights with decay F in "
+                             "[0, 1); the per-epoch evaluation, the panels, --validation and --testing use it and checkpoints gain "
+                             "Gsi_ema / Gis_ema (default: off)")
+    args = parser.parse_args(argv, namespace=_Args())
+    if args.adamw and not args.weight_decay > 0.0:
+        parser.error("--adamw decouples the weight decay from the gradient: it needs --weight_decay F with F > 0")
+    if args.weight_decay < 0.0 or args.weight_decay != args.weight_decay:
+        parser.error("--weight_decay must be >= 0")
+    if args.clip_grad_norm is not None and not args.clip_grad_norm > 0.0:
+        parser.error("--clip_grad_norm must be > 0")
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay < 1.0:
+        parser.error("--ema_decay must lie in [0, 1)")
+    return args
 
 
 def main(argv=None):

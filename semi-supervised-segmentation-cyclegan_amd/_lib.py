@@ -129,6 +129,10 @@ SIGNATURES = {
     "sscg_l1_bwd": (_i, [_p, _p, _i64, _p, _f, _p, _p]),
     "sscg_weighted_sum": (_i, [C.POINTER(_p), C.POINTER(_f), _i, _p, _p]),
     "sscg_adam_step": (_i, [_p, _p, _p, _p, _p, _i, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _i, _f, _p]),
+    "sscg_grad_norm_workspace": (_sz, [_i64]),
+    "sscg_grad_norm": (_i, [_p, _i64, _f, _f, _p, _p, _p, _sz, _p]),
+    "sscg_adam_step_ex": (_i, [_p, _p, _p, _p, _p, _i, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _i, _f, _p,
+                               C.c_double, _i, C.c_double, _p]),
     "sscg_fill": (_i, [_p, _i64, _f, _p]),
 }
 

@@ -1535,6 +1535,29 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow_bf
                              eps, step, grad_scale, _stream()), "sscg_adam_step")
 
 
+def grad_norm(g, max_norm, grad_scale=1.0, norm=None, clip=None):
+    """Global L2 norm of the flat fp32 gradient `g` times grad_scale and clip_grad_norm_'s coefficient min(1, max_norm / (norm + 1e-6)),
+    both 0-dim device tensors (written into `norm` / `clip` when given): two launches, fp64 fixed-order sums, no host round trip."""
+    if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+        raise _lib.SscgError("grad_norm: contiguous fp32 tensor on the MI355X expected")
+    norm = _scalar(g.device) if norm is None else norm
+    clip = _scalar(g.device) if clip is None else clip
+    ws = _WS.get(lib.sscg_grad_norm_workspace(g.numel()), g.device)
+    check(lib.sscg_grad_norm(g.data_ptr(), g.numel(), grad_scale, max_norm, norm.data_ptr(), clip.data_ptr(), ws.data_ptr(), ws.numel(),
+                             _stream()), "sscg_grad_norm")
+    return norm, clip
+
+
+def adam_step_ex(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow_bf16=None, shadow_split=None, clip=None,
+                 weight_decay=0.0, decoupled=False, ema=None, ema_decay=0.0):
+    """adam_step with the optimiser options: `clip` a 0-dim device coefficient (grad_norm), weight decay as torch.optim.Adam's L2 term
+    or decoupled (torch.optim.AdamW), `ema` an fp32 arena updated as ema.lerp_(p, 1 - ema_decay) in the same launch."""
+    sh, sdt = (shadow_split, BF16X3) if shadow_split is not None else (shadow_bf16, BF16)
+    check(lib.sscg_adam_step_ex(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(sh), sdt, _ptr(ema), p.numel(), lr, beta1,
+                                beta2, eps, step, grad_scale, _ptr(clip), weight_decay, 1 if decoupled else 0, ema_decay, _stream()),
+          "sscg_adam_step_ex")
+
+
 # ----------------------------------------------------------------------------- autograd functions
 _WEIGHT_EPOCH = [0]     # weights owned by no arena optimiser (stock torch optimisers rewrite `_version` instead)
 

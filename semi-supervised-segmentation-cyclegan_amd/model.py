@@ -11,6 +11,7 @@ that are deliberate and MI355X-first:
   * gradients accumulate into flat arenas (optim.FusedAdam) that RCCL all-reduces in one piece per
     optimiser under data parallelism (parallel.py).
 `supervised_model` mirrors model.py:33-199 (BASELINE config 1)."""
+import functools
 import itertools
 import os
 
@@ -112,6 +113,24 @@ def write_panels(panels, epoch, writer=None, panel_dir=None):
         if panel_dir is not None:
             os.makedirs(panel_dir, exist_ok=True)
             utils.save_panel_png(arr, os.path.join(panel_dir, "epoch%03d_%d.png" % (epoch, i + 1)))
+
+
+def _optim_options(args, ema):
+    """--clip_grad_norm / --weight_decay / --adamw / --ema_decay (opt-in; the reference has none of them) -> FusedAdam's keyword
+    arguments.  `ema`: this optimiser keeps the EMA copy (the generators' and the supervised Gsi's do, the discriminators' does not)."""
+    return dict(weight_decay=getattr(args, "weight_decay", 0.0) or 0.0, decoupled=bool(getattr(args, "adamw", False)),
+                max_grad_norm=getattr(args, "clip_grad_norm", None), ema_decay=getattr(args, "ema_decay", None) if ema else None)
+
+
+def _with_ema(opt_name):
+    """Run a method inside `ema_weights()` of the optimiser the attribute names (a no-op without --ema_decay)."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def run(self, *a, **k):
+            with getattr(self, opt_name).ema_weights():
+                return fn(self, *a, **k)
+        return run
+    return deco
 
 
 class _WeightedCE(object):
@@ -219,8 +238,10 @@ class semisuper_cycleGAN(_WeightedCE):
         self.dp = data_parallel
         self._init_ce(args, C)
 
-        self.g_optimizer = FusedAdam(itertools.chain(self.Gis.parameters(), self.Gsi.parameters()), lr=args.lr, betas=(0.5, 0.999))
-        self.d_optimizer = FusedAdam(itertools.chain(self.Di.parameters(), self.Ds.parameters()), lr=args.lr, betas=(0.5, 0.999))
+        self.g_optimizer = FusedAdam(itertools.chain(self.Gis.parameters(), self.Gsi.parameters()), lr=args.lr, betas=(0.5, 0.999),
+                                     **_optim_options(args, ema=True))
+        self.d_optimizer = FusedAdam(itertools.chain(self.Di.parameters(), self.Ds.parameters()), lr=args.lr, betas=(0.5, 0.999),
+                                     **_optim_options(args, ema=False))
         if self.dp is not None:
             self.dp.attach(self.g_optimizer, self.d_optimizer, [self.Gis, self.Gsi, self.Di, self.Ds, self.old_Gis, self.old_Gsi, self.old_Di])
         lam = utils.LambdaLR(args.epochs, 0, args.decay_epoch).step
@@ -238,6 +259,9 @@ class semisuper_cycleGAN(_WeightedCE):
                 getattr(self, k).load_state_dict(ck[k])
             self.d_optimizer.load_state_dict(ck['d_optimizer'])
             self.g_optimizer.load_state_dict(ck['g_optimizer'])
+            if self.g_optimizer.ema_decay is not None and 'Gsi_ema' in ck and 'Gis_ema' in ck:    # (else: the EMA restarts from the weights)
+                self.g_optimizer.load_ema_state_dict(self.Gsi, ck['Gsi_ema'])
+                self.g_optimizer.load_ema_state_dict(self.Gis, ck['Gis_ema'])
             self.best_iou = ck['best_iou']
         except Exception:
             print(' [*] No checkpoint!')
@@ -553,6 +577,7 @@ class semisuper_cycleGAN(_WeightedCE):
         return (img_dis_loss, gt_dis_loss, cycle_img_dis_loss)
 
     # ------------------------------------------------------------------------------------------ evaluation (model.py:555-574)
+    @_with_ema("g_optimizer")
     @torch.no_grad()
     def evaluate(self, val_loader, first_batch=None, tta=None):
         """`first_batch`: a list that receives the first batch's (val_img, val_gt) as they went through the network - the batch the
@@ -581,6 +606,7 @@ class semisuper_cycleGAN(_WeightedCE):
         return score["Mean IoU : \t"], class_iou
 
     # ------------------------------------------------------------------------------------------ image panels (model.py:576-638)
+    @_with_ema("g_optimizer")
     @torch.no_grad()
     def panels(self, val_img, val_gt):
         """The five image grids the reference sends to TensorBoard after every epoch, from one validation batch on the device:
@@ -629,9 +655,12 @@ class semisuper_cycleGAN(_WeightedCE):
                 done += 1
                 if (i % log_every == 0) and rank0:
                     self.sync_losses()
-                    vals = torch.stack([losses[k] for k in LOSS_KEYS]).cpu().tolist()   # the only host sync of the step
+                    norms = [o.last_grad_norm for o in (self.g_optimizer, self.d_optimizer) if o.last_grad_norm is not None]
+                    vals = torch.stack([losses[k] for k in LOSS_KEYS] + norms).cpu().tolist()   # the only host sync of the step
                     rec = dict(zip(LOSS_KEYS, vals))
                     history.append(rec)
+                    if norms:       # --clip_grad_norm: the norms the two updates of this step clipped
+                        print("Grad norm G:%.3e D:%.3e (clip %.3e)" % (vals[-2], vals[-1], self.g_optimizer.max_grad_norm))
                     print("Epoch: (%3d) (%5d/%5d) | Dis Loss:%.2e | Unlab Gen Loss:%.2e | Lab Gen loss:%.2e" % (
                         epoch, i + 1, n_it, rec["img_dis_loss"] + rec["gt_dis_loss"],
                         args.adversarial_weight * (rec["img_gen_loss"] + rec["gt_gen_loss"]) + rec["img_cycle_loss"] + rec["gt_cycle_loss"] * args.lamda_gt,
@@ -647,18 +676,22 @@ class semisuper_cycleGAN(_WeightedCE):
             if val_loader is not None:
                 want_panels = rank0 and (writer is not None or panel_dir is not None)
                 first = [] if want_panels else None
-                miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
-                if rank0:
-                    print("The mIoU for the epoch is: ", miou)
-                if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
-                    write_panels(self.panels(*first), epoch, writer, panel_dir)
+                with self.g_optimizer.ema_weights():    # --ema_decay: the epoch's mIoU and panels are the averaged weights' (one swap)
+                    miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
+                    if rank0:
+                        print("The mIoU for the epoch is: ", miou)
+                    if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
+                        write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank0:                                 # model.py:641-655
                     self.best_iou = miou
-                    utils.save_checkpoint({'epoch': epoch + 1, 'Di': self.Di.state_dict(), 'Ds': self.Ds.state_dict(),
-                                           'Gis': self.Gis.state_dict(), 'Gsi': self.Gsi.state_dict(),
-                                           'd_optimizer': self.d_optimizer.state_dict(), 'g_optimizer': self.g_optimizer.state_dict(),
-                                           'best_iou': self.best_iou, 'class_iou': class_iou},
-                                          '%s/latest_semisuper_cycleGAN.ckpt' % (args.checkpoint_dir))
+                    ck = {'epoch': epoch + 1, 'Di': self.Di.state_dict(), 'Ds': self.Ds.state_dict(),
+                          'Gis': self.Gis.state_dict(), 'Gsi': self.Gsi.state_dict(),
+                          'd_optimizer': self.d_optimizer.state_dict(), 'g_optimizer': self.g_optimizer.state_dict(),
+                          'best_iou': self.best_iou, 'class_iou': class_iou}
+                    if self.g_optimizer.ema_decay is not None:
+                        ck['Gis_ema'] = self.g_optimizer.ema_state_dict(self.Gis)
+                        ck['Gsi_ema'] = self.g_optimizer.ema_state_dict(self.Gsi)
+                    utils.save_checkpoint(ck, '%s/latest_semisuper_cycleGAN.ckpt' % (args.checkpoint_dir))
             self.g_lr_scheduler.step()                                              # model.py:659-660
             self.d_lr_scheduler.step()
         return history
@@ -676,7 +709,7 @@ class supervised_model(_WeightedCE):
                               use_dropout=not args.no_dropout, gpu_ids=args.gpu_ids)
         utils.print_networks([self.Gsi], ['Gsi'])
         self.crop = (args.crop_height, args.crop_width)
-        self.gsi_optimizer = FusedAdam(self.Gsi.parameters(), lr=args.lr, betas=(0.9, 0.999))   # model.py:69
+        self.gsi_optimizer = FusedAdam(self.Gsi.parameters(), lr=args.lr, betas=(0.9, 0.999), **_optim_options(args, ema=True))   # model.py:69
         self.dp = data_parallel
         if self.dp is not None:
             self.dp.attach_one(self.gsi_optimizer, [self.Gsi])
@@ -689,6 +722,8 @@ class supervised_model(_WeightedCE):
             self.start_epoch = ck['epoch']
             self.Gsi.load_state_dict(ck['Gsi'])
             self.gsi_optimizer.load_state_dict(ck['gsi_optimizer'])
+            if self.gsi_optimizer.ema_decay is not None and 'Gsi_ema' in ck:      # (else: the EMA restarts from the weights)
+                self.gsi_optimizer.load_ema_state_dict(self.Gsi, ck['Gsi_ema'])
             self.best_iou = ck['best_iou']
         except Exception:
             print(' [*] No checkpoint!')
@@ -707,6 +742,7 @@ class supervised_model(_WeightedCE):
         self.gsi_optimizer.step()
         return loss.detach()
 
+    @_with_ema("gsi_optimizer")
     @torch.no_grad()
     def evaluate(self, val_loader, first_batch=None, tta=None):
         """model.py:145-162.  The reference interpolates to a hard-coded 512x512 (`interp_val`, model.py:63,152), which only
@@ -733,6 +769,7 @@ class supervised_model(_WeightedCE):
         self.Gsi.train()
         return score["Mean IoU : \t"], class_iou
 
+    @_with_ema("gsi_optimizer")
     @torch.no_grad()
     def panels(self, val_img, val_gt):
         """The two image grids of model.py:164-186 (prediction, ground truth) from one validation batch: tag -> uint8 [3,GH,GW]
@@ -762,6 +799,8 @@ class supervised_model(_WeightedCE):
                 history.append(loss)
                 if rank == 0:
                     print("Epoch: (%3d) (%5d/%5d) | Crossentropy Loss:%.2e" % (epoch, i + 1, len(labeled_loader), loss))
+                    if self.gsi_optimizer.last_grad_norm is not None:       # --clip_grad_norm: the norm this step's update clipped
+                        print("Grad norm:%.3e (clip %.3e)" % (float(self.gsi_optimizer.last_grad_norm), self.gsi_optimizer.max_grad_norm))
                     if writer is not None:                                          # model.py:143
                         writer.add_scalars('Supervised Loss', {'CE Loss ': loss}, len(labeled_loader) * epoch + i)
                 done += 1
@@ -769,14 +808,17 @@ class supervised_model(_WeightedCE):
                     return history
             if val_loader is not None:                                              # model.py:145-197
                 first = [] if rank == 0 and (writer is not None or panel_dir is not None) else None
-                miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
-                if rank == 0:
-                    print("The mIoU for the epoch is: ", miou)
-                if first:                                                           # model.py:164-186
-                    write_panels(self.panels(*first), epoch, writer, panel_dir)
+                with self.gsi_optimizer.ema_weights():  # --ema_decay: the epoch's mIoU and panels are the averaged weights' (one swap)
+                    miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
+                    if rank == 0:
+                        print("The mIoU for the epoch is: ", miou)
+                    if first:                                                       # model.py:164-186
+                        write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank == 0:
                     self.best_iou = miou
-                    utils.save_checkpoint({'epoch': epoch + 1, 'Gsi': self.Gsi.state_dict(),
-                                           'gsi_optimizer': self.gsi_optimizer.state_dict(), 'best_iou': self.best_iou,
-                                           'class_iou': class_iou}, '%s/latest_supervised_model.ckpt' % (self.args.checkpoint_dir))
+                    ck = {'epoch': epoch + 1, 'Gsi': self.Gsi.state_dict(), 'gsi_optimizer': self.gsi_optimizer.state_dict(),
+                          'best_iou': self.best_iou, 'class_iou': class_iou}
+                    if self.gsi_optimizer.ema_decay is not None:
+                        ck['Gsi_ema'] = self.gsi_optimizer.ema_state_dict(self.Gsi)
+                    utils.save_checkpoint(ck, '%s/latest_supervised_model.ckpt' % (self.args.checkpoint_dir))
         return history

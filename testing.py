@@ -32,6 +32,8 @@ def test(args, test_loader=None):
     try:
         ckpt = utils.load_checkpoint('%s/latest_%s.ckpt' % (args.checkpoint_dir, 'semisuper_cycleGAN' if semi else 'supervised_model'))
         Gsi.load_state_dict(ckpt['Gsi'])
+        if getattr(args, 'ema_decay', None) is not None and 'Gsi_ema' in ckpt:      # --ema_decay: the averaged parameters (buffers stay)
+            Gsi.load_state_dict(ckpt['Gsi_ema'], strict=False)
     except Exception:
         print(' [*] No checkpoint!')
     out = os.path.join(args.results_dir, 'unsupervised' if semi else 'supervised')

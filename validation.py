@@ -42,6 +42,10 @@ def validation(args, val_loader=None):
         Gsi.load_state_dict(ckpt['Gsi'])
         if semi:
             Gis.load_state_dict(ckpt['Gis'])
+        if getattr(args, 'ema_decay', None) is not None:       # --ema_decay: the averaged parameters over the trained ones (buffers stay)
+            for net, key in ((Gsi, 'Gsi_ema'), (Gis, 'Gis_ema')):
+                if key in ckpt:
+                    net.load_state_dict(ckpt[key], strict=False)
         best_iou = ckpt['best_iou']
     except Exception:
         print(' [*] No checkpoint!')
