@@ -380,6 +380,45 @@ int sscg_upsample_head_fwd_w(const float* x, const int64_t* labels, const float*
                              void* stream);
 int sscg_upsample_head_bwd(const float* x, const float* dy_soft, const float* dlogits, const float* g_ce, const float* valid, float* dx,
                            int N, int H, int W, int C, int OH, int OW, void* stream);
+/* Soft Dice loss of the same head (opt-in; the reference has none).  x = logits [N][H][W][C] (C <= 64), labels [N][OH][OW];
+ * p = softmax over C of the logits resized to [OH][OW] (bilinear, align_corners=True, the arithmetic of sscg_upsample_bilinear_fwd;
+ * OH == H && OW == W: the logits themselves - the flat Dice of [rows][C] logits, no interpolation arithmetic).  class_w: device
+ * pointer to [C] fp32 weights w_c >= 0, NULL = all ones; smooth s > 0; batch in {0, 1}.  A pixel is COUNTED when 0 <= y < C
+ * (sscg_ce_fwd's rule: 255 and -100 are void).  Groups: G = N, one per sample (batch == 0), or G = 1, the whole call (batch == 1).
+ * Per group g and class c, over the counted pixels of the group:
+ *     I = sum p_c [y == c]     P = sum p_c     T = sum [y == c]          Num = 2 I + s     Den = P + T + s
+ *     dice[g][c] = Num / Den                  loss = 1 - sum_{g,c} w_c dice[g][c] / (G sum_c w_c)
+ * and with k_c = w_c / (G sum_c w_c) the derivative with respect to a counted pixel's probability is A[g][c] [y == c] + B[g][c],
+ *     A = -2 k_c / Den          B = k_c Num / Den^2
+ * (0 for a pixel not counted); then d loss / d z_c = p_c (g_c - sum_k p_k g_k), through the adjoint of the resize.
+ * s > 0 keeps every Den positive: a group with no counted pixel has dice = 1 for every class (it adds nothing to the loss and gets a
+ * zero gradient - never a NaN), a class absent from a group's labels (T = 0) still gets the B part.  The weights are not checked here
+ * (the host checks them once: finite, >= 0, not all zero).  Under data parallelism the sums are per rank.
+ * sscg_dice_fwd: `loss` (fp32 scalar), `sums` (nullable) [G][C][3] fp64 in the order (I, P, T), `coef` [G][C][2] fp32 in the order
+ *   (A, B) - all the backward needs.  Three launches: the statistics (one thread per output pixel, no block straddles a sample, fp64
+ *   records in the workspace), their sum per (sample, class), and the finish (one small block; with batch the samples are added in
+ *   index order).  Deterministic: no float atomics, every sum in a fixed order - the
+ *   same call twice gives the same bits, and the resized form gives the bits of the identity form on sscg_upsample_bilinear_fwd's
+ *   output.  Neither the resized logits nor the probabilities are written.  ws: sscg_dice_workspace(N, OH, OW, C) bytes.
+ * sscg_dice_bwd: the flat backward (logits [N][H][W][C], labels [N][H][W], the coef of an identity-size sscg_dice_fwd with the same
+ *   N and batch): dx = (g ? *g : 1) * w * p_c (g_c - sum_k p_k g_k), a zero row for a pixel that is not counted.
+ * sscg_upsample_head_bwd_d: the WHOLE backward of the head in one launch when the Dice branch is live - sscg_upsample_head_bwd plus
+ *   the Dice term: dx = adjoint of the resize applied to softmax_bwd(dy_soft + g_dice * (A [y == c] + B), y_soft)
+ *   + dlogits * g_ce / valid.  dy_soft and dlogits are nullable (those branches unused; g_ce NULL = 1, g_dice NULL = 1); coef and
+ *   labels are required.  Gather form (one block per source pixel), fixed summation order.  dlogits / valid are what
+ *   sscg_upsample_head_fwd[_w] left - with Dice on, the head's forward is that entry (where the cross entropy or y_soft is wanted)
+ *   plus sscg_dice_fwd; those entries are untouched.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, C outside 1..64, non-positive sizes, smooth <= 0 / NaN / infinite,
+ * batch outside {0, 1}, dlogits without valid), SSCG_ERR_UNSUPPORTED (N*OH*OW or N*H*W >= 2^31), SSCG_ERR_WORKSPACE.
+ * (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+size_t sscg_dice_workspace(int N, int OH, int OW, int C);
+int sscg_dice_fwd(const float* x, const int64_t* labels, int N, int H, int W, int C, int OH, int OW, const float* class_w, float smooth,
+                  int batch, float* loss, double* sums, float* coef, void* ws, size_t ws_bytes, void* stream);
+int sscg_dice_bwd(const float* x, const int64_t* labels, int N, int H, int W, int C, const float* coef, int batch, const float* g,
+                  float w, float* dx, void* stream);
+int sscg_upsample_head_bwd_d(const float* x, const int64_t* labels, const float* dy_soft, const float* dlogits, const float* g_ce,
+                             const float* valid, const float* coef, const float* g_dice, int batch, float* dx, int N, int H, int W,
+                             int C, int OH, int OW, void* stream);
 /* ------------------------------------------------------------------ inference heads (ABI v18): one launch from a generator's output
  * to what its consumer keeps.  Forward only; never launched by the training step.
  *

@@ -2,7 +2,7 @@
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
---ema_decay.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -40,6 +40,10 @@ class _Args(Namespace):
     weight_decay = 0.0
     adamw = False
     ema_decay = None
+    dice_weight = 0.0
+    dice_smooth = 1.0
+    dice_skip = ""
+    dice_batch = False
 
 
 def get_args(argv=None):
@@ -96,7 +100,29 @@ def get_args(argv=None):
                         help="keep an exponential moving average of the generators' (the supervised Gsi's) weights with decay F in "
                              "[0, 1); the per-epoch evaluation, the panels, --validation and --testing use it and checkpoints gain "
                              "Gsi_ema / Gis_ema (default: off)")
+    parser.add_argument("--dice_weight", type=float, default=SUPPRESS, metavar="F",
+                        help="add F times the soft Dice loss to every ground-truth cross entropy (lab_loss_CE, gt_cycle_loss, the "
+                             "supervised loss), inside that term's own weight: L + F * Dice of the same resized logits; reported as "
+                             "lab_loss_dice / gt_cycle_dice / dice_loss, and the evaluation also scores the mean and per-class Dice; "
+                             "F >= 0, 0 = off (default: off, the reference's losses)")
+    parser.add_argument("--dice_smooth", type=float, default=SUPPRESS, metavar="F",
+                        help="the smoothing constant s > 0 of the Dice ratio (2 I + s) / (P + T + s) (default: 1.0)")
+    parser.add_argument("--dice_skip", type=str, default=SUPPRESS, metavar="LIST",
+                        help="comma list of class ids the Dice loss leaves out (weight 0), e.g. 0 for VOC's background, 19 for the "
+                             "Cityscapes void class - the classes the mIoU drops (default: none)")
+    parser.add_argument("--dice_batch", action="store_true", default=SUPPRESS,
+                        help="one Dice per class over the whole batch instead of one per sample and class (per rank under data "
+                             "parallelism)")
     args = parser.parse_args(argv, namespace=_Args())
+    if not args.dice_weight >= 0.0 or args.dice_weight == float("inf"):
+        parser.error("--dice_weight must be a finite number >= 0")
+    if not (args.dice_smooth > 0.0 and args.dice_smooth < float("inf")):
+        parser.error("--dice_smooth must be a finite number > 0")
+    if args.dice_skip.strip():
+        toks = [t.strip() for t in args.dice_skip.split(",")]
+        n_cls = {"voc2012": 21, "cityscapes": 20, "acdc": 4}[args.dataset]
+        if not all(t.isdigit() and int(t) < n_cls for t in toks) or len(set(int(t) for t in toks)) >= n_cls:
+            parser.error("--dice_skip must be a comma list of class ids in [0, %d) that leaves a class over" % n_cls)
     if args.adamw and not args.weight_decay > 0.0:
         parser.error("--adamw decouples the weight decay from the gradient: it needs --weight_decay F with F > 0")
     if args.weight_decay < 0.0 or args.weight_decay != args.weight_decay:

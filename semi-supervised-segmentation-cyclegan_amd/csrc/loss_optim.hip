@@ -2,12 +2,12 @@
 // are listed in include/sscg.h.  Losses are mean reductions accumulated in fp64 in two fixed-order
 // stages (deterministic), written as one fp32 device scalar.
 #include "common.h"
+#include "head_geom.h"
 #include "sscg_internal.h"
 
 namespace {
 
 constexpr int LOSS_BLOCKS = 1024;
-constexpr int MAXC = 64;  // class axis is 4 / 20 / 21 in the reference (model.py:205-210)
 
 inline int ew_blocks(size_t n, int cap = 8192) {
     size_t b = (n + 255) / 256;
@@ -200,41 +200,6 @@ __global__ void ce_bwd_kernel(const float* __restrict__ x, const int64_t* __rest
 //   * every block sums weight * d(loss)/d(resized logit) of its output pixels: the gradient with respect to the low-resolution
 //     logits, which for the cross entropy depends on nothing but logits and labels - so the FORWARD pass already leaves it
 //     (unscaled; the backward is an elementwise scale by g / valid).
-struct HeadGeom { int N, H, W, C, OH, OW; float sh, sw, inv_sh, inv_sw; };
-
-template <int CT>
-__device__ __forceinline__ void head_logits(const float* __restrict__ xn, const HeadGeom& g, int oy, int ox, int C, float* v,
-                                            int* y0o, int* x0o) {
-    // the arithmetic of upsample_fwd_kernel (pointwise.hip)
-    const float fy = g.sh * oy, fx = g.sw * ox;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int yp = y0 < g.H - 1 ? 1 : 0, xp = x0 < g.W - 1 ? 1 : 0;
-    const float ly = fy - y0, lx = fx - x0;
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    const float* r00 = xn + ((size_t)y0 * g.W + x0) * C;
-    const float* r01 = r00 + (size_t)xp * C;
-    const float* r10 = r00 + (size_t)yp * g.W * C;
-    const float* r11 = r10 + (size_t)xp * C;
-#pragma unroll
-    for (int c = 0; c < (CT ? CT : MAXC); ++c) {
-        if (CT == 0 && c >= C) break;
-        v[c] = hy * (hx * r00[c] + lx * r01[c]) + ly * (hx * r10[c] + lx * r11[c]);
-    }
-    *y0o = y0; *x0o = x0;
-}
-
-// weight of source row / column `i` in the stencil of output row / column `o` (upsample_bwd_kernel's)
-__device__ __forceinline__ float head_weight(float scale, int o, int i, int n_src) {
-    const float f = scale * o;
-    const int i0 = (int)f;
-    const int ip = i0 < n_src - 1 ? 1 : 0;
-    const float l = f - i0;
-    float w = 0.f;
-    if (i0 == i) w += 1.f - l;
-    if (i0 + ip == i) w += l;
-    return w;
-}
-
 // MODE 0: forward (labels and / or softmax output); MODE 1: backward of the softmax output (dy_soft), plus the scaled
 // cross-entropy gradient the forward left.  WT (MODE 0 only): the class-weighted / label-smoothed cross entropy - see ce_fwd_kernel;
 // `cnt` then sums w[y], and what is left in dlo is still the gradient up to g / valid, so MODE 1 and head_scale_kernel serve it as is.
@@ -586,17 +551,6 @@ extern "C" int sscg_ce_fwd_w(const float* logits, const int64_t* labels, int64_t
     hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nb, loss, valid);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
-}
-
-static bool head_geom(HeadGeom* g, int N, int H, int W, int C, int OH, int OW) {
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > MAXC || OH <= 0 || OW <= 0) return false;
-    if ((size_t)N * H * W >= ((size_t)1 << 31)) return false;
-    g->N = N; g->H = H; g->W = W; g->C = C; g->OH = OH; g->OW = OW;
-    g->sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-    g->sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-    g->inv_sh = g->sh > 0.f ? 1.f / g->sh : (float)OH;
-    g->inv_sw = g->sw > 0.f ? 1.f / g->sw : (float)OW;
-    return true;
 }
 
 template <int MODE, bool WT = false>

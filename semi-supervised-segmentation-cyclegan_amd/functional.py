@@ -2655,6 +2655,154 @@ def upsample_softmax_ce(x, size, labels=None, want_soft=True, weight=None, label
     return (softmax2d(up) if want_soft else None), (cross_entropy(up, labels, weight, label_smoothing) if labels is not None else None)
 
 
+# ----------------------------------------------------------------------------- soft Dice (opt-in; include/sscg.h: sscg_dice_fwd)
+def dice_weight(values, num_classes, device):
+    """The class-weight operand of the Dice loss, as ce_weight: `values` (C numbers) checked on the host - length C, every entry finite
+    and >= 0, and not all zero (the loss divides by their sum) - and sent to `device` as fp32 [C]."""
+    w = ce_weight(values, num_classes, torch.device("cpu"))
+    if not float(w.sum()) > 0.0:
+        raise ValueError("dice weights: every entry is 0 (the loss divides by their sum)")
+    return w.to(device)
+
+
+class DiceOptions(object):
+    """The Dice branch of upsample_softmax_ce_dice: weight (dice_weight's tensor, or None = all ones), smooth (> 0), batch (False: one
+    Dice per sample and class, averaged; True: the whole call is one group), ce (False: the cross entropy is not wanted - Dice only)."""
+    __slots__ = ("weight", "smooth", "batch", "ce")
+
+    def __init__(self, weight=None, smooth=1.0, batch=False, ce=True):
+        self.weight, self.smooth, self.batch, self.ce = weight, float(smooth), bool(batch), bool(ce)
+
+
+def _dice_options(weight, smooth, batch, c, device):
+    s = float(smooth)
+    if not (s > 0.0 and s < float("inf")):
+        raise ValueError("dice smooth %r is not a finite number > 0" % (smooth,))
+    if weight is not None:
+        if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and weight.device == device
+                and weight.dim() == 1 and weight.numel() == c and weight.is_contiguous()):
+            raise _lib.SscgError("dice weights must be a contiguous fp32 [%d] tensor on %s (functional.dice_weight makes one)" % (c, device))
+    return weight, s, 1 if batch else 0
+
+
+def dice_fwd(x, labels, size, weight=None, smooth=1.0, batch=False, want_sums=False):
+    """sscg_dice_fwd on channels-last fp32 logits x [N,C,H,W] and int64 labels [N,OH,OW] (size = (OH, OW); (H, W): the flat Dice):
+    (loss, coef [G,C,2] = (A, B), sums [G,C,3] fp64 = (I, P, T) or None).  No autograd: dice_loss / upsample_softmax_ce_dice wrap it."""
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    if labels.numel() != n * oh * ow or labels.dtype != torch.int64:
+        raise _lib.SscgError("labels must be int64 with N*OH*OW elements")
+    weight, s, b = _dice_options(weight, smooth, batch, c, x.device)
+    groups = 1 if b else n
+    loss = _scalar(x.device)
+    coef = torch.empty((groups, c, 2), dtype=torch.float32, device=x.device)
+    sums = torch.empty((groups, c, 3), dtype=torch.float64, device=x.device) if want_sums else None
+    ws = torch.empty(lib.sscg_dice_workspace(n, oh, ow, c), dtype=torch.uint8, device=x.device)
+    check(lib.sscg_dice_fwd(x.data_ptr(), labels.data_ptr(), n, h, w, c, oh, ow, _ptr(weight), s, b, loss.data_ptr(), _ptr(sums),
+                            coef.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sscg_dice_fwd")
+    return loss, coef, sums
+
+
+class DiceLossFn(torch.autograd.Function):
+    """Soft Dice loss of logits [N,C,H,W] against labels [N,H,W] (include/sscg.h: sscg_dice_fwd / sscg_dice_bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, smooth, batch):
+        _need_hip(logits, f32_only=True)
+        logits = to_nhwc(logits)
+        labels = labels.contiguous()
+        loss, coef, _ = dice_fwd(logits, labels, logits.shape[2:], weight, smooth, batch)
+        ctx.batch = 1 if batch else 0
+        ctx.save_for_backward(logits, labels, coef)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, coef = ctx.saved_tensors
+        n, c, h, w = logits.shape
+        dx = torch.empty_like(logits, memory_format=CL)
+        check(lib.sscg_dice_bwd(logits.data_ptr(), labels.data_ptr(), n, h, w, c, coef.data_ptr(), ctx.batch, g.data_ptr(), 1.0,
+                                dx.data_ptr(), _stream()), "sscg_dice_bwd")
+        return dx, None, None, None, None
+
+
+def dice_loss(logits, labels, weight=None, smooth=1.0, batch=False):
+    """1 - mean over (group, class) of the class-weighted soft Dice of softmax(logits) against labels; labels outside [0, C) are void.
+    weight: dice_weight's tensor.  batch=False: one group per sample; True: the whole batch is one group."""
+    return DiceLossFn.apply(logits, labels, weight, smooth, batch)
+
+
+class UpsampleHeadDiceFn(torch.autograd.Function):
+    """UpsampleHeadFn with the Dice branch: returns (softmax map or None, cross entropy or None, Dice loss).  Forward: the head's own
+    launch where the softmax map or the cross entropy is wanted (the same entries, the same bits), then the Dice statistics and their
+    finish - the resized logits still never reach memory.  Dice couples the pixels of a group, so its gradient cannot be left by the
+    forward: the backward is ONE stencil launch (sscg_upsample_head_bwd_d) that serves every live branch."""
+
+    @staticmethod
+    def forward(ctx, x, oh, ow, labels, want_soft, want_ce, ce_w, eps, d_w, smooth, batch):
+        _need_hip(x, f32_only=True)
+        x = to_nhwc(x)
+        n, c, h, w = x.shape
+        labels = labels.contiguous()
+        if labels.numel() != n * oh * ow or labels.dtype != torch.int64:
+            raise _lib.SscgError("labels must be int64 with N*OH*OW elements")
+        ce_w, eps, weighted = _ce_options(ce_w, eps, c, x.device)
+        y = empty_nhwc(n, c, oh, ow, x.device) if want_soft else None
+        loss = valid = dl = ws = None
+        if want_ce:
+            loss, valid = _scalar(x.device), _scalar(x.device)
+            dl = empty_nhwc(n, c, h, w, x.device)
+            ws = torch.empty(lib.sscg_upsample_head_workspace(n, h, w), dtype=torch.uint8, device=x.device)
+        if want_ce and weighted:
+            check(lib.sscg_upsample_head_fwd_w(x.data_ptr(), labels.data_ptr(), _ptr(ce_w), eps, _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl),
+                                               n, h, w, c, oh, ow, _ptr(ws), ws.numel(), _stream()), "sscg_upsample_head_fwd_w")
+        elif want_ce or want_soft:
+            check(lib.sscg_upsample_head_fwd(x.data_ptr(), labels.data_ptr() if want_ce else None, _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl),
+                                             n, h, w, c, oh, ow, _ptr(ws), ws.numel() if ws is not None else 0, _stream()),
+                  "sscg_upsample_head_fwd")
+        dice, coef, _ = dice_fwd(x, labels, (oh, ow), d_w, smooth, batch)
+        ctx.geom = (oh, ow, 1 if batch else 0)
+        ctx.save_for_backward(x, labels, dl, valid, coef)
+        ctx.set_materialize_grads(False)
+        return y, loss, dice
+
+    @staticmethod
+    def backward(ctx, dy, g_ce, g_dice):
+        x, labels, dl, valid, coef = ctx.saved_tensors
+        oh, ow, batch = ctx.geom
+        n, c, h, w = x.shape
+        use_ce = g_ce is not None and dl is not None
+        if dy is None and not use_ce and g_dice is None:
+            return (None,) * 11
+        if dy is not None:
+            dy = to_nhwc(dy)
+        dx = empty_nhwc(n, c, h, w, x.device)
+        if g_dice is None:      # the Dice term took no part in what was differentiated: the head's own backward
+            check(lib.sscg_upsample_head_bwd(x.data_ptr(), _ptr(dy), _ptr(dl if use_ce else None), _ptr(g_ce if use_ce else None),
+                                             _ptr(valid if use_ce else None), dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
+                  "sscg_upsample_head_bwd")
+        else:
+            check(lib.sscg_upsample_head_bwd_d(x.data_ptr(), labels.data_ptr(), _ptr(dy), _ptr(dl if use_ce else None),
+                                               _ptr(g_ce if use_ce else None), _ptr(valid if use_ce else None), coef.data_ptr(),
+                                               g_dice.data_ptr(), batch, dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
+                  "sscg_upsample_head_bwd_d")
+        return (dx,) + (None,) * 10
+
+
+def upsample_softmax_ce_dice(x, size, labels, want_soft=True, weight=None, label_smoothing=0.0, dice=None):
+    """upsample_softmax_ce plus the soft Dice loss of the same resized logits: (softmax2d(interp(x)) or None, cross entropy or None, Dice).
+    dice: a DiceOptions (or a dict of its arguments; None = the defaults).  Fused when the resize grows the map - the head's forward
+    launch, the Dice statistics and their finish; one stencil launch backward - else the separate passes."""
+    if dice is None or isinstance(dice, dict):
+        dice = DiceOptions(**(dice or {}))
+    oh, ow = int(size[0]), int(size[1])
+    if _head_applies(x, oh, ow):
+        return UpsampleHeadDiceFn.apply(x, oh, ow, labels, want_soft, dice.ce, weight, label_smoothing, dice.weight, dice.smooth, dice.batch)
+    up = upsample_bilinear(x, size)
+    return ((softmax2d(up) if want_soft else None), (cross_entropy(up, labels, weight, label_smoothing) if dice.ce else None),
+            dice_loss(up, labels, dice.weight, dice.smooth, dice.batch))
+
+
 class MSEConstFn(torch.autograd.Function):
     """nn.MSELoss()(x, full_like(x, target)) - the LSGAN terms."""
 

@@ -150,6 +150,39 @@ class _WeightedCE(object):
             self._set_ce_weight(spec, "--ce_weights")
         else:
             self._ce_rule = spec
+        self._init_dice(args, C)
+
+    # --dice_weight / --dice_smooth / --dice_skip / --dice_batch (opt-in; the reference has no Dice): every ground-truth cross entropy L
+    # becomes L + dice_w * D inside its existing weight, D = the soft Dice loss of the same resized logits (functional.dice_loss)
+    dice_w = 0.0            # 0 = off: no Dice launch, no extra loss key, the evaluation's result as it always was
+    dice_options = None     # functional.DiceOptions when on
+
+    def _init_dice(self, args, C):
+        self.dice_w = float(getattr(args, "dice_weight", 0.0) or 0.0)
+        if not self.dice_w >= 0.0:
+            raise ValueError("--dice_weight %r must be >= 0" % (getattr(args, "dice_weight", None),))
+        if self.dice_w == 0.0:
+            return
+        weight = None
+        skip = utils.parse_dice_skip(getattr(args, "dice_skip", ""), C)
+        if skip:
+            weight = F.dice_weight([0.0 if c in skip else 1.0 for c in range(C)], C, self._ce_device())
+        self.dice_options = F.DiceOptions(weight=weight, smooth=float(getattr(args, "dice_smooth", 1.0)),
+                                          batch=bool(getattr(args, "dice_batch", False)))
+        if not (self.dice_options.smooth > 0.0 and self.dice_options.smooth < float("inf")):
+            raise ValueError("--dice_smooth %r must be a finite number > 0" % (getattr(args, "dice_smooth", None),))
+
+    def _head(self, logits, labels, want_soft):
+        """(softmax map or None, cross entropy, Dice loss or None) of the ground-truth head: the plain fused head by default."""
+        if self.dice_options is None:
+            return F.upsample_softmax_ce(logits, self.crop, labels, want_soft=want_soft, **self._ce_kwargs()) + (None,)
+        return F.upsample_softmax_ce_dice(logits, self.crop, labels, want_soft=want_soft, dice=self.dice_options, **self._ce_kwargs())
+
+    def _dice_scores(self, running):
+        """--dice_weight: the per-class Dice of the confusion matrix the evaluation has just scored (utils.dice_scores), with the class
+        dropping of runningScore - kept in `self.eval_dice` = {"mean_dice", "class_dice"}.  Off: nothing is computed or kept."""
+        if self.dice_options is not None:
+            self.eval_dice = running.get_dice()
 
     def _ce_device(self):
         ids = getattr(self.args, "gpu_ids", None)
@@ -356,8 +389,7 @@ class semisuper_cycleGAN(_WeightedCE):
             gsi_second.record(main)
         # :391-392 (interp), :398 (CE of the resized logits), :401-402 (their softmax) from the low-resolution logits in one pass each:
         # the resized [B, C, crop] logits are never written (functional.UpsampleHeadFn)
-        ce = self._ce_kwargs()      # {} by default: the reference's plain nn.CrossEntropyLoss()
-        lab_gt, lab_loss_CE = F.upsample_softmax_ce(lab_logits, self.crop, labels, **ce)
+        lab_gt, lab_loss_CE, lab_loss_dice = self._head(lab_logits, labels, True)      # (plain nn.CrossEntropyLoss() by default)
         fake_gt, _ = F.upsample_softmax_ce(fake_logits, self.crop)
         if fork:
             main.wait_event(gis_first)
@@ -394,6 +426,10 @@ class semisuper_cycleGAN(_WeightedCE):
             fake_img, fake_img_d, fake_img_l1 = F.split(fake_img, 3)                 # consumers: Gsi, Di, L1
             recon_logits = self.Gsi(fake_img)                                        # :410
         extra_terms, extra_weights, extras = [], [], {}
+        if lab_loss_dice is not None:                                                # --dice_weight: inside lab_loss_CE's weight
+            extras["lab_loss_dice"] = lab_loss_dice
+            extra_terms.append(lab_loss_dice)
+            extra_weights.append(a.lab_CE_weight * self.dice_w)
         if "l1_cycle" in self.variants:                                              # :453 (commented out in the reference)
             recon_img, recon_img_l1 = F.split(recon_img, 2)
             extras["img_cycle_l1"] = F.l1_loss(recon_img_l1, unl_img)
@@ -426,7 +462,11 @@ class semisuper_cycleGAN(_WeightedCE):
         img_gen_loss = F.mse_const(fake_img_dis, 1.0)                                # :445
         gt_gen_loss = F.mse_const(fake_gt_dis, 1.0)                                  # :446
         img_cycle_loss = F.mse_const(resnet_fake_img_dis, 1.0)                       # :452
-        _, gt_cycle_loss = F.upsample_softmax_ce(recon_logits, self.crop, labels, want_soft=False, **ce)    # :415 (interp), :455
+        _, gt_cycle_loss, gt_cycle_dice = self._head(recon_logits, labels, False)    # :415 (interp), :455
+        if gt_cycle_dice is not None:                                                # --dice_weight: inside gt_cycle_loss's weight
+            extras["gt_cycle_dice"] = gt_cycle_dice
+            extra_terms.append(gt_cycle_dice)
+            extra_weights.append(a.lamda_gt * self.dice_w)
         lab_loss_MSE = F.l1_loss(fake_img_l1, l_img)                                 # :461
         # :464-468  gen_loss = CE_w*CE + MSE_w*L1 + adv_w*(img_gen + gt_gen) + img_cycle + lamda_gt*gt_cycle
         gen_loss = F.weighted_sum(
@@ -506,8 +546,11 @@ class semisuper_cycleGAN(_WeightedCE):
         x_img = fake_img.detach().clone().requires_grad_(True)
         recon_img = self.interp(self.Gis(x_gt))                                          # :408,413
         img_cycle_loss = F.mse_const(self.old_Di(recon_img), 1.0)                        # :432,452
-        _, gt_cycle_loss = F.upsample_softmax_ce(self.Gsi(x_img), self.crop, labels, want_soft=False, **self._ce_kwargs())    # :410,415,455
-        F.backward(F.weighted_sum([img_cycle_loss, gt_cycle_loss], [1.0, 1.0]))          # (each term reaches one of the two inputs only)
+        _, gt_cycle_loss, gt_cycle_dice = self._head(self.Gsi(x_img), labels, False)     # :410,415,455
+        if gt_cycle_dice is None:
+            F.backward(F.weighted_sum([img_cycle_loss, gt_cycle_loss], [1.0, 1.0]))      # (each term reaches one of the two inputs only)
+        else:                                                                            # --dice_weight: gt_cycle_loss + dice_w * Dice
+            F.backward(F.weighted_sum([img_cycle_loss, gt_cycle_loss, gt_cycle_dice], [1.0, 1.0, self.dice_w]))
         F.SideStream.join(l_gt.device)
         with torch.no_grad():
             resnet_recon_img = self.old_Gis(F.softmax2d(self.old_Gsi(unl_img)))          # :418,421,422
@@ -515,8 +558,11 @@ class semisuper_cycleGAN(_WeightedCE):
             f_c = F.mse_const(self.old_Di(recon_img.detach()), 0.0)                      # :502,528 (the pool returns the current item)
             cycle_img_dis_loss = F.weighted_sum([r_c, f_c], [1.0, 1.0])                  # :534
         self.g_optimizer.zero_grad()
-        return dict(img_cycle_loss=img_cycle_loss.detach(), gt_cycle_loss=gt_cycle_loss.detach(), cycle_img_dis_loss=cycle_img_dis_loss,
-                    d_fake_gt=x_gt.grad, d_fake_img=x_img.grad, recon_img=recon_img.detach())
+        out = dict(img_cycle_loss=img_cycle_loss.detach(), gt_cycle_loss=gt_cycle_loss.detach(), cycle_img_dis_loss=cycle_img_dis_loss,
+                   d_fake_gt=x_gt.grad, d_fake_img=x_img.grad, recon_img=recon_img.detach())
+        if gt_cycle_dice is not None:
+            out["gt_cycle_dice"] = gt_cycle_dice.detach()
+        return out
 
     def _refresh_generator_copies(self, dev):
         """Data parallel: the generator update lands AFTER the discriminator step was queued, so the operand copies of the
@@ -601,6 +647,7 @@ class semisuper_cycleGAN(_WeightedCE):
             outputs = F.softmax2d(self.interp(logits))
             self.running_metrics_val.update_device(val_gt.squeeze(1), F.argmax_index(outputs))   # :566-569 without the host round trip
         score, class_iou = self.running_metrics_val.get_scores()
+        self._dice_scores(self.running_metrics_val)
         self.Gsi.train()
         self.Gis.train()
         return score["Mean IoU : \t"], class_iou
@@ -680,6 +727,8 @@ class semisuper_cycleGAN(_WeightedCE):
                     miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
                     if rank0:
                         print("The mIoU for the epoch is: ", miou)
+                        if self.dice_options is not None:
+                            print("The mean Dice for the epoch is: ", self.eval_dice["mean_dice"])
                     if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank0:                                 # model.py:641-655
@@ -733,9 +782,12 @@ class supervised_model(_WeightedCE):
     def step(self, l_img, l_gt):
         """model.py:120-143."""
         self.gsi_optimizer.zero_grad()
-        _, loss = F.upsample_softmax_ce(self.Gsi(l_img), self.crop, l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3]),
-                                        want_soft=False, **self._ce_kwargs())
-        F.backward(loss)
+        _, loss, dice = self._head(self.Gsi(l_img), l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3]), False)
+        if dice is None:
+            F.backward(loss)
+        else:       # --dice_weight: CE + dice_w * Dice; the step still returns the cross entropy, the Dice term goes to self.extras
+            self.extras = {"dice_loss": dice.detach()}
+            F.backward(F.weighted_sum([loss, dice], [1.0, self.dice_w]))
         if self.dp is not None:
             F.SideStream.join(l_img.device)
             self.dp.sync_grads(self.gsi_optimizer)
@@ -765,6 +817,7 @@ class supervised_model(_WeightedCE):
             outputs = F.softmax2d(F.upsample_bilinear(logits, self.crop))
             self.running_metrics_val.update_device(val_gt.squeeze(1), F.argmax_index(outputs))
         score, class_iou = self.running_metrics_val.get_scores()
+        self._dice_scores(self.running_metrics_val)
         self.running_metrics_val.reset()
         self.Gsi.train()
         return score["Mean IoU : \t"], class_iou
@@ -799,6 +852,8 @@ class supervised_model(_WeightedCE):
                 history.append(loss)
                 if rank == 0:
                     print("Epoch: (%3d) (%5d/%5d) | Crossentropy Loss:%.2e" % (epoch, i + 1, len(labeled_loader), loss))
+                    if self.dice_options is not None:
+                        print("Dice Loss:%.2e (weight %g)" % (float(self.extras["dice_loss"]), self.dice_w))
                     if self.gsi_optimizer.last_grad_norm is not None:       # --clip_grad_norm: the norm this step's update clipped
                         print("Grad norm:%.3e (clip %.3e)" % (float(self.gsi_optimizer.last_grad_norm), self.gsi_optimizer.max_grad_norm))
                     if writer is not None:                                          # model.py:143
@@ -812,6 +867,8 @@ class supervised_model(_WeightedCE):
                     miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
                     if rank == 0:
                         print("The mIoU for the epoch is: ", miou)
+                        if self.dice_options is not None:
+                            print("The mean Dice for the epoch is: ", self.eval_dice["mean_dice"])
                     if first:                                                       # model.py:164-186
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank == 0:

@@ -205,9 +205,46 @@ class runningScore(object):
         cls_iu = dict(zip(range(len(iu)), iu))
         return {"Overall Acc: \t": acc, "Mean Acc : \t": acc_cls, "Mean IoU : \t": np.nanmean(iu)}, cls_iu
 
+    def get_dice(self):
+        """{"mean_dice", "class_dice"} of the accumulated confusion matrix (dice_scores), over the classes get_scores() keeps."""
+        self._fold_device()
+        h, n = self.confusion_matrix, self.n_classes
+        sub = h[1:, 1:] if self.dataset == "voc2012" else (h[:n - 1, :n - 1] if self.dataset == "cityscapes" else h)
+        d = dice_scores(sub)
+        with np.errstate(invalid="ignore"):
+            mean = float(np.nanmean(d)) if np.isfinite(d).any() else float("nan")
+        return {"mean_dice": mean, "class_dice": dict(zip(range(len(d)), d))}
+
     def reset(self):
         self.confusion_matrix = np.zeros((self.n_classes, self.n_classes))
         self._device_hist = None
+
+
+def dice_scores(hist):
+    """Per-class Dice 2 TP / (2 TP + FP + FN) of a confusion matrix hist[true][predicted]; NaN for a class with an empty denominator
+    (it occurs in neither the labels nor the predictions)."""
+    h = np.asarray(hist, dtype=np.float64)
+    tp = np.diag(h)
+    den = h.sum(axis=1) + h.sum(axis=0)          # (TP + FN) + (TP + FP)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, 2.0 * tp / den, np.nan)
+
+
+def parse_dice_skip(spec, n_classes):
+    """--dice_skip: a comma list of class ids the Dice loss gives weight 0 (e.g. 0: VOC's background; 19: the Cityscapes void class) ->
+    a sorted list of distinct ids in [0, n_classes); "" / None -> [].  Skipping every class is refused (the loss divides by the sum of
+    the weights).  Raises ValueError naming the bad token."""
+    if spec is None or not str(spec).strip():
+        return []
+    ids = set()
+    for tok in str(spec).split(","):
+        t = tok.strip()
+        if not (t.isdigit() and int(t) < int(n_classes)):
+            raise ValueError("--dice_skip: %r is not a class id in [0, %d)" % (t, n_classes))
+        ids.add(int(t))
+    if len(ids) >= int(n_classes):
+        raise ValueError("--dice_skip: %r skips every class" % (spec,))
+    return sorted(ids)
 
 
 MAX_TTA_VIEWS = 8
