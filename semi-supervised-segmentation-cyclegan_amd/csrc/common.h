@@ -155,6 +155,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// grid of a grid-stride kernel with 256 threads per block over n items: at least 1 block, at most `cap`
+static inline int ew_blocks(size_t n, int cap = 8192) {
+    size_t b = (n + 255) / 256;
+    if (b > (size_t)cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
 // wave64 all-lane sum (double) through ds_bpermute-free shuffles
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

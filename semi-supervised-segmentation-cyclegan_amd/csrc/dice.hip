@@ -13,9 +13,9 @@
 //                          class) with d loss / d p_c = A [y == c] + B at a counted pixel (A = -2 k / Den, B = k Num / Den^2,
 //                          k = w_c / (G sum w)).  (One block per GROUP over the records was measured first: with batch == 1 a single
 //                          block then reads every record - 1-2 MB at the step's sizes - and cost more than the statistics.)
-//   3. the backward        flat (dice_bwd_kernel: one thread per pixel) or through the adjoint of the resize (head_dice_bwd_kernel: the
-//                          sibling of head_kernel's MODE 1 in loss_optim.hip - one block per SOURCE pixel gathers its stencil, and the
-//                          softmax-output and cross-entropy branches of the head ride in the same launch).
+//   3. the backward        flat (dice_bwd_kernel: one thread per pixel) or through the adjoint of the resize (head_dice_bwd_kernel:
+//                          the gather frame of head_geom.h - one block per SOURCE pixel gathers its stencil, and the softmax-output
+//                          and cross-entropy branches of the head ride in the same launch).
 #include "common.h"
 #include "head_common.h"
 #include "head_geom.h"
@@ -25,17 +25,8 @@ namespace {
 
 constexpr int DICE_BLOCKS = 256;   // statistics blocks per sample, grid-stride beyond: bounds the records the finish step reads
 
-inline int ew_blocks(size_t n, int cap = 8192) {
-    size_t b = (n + 255) / 256;
-    if (b > (size_t)cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 struct DiceGeom {
-    int H, W, C, OH, OW;
-    float sh, sw;
-    FastDiv dow;
+    sscg_resize_geom r;
     int npix;      // OH * OW: output pixels of a sample
     int bps;       // blocks (= records) per sample
 };
@@ -49,45 +40,30 @@ struct DiceGeom {
 template <int CT, bool RESIZE>
 __global__ __launch_bounds__(256) void dice_stats_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab,
                                                          double* __restrict__ part, DiceGeom g) {
-    __shared__ float redf[4][2 * MAXC];
-    __shared__ int redt[4][MAXC];
-    const int C = CT ? CT : g.C;
+    __shared__ float redf[4][2 * SSCG_MAXC];
+    __shared__ int redt[4][SSCG_MAXC];
+    const int C = CT ? CT : g.r.C;
     const int n = blockIdx.x / g.bps, blk = blockIdx.x - n * g.bps;
-    const float* xn = x + (size_t)n * g.H * g.W * C;
+    const float* xn = x + (size_t)n * g.r.H * g.r.W * C;
     const int64_t* ln = lab + (size_t)n * g.npix;
-    float P[CT ? CT : MAXC], I[CT ? CT : MAXC];
-    int T[CT ? CT : MAXC];
+    float P[CT ? CT : SSCG_MAXC], I[CT ? CT : SSCG_MAXC];
+    int T[CT ? CT : SSCG_MAXC];
 #pragma unroll
-    for (int c = 0; c < (CT ? CT : MAXC); ++c) { P[c] = 0.f; I[c] = 0.f; T[c] = 0; }
+    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { P[c] = 0.f; I[c] = 0.f; T[c] = 0; }
     // every thread of the block makes the same number of trips (the ballots below need the whole wave): a thread past the end
     // computes the sample's last pixel and adds nothing
     for (long base = (long)blk * 256; base < g.npix; base += (long)g.bps * 256) {      // (long: npix may sit just below 2^31)
         const long o_raw = base + threadIdx.x;
         const bool in = o_raw < g.npix;
         const int o = in ? (int)o_raw : g.npix - 1;
-        float v[CT ? CT : MAXC];
-        if (RESIZE) {
-            const int oy = fd_div(o, g.dow);
-            const int ox = o - oy * g.OW;
-            const sscg_bilin b = sscg_bilin_at(oy, ox, g.H, g.W, g.sh, g.sw);
-            const float* r00 = xn + ((size_t)b.y0 * g.W + b.x0) * C;
-            const float* r01 = r00 + (size_t)b.xp * C;
-            const float* r10 = r00 + (size_t)b.yp * g.W * C;
-            const float* r11 = r10 + (size_t)b.xp * C;
-#pragma unroll
-            for (int c = 0; c < (CT ? CT : MAXC); ++c)
-                if (CT || c < C) v[c] = sscg_bilerp(b, r00[c], r01[c], r10[c], r11[c]);
-        } else {
-            const float* r = xn + (size_t)o * C;
-#pragma unroll
-            for (int c = 0; c < (CT ? CT : MAXC); ++c)
-                if (CT || c < C) v[c] = r[c];
-        }
+        float v[CT ? CT : SSCG_MAXC];
+        const int oy = RESIZE ? fd_div(o, g.r.dow) : 0;       // the pixel within its sample: xn is the sample's map
+        sscg_pixel_logits<CT, !RESIZE>(xn, 0, oy, o - oy * g.r.OW, g.r.H, g.r.W, g.r.sh, g.r.sw, C, v);
         const int64_t l64 = ln[o];
         const int l = (in && l64 >= 0 && l64 < C) ? (int)l64 : -1;
         const float inv = sscg_softmax_exp<CT>(v, C);
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c)
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
             if (CT || c < C) {
                 const float p = v[c] * inv;
                 P[c] += l >= 0 ? p : 0.f;
@@ -97,17 +73,17 @@ __global__ __launch_bounds__(256) void dice_stats_kernel(const float* __restrict
     }
     const int wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int c = 0; c < (CT ? CT : MAXC); ++c)
+    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
         if (CT || c < C) {
             const float sp = wave_sum(P[c]), si = wave_sum(I[c]);
-            if ((threadIdx.x & 63) == 0) { redf[wave][c] = si; redf[wave][MAXC + c] = sp; redt[wave][c] = T[c]; }
+            if ((threadIdx.x & 63) == 0) { redf[wave][c] = si; redf[wave][SSCG_MAXC + c] = sp; redt[wave][c] = T[c]; }
         }
     __syncthreads();
     if ((int)threadIdx.x < C) {
         const int c = threadIdx.x;
         double* rec = part + ((size_t)blockIdx.x * C + c) * 3;
         rec[0] = ((double)redf[0][c] + (double)redf[1][c]) + ((double)redf[2][c] + (double)redf[3][c]);
-        rec[1] = ((double)redf[0][MAXC + c] + (double)redf[1][MAXC + c]) + ((double)redf[2][MAXC + c] + (double)redf[3][MAXC + c]);
+        rec[1] = ((double)redf[0][SSCG_MAXC + c] + (double)redf[1][SSCG_MAXC + c]) + ((double)redf[2][SSCG_MAXC + c] + (double)redf[3][SSCG_MAXC + c]);
         rec[2] = (double)((redt[0][c] + redt[1][c]) + (redt[2][c] + redt[3][c]));
     }
 }
@@ -182,37 +158,37 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
         float* dr = dx + r * C;
         if (l64 < 0 || l64 >= C) {
 #pragma unroll
-            for (int c = 0; c < (CT ? CT : MAXC); ++c)
+            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
                 if (CT || c < C) dr[c] = 0.f;
             continue;
         }
         const int l = (int)l64;
         const float* xr = x + r * C;
         const float* q = coef + (per_group ? (r / (size_t)per_group) : 0) * C * 2;
-        float v[CT ? CT : MAXC];
+        float v[CT ? CT : SSCG_MAXC];
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c)
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
             if (CT || c < C) v[c] = xr[c];
         const float inv = sscg_softmax_exp<CT>(v, C);
         float dot = 0.f;
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c)
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
             if (CT || c < C) {
                 v[c] *= inv;
                 dot += v[c] * ((c == l ? q[2 * c] : 0.f) + q[2 * c + 1]);
             }
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c)
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
             if (CT || c < C) dr[c] = scale * (v[c] * (((c == l ? q[2 * c] : 0.f) + q[2 * c + 1]) - dot));
     }
 }
 
 // The whole backward of the head in one launch when the Dice branch is live: head_kernel's MODE 1 (loss_optim.hip) with the Dice term.
-// One block per SOURCE pixel gathers the output pixels whose stencil touches it (head_logits / head_weight: the same candidates, the
-// same weights, the same order).  Per output pixel the gradient with respect to its probabilities is
+// One block per SOURCE pixel gathers the output pixels whose stencil touches it (head_window / head_logits / head_weight of
+// head_geom.h: the same candidates, the same weights, the same order).  Per output pixel the gradient with respect to its probabilities is
 //     q_c = g_dice * (A[c] [y == c] + B[c])   (counted pixels; 0 otherwise)   + dy_soft[c]   (SOFT)
 // then the softmax backward p_c (q_c - sum_k p_k q_k), weighted by the stencil weight.  After the block reduction the cross-entropy
-// gradient the forward left is added exactly as MODE 1 adds it: dl_ce * g_ce / valid.  The group's (A, B) rows, scaled by g_dice, sit
+// gradient the forward left is added by the same head_store_sum: dl_ce * g_ce / valid.  The group's (A, B) rows, scaled by g_dice, sit
 // in LDS (block-uniform reads).
 template <int CT, bool SOFT>
 __global__ __launch_bounds__(256) void head_dice_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab,
@@ -220,11 +196,12 @@ __global__ __launch_bounds__(256) void head_dice_bwd_kernel(const float* __restr
                                                             const float* __restrict__ g_ce, const float* __restrict__ valid,
                                                             const float* __restrict__ coef, const float* __restrict__ g_dice, int batch,
                                                             float* __restrict__ dx, HeadGeom g) {
-    __shared__ float red[4][MAXC];
-    __shared__ float sA[MAXC], sB[MAXC];
+    __shared__ float red[4][SSCG_MAXC];
+    __shared__ float sA[SSCG_MAXC], sB[SSCG_MAXC];
     const int C = CT ? CT : g.C;
     const int b = blockIdx.x;
-    const int ix = b % g.W, iy = (b / g.W) % g.H, n = b / (g.W * g.H);
+    const HeadWindow win = head_window(g, b);
+    const int ix = win.ix, iy = win.iy, n = win.n, oy_lo = win.oy_lo, ox_lo = win.ox_lo;
     if ((int)threadIdx.x < C) {
         const float gd = g_dice ? *g_dice : 1.f;
         const float* q = coef + ((size_t)(batch ? 0 : n) * C + threadIdx.x) * 2;
@@ -232,15 +209,11 @@ __global__ __launch_bounds__(256) void head_dice_bwd_kernel(const float* __restr
         sB[threadIdx.x] = gd * q[1];
     }
     __syncthreads();
-    int oy_lo = (int)floorf((iy - 1) * g.inv_sh) - 1, oy_hi = (int)ceilf((iy + 1) * g.inv_sh) + 1;
-    int ox_lo = (int)floorf((ix - 1) * g.inv_sw) - 1, ox_hi = (int)ceilf((ix + 1) * g.inv_sw) + 1;
-    oy_lo = max(oy_lo, 0); ox_lo = max(ox_lo, 0);
-    oy_hi = min(oy_hi, g.OH - 1); ox_hi = min(ox_hi, g.OW - 1);
-    const int nx = ox_hi - ox_lo + 1, cand = (oy_hi - oy_lo + 1) * nx;
+    const int nx = win.ox_hi - ox_lo + 1, cand = (win.oy_hi - oy_lo + 1) * nx;
     const float* xn = x + (size_t)n * g.H * g.W * C;
-    float acc[CT ? CT : MAXC];
+    float acc[CT ? CT : SSCG_MAXC];
 #pragma unroll
-    for (int c = 0; c < (CT ? CT : MAXC); ++c) acc[c] = 0.f;
+    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) acc[c] = 0.f;
     for (int t = threadIdx.x; t < cand; t += 256) {
         const int oy = oy_lo + t / nx, ox = ox_lo + t % nx;
         const float wy = head_weight(g.sh, oy, iy, g.H);
@@ -252,14 +225,14 @@ __global__ __launch_bounds__(256) void head_dice_bwd_kernel(const float* __restr
         const int64_t l64 = lab[o];
         const int l = (l64 < 0 || l64 >= C) ? -1 : (int)l64;
         if (!SOFT && l < 0) continue;           // not counted and no softmax branch: nothing flows through this pixel
-        float v[CT ? CT : MAXC];
+        float v[CT ? CT : SSCG_MAXC];
         int y0, x0;
         head_logits<CT>(xn, g, oy, ox, C, v, &y0, &x0);
         const float inv = sscg_softmax_exp<CT>(v, C);
         const float* gr = SOFT ? dy_soft + o * C : nullptr;
         float dot = 0.f;
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c)
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
             if (CT || c < C) {
                 v[c] *= inv;
                 float q = l >= 0 ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
@@ -267,29 +240,14 @@ __global__ __launch_bounds__(256) void head_dice_bwd_kernel(const float* __restr
                 dot += v[c] * q;
             }
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c)
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
             if (CT || c < C) {
                 float q = l >= 0 ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
                 if (SOFT) q += gr[c];
                 acc[c] += w * (v[c] * (q - dot));
             }
     }
-#pragma unroll
-    for (int c = 0; c < (CT ? CT : MAXC); ++c)
-        if (CT || c < C) {
-            const float r = wave_sum(acc[c]);
-            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = r;
-        }
-    __syncthreads();
-    if ((int)threadIdx.x < C) {
-        const int c = threadIdx.x;
-        float r = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
-        if (dl_ce) {
-            const float nv = valid ? *valid : 0.f;
-            r += dl_ce[(size_t)b * C + c] * ((g_ce ? *g_ce : 1.f) * (nv > 0.f ? 1.f / nv : 0.f));
-        }
-        dx[(size_t)b * C + c] = r;
-    }
+    head_store_sum<CT>(acc, red, C, b, dl_ce, g_ce, valid, dx);
 }
 
 int dice_bps(int OH, int OW) {
@@ -301,23 +259,21 @@ int dice_bps(int OH, int OW) {
 template <bool RESIZE>
 void launch_stats(const DiceGeom& g, int N, hipStream_t st, const float* x, const int64_t* lab, double* part) {
     const dim3 grid((unsigned)N * g.bps), blk(256);
-    if (g.C == 21) hipLaunchKernelGGL((dice_stats_kernel<21, RESIZE>), grid, blk, 0, st, x, lab, part, g);
-    else if (g.C == 20) hipLaunchKernelGGL((dice_stats_kernel<20, RESIZE>), grid, blk, 0, st, x, lab, part, g);
-    else if (g.C == 4) hipLaunchKernelGGL((dice_stats_kernel<4, RESIZE>), grid, blk, 0, st, x, lab, part, g);
-    else hipLaunchKernelGGL((dice_stats_kernel<0, RESIZE>), grid, blk, 0, st, x, lab, part, g);
+    sscg_dispatch_classes(g.r.C, [&](auto ct) {
+        hipLaunchKernelGGL((dice_stats_kernel<decltype(ct)::value, RESIZE>), grid, blk, 0, st, x, lab, part, g);
+    });
 }
 
 template <bool SOFT>
 void launch_head_bwd(const HeadGeom& g, hipStream_t st, const float* x, const int64_t* lab, const float* dy_soft, const float* dl_ce,
                      const float* g_ce, const float* valid, const float* coef, const float* g_dice, int batch, float* dx) {
     const dim3 grid((unsigned)(g.N * g.H * g.W)), blk(256);
-    if (g.C == 21) hipLaunchKernelGGL((head_dice_bwd_kernel<21, SOFT>), grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, dx, g);
-    else if (g.C == 20) hipLaunchKernelGGL((head_dice_bwd_kernel<20, SOFT>), grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, dx, g);
-    else if (g.C == 4) hipLaunchKernelGGL((head_dice_bwd_kernel<4, SOFT>), grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, dx, g);
-    else hipLaunchKernelGGL((head_dice_bwd_kernel<0, SOFT>), grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, dx, g);
+    sscg_dispatch_classes(g.C, [&](auto ct) {
+        hipLaunchKernelGGL((head_dice_bwd_kernel<decltype(ct)::value, SOFT>), grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, dx, g);
+    });
 }
 
-bool sizes_ok(int N, int H, int W, int C, int OH, int OW) { return N > 0 && H > 0 && W > 0 && C > 0 && C <= MAXC && OH > 0 && OW > 0; }
+bool sizes_ok(int N, int H, int W, int C, int OH, int OW) { return N > 0 && H > 0 && W > 0 && C > 0 && C <= SSCG_MAXC && OH > 0 && OW > 0; }
 
 bool too_large(int N, int H, int W, int OH, int OW) {
     const size_t lim = (size_t)1 << 31;
@@ -338,13 +294,7 @@ extern "C" int sscg_dice_fwd(const float* x, const int64_t* labels, int N, int H
     if (too_large(N, H, W, OH, OW)) return SSCG_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < sscg_dice_workspace(N, OH, OW, C)) return SSCG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    DiceGeom g;
-    g.H = H; g.W = W; g.C = C; g.OH = OH; g.OW = OW;
-    g.sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-    g.sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-    g.dow = make_fastdiv(OW);
-    g.npix = OH * OW;
-    g.bps = dice_bps(OH, OW);
+    const DiceGeom g = {sscg_make_resize_geom(H, W, C, OH, OW), OH * OW, dice_bps(OH, OW)};
     double* part = reinterpret_cast<double*>(ws);
     if (OH == H && OW == W) launch_stats<false>(g, N, st, x, labels, part);
     else launch_stats<true>(g, N, st, x, labels, part);
@@ -357,17 +307,16 @@ extern "C" int sscg_dice_fwd(const float* x, const int64_t* labels, int N, int H
 
 extern "C" int sscg_dice_bwd(const float* x, const int64_t* labels, int N, int H, int W, int C, const float* coef, int batch,
                              const float* g, float w, float* dx, void* stream) {
-    if (!x || !labels || !coef || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
+    if (!x || !labels || !coef || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > SSCG_MAXC) return SSCG_ERR_BAD_ARG;
     if (batch != 0 && batch != 1) return SSCG_ERR_BAD_ARG;
     if (too_large(N, H, W, H, W)) return SSCG_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const size_t rows = (size_t)N * H * W;
     const int per_group = batch ? 0 : H * W;
     const dim3 grid(ew_blocks(rows)), blk(256);
-    if (C == 21) hipLaunchKernelGGL(dice_bwd_kernel<21>, grid, blk, 0, st, x, labels, rows, C, per_group, coef, g, w, dx);
-    else if (C == 20) hipLaunchKernelGGL(dice_bwd_kernel<20>, grid, blk, 0, st, x, labels, rows, C, per_group, coef, g, w, dx);
-    else if (C == 4) hipLaunchKernelGGL(dice_bwd_kernel<4>, grid, blk, 0, st, x, labels, rows, C, per_group, coef, g, w, dx);
-    else hipLaunchKernelGGL(dice_bwd_kernel<0>, grid, blk, 0, st, x, labels, rows, C, per_group, coef, g, w, dx);
+    sscg_dispatch_classes(C, [&](auto ct) {
+        hipLaunchKernelGGL(dice_bwd_kernel<decltype(ct)::value>, grid, blk, 0, st, x, labels, rows, C, per_group, coef, g, w, dx);
+    });
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

@@ -9,8 +9,12 @@
 //     strict > from class 0 up).  No multiply feeds an add there, so nothing can contract.
 //   * The sum of several views' probabilities (tta.hip): there a multiply does feed an add - the probability v[c] * inv, which the
 //     separate passes store as an fp32 value, into the accumulator - so that function is pinned as well.
+// Around that arithmetic, everything else the class-axis kernels share (predict.hip, tta.hip, panels.hip, dice.hip, loss_optim.hip):
+// the class limit, the resize scales and the output-pixel geometry, the loader of one pixel's logits, the element fetch of the
+// element-wise resizes, the per-workgroup confusion bins and the host dispatch over the instantiated class counts.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 constexpr int SSCG_MAXC = 64;   // class axis is 4 / 20 / 21 in the reference (model.py:205-210)
 
@@ -39,6 +43,69 @@ __device__ __forceinline__ float sscg_bilerp(const sscg_bilin& b, float v00, flo
     const float bot = __builtin_fmaf(b.lx, v11, b.hx * v10);
     const float a = b.hy * top, c = b.ly * bot;
     return a + c;
+}
+
+// ---- host: the align_corners=True scale of one axis (src = scale * dst) and the bound the gather kernels invert it by
+static inline float sscg_resize_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
+// scale == 0 (a single source row / column) => every output row touches it: scan the full range
+static inline float sscg_resize_inv_scale(float scale, int out) { return scale > 0.f ? 1.f / scale : (float)out; }
+
+// output pixel -> source stencil: what a kernel with one thread per output pixel / element needs
+struct sscg_resize_geom {
+    int H, W, C, OH, OW;
+    float sh, sw;
+    FastDiv dow, doh;
+};
+
+static inline sscg_resize_geom sscg_make_resize_geom(int H, int W, int C, int OH, int OW) {
+    sscg_resize_geom g;
+    g.H = H; g.W = W; g.C = C; g.OH = OH; g.OW = OW;
+    g.sh = sscg_resize_scale(H, OH); g.sw = sscg_resize_scale(W, OW);
+    g.dow = make_fastdiv(OW); g.doh = make_fastdiv(OH);
+    return g;
+}
+
+struct sscg_pixel { int n, oy, ox; };
+
+// output index o = (n * OH + oy) * OW + ox
+__device__ __forceinline__ sscg_pixel sscg_pixel_of(int o, const sscg_resize_geom& g) {
+    sscg_pixel p;
+    const int t = fd_div(o, g.dow);
+    p.ox = o - t * g.OW;
+    p.n = fd_div(t, g.doh);
+    p.oy = t - p.n * g.OH;
+    return p;
+}
+
+// The C logits of output pixel (n, oy, ox) in registers, from the [.][H][W][C] map x.  IDENT: the map has the output's size - the pixel's
+// own row (n = oy = 0 and ox = the flat pixel index address the same row without the split); else the four source rows through the
+// pinned stencil.  ox is the column in the MAP's coordinates: a mirrored view passes OW - 1 - ox.
+// CT: class count at compile time (0 = any C <= SSCG_MAXC, every loop predicated on c < C so that v[] stays in registers).
+template <int CT, bool IDENT>
+__device__ __forceinline__ void sscg_pixel_logits(const float* __restrict__ x, int n, int oy, int ox, int H, int W, float sh, float sw,
+                                                  int C, float* v) {
+    if (IDENT) {
+        const float* r = x + (((size_t)n * H + oy) * W + ox) * C;
+#pragma unroll
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
+            if (CT || c < C) v[c] = r[c];
+    } else {
+        const sscg_bilin b = sscg_bilin_at(oy, ox, H, W, sh, sw);
+        const float* r00 = x + (((size_t)n * H + b.y0) * W + b.x0) * C;
+        const float* r01 = r00 + (size_t)b.xp * C;
+        const float* r10 = r00 + (size_t)b.yp * W * C;
+        const float* r11 = r10 + (size_t)b.xp * C;
+#pragma unroll
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
+            if (CT || c < C) v[c] = sscg_bilerp(b, r00[c], r01[c], r10[c], r11[c]);
+    }
+}
+
+// One element through the stencil: p = the sample's map + the channel, C floats from pixel to pixel.
+__device__ __forceinline__ float sscg_bilerp_elem(const float* __restrict__ p, const sscg_bilin& b, int W, int C) {
+    const float v00 = p[((size_t)b.y0 * W + b.x0) * C], v01 = p[((size_t)b.y0 * W + b.x0 + b.xp) * C];
+    const float v10 = p[((size_t)(b.y0 + b.yp) * W + b.x0) * C], v11 = p[((size_t)(b.y0 + b.yp) * W + b.x0 + b.xp) * C];
+    return sscg_bilerp(b, v00, v01, v10, v11);
 }
 
 // nn.Softmax2d of one pixel's C values, in place: v[c] <- exp(v[c] - max); returns 1 / sum, the factor every v[c] is multiplied by.
@@ -95,4 +162,31 @@ __device__ __forceinline__ int sscg_first_max(const float* a, int C) {
             if (a[c] > best) { best = a[c]; bi = c; }
         }
     return bi;
+}
+
+// ---- the [C][C] confusion counts of one workgroup of 256 threads in LDS (nb = C * C bins; nb == 0, block-uniform: no histogram asked
+// for, nothing happens): clear, count while the pixels are walked, flush with one 64-bit atomic per bin that was hit.  Integer sums:
+// the result does not depend on the order.
+__device__ __forceinline__ void sscg_bins_clear(unsigned int* bins, int nb) {
+    for (int i = threadIdx.x; i < nb; i += 256) bins[i] = 0u;
+    if (nb) __syncthreads();
+}
+
+__device__ __forceinline__ void sscg_bins_count(unsigned int* bins, int C, int64_t truth, int pred) {      // pred in [0, C)
+    if (truth >= 0 && truth < C) atomicAdd(&bins[(int)truth * C + pred], 1u);
+}
+
+__device__ __forceinline__ void sscg_bins_flush(const unsigned int* bins, int nb, unsigned long long* __restrict__ hist) {
+    if (nb) __syncthreads();
+    for (int i = threadIdx.x; i < nb; i += 256)
+        if (bins[i]) atomicAdd(&hist[i], (unsigned long long)bins[i]);
+}
+
+// ---- host: f(std::integral_constant<int, CT>) for the instantiated class count that serves C - 21, 20, 4, or 0 = C at run time
+template <class F>
+static inline void sscg_dispatch_classes(int C, F&& f) {
+    if (C == 21) f(std::integral_constant<int, 21>{});
+    else if (C == 20) f(std::integral_constant<int, 20>{});
+    else if (C == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 0>{});
 }

@@ -1,13 +1,13 @@
 // The geometry of the fused label head (resize -> softmax -> losses from the low-resolution logits), shared by loss_optim.hip (the
 // cross-entropy head) and dice.hip (the Dice statistics and the head backward with Dice): the launch geometry, the resized logits
-// of one output pixel and the stencil weight of a source row / column.  Device code is not linked across translation units: this
+// of one output pixel, the stencil weight of a source row / column, and the frame of a gather block - one block per SOURCE pixel: its
+// window of candidate output pixels (also upsample_bwd_kernel's, pointwise.hip) and the block sum that ends it.  Device code is not linked across translation units: this
 // header is instantiated in each, in an unnamed namespace as the kernels that use it are.
 #pragma once
 #include "common.h"
+#include "head_common.h"
 
 namespace {
-
-constexpr int MAXC = 64;  // class axis is 4 / 20 / 21 in the reference (model.py:205-210)
 
 struct HeadGeom { int N, H, W, C, OH, OW; float sh, sw, inv_sh, inv_sw; };
 
@@ -15,6 +15,7 @@ template <int CT>
 __device__ __forceinline__ void head_logits(const float* __restrict__ xn, const HeadGeom& g, int oy, int ox, int C, float* v,
                                             int* y0o, int* x0o) {
     // the arithmetic of upsample_fwd_kernel (pointwise.hip)
+    // NOT head_common.h's pinned sscg_bilerp, on purpose: contraction is the compiler's here and the training step's bits depend on it
     const float fy = g.sh * oy, fx = g.sw * ox;
     const int y0 = (int)fy, x0 = (int)fx;
     const int yp = y0 < g.H - 1 ? 1 : 0, xp = x0 < g.W - 1 ? 1 : 0;
@@ -25,7 +26,7 @@ __device__ __forceinline__ void head_logits(const float* __restrict__ xn, const 
     const float* r10 = r00 + (size_t)yp * g.W * C;
     const float* r11 = r10 + (size_t)xp * C;
 #pragma unroll
-    for (int c = 0; c < (CT ? CT : MAXC); ++c) {
+    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) {
         if (CT == 0 && c >= C) break;
         v[c] = hy * (hx * r00[c] + lx * r01[c]) + ly * (hx * r10[c] + lx * r11[c]);
     }
@@ -44,15 +45,59 @@ __device__ __forceinline__ float head_weight(float scale, int o, int i, int n_sr
     return w;
 }
 
+// source pixel (n, iy, ix) and the output rows / columns whose stencil can touch it (a superset: head_weight decides)
+struct HeadWindow { int n, iy, ix, oy_lo, oy_hi, ox_lo, ox_hi; };
+
+__device__ __forceinline__ HeadWindow head_window_at(int n, int iy, int ix, int OH, int OW, float inv_sh, float inv_sw) {
+    HeadWindow w;
+    w.n = n; w.iy = iy; w.ix = ix;
+    int oy_lo = (int)floorf((iy - 1) * inv_sh) - 1, oy_hi = (int)ceilf((iy + 1) * inv_sh) + 1;
+    int ox_lo = (int)floorf((ix - 1) * inv_sw) - 1, ox_hi = (int)ceilf((ix + 1) * inv_sw) + 1;
+    w.oy_lo = max(oy_lo, 0); w.ox_lo = max(ox_lo, 0);
+    w.oy_hi = min(oy_hi, OH - 1); w.ox_hi = min(ox_hi, OW - 1);
+    return w;
+}
+
+// block b of a grid of N * H * W: its source pixel and window
+__device__ __forceinline__ HeadWindow head_window(const HeadGeom& g, int b) {
+    return head_window_at(b / (g.W * g.H), (b / g.W) % g.H, b % g.W, g.OH, g.OW, g.inv_sh, g.inv_sw);
+}
+
+// The end of a gather block: acc[c] summed over the block's 256 threads (wave butterflies, then the four waves in a fixed order), plus
+// - dl_ce != NULL - the cross-entropy gradient the forward left, scaled by g_ce / valid; row b of out.
+template <int CT>
+__device__ __forceinline__ void head_store_sum(const float (&acc)[CT ? CT : SSCG_MAXC], float (&red)[4][SSCG_MAXC], int C, int b, const float* __restrict__ dl_ce,
+                                               const float* __restrict__ g_ce, const float* __restrict__ valid, float* __restrict__ out) {
+#pragma unroll
+    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
+        if (CT || c < C) {
+            const float r = wave_sum(acc[c]);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = r;
+        }
+    __syncthreads();
+    if ((int)threadIdx.x < C) {
+        const int c = threadIdx.x;
+        float r = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+        if (dl_ce) {
+            const float nv = valid ? *valid : 0.f;
+            r += dl_ce[(size_t)b * C + c] * ((g_ce ? *g_ce : 1.f) * (nv > 0.f ? 1.f / nv : 0.f));
+        }
+        out[(size_t)b * C + c] = r;
+    }
+}
+
 }  // namespace
 
-static bool head_geom(HeadGeom* g, int N, int H, int W, int C, int OH, int OW) {
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > MAXC || OH <= 0 || OW <= 0) return false;
-    if ((size_t)N * H * W >= ((size_t)1 << 31)) return false;
+// the scales of a resize H x W -> OH x OW and the bounds the windows invert them by
+static void head_scales(HeadGeom* g, int N, int H, int W, int C, int OH, int OW) {
     g->N = N; g->H = H; g->W = W; g->C = C; g->OH = OH; g->OW = OW;
-    g->sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-    g->sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-    g->inv_sh = g->sh > 0.f ? 1.f / g->sh : (float)OH;
-    g->inv_sw = g->sw > 0.f ? 1.f / g->sw : (float)OW;
+    g->sh = sscg_resize_scale(H, OH); g->sw = sscg_resize_scale(W, OW);
+    g->inv_sh = sscg_resize_inv_scale(g->sh, OH); g->inv_sw = sscg_resize_inv_scale(g->sw, OW);
+}
+
+static bool head_geom(HeadGeom* g, int N, int H, int W, int C, int OH, int OW) {
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > SSCG_MAXC || OH <= 0 || OW <= 0) return false;
+    if ((size_t)N * H * W >= ((size_t)1 << 31)) return false;
+    head_scales(g, N, H, W, C, OH, OW);
     return true;
 }

@@ -9,13 +9,6 @@ namespace {
 
 constexpr int LOSS_BLOCKS = 1024;
 
-inline int ew_blocks(size_t n, int cap = 8192) {
-    size_t b = (n + 255) / 256;
-    if (b > (size_t)cap) b = cap;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 __device__ __forceinline__ void block_sum_to(double v, double* out) {
     __shared__ double sm[4];
     v = wave_sum(v);
@@ -41,7 +34,7 @@ __global__ void finish_loss_kernel(const double* __restrict__ part, int nparts, 
 __global__ void softmax_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, size_t rows, int C) {
     for (size_t r = (size_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (size_t)gridDim.x * 256) {
         const float* xr = x + r * C;
-        float v[MAXC];
+        float v[SSCG_MAXC];
         float m = -INFINITY;
         for (int c = 0; c < C; ++c) { v[c] = xr[c]; m = fmaxf(m, v[c]); }
         float s = 0.f;
@@ -173,7 +166,7 @@ __global__ void ce_bwd_kernel(const float* __restrict__ x, const int64_t* __rest
             for (int c = 0; c < C; ++c) dr[c] = 0.f;
             continue;
         }
-        float v[MAXC];
+        float v[SSCG_MAXC];
         float m = -INFINITY;
         for (int c = 0; c < C; ++c) { v[c] = xr[c]; m = fmaxf(m, v[c]); }
         float s = 0.f;
@@ -209,25 +202,22 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
                                                    const float* __restrict__ g_ce, const float* __restrict__ valid,
                                                    double* __restrict__ part, int nparts, HeadGeom g,
                                                    const float* __restrict__ class_w, float smoothing) {
-    __shared__ float red[4][MAXC];
+    __shared__ float red[4][SSCG_MAXC];
     const int C = CT ? CT : g.C;
     const int b = blockIdx.x;
-    const int ix = b % g.W, iy = (b / g.W) % g.H, n = b / (g.W * g.H);
-    int oy_lo = (int)floorf((iy - 1) * g.inv_sh) - 1, oy_hi = (int)ceilf((iy + 1) * g.inv_sh) + 1;
-    int ox_lo = (int)floorf((ix - 1) * g.inv_sw) - 1, ox_hi = (int)ceilf((ix + 1) * g.inv_sw) + 1;
-    oy_lo = max(oy_lo, 0); ox_lo = max(ox_lo, 0);
-    oy_hi = min(oy_hi, g.OH - 1); ox_hi = min(ox_hi, g.OW - 1);
-    const int nx = ox_hi - ox_lo + 1, cand = (oy_hi - oy_lo + 1) * nx;
+    const HeadWindow win = head_window(g, b);
+    const int ix = win.ix, iy = win.iy, n = win.n, oy_lo = win.oy_lo, ox_lo = win.ox_lo;
+    const int nx = win.ox_hi - ox_lo + 1, cand = (win.oy_hi - oy_lo + 1) * nx;
     const float* xn = x + (size_t)n * g.H * g.W * C;
-    float acc[CT ? CT : MAXC];
+    float acc[CT ? CT : SSCG_MAXC];
 #pragma unroll
-    for (int c = 0; c < (CT ? CT : MAXC); ++c) acc[c] = 0.f;
+    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) acc[c] = 0.f;
     double loss = 0.0, cnt = 0.0;
-    float wr[WT ? (CT ? CT : MAXC) : 1];      // WT: the class weights (block-uniform loads) and their sum, once per block
+    float wr[WT ? (CT ? CT : SSCG_MAXC) : 1];      // WT: the class weights (block-uniform loads) and their sum, once per block
     float wsum = 0.f;
     if (WT) {
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c) {
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) {
             if (CT == 0 && c >= C) break;
             wr[c] = class_weight(class_w, c);
             wsum += wr[c];
@@ -240,14 +230,14 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
         const float wx = head_weight(g.sw, ox, ix, g.W);
         if (wx == 0.f) continue;
         const float w = wy * wx;
-        float v[CT ? CT : MAXC];
+        float v[CT ? CT : SSCG_MAXC];
         int y0, x0;
         head_logits<CT>(xn, g, oy, ox, C, v, &y0, &x0);
         const bool owner = y0 == iy && x0 == ix;
         const size_t o = ((size_t)n * g.OH + oy) * g.OW + ox;
         float m = -INFINITY;
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c) { if (CT == 0 && c >= C) break; m = fmaxf(m, v[c]); }
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; m = fmaxf(m, v[c]); }
         int l = -1;
         float vl = 0.f;
         if (MODE == 0 && lab) {
@@ -256,7 +246,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
         }
         float s = 0.f, swd = 0.f;
 #pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c) {
+        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) {
             if (CT == 0 && c >= C) break;
             if (c == l) vl = v[c];
             if (WT) swd += wr[c] * (v[c] - m);
@@ -268,7 +258,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
             if (owner && y_soft) {
                 float* yr = y_soft + o * C;
 #pragma unroll
-                for (int c = 0; c < (CT ? CT : MAXC); ++c) { if (CT == 0 && c >= C) break; yr[c] = v[c] * inv; }
+                for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; yr[c] = v[c] * inv; }
             }
             if (l >= 0) {
                 const float wl = class_weight(class_w, l);
@@ -280,7 +270,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
                 }
                 const float k = a + bs * wsum;
 #pragma unroll
-                for (int c = 0; c < (CT ? CT : MAXC); ++c) {
+                for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) {
                     if (CT == 0 && c >= C) break;
                     acc[c] += w * (v[c] * inv * k - (c == l ? a : 0.f) - bs * wr[c]);
                 }
@@ -290,40 +280,23 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
             if (owner && y_soft) {
                 float* yr = y_soft + o * C;
 #pragma unroll
-                for (int c = 0; c < (CT ? CT : MAXC); ++c) { if (CT == 0 && c >= C) break; yr[c] = v[c] * inv; }
+                for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; yr[c] = v[c] * inv; }
             }
             if (l >= 0) {
 #pragma unroll
-                for (int c = 0; c < (CT ? CT : MAXC); ++c) { if (CT == 0 && c >= C) break; acc[c] += w * (v[c] * inv - (c == l ? 1.f : 0.f)); }
+                for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; acc[c] += w * (v[c] * inv - (c == l ? 1.f : 0.f)); }
             }
         } else {
             const float* gr = dy_soft + o * C;
             float dot = 0.f;
 #pragma unroll
-            for (int c = 0; c < (CT ? CT : MAXC); ++c) { if (CT == 0 && c >= C) break; v[c] *= inv; dot += v[c] * gr[c]; }
+            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; v[c] *= inv; dot += v[c] * gr[c]; }
 #pragma unroll
-            for (int c = 0; c < (CT ? CT : MAXC); ++c) { if (CT == 0 && c >= C) break; acc[c] += w * (v[c] * (gr[c] - dot)); }
+            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; acc[c] += w * (v[c] * (gr[c] - dot)); }
         }
     }
     const bool want_sum = MODE == 1 || (lab && dlo);
-    if (want_sum) {
-#pragma unroll
-        for (int c = 0; c < (CT ? CT : MAXC); ++c) {
-            if (CT == 0 && c >= C) break;
-            const float r = wave_sum(acc[c]);
-            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = r;
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < C) {
-            const int c = threadIdx.x;
-            float r = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
-            if (MODE == 1 && dl_ce) {
-                const float nv = valid ? *valid : 0.f;
-                r += dl_ce[(size_t)b * C + c] * ((g_ce ? *g_ce : 1.f) * (nv > 0.f ? 1.f / nv : 0.f));
-            }
-            dlo[(size_t)b * C + c] = r;
-        }
-    }
+    if (want_sum) head_store_sum<CT>(acc, red, C, b, MODE == 1 ? dl_ce : nullptr, g_ce, valid, dlo);
     if (MODE == 0 && lab && part) {
         __syncthreads();
         block_sum_to(loss, part + b);
@@ -434,14 +407,14 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 }  // namespace
 
 extern "C" int sscg_softmax_fwd(const float* x, float* y, int64_t rows, int C, void* stream) {
-    if (!x || !y || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
+    if (!x || !y || rows <= 0 || C <= 0 || C > SSCG_MAXC) return SSCG_ERR_BAD_ARG;
     hipLaunchKernelGGL(softmax_fwd_kernel, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, y, (size_t)rows, C);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }
 
 extern "C" int sscg_softmax_bwd(const float* dy, const float* y, float* dx, int64_t rows, int C, void* stream) {
-    if (!dy || !y || !dx || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
+    if (!dy || !y || !dx || rows <= 0 || C <= 0 || C > SSCG_MAXC) return SSCG_ERR_BAD_ARG;
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, (size_t)rows, C);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
@@ -469,21 +442,17 @@ __global__ __launch_bounds__(256) void confusion_hist_kernel(const int64_t* __re
                                                               int64_t n, int C, unsigned long long* __restrict__ hist) {
     extern __shared__ unsigned int bins[];
     const int nb = C * C;
-    for (int i = threadIdx.x; i < nb; i += 256) bins[i] = 0u;
-    __syncthreads();
+    sscg_bins_clear(bins, nb);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t t = lt[i];
         const int64_t q = lp[i];
-        if (t >= 0 && t < C && q >= 0 && q < C) atomicAdd(&bins[(int)t * C + (int)q], 1u);
+        if (q >= 0 && q < C) sscg_bins_count(bins, C, lt[i], (int)q);
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nb; i += 256)
-        if (bins[i]) atomicAdd(&hist[i], (unsigned long long)bins[i]);
+    sscg_bins_flush(bins, nb, hist);
 }
 
 extern "C" int sscg_confusion_hist(const int64_t* label_true, const int64_t* label_pred, int64_t n, int C, int64_t* hist,
                                    void* stream) {
-    if (!label_true || !label_pred || !hist || n < 0 || C <= 0 || C > 64) return SSCG_ERR_BAD_ARG;
+    if (!label_true || !label_pred || !hist || n < 0 || C <= 0 || C > SSCG_MAXC) return SSCG_ERR_BAD_ARG;
     if (n == 0) return SSCG_OK;
     int64_t blocks = (n + 256 * 16 - 1) / (256 * 16);   // ~16 pixels per thread: few global atomics
     if (blocks > 1024) blocks = 1024;
@@ -496,8 +465,8 @@ extern "C" int sscg_confusion_hist(const int64_t* label_true, const int64_t* lab
 // Class frequencies of a label map (the input of the class-weight rules): the same scheme with C bins.
 __global__ __launch_bounds__(256) void label_hist_kernel(const int64_t* __restrict__ lab, int64_t n, int C,
                                                           unsigned long long* __restrict__ counts) {
-    __shared__ unsigned int bins[64];
-    if (threadIdx.x < 64) bins[threadIdx.x] = 0u;
+    __shared__ unsigned int bins[SSCG_MAXC];
+    if (threadIdx.x < SSCG_MAXC) bins[threadIdx.x] = 0u;
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t l = lab[i];
@@ -508,7 +477,7 @@ __global__ __launch_bounds__(256) void label_hist_kernel(const int64_t* __restri
 }
 
 extern "C" int sscg_label_hist(const int64_t* labels, int64_t n, int C, int64_t* counts, void* stream) {
-    if (!labels || !counts || n < 0 || C <= 0 || C > 64) return SSCG_ERR_BAD_ARG;
+    if (!labels || !counts || n < 0 || C <= 0 || C > SSCG_MAXC) return SSCG_ERR_BAD_ARG;
     if (n == 0) return SSCG_OK;
     int64_t blocks = (n + 256 * 16 - 1) / (256 * 16);   // as sscg_confusion_hist: a block's int32 bins hold at most n / blocks < 2^32 counts
     if (blocks > 1024) blocks = 1024;
@@ -523,34 +492,35 @@ extern "C" size_t sscg_loss_workspace(int64_t n) {
     return (size_t)2 * LOSS_BLOCKS * sizeof(double);   // cross entropy keeps (sum, count) partials
 }
 
-extern "C" int sscg_ce_fwd(const float* logits, const int64_t* labels, int64_t rows, int C, float* loss, float* valid,
-                           void* ws, size_t ws_bytes, void* stream) {
-    if (!logits || !labels || !loss || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
+// The plain entries and their _w twins share one implementation each.  A _w entry refuses a smoothing outside [0, 1) first; with no
+// class weights and no smoothing (class_w == NULL, smoothing == 0: what the plain entry passes) the plain instantiation runs.
+static bool smoothing_ok(float smoothing) { return smoothing >= 0.f && smoothing < 1.f; }     // (false for a NaN)
+
+static int ce_fwd(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing, float* loss,
+                  float* valid, void* ws, size_t ws_bytes, void* stream) {
+    if (!logits || !labels || !loss || rows <= 0 || C <= 0 || C > SSCG_MAXC) return SSCG_ERR_BAD_ARG;
     if (!ws || ws_bytes < sscg_loss_workspace(rows)) return SSCG_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     int nb = ew_blocks(rows, LOSS_BLOCKS);
     double* part = reinterpret_cast<double*>(ws);
-    hipLaunchKernelGGL(ce_fwd_kernel<false>, dim3(nb), dim3(256), 0, st, logits, labels, (size_t)rows, C, part, nb, (const float*)nullptr, 0.f);
+    if (class_w || smoothing != 0.f)
+        hipLaunchKernelGGL(ce_fwd_kernel<true>, dim3(nb), dim3(256), 0, st, logits, labels, (size_t)rows, C, part, nb, class_w, smoothing);
+    else
+        hipLaunchKernelGGL(ce_fwd_kernel<false>, dim3(nb), dim3(256), 0, st, logits, labels, (size_t)rows, C, part, nb, class_w, smoothing);
     hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nb, loss, valid);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }
 
-static bool smoothing_ok(float smoothing) { return smoothing >= 0.f && smoothing < 1.f; }     // (false for a NaN)
+extern "C" int sscg_ce_fwd(const float* logits, const int64_t* labels, int64_t rows, int C, float* loss, float* valid,
+                           void* ws, size_t ws_bytes, void* stream) {
+    return ce_fwd(logits, labels, rows, C, nullptr, 0.f, loss, valid, ws, ws_bytes, stream);
+}
 
 extern "C" int sscg_ce_fwd_w(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing,
                              float* loss, float* valid, void* ws, size_t ws_bytes, void* stream) {
     if (!smoothing_ok(smoothing)) return SSCG_ERR_BAD_ARG;
-    if (!class_w && smoothing == 0.f) return sscg_ce_fwd(logits, labels, rows, C, loss, valid, ws, ws_bytes, stream);
-    if (!logits || !labels || !loss || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
-    if (!ws || ws_bytes < sscg_loss_workspace(rows)) return SSCG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    int nb = ew_blocks(rows, LOSS_BLOCKS);
-    double* part = reinterpret_cast<double*>(ws);
-    hipLaunchKernelGGL(ce_fwd_kernel<true>, dim3(nb), dim3(256), 0, st, logits, labels, (size_t)rows, C, part, nb, class_w, smoothing);
-    hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nb, loss, valid);
-    SSCG_LAUNCH_CHECK();
-    return SSCG_OK;
+    return ce_fwd(logits, labels, rows, C, class_w, smoothing, loss, valid, ws, ws_bytes, stream);
 }
 
 template <int MODE, bool WT = false>
@@ -558,18 +528,17 @@ static void launch_head(const HeadGeom& g, hipStream_t st, const float* x, const
                         float* dlo, const float* dl_ce, const float* g_ce, const float* valid, double* part, int nparts,
                         const float* class_w = nullptr, float smoothing = 0.f) {
     const dim3 grid(nparts), blk(256);
-    if (g.C == 21) hipLaunchKernelGGL((head_kernel<21, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
-    else if (g.C == 20) hipLaunchKernelGGL((head_kernel<20, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
-    else if (g.C == 4) hipLaunchKernelGGL((head_kernel<4, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
-    else hipLaunchKernelGGL((head_kernel<0, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
+    sscg_dispatch_classes(g.C, [&](auto ct) {
+        hipLaunchKernelGGL((head_kernel<decltype(ct)::value, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
+    });
 }
 
 extern "C" size_t sscg_upsample_head_workspace(int N, int H, int W) {
     return (size_t)2 * (size_t)(N > 0 ? N : 0) * (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0) * sizeof(double);
 }
 
-extern "C" int sscg_upsample_head_fwd(const float* x, const int64_t* labels, float* y_soft, float* loss, float* valid, float* dlogits,
-                                      int N, int H, int W, int C, int OH, int OW, void* ws, size_t ws_bytes, void* stream) {
+static int head_fwd(const float* x, const int64_t* labels, const float* class_w, float smoothing, float* y_soft, float* loss, float* valid,
+                    float* dlogits, int N, int H, int W, int C, int OH, int OW, void* ws, size_t ws_bytes, void* stream) {
     HeadGeom g;
     if (!x || !head_geom(&g, N, H, W, C, OH, OW) || (!labels && !y_soft)) return SSCG_ERR_BAD_ARG;
     if (labels && (!loss || !valid || !dlogits)) return SSCG_ERR_BAD_ARG;
@@ -577,29 +546,26 @@ extern "C" int sscg_upsample_head_fwd(const float* x, const int64_t* labels, flo
     hipStream_t st = (hipStream_t)stream;
     const int nparts = N * H * W;
     double* part = labels ? reinterpret_cast<double*>(ws) : nullptr;
-    launch_head<0>(g, st, x, labels, y_soft, nullptr, labels ? dlogits : nullptr, nullptr, nullptr, nullptr, part, nparts);
+    float* dlo = labels ? dlogits : nullptr;
+    if (labels && (class_w || smoothing != 0.f))      // else nothing weighted to compute: the plain instantiations
+        launch_head<0, true>(g, st, x, labels, y_soft, nullptr, dlo, nullptr, nullptr, nullptr, part, nparts, class_w, smoothing);
+    else
+        launch_head<0>(g, st, x, labels, y_soft, nullptr, dlo, nullptr, nullptr, nullptr, part, nparts);
     if (labels) hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nparts, loss, valid);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
+}
+
+extern "C" int sscg_upsample_head_fwd(const float* x, const int64_t* labels, float* y_soft, float* loss, float* valid, float* dlogits,
+                                      int N, int H, int W, int C, int OH, int OW, void* ws, size_t ws_bytes, void* stream) {
+    return head_fwd(x, labels, nullptr, 0.f, y_soft, loss, valid, dlogits, N, H, W, C, OH, OW, ws, ws_bytes, stream);
 }
 
 extern "C" int sscg_upsample_head_fwd_w(const float* x, const int64_t* labels, const float* class_w, float smoothing, float* y_soft,
                                         float* loss, float* valid, float* dlogits, int N, int H, int W, int C, int OH, int OW, void* ws,
                                         size_t ws_bytes, void* stream) {
     if (!smoothing_ok(smoothing)) return SSCG_ERR_BAD_ARG;
-    if (!labels || (!class_w && smoothing == 0.f))      // nothing weighted to compute: the plain instantiations
-        return sscg_upsample_head_fwd(x, labels, y_soft, loss, valid, dlogits, N, H, W, C, OH, OW, ws, ws_bytes, stream);
-    HeadGeom g;
-    if (!x || !head_geom(&g, N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
-    if (!loss || !valid || !dlogits) return SSCG_ERR_BAD_ARG;
-    if (!ws || ws_bytes < sscg_upsample_head_workspace(N, H, W)) return SSCG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int nparts = N * H * W;
-    double* part = reinterpret_cast<double*>(ws);
-    launch_head<0, true>(g, st, x, labels, y_soft, nullptr, dlogits, nullptr, nullptr, nullptr, part, nparts, class_w, smoothing);
-    hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nparts, loss, valid);
-    SSCG_LAUNCH_CHECK();
-    return SSCG_OK;
+    return head_fwd(x, labels, class_w, smoothing, y_soft, loss, valid, dlogits, N, H, W, C, OH, OW, ws, ws_bytes, stream);
 }
 
 extern "C" int sscg_upsample_head_bwd(const float* x, const float* dy_soft, const float* dlogits, const float* g_ce, const float* valid,
@@ -619,24 +585,28 @@ extern "C" int sscg_upsample_head_bwd(const float* x, const float* dy_soft, cons
     return SSCG_OK;
 }
 
-extern "C" int sscg_ce_bwd(const float* logits, const int64_t* labels, int64_t rows, int C, const float* gscale, float w,
-                           const float* valid, float* dx, void* stream) {
-    if (!logits || !labels || !dx || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
-    hipLaunchKernelGGL(ce_bwd_kernel<false>, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, logits, labels, (size_t)rows,
-                       C, gscale, w, valid, dx, (const float*)nullptr, 0.f);
+static int ce_bwd(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing,
+                  const float* gscale, float w, const float* valid, float* dx, void* stream) {
+    if (!logits || !labels || !dx || rows <= 0 || C <= 0 || C > SSCG_MAXC) return SSCG_ERR_BAD_ARG;
+    const dim3 grid(ew_blocks(rows)), blk(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (class_w || smoothing != 0.f)
+        hipLaunchKernelGGL(ce_bwd_kernel<true>, grid, blk, 0, st, logits, labels, (size_t)rows, C, gscale, w, valid, dx, class_w, smoothing);
+    else
+        hipLaunchKernelGGL(ce_bwd_kernel<false>, grid, blk, 0, st, logits, labels, (size_t)rows, C, gscale, w, valid, dx, class_w, smoothing);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
+}
+
+extern "C" int sscg_ce_bwd(const float* logits, const int64_t* labels, int64_t rows, int C, const float* gscale, float w,
+                           const float* valid, float* dx, void* stream) {
+    return ce_bwd(logits, labels, rows, C, nullptr, 0.f, gscale, w, valid, dx, stream);
 }
 
 extern "C" int sscg_ce_bwd_w(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing,
                              const float* gscale, float w, const float* valid, float* dx, void* stream) {
     if (!smoothing_ok(smoothing)) return SSCG_ERR_BAD_ARG;
-    if (!class_w && smoothing == 0.f) return sscg_ce_bwd(logits, labels, rows, C, gscale, w, valid, dx, stream);
-    if (!logits || !labels || !dx || rows <= 0 || C <= 0 || C > MAXC) return SSCG_ERR_BAD_ARG;
-    hipLaunchKernelGGL(ce_bwd_kernel<true>, dim3(ew_blocks(rows)), dim3(256), 0, (hipStream_t)stream, logits, labels, (size_t)rows,
-                       C, gscale, w, valid, dx, class_w, smoothing);
-    SSCG_LAUNCH_CHECK();
-    return SSCG_OK;
+    return ce_bwd(logits, labels, rows, C, class_w, smoothing, gscale, w, valid, dx, stream);
 }
 
 extern "C" int sscg_mse_const_fwd(const float* x, int64_t n, float target, float* loss, void* ws, size_t ws_bytes,

@@ -20,13 +20,12 @@ constexpr int PANEL_MAX_BLOCKS = 1024;
 
 // ------------------------------------------------------------------------------------------------------------------ labels
 struct LabelGeom {
-    int H, W, C, OH, OW;
-    float sh, sw;
-    FastDiv dow, doh, dc;
+    sscg_resize_geom r;
+    FastDiv dc;
 };
 
-// A workgroup takes 256 consecutive output pixels at a time.  Phase 1 is predict_head_kernel's: one thread per pixel, its C logits in
-// registers, the functions of head_common.h - the id goes to LDS.  Phase 2 writes what the 256 ids stand for: their bytes as 16
+// A workgroup takes 256 consecutive output pixels at a time.  Phase 1: one thread per pixel, its C logits in registers, the functions
+// of head_common.h as in predict_head_kernel - the id goes to LDS.  Phase 2 writes what the 256 ids stand for: their bytes as 16
 // 16-byte stores, and the chunk's 256 * C one-hot floats - one contiguous range of the [pixels][C] map - as 16-byte vectors, a wave's
 // store covering 1 KB of consecutive addresses (a thread per pixel would scatter C four-byte stores 4 * C bytes apart).  `mis`: floats
 // by which the one-hot base misses 16-byte alignment (0..3; 4 = not even float aligned: scalar stores only); elements in front of the
@@ -35,7 +34,7 @@ template <int CT, bool IDENT>
 __global__ __launch_bounds__(PANEL_THREADS) void panel_labels_kernel(const float* __restrict__ x, uint8_t* __restrict__ label_u8,
                                                                      float* __restrict__ onehot, int total, int mis, LabelGeom g) {
     __shared__ __attribute__((aligned(16))) uint8_t ids[PANEL_THREADS];
-    const int C = CT ? CT : g.C;
+    const int C = CT ? CT : g.r.C;
     const int chunks = (total + PANEL_THREADS - 1) / PANEL_THREADS;
     const bool u8_vec = ((size_t)label_u8 & 15) == 0;
     for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
@@ -44,25 +43,8 @@ __global__ __launch_bounds__(PANEL_THREADS) void panel_labels_kernel(const float
         const int o = p0 + (int)threadIdx.x;
         if (o < total) {
             float v[CT ? CT : SSCG_MAXC];
-            if (IDENT) {
-                const float* r = x + (size_t)o * C;
-#pragma unroll
-                for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-                    if (CT || c < C) v[c] = r[c];
-            } else {
-                const int t = fd_div(o, g.dow);
-                const int ox = o - t * g.OW;
-                const int n = fd_div(t, g.doh);
-                const int oy = t - n * g.OH;
-                const sscg_bilin b = sscg_bilin_at(oy, ox, g.H, g.W, g.sh, g.sw);
-                const float* r00 = x + (((size_t)n * g.H + b.y0) * g.W + b.x0) * C;
-                const float* r01 = r00 + (size_t)b.xp * C;
-                const float* r10 = r00 + (size_t)b.yp * g.W * C;
-                const float* r11 = r10 + (size_t)b.xp * C;
-#pragma unroll
-                for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-                    if (CT || c < C) v[c] = sscg_bilerp(b, r00[c], r01[c], r10[c], r11[c]);
-            }
+            const sscg_pixel p = IDENT ? sscg_pixel{0, 0, o} : sscg_pixel_of(o, g.r);
+            sscg_pixel_logits<CT, IDENT>(x, p.n, p.oy, p.ox, g.r.H, g.r.W, g.r.sh, g.r.sw, C, v);
             const float inv = sscg_softmax_exp<CT>(v, C);
             ids[threadIdx.x] = (uint8_t)sscg_first_max_scaled<CT>(v, inv, C);
         }
@@ -109,10 +91,9 @@ template <bool IDENT>
 void launch_labels(const LabelGeom& g, int total, int mis, hipStream_t st, const float* x, uint8_t* label_u8, float* onehot) {
     const int chunks = (total + PANEL_THREADS - 1) / PANEL_THREADS;
     const dim3 grid(chunks > PANEL_MAX_BLOCKS ? PANEL_MAX_BLOCKS : chunks), blk(PANEL_THREADS);
-    if (g.C == 21) hipLaunchKernelGGL((panel_labels_kernel<21, IDENT>), grid, blk, 0, st, x, label_u8, onehot, total, mis, g);
-    else if (g.C == 20) hipLaunchKernelGGL((panel_labels_kernel<20, IDENT>), grid, blk, 0, st, x, label_u8, onehot, total, mis, g);
-    else if (g.C == 4) hipLaunchKernelGGL((panel_labels_kernel<4, IDENT>), grid, blk, 0, st, x, label_u8, onehot, total, mis, g);
-    else hipLaunchKernelGGL((panel_labels_kernel<0, IDENT>), grid, blk, 0, st, x, label_u8, onehot, total, mis, g);
+    sscg_dispatch_classes(g.r.C, [&](auto ct) {
+        hipLaunchKernelGGL((panel_labels_kernel<decltype(ct)::value, IDENT>), grid, blk, 0, st, x, label_u8, onehot, total, mis, g);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------------ values
@@ -311,13 +292,7 @@ extern "C" int sscg_panel_labels(const float* x, int N, int H, int W, int C, int
     if (C > SSCG_MAXC) return SSCG_ERR_UNSUPPORTED;
     const size_t pixels = (size_t)N * OH * OW;
     if (pixels * (onehot ? (size_t)C : 1) >= ((size_t)1 << 31)) return SSCG_ERR_UNSUPPORTED;
-    LabelGeom g;
-    g.H = H; g.W = W; g.C = C; g.OH = OH; g.OW = OW;
-    g.sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;      // sscg_upsample_bilinear_fwd's scales
-    g.sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-    g.dow = make_fastdiv(OW);
-    g.doh = make_fastdiv(OH);
-    g.dc = make_fastdiv(C);
+    const LabelGeom g = {sscg_make_resize_geom(H, W, C, OH, OW), make_fastdiv(C)};
     const int mis = ((size_t)onehot & 3) ? 4 : (int)(((size_t)onehot >> 2) & 3);
     if (OH == H && OW == W) launch_labels<true>(g, (int)pixels, mis, (hipStream_t)stream, x, label_u8, onehot);
     else launch_labels<false>(g, (int)pixels, mis, (hipStream_t)stream, x, label_u8, onehot);

@@ -2,16 +2,10 @@
 // listed per entry point in include/sscg.h.
 #include "common.h"
 #include "head_common.h"
+#include "head_geom.h"
 #include "sscg_internal.h"
 
 namespace {
-
-inline int ew_blocks(size_t n) {
-    size_t b = (n + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 template <typename T>
 __global__ void act_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, size_t n, int act, float slope) {
@@ -221,10 +215,7 @@ __global__ void upsample_fwd_kernel(const float* __restrict__ x, float* __restri
         int oy = (int)(t % OH);
         int n = (int)(t / OH);
         const sscg_bilin g = sscg_bilin_at(oy, ox, H, W, sh, sw);
-        const float* b = x + (size_t)n * H * W * C + c;
-        float v00 = b[((size_t)g.y0 * W + g.x0) * C], v01 = b[((size_t)g.y0 * W + g.x0 + g.xp) * C];
-        float v10 = b[((size_t)(g.y0 + g.yp) * W + g.x0) * C], v11 = b[((size_t)(g.y0 + g.yp) * W + g.x0 + g.xp) * C];
-        y[i] = sscg_bilerp(g, v00, v01, v10, v11);
+        y[i] = sscg_bilerp_elem(x + (size_t)n * H * W * C + c, g, W, C);
     }
 }
 
@@ -238,12 +229,9 @@ __global__ void upsample_bwd_kernel(const float* __restrict__ dy, float* __restr
         int ix = (int)(t % W); t /= W;
         int iy = (int)(t % H);
         int n = (int)(t / H);
-        int oy_lo = (int)floorf((iy - 1) * inv_sh) - 1, oy_hi = (int)ceilf((iy + 1) * inv_sh) + 1;
-        int ox_lo = (int)floorf((ix - 1) * inv_sw) - 1, ox_hi = (int)ceilf((ix + 1) * inv_sw) + 1;
-        oy_lo = max(oy_lo, 0); ox_lo = max(ox_lo, 0);
-        oy_hi = min(oy_hi, OH - 1); ox_hi = min(ox_hi, OW - 1);
+        const HeadWindow win = head_window_at(n, iy, ix, OH, OW, inv_sh, inv_sw);
         float s = 0.f;
-        for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+        for (int oy = win.oy_lo; oy <= win.oy_hi; ++oy) {
             float fy = sh * oy;
             int y0 = (int)fy;
             int yp = y0 < H - 1 ? 1 : 0;
@@ -252,7 +240,7 @@ __global__ void upsample_bwd_kernel(const float* __restrict__ dy, float* __restr
             if (y0 == iy) wy += 1.f - ly;
             if (y0 + yp == iy) wy += ly;
             if (wy == 0.f) continue;
-            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+            for (int ox = win.ox_lo; ox <= win.ox_hi; ++ox) {
                 float fx = sw * ox;
                 int x0 = (int)fx;
                 int xp = x0 < W - 1 ? 1 : 0;
@@ -502,8 +490,7 @@ extern "C" int sscg_maxpool2x2_bwd(const void* dy, const uint8_t* idx, void* dx,
 extern "C" int sscg_upsample_bilinear_fwd(const float* x, float* y, int N, int H, int W, int C, int OH, int OW,
                                           void* stream) {
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0) return SSCG_ERR_BAD_ARG;
-    float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-    float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+    const float sh = sscg_resize_scale(H, OH), sw = sscg_resize_scale(W, OW);
     size_t total = (size_t)N * OH * OW * C;
     hipLaunchKernelGGL(upsample_fwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, OH, OW, sh, sw);
     SSCG_LAUNCH_CHECK();
@@ -513,14 +500,11 @@ extern "C" int sscg_upsample_bilinear_fwd(const float* x, float* y, int N, int H
 extern "C" int sscg_upsample_bilinear_bwd(const float* dy, float* dx, int N, int H, int W, int C, int OH, int OW,
                                           void* stream) {
     if (!dy || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0) return SSCG_ERR_BAD_ARG;
-    float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-    float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-    // sh == 0 (single source row) => every output row touches row 0: scan the full range
-    float inv_sh = sh > 0.f ? 1.f / sh : (float)OH;
-    float inv_sw = sw > 0.f ? 1.f / sw : (float)OW;
+    HeadGeom g;
+    head_scales(&g, N, H, W, C, OH, OW);
     size_t total = (size_t)N * H * W * C;
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, H, W, C, OH, OW,
-                       sh, sw, inv_sh, inv_sw);
+                       g.sh, g.sw, g.inv_sh, g.inv_sw);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

@@ -11,11 +11,7 @@ namespace {
 
 constexpr int MAX_BLOCKS = 2048;   // 8 workgroups per CU, grid-stride beyond: bounds the LDS histograms flushed per launch
 
-struct PredGeom {
-    int H, W, C, OH, OW;
-    float sh, sw;
-    FastDiv dow, doh;
-};
+typedef sscg_resize_geom PredGeom;
 
 // One thread per OUTPUT pixel, consecutive lanes on consecutive pixels of a row: a wave's uint8 stores form one 64-byte segment, its
 // int64 stores one of 512 bytes.  The C logits of the pixel live in registers; the four source rows are contiguous C-vectors of the
@@ -29,43 +25,18 @@ __global__ __launch_bounds__(256) void predict_head_kernel(const float* __restri
     extern __shared__ unsigned int bins[];      // [C][C] counts of this workgroup (hist != NULL only)
     const int C = CT ? CT : g.C;
     const int nb = hist ? C * C : 0;
-    for (int i = threadIdx.x; i < nb; i += 256) bins[i] = 0u;
-    if (hist) __syncthreads();
+    sscg_bins_clear(bins, nb);
     for (int o = blockIdx.x * 256 + threadIdx.x; o < total; o += gridDim.x * 256) {
         float v[CT ? CT : SSCG_MAXC];
-        if (IDENT) {
-            const float* r = x + (size_t)o * C;
-#pragma unroll
-            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-                if (CT || c < C) v[c] = r[c];
-        } else {
-            const int t = fd_div(o, g.dow);
-            const int ox = o - t * g.OW;
-            const int n = fd_div(t, g.doh);
-            const int oy = t - n * g.OH;
-            const sscg_bilin b = sscg_bilin_at(oy, ox, g.H, g.W, g.sh, g.sw);
-            const float* r00 = x + (((size_t)n * g.H + b.y0) * g.W + b.x0) * C;
-            const float* r01 = r00 + (size_t)b.xp * C;
-            const float* r10 = r00 + (size_t)b.yp * g.W * C;
-            const float* r11 = r10 + (size_t)b.xp * C;
-#pragma unroll
-            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-                if (CT || c < C) v[c] = sscg_bilerp(b, r00[c], r01[c], r10[c], r11[c]);
-        }
+        const sscg_pixel p = IDENT ? sscg_pixel{0, 0, o} : sscg_pixel_of(o, g);
+        sscg_pixel_logits<CT, IDENT>(x, p.n, p.oy, p.ox, g.H, g.W, g.sh, g.sw, C, v);
         const float inv = sscg_softmax_exp<CT>(v, C);
         const int bi = sscg_first_max_scaled<CT>(v, inv, C);
         if (index) index[o] = bi;
         if (label_u8) label_u8[o] = (uint8_t)bi;
-        if (hist) {
-            const int64_t t = lt[o];
-            if (t >= 0 && t < C) atomicAdd(&bins[(int)t * C + bi], 1u);
-        }
+        if (hist) sscg_bins_count(bins, C, lt[o], bi);
     }
-    if (hist) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < nb; i += 256)
-            if (bins[i]) atomicAdd(&hist[i], (unsigned long long)bins[i]);
-    }
+    sscg_bins_flush(bins, nb, hist);
 }
 
 // t * 0.5 + 0.5 (validation.py), then x * 255 + 0.5, clamp, truncate (save_image): the host rounds each of the four operations to fp32
@@ -80,7 +51,7 @@ __device__ __forceinline__ uint8_t pixel_u8(float t) {
     return (uint8_t)(int)fminf(fmaxf(px, 0.f), 255.f);
 }
 
-// One thread per output ELEMENT (n, oy, ox, c), upsample_fwd_kernel's mapping: fp32 and uint8 stores of a wave are contiguous.
+// One thread per output ELEMENT (n, oy, ox, c): fp32 and uint8 stores of a wave are contiguous.
 template <bool IDENT>
 __global__ __launch_bounds__(256) void image_head_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ rgb,
                                                          int total, PredGeom g, FastDiv dc) {
@@ -91,15 +62,9 @@ __global__ __launch_bounds__(256) void image_head_kernel(const float* __restrict
         } else {
             const int t = fd_div(i, dc);
             const int c = i - t * g.C;
-            const int u = fd_div(t, g.dow);
-            const int ox = t - u * g.OW;
-            const int n = fd_div(u, g.doh);
-            const int oy = u - n * g.OH;
-            const sscg_bilin b = sscg_bilin_at(oy, ox, g.H, g.W, g.sh, g.sw);
-            const float* p = x + (size_t)n * g.H * g.W * g.C + c;
-            const float v00 = p[((size_t)b.y0 * g.W + b.x0) * g.C], v01 = p[((size_t)b.y0 * g.W + b.x0 + b.xp) * g.C];
-            const float v10 = p[((size_t)(b.y0 + b.yp) * g.W + b.x0) * g.C], v11 = p[((size_t)(b.y0 + b.yp) * g.W + b.x0 + b.xp) * g.C];
-            r = sscg_bilerp(b, v00, v01, v10, v11);
+            const sscg_pixel p = sscg_pixel_of(t, g);
+            const sscg_bilin b = sscg_bilin_at(p.oy, p.ox, g.H, g.W, g.sh, g.sw);
+            r = sscg_bilerp_elem(x + (size_t)p.n * g.H * g.W * g.C + c, b, g.W, g.C);
         }
         const float th = sscg_act(r, SSCG_ACT_TANH, 0.f);       // sscg_act_fwd's routine
         if (y) y[i] = th;
@@ -110,28 +75,18 @@ __global__ __launch_bounds__(256) void image_head_kernel(const float* __restrict
 bool pred_geom(PredGeom* g, int* total, int N, int H, int W, int C, int OH, int OW, int per_pixel) {
     const size_t n_out = (size_t)N * OH * OW * per_pixel;
     if (n_out >= ((size_t)1 << 31)) return false;
-    g->H = H; g->W = W; g->C = C; g->OH = OH; g->OW = OW;
-    g->sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;      // sscg_upsample_bilinear_fwd's scales
-    g->sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-    g->dow = make_fastdiv(OW);
-    g->doh = make_fastdiv(OH);
+    *g = sscg_make_resize_geom(H, W, C, OH, OW);
     *total = (int)n_out;
     return true;
-}
-
-inline int head_blocks(int total) {
-    const int b = (total + 255) / 256;
-    return b > MAX_BLOCKS ? MAX_BLOCKS : b;
 }
 
 template <bool IDENT>
 void launch_predict(const PredGeom& g, int total, size_t lds, hipStream_t st, const float* x, int64_t* index, uint8_t* label_u8,
                     const int64_t* lt, unsigned long long* hist) {
-    const dim3 grid(head_blocks(total)), blk(256);
-    if (g.C == 21) hipLaunchKernelGGL((predict_head_kernel<21, IDENT>), grid, blk, lds, st, x, index, label_u8, lt, hist, total, g);
-    else if (g.C == 20) hipLaunchKernelGGL((predict_head_kernel<20, IDENT>), grid, blk, lds, st, x, index, label_u8, lt, hist, total, g);
-    else if (g.C == 4) hipLaunchKernelGGL((predict_head_kernel<4, IDENT>), grid, blk, lds, st, x, index, label_u8, lt, hist, total, g);
-    else hipLaunchKernelGGL((predict_head_kernel<0, IDENT>), grid, blk, lds, st, x, index, label_u8, lt, hist, total, g);
+    const dim3 grid(ew_blocks(total, MAX_BLOCKS)), blk(256);
+    sscg_dispatch_classes(g.C, [&](auto ct) {
+        hipLaunchKernelGGL((predict_head_kernel<decltype(ct)::value, IDENT>), grid, blk, lds, st, x, index, label_u8, lt, hist, total, g);
+    });
 }
 
 }  // namespace
@@ -156,7 +111,7 @@ extern "C" int sscg_image_head(const float* x, int N, int H, int W, int C, int O
     PredGeom g;
     int total;
     if (!pred_geom(&g, &total, N, H, W, C, OH, OW, C)) return SSCG_ERR_UNSUPPORTED;
-    const dim3 grid(head_blocks(total)), blk(256);
+    const dim3 grid(ew_blocks(total, MAX_BLOCKS)), blk(256);
     if (OH == H && OW == W)
         hipLaunchKernelGGL(image_head_kernel<true>, grid, blk, 0, (hipStream_t)stream, x, y_nhwc, rgb_u8, total, g, make_fastdiv(C));
     else

@@ -10,7 +10,7 @@
 
 namespace {
 
-constexpr int MAX_BLOCKS = 2048;   // predict_head_kernel's cap: 8 workgroups per CU, grid-stride beyond
+constexpr int MAX_BLOCKS = 2048;   // 8 workgroups per CU, grid-stride beyond: bounds the LDS histograms flushed per launch
 constexpr int MAX_VIEWS = 8;
 
 // The views travel in the kernel's argument block: the host arrays are copied here during the call, no pointer table on the device.
@@ -22,13 +22,10 @@ struct MsViews {
     uint32_t flip;
 };
 
-struct MsGeom {
-    int C, OH, OW;
-    FastDiv dow, doh;
-};
+typedef sscg_resize_geom MsGeom;      // C, OH, OW and the pixel split; H, W and the scales are per view (MsViews)
 
-// predict_head_kernel's mapping - one thread per OUTPUT pixel, consecutive lanes on consecutive pixels of a row - with a loop over
-// the views inside: v[] holds the view's C logits / exponentials, acc[] the running sum of the views' probabilities, both in
+// One thread per OUTPUT pixel, consecutive lanes on consecutive pixels of a row, with a loop over the views inside: v[] holds the
+// view's C logits / exponentials (sscg_pixel_logits), acc[] the running sum of the views' probabilities, both in
 // registers (every class loop is unrolled, so no index is a run-time one).  The views are walked in order and every lane of a wave
 // walks the same one: its geometry comes from the argument block through uniform loads.  The low-resolution maps are about a
 // megabyte each and stay cache resident; only the outputs asked for are written.
@@ -40,35 +37,18 @@ __global__ __launch_bounds__(256) void predict_head_ms_kernel(MsViews vw, float*
     extern __shared__ unsigned int bins[];      // [C][C] counts of this workgroup (hist != NULL only)
     const int C = CT ? CT : g.C;
     const int nb = hist ? C * C : 0;
-    for (int i = threadIdx.x; i < nb; i += 256) bins[i] = 0u;
-    if (hist) __syncthreads();
+    sscg_bins_clear(bins, nb);
     for (int o = blockIdx.x * 256 + threadIdx.x; o < total; o += gridDim.x * 256) {
-        const int t = fd_div(o, g.dow);
-        const int ox = o - t * g.OW;
-        const int n = fd_div(t, g.doh);
-        const int oy = t - n * g.OH;
+        const sscg_pixel p = sscg_pixel_of(o, g);
         float acc[CT ? CT : SSCG_MAXC] = {};
 #pragma nounroll
         for (int s = 0; s < vw.S; ++s) {
             const int H = vw.H[s], W = vw.W[s];
             const float* __restrict__ x = vw.x[s];
-            const int oxs = (vw.flip >> s) & 1u ? g.OW - 1 - ox : ox;       // a mirrored view's map is in mirrored coordinates
+            const int oxs = (vw.flip >> s) & 1u ? g.OW - 1 - p.ox : p.ox;       // a mirrored view's map is in mirrored coordinates
             float v[CT ? CT : SSCG_MAXC];
-            if (H == g.OH && W == g.OW) {                                    // identity resize: the pixel's own logits
-                const float* r = x + (((size_t)n * H + oy) * W + oxs) * C;
-#pragma unroll
-                for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-                    if (CT || c < C) v[c] = r[c];
-            } else {
-                const sscg_bilin b = sscg_bilin_at(oy, oxs, H, W, vw.sh[s], vw.sw[s]);
-                const float* r00 = x + (((size_t)n * H + b.y0) * W + b.x0) * C;
-                const float* r01 = r00 + (size_t)b.xp * C;
-                const float* r10 = r00 + (size_t)b.yp * W * C;
-                const float* r11 = r10 + (size_t)b.xp * C;
-#pragma unroll
-                for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-                    if (CT || c < C) v[c] = sscg_bilerp(b, r00[c], r01[c], r10[c], r11[c]);
-            }
+            if (H == g.OH && W == g.OW) sscg_pixel_logits<CT, true>(x, p.n, p.oy, oxs, H, W, 0.f, 0.f, C, v);      // identity resize
+            else sscg_pixel_logits<CT, false>(x, p.n, p.oy, oxs, H, W, vw.sh[s], vw.sw[s], C, v);
             const float inv = sscg_softmax_exp<CT>(v, C);
             sscg_prob_accumulate<CT>(acc, v, inv, C, s == 0);
         }
@@ -81,24 +61,14 @@ __global__ __launch_bounds__(256) void predict_head_ms_kernel(MsViews vw, float*
         const int bi = sscg_first_max<CT>(acc, C);
         if (index) index[o] = bi;
         if (label_u8) label_u8[o] = (uint8_t)bi;
-        if (hist) {
-            const int64_t tl = lt[o];
-            if (tl >= 0 && tl < C) atomicAdd(&bins[(int)tl * C + bi], 1u);
-        }
+        if (hist) sscg_bins_count(bins, C, lt[o], bi);
     }
-    if (hist) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < nb; i += 256)
-            if (bins[i]) atomicAdd(&hist[i], (unsigned long long)bins[i]);
-    }
+    sscg_bins_flush(bins, nb, hist);
 }
 
-struct FlipGeom {
-    int H, W, C, OH, OW;
-    float sh, sw;
-};
+typedef sscg_resize_geom FlipGeom;      // (the 64-bit element index is split by plain divisions: dow / doh are not used)
 
-// One thread per output ELEMENT (n, oy, ox, c), upsample_fwd_kernel's mapping and arithmetic; output column ox takes the resized
+// One thread per output ELEMENT (n, oy, ox, c); output column ox takes the resized
 // map's column OW - 1 - ox when FLIP.  IDENT: OH == H && OW == W, a pure mirror copy.
 template <bool IDENT, bool FLIP>
 __global__ __launch_bounds__(256) void resize_flip_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total, FlipGeom g) {
@@ -113,17 +83,9 @@ __global__ __launch_bounds__(256) void resize_flip_kernel(const float* __restric
         if (IDENT) {
             y[i] = b[((size_t)oy * g.W + oxs) * g.C];
         } else {
-            const sscg_bilin q = sscg_bilin_at(oy, oxs, g.H, g.W, g.sh, g.sw);
-            const float v00 = b[((size_t)q.y0 * g.W + q.x0) * g.C], v01 = b[((size_t)q.y0 * g.W + q.x0 + q.xp) * g.C];
-            const float v10 = b[((size_t)(q.y0 + q.yp) * g.W + q.x0) * g.C], v11 = b[((size_t)(q.y0 + q.yp) * g.W + q.x0 + q.xp) * g.C];
-            y[i] = sscg_bilerp(q, v00, v01, v10, v11);
+            y[i] = sscg_bilerp_elem(b, sscg_bilin_at(oy, oxs, g.H, g.W, g.sh, g.sw), g.W, g.C);
         }
     }
-}
-
-inline int capped_blocks(size_t n, int cap) {
-    const size_t b = (n + 255) / 256;
-    return b > (size_t)cap ? cap : (int)b;
 }
 
 }  // namespace
@@ -139,36 +101,30 @@ extern "C" int sscg_predict_head_ms(const float* const* xs, const int* Hs, const
         const int u = s < S ? s : 0;            // the unused slots repeat view 0: never read, never garbage
         if (!xs[u] || Hs[u] <= 0 || Ws[u] <= 0) return SSCG_ERR_BAD_ARG;
         vw.x[s] = xs[u]; vw.H[s] = Hs[u]; vw.W[s] = Ws[u];
-        vw.sh[s] = OH > 1 ? (float)(Hs[u] - 1) / (float)(OH - 1) : 0.f;      // sscg_upsample_bilinear_fwd's scales
-        vw.sw[s] = OW > 1 ? (float)(Ws[u] - 1) / (float)(OW - 1) : 0.f;
+        vw.sh[s] = sscg_resize_scale(Hs[u], OH);
+        vw.sw[s] = sscg_resize_scale(Ws[u], OW);
     }
     vw.S = S; vw.flip = flip_mask;
     const size_t pixels = (size_t)N * OH * OW;
     if (pixels >= ((size_t)1 << 31) || (prob_sum && pixels * C >= ((size_t)1 << 31))) return SSCG_ERR_UNSUPPORTED;
-    MsGeom g;
-    g.C = C; g.OH = OH; g.OW = OW;
-    g.dow = make_fastdiv(OW); g.doh = make_fastdiv(OH);
+    const MsGeom g = sscg_make_resize_geom(OH, OW, C, OH, OW);
     const int total = (int)pixels;
     const size_t lds = hist ? (size_t)C * C * sizeof(unsigned int) : 0;       // <= 16 KB
     unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
-    const dim3 grid(capped_blocks(pixels, MAX_BLOCKS)), blk(256);
+    const dim3 grid(ew_blocks(pixels, MAX_BLOCKS)), blk(256);
     hipStream_t st = (hipStream_t)stream;
-    if (C == 21) hipLaunchKernelGGL(predict_head_ms_kernel<21>, grid, blk, lds, st, vw, prob_sum, index, label_u8, label_true, h, total, g);
-    else if (C == 20) hipLaunchKernelGGL(predict_head_ms_kernel<20>, grid, blk, lds, st, vw, prob_sum, index, label_u8, label_true, h, total, g);
-    else if (C == 4) hipLaunchKernelGGL(predict_head_ms_kernel<4>, grid, blk, lds, st, vw, prob_sum, index, label_u8, label_true, h, total, g);
-    else hipLaunchKernelGGL(predict_head_ms_kernel<0>, grid, blk, lds, st, vw, prob_sum, index, label_u8, label_true, h, total, g);
+    sscg_dispatch_classes(C, [&](auto ct) {
+        hipLaunchKernelGGL(predict_head_ms_kernel<decltype(ct)::value>, grid, blk, lds, st, vw, prob_sum, index, label_u8, label_true, h, total, g);
+    });
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }
 
 extern "C" int sscg_resize_flip(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, int flip, void* stream) {
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0) return SSCG_ERR_BAD_ARG;
-    FlipGeom g;
-    g.H = H; g.W = W; g.C = C; g.OH = OH; g.OW = OW;
-    g.sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;      // sscg_upsample_bilinear_fwd's scales
-    g.sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+    const FlipGeom g = sscg_make_resize_geom(H, W, C, OH, OW);
     const size_t total = (size_t)N * OH * OW * C;
-    const dim3 grid(capped_blocks(total, 8192)), blk(256);
+    const dim3 grid(ew_blocks(total)), blk(256);
     hipStream_t st = (hipStream_t)stream;
     const bool ident = OH == H && OW == W;
     if (ident && flip) hipLaunchKernelGGL((resize_flip_kernel<true, true>), grid, blk, 0, st, x, y, total, g);

@@ -2527,15 +2527,25 @@ def ce_weight(values, num_classes, device):
     return torch.tensor(vals, dtype=torch.float32).to(device)
 
 
+def _class_weight_ok(weight, c, device, what):
+    """A class-weight operand (what: "class" = the cross entropy's, "dice") is None or what ce_weight / dice_weight make."""
+    if weight is not None and not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and weight.device == device
+                                   and weight.dim() == 1 and weight.numel() == c and weight.is_contiguous()):
+        raise _lib.SscgError("%s weights must be a contiguous fp32 [%d] tensor on %s (functional.%s_weight makes one)"
+                             % (what, c, device, "ce" if what == "class" else what))
+
+
+def _check_labels(labels, count):
+    if labels.numel() != count or labels.dtype != torch.int64:
+        raise _lib.SscgError("labels must be int64 with N*OH*OW elements (N*H*W without a resize): %d" % count)
+
+
 def _ce_options(weight, label_smoothing, c, device):
     """(weight tensor or None, smoothing as a float, whether the weighted entries are needed) of a cross-entropy call."""
     eps = float(label_smoothing)
     if not 0.0 <= eps < 1.0:
         raise ValueError("label_smoothing %r is outside [0, 1)" % (label_smoothing,))
-    if weight is not None:
-        if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and weight.device == device
-                and weight.dim() == 1 and weight.numel() == c and weight.is_contiguous()):
-            raise _lib.SscgError("class weights must be a contiguous fp32 [%d] tensor on %s (functional.ce_weight makes one)" % (c, device))
+    _class_weight_ok(weight, c, device, "class")
     return weight, eps, weight is not None or eps != 0.0
 
 
@@ -2549,8 +2559,7 @@ class CrossEntropyFn(torch.autograd.Function):
         logits = to_nhwc(logits)
         labels = labels.contiguous()
         n, c, h, w = logits.shape
-        if labels.numel() != n * h * w or labels.dtype != torch.int64:
-            raise _lib.SscgError("labels must be int64 with N*H*W elements")
+        _check_labels(labels, n * h * w)
         weight, eps, weighted = _ce_options(opt[0] if opt else None, opt[1] if len(opt) > 1 else 0.0, c, logits.device)
         loss = _scalar(logits.device)
         valid = _scalar(logits.device)      # pixels with a label in [0, C): the divisor of the mean (all of them in the reference)
@@ -2583,10 +2592,55 @@ class CrossEntropyFn(torch.autograd.Function):
 FUSE_HEAD = [os.environ.get("SSCG_FUSE_HEAD", "1") != "0"]      # interp -> {softmax, cross entropy} without the resized logits in memory
 
 
+MAX_CLASSES = 64      # SSCG_MAXC of csrc/head_common.h: the class-axis kernels hold one pixel's classes in registers
+
+
 def _head_applies(x, oh, ow):
     """One block per source pixel gathers the output pixels around it: worth it when the map grows (DeepLab's 33x33 -> the crop)."""
-    return (FUSE_HEAD[0] and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] <= 64
+    return (FUSE_HEAD[0] and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] <= MAX_CLASSES
             and oh * ow >= 16 * x.shape[2] * x.shape[3])
+
+
+def _label_head_forward(x, oh, ow, labels, want_soft, want_ce, weight, eps):
+    """The forward launch of the label head on channels-last x: (softmax map, loss, valid, dl), each None where its branch is off.
+    weight / eps: _ce_options' - the weighted entry runs only where there is something weighted to compute."""
+    n, c, h, w = x.shape
+    y = empty_nhwc(n, c, oh, ow, x.device) if want_soft else None
+    loss = valid = dl = ws = None
+    if want_ce:
+        loss, valid = _scalar(x.device), _scalar(x.device)
+        dl = empty_nhwc(n, c, h, w, x.device)
+        ws = torch.empty(lib.sscg_upsample_head_workspace(n, h, w), dtype=torch.uint8, device=x.device)
+    if want_ce and (weight is not None or eps != 0.0):
+        check(lib.sscg_upsample_head_fwd_w(x.data_ptr(), labels.data_ptr(), _ptr(weight), eps, _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl),
+                                           n, h, w, c, oh, ow, _ptr(ws), ws.numel(), _stream()), "sscg_upsample_head_fwd_w")
+    else:
+        check(lib.sscg_upsample_head_fwd(x.data_ptr(), _ptr(labels if want_ce else None), _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl),
+                                         n, h, w, c, oh, ow, _ptr(ws), ws.numel() if ws is not None else 0, _stream()),
+              "sscg_upsample_head_fwd")
+    return y, loss, valid, dl
+
+
+def _label_head_backward(x, oh, ow, dy, dl, valid, g_ce, dice=None):
+    """dx of the label head, or None where nothing was differentiated.  The cross-entropy branch is live when its loss received a
+    gradient and the forward left dl.  dice = (labels, coef, g_dice, batch) when the Dice loss received one: the one stencil launch
+    that serves every live branch; else the head's own backward."""
+    use_ce = g_ce is not None and dl is not None
+    if dy is None and not use_ce and dice is None:
+        return None
+    n, c, h, w = x.shape
+    dx = empty_nhwc(n, c, h, w, x.device)
+    if dy is not None:
+        dy = to_nhwc(dy)
+    ce = (_ptr(dl if use_ce else None), _ptr(g_ce if use_ce else None), _ptr(valid if use_ce else None))
+    if dice is None:
+        check(lib.sscg_upsample_head_bwd(x.data_ptr(), _ptr(dy), ce[0], ce[1], ce[2], dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
+              "sscg_upsample_head_bwd")
+    else:
+        labels, coef, g_dice, batch = dice
+        check(lib.sscg_upsample_head_bwd_d(x.data_ptr(), labels.data_ptr(), _ptr(dy), ce[0], ce[1], ce[2], coef.data_ptr(), g_dice.data_ptr(),
+                                           batch, dx.data_ptr(), n, h, w, c, oh, ow, _stream()), "sscg_upsample_head_bwd_d")
+    return dx
 
 
 class UpsampleHeadFn(torch.autograd.Function):
@@ -2600,23 +2654,12 @@ class UpsampleHeadFn(torch.autograd.Function):
     def forward(ctx, x, oh, ow, labels, want_soft, *opt):
         _need_hip(x, f32_only=True)
         x = to_nhwc(x)
-        n, c, h, w = x.shape
-        y = empty_nhwc(n, c, oh, ow, x.device) if want_soft else None
-        loss = valid = dl = ws = None
+        n, c = x.shape[:2]
         if labels is not None:
             labels = labels.contiguous()
-            if labels.numel() != n * oh * ow or labels.dtype != torch.int64:
-                raise _lib.SscgError("labels must be int64 with N*OH*OW elements")
-            loss, valid = _scalar(x.device), _scalar(x.device)
-            dl = empty_nhwc(n, c, h, w, x.device)
-            ws = torch.empty(lib.sscg_upsample_head_workspace(n, h, w), dtype=torch.uint8, device=x.device)
-        weight, eps, weighted = _ce_options(opt[0] if opt else None, opt[1] if len(opt) > 1 else 0.0, c, x.device)
-        if weighted and labels is not None:
-            check(lib.sscg_upsample_head_fwd_w(x.data_ptr(), _ptr(labels), _ptr(weight), eps, _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl),
-                                               n, h, w, c, oh, ow, _ptr(ws), ws.numel(), _stream()), "sscg_upsample_head_fwd_w")
-        else:
-            check(lib.sscg_upsample_head_fwd(x.data_ptr(), _ptr(labels), _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl), n, h, w, c, oh, ow,
-                                             _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "sscg_upsample_head_fwd")
+            _check_labels(labels, n * oh * ow)
+        weight, eps, _ = _ce_options(opt[0] if opt else None, opt[1] if len(opt) > 1 else 0.0, c, x.device)
+        y, loss, valid, dl = _label_head_forward(x, oh, ow, labels, want_soft, labels is not None, weight, eps)
         ctx.n_opt = len(opt)
         ctx.geom = (oh, ow)
         ctx.save_for_backward(x, dl, valid)
@@ -2629,17 +2672,7 @@ class UpsampleHeadFn(torch.autograd.Function):
     def backward(ctx, dy, g):
         x, dl, valid = ctx.saved_tensors
         oh, ow = ctx.geom
-        n, c, h, w = x.shape
-        if dy is None and (g is None or dl is None):
-            return (None,) * (5 + ctx.n_opt)
-        if dy is not None:
-            dy = to_nhwc(dy)
-        use_ce = g is not None and dl is not None
-        dx = empty_nhwc(n, c, h, w, x.device)
-        check(lib.sscg_upsample_head_bwd(x.data_ptr(), _ptr(dy), _ptr(dl if use_ce else None), _ptr(g if use_ce else None),
-                                         _ptr(valid if use_ce else None), dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
-              "sscg_upsample_head_bwd")
-        return (dx, None, None, None, None) + (None,) * ctx.n_opt
+        return (_label_head_backward(x, oh, ow, dy, dl, valid, g),) + (None,) * (4 + ctx.n_opt)
 
 
 def upsample_softmax_ce(x, size, labels=None, want_soft=True, weight=None, label_smoothing=0.0):
@@ -2678,10 +2711,7 @@ def _dice_options(weight, smooth, batch, c, device):
     s = float(smooth)
     if not (s > 0.0 and s < float("inf")):
         raise ValueError("dice smooth %r is not a finite number > 0" % (smooth,))
-    if weight is not None:
-        if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and weight.device == device
-                and weight.dim() == 1 and weight.numel() == c and weight.is_contiguous()):
-            raise _lib.SscgError("dice weights must be a contiguous fp32 [%d] tensor on %s (functional.dice_weight makes one)" % (c, device))
+    _class_weight_ok(weight, c, device, "dice")
     return weight, s, 1 if batch else 0
 
 
@@ -2690,8 +2720,7 @@ def dice_fwd(x, labels, size, weight=None, smooth=1.0, batch=False, want_sums=Fa
     (loss, coef [G,C,2] = (A, B), sums [G,C,3] fp64 = (I, P, T) or None).  No autograd: dice_loss / upsample_softmax_ce_dice wrap it."""
     n, c, h, w = x.shape
     oh, ow = int(size[0]), int(size[1])
-    if labels.numel() != n * oh * ow or labels.dtype != torch.int64:
-        raise _lib.SscgError("labels must be int64 with N*OH*OW elements")
+    _check_labels(labels, n * oh * ow)
     weight, s, b = _dice_options(weight, smooth, batch, c, x.device)
     groups = 1 if b else n
     loss = _scalar(x.device)
@@ -2742,24 +2771,13 @@ class UpsampleHeadDiceFn(torch.autograd.Function):
     def forward(ctx, x, oh, ow, labels, want_soft, want_ce, ce_w, eps, d_w, smooth, batch):
         _need_hip(x, f32_only=True)
         x = to_nhwc(x)
-        n, c, h, w = x.shape
+        n, c = x.shape[:2]
         labels = labels.contiguous()
-        if labels.numel() != n * oh * ow or labels.dtype != torch.int64:
-            raise _lib.SscgError("labels must be int64 with N*OH*OW elements")
-        ce_w, eps, weighted = _ce_options(ce_w, eps, c, x.device)
-        y = empty_nhwc(n, c, oh, ow, x.device) if want_soft else None
-        loss = valid = dl = ws = None
-        if want_ce:
-            loss, valid = _scalar(x.device), _scalar(x.device)
-            dl = empty_nhwc(n, c, h, w, x.device)
-            ws = torch.empty(lib.sscg_upsample_head_workspace(n, h, w), dtype=torch.uint8, device=x.device)
-        if want_ce and weighted:
-            check(lib.sscg_upsample_head_fwd_w(x.data_ptr(), labels.data_ptr(), _ptr(ce_w), eps, _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl),
-                                               n, h, w, c, oh, ow, _ptr(ws), ws.numel(), _stream()), "sscg_upsample_head_fwd_w")
-        elif want_ce or want_soft:
-            check(lib.sscg_upsample_head_fwd(x.data_ptr(), labels.data_ptr() if want_ce else None, _ptr(y), _ptr(loss), _ptr(valid), _ptr(dl),
-                                             n, h, w, c, oh, ow, _ptr(ws), ws.numel() if ws is not None else 0, _stream()),
-                  "sscg_upsample_head_fwd")
+        _check_labels(labels, n * oh * ow)
+        ce_w, eps, _ = _ce_options(ce_w, eps, c, x.device)
+        y = loss = valid = dl = None
+        if want_ce or want_soft:
+            y, loss, valid, dl = _label_head_forward(x, oh, ow, labels, want_soft, want_ce, ce_w, eps)
         dice, coef, _ = dice_fwd(x, labels, (oh, ow), d_w, smooth, batch)
         ctx.geom = (oh, ow, 1 if batch else 0)
         ctx.save_for_backward(x, labels, dl, valid, coef)
@@ -2770,23 +2788,9 @@ class UpsampleHeadDiceFn(torch.autograd.Function):
     def backward(ctx, dy, g_ce, g_dice):
         x, labels, dl, valid, coef = ctx.saved_tensors
         oh, ow, batch = ctx.geom
-        n, c, h, w = x.shape
-        use_ce = g_ce is not None and dl is not None
-        if dy is None and not use_ce and g_dice is None:
-            return (None,) * 11
-        if dy is not None:
-            dy = to_nhwc(dy)
-        dx = empty_nhwc(n, c, h, w, x.device)
-        if g_dice is None:      # the Dice term took no part in what was differentiated: the head's own backward
-            check(lib.sscg_upsample_head_bwd(x.data_ptr(), _ptr(dy), _ptr(dl if use_ce else None), _ptr(g_ce if use_ce else None),
-                                             _ptr(valid if use_ce else None), dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
-                  "sscg_upsample_head_bwd")
-        else:
-            check(lib.sscg_upsample_head_bwd_d(x.data_ptr(), labels.data_ptr(), _ptr(dy), _ptr(dl if use_ce else None),
-                                               _ptr(g_ce if use_ce else None), _ptr(valid if use_ce else None), coef.data_ptr(),
-                                               g_dice.data_ptr(), batch, dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
-                  "sscg_upsample_head_bwd_d")
-        return (dx,) + (None,) * 10
+        # (g_dice None: the Dice term took no part in what was differentiated)
+        dice = None if g_dice is None else (labels, coef, g_dice, batch)
+        return (_label_head_backward(x, oh, ow, dy, dl, valid, g_ce, dice),) + (None,) * 10
 
 
 def upsample_softmax_ce_dice(x, size, labels, want_soft=True, weight=None, label_smoothing=0.0, dice=None):
