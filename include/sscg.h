@@ -206,15 +206,27 @@ int sscg_norm_apply(const void* x, const float* mean, const float* rstd, const f
  * (dx, nx) for the sums; y / dres (nullable): the unit's forward output and the residual's gradient, for a unit a residual joined.
  * sscg_conv2d_dgrad_bsums_bytes returns 0 when the fusion does not apply to the geometry (strided / few-channel data gradients,
  * groups shorter than a tile): use sscg_conv2d_dgrad + sscg_norm_bwd.
- * sscg_conv2d_dgrad_add: the addend alone (no sums), wherever sscg_conv2d_dgrad_add_applies (the split family, any stride). */
+ * sscg_conv2d_dgrad_add: the addend alone (no sums), wherever sscg_conv2d_dgrad_add_applies (the split family, any stride).
+ * sscg_conv2d_dgrad_bsums_masked: the same arguments, the same sums; dx receives the MASKED gradient gg = mask ? dgrad + addend : +0
+ * instead of the total - bit for bit what sscg_norm_bwd_from_sums would form from the total and the mask source (and write to dres).
+ * That call then runs with act = SSCG_ACT_NONE, y = NULL, dres = NULL on this dx (the same expression on the same values, one
+ * tensor less read and one less written); the residual's gradient is dx itself.  act == SSCG_ACT_RELU only - a 0 / 1 mask may be
+ * applied a second time by a caller that lost the records, LeakyReLU's may not.  SSCG_ERR_UNSUPPORTED, before any launch: any other
+ * activation, the bf16 family, every geometry for which sscg_conv2d_dgrad_bsums_bytes is 0.  (An addition: no existing entry
+ * changes meaning, so SSCG_ABI_VERSION stays 18.) */
 size_t sscg_conv2d_dgrad_bsums_bytes(const sscg_conv_desc* d, int G, int64_t L);
 int sscg_conv2d_dgrad_bsums(const sscg_conv_desc* d, const void* dy, const void* wt, void* dx, const void* nx, const void* nz,
                             const void* addend, const float* mean, const float* rstd, const float* gamma, const float* beta, int G,
                             int64_t L, int act, float slope, void* sums, size_t sums_bytes, void* ws, size_t ws_bytes, void* stream);
+int sscg_conv2d_dgrad_bsums_masked(const sscg_conv_desc* d, const void* dy, const void* wt, void* dx, const void* nx, const void* nz,
+                                   const void* addend, const float* mean, const float* rstd, const float* gamma, const float* beta, int G,
+                                   int64_t L, int act, float slope, void* sums, size_t sums_bytes, void* ws, size_t ws_bytes,
+                                   void* stream);
 int sscg_conv2d_dgrad_add_applies(const sscg_conv_desc* d);
 int sscg_conv2d_dgrad_add(const sscg_conv_desc* d, const void* dy, const void* wt, const void* addend, void* dx, void* ws,
                           size_t ws_bytes, void* stream);
-/* flags: bit 1 = dgamma / dbeta are written (else accumulated); ws: G * C * 2 floats */
+/* flags: bit 1 = dgamma / dbeta are written (else accumulated); ws: G * C * 2 floats.
+ * A dy left by sscg_conv2d_dgrad_bsums_masked already IS gg: pass act = SSCG_ACT_NONE, y = NULL, dres = NULL. */
 int sscg_norm_bwd_from_sums(const sscg_conv_desc* d, const void* sums, const void* dy, const void* x, const void* y, const float* mean,
                             const float* rstd, const float* gamma, const float* beta, void* dx, void* dres, float* dgamma, float* dbeta,
                             int dtype, int G, int64_t L, int C, int act, float slope, int flags, void* ws, size_t ws_bytes, void* stream);

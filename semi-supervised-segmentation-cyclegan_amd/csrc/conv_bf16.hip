@@ -1049,7 +1049,7 @@ int sscg_conv16_dgrad(const sscg_conv_desc* d, const void* dy, const void* wt, c
     }
     if (bs) {
         int bm, wm, chunks;
-        if (bias || act != SSCG_ACT_NONE || !sscg_conv16_bsums_geometry(d, bs->G, bs->L, &bm, &wm, &chunks)) return SSCG_ERR_UNSUPPORTED;
+        if (bias || act != SSCG_ACT_NONE || bs->premask || !sscg_conv16_bsums_geometry(d, bs->G, bs->L, &bm, &wm, &chunks)) return SSCG_ERR_UNSUPPORTED;
         p.bn_x = reinterpret_cast<const bf16*>(bs->nx); p.bn_mean = bs->mean; p.bn_rstd = bs->rstd; p.bn_gamma = bs->gamma; p.bn_beta = bs->beta;
         p.bn_sums = reinterpret_cast<double*>(bs->sums); p.bn_L = (int)bs->L; p.bn_G = bs->G; p.bn_chunks = chunks;
         p.bn_act = bs->act; p.bn_slope = bs->slope;

@@ -913,22 +913,39 @@ extern "C" size_t sscg_conv2d_dgrad_bsums_bytes(const sscg_conv_desc* d, int G, 
     return (size_t)G * chunks * d->C * 2 * sizeof(double);
 }
 
-extern "C" int sscg_conv2d_dgrad_bsums(const sscg_conv_desc* d, const void* dy, const void* wt, void* dx, const void* nx, const void* nz,
-                                       const void* addend, const float* mean, const float* rstd, const float* gamma, const float* beta, int G,
-                                       int64_t L, int act, float slope, void* sums, size_t sums_bytes, void* ws, size_t ws_bytes,
-                                       void* stream) {
+static int dgrad_bsums(const sscg_conv_desc* d, const void* dy, const void* wt, void* dx, const void* nx, const void* nz, const void* addend,
+                       const float* mean, const float* rstd, const float* gamma, const float* beta, int G, int64_t L, int act, float slope,
+                       void* sums, size_t sums_bytes, void* ws, size_t ws_bytes, void* stream, bool premask) {
     if (!d || !dy || !wt || !dx || !nx || !mean || !rstd || !sums) return SSCG_ERR_BAD_ARG;
     if ((gamma != nullptr) != (beta != nullptr)) return SSCG_ERR_BAD_ARG;
     if (act != SSCG_ACT_NONE && act != SSCG_ACT_RELU && act != SSCG_ACT_LRELU) return SSCG_ERR_UNSUPPORTED;      // the mask is recomputed from nx / read off nz
+    if (premask && act != SSCG_ACT_RELU) return SSCG_ERR_UNSUPPORTED;       // (a 0 / 1 mask: applying it a second time changes nothing)
     const size_t need = sscg_conv2d_dgrad_bsums_bytes(d, G, L);
     if (need == 0) return SSCG_ERR_UNSUPPORTED;
+    if (premask && sscg_conv16_dgrad_applies(d)) return SSCG_ERR_UNSUPPORTED;      // (the bf16 kernel stores the total)
     if (sums_bytes < need) return SSCG_ERR_WORKSPACE;
-    sscg_bsums bs = {nx, nz, mean, rstd, gamma, beta, sums, G, (long)L, act, slope};
+    sscg_bsums bs = {nx, nz, mean, rstd, gamma, beta, sums, G, (long)L, act, slope, premask ? 1 : 0};
     if (sscg_conv16_dgrad_applies(d)) {
         if (nz || addend) return SSCG_ERR_UNSUPPORTED;          // (the bf16 kernel: sums of residual-free units only)
         return sscg_conv16_dgrad(d, dy, wt, nullptr, dx, SSCG_ACT_NONE, 0.f, ws, ws_bytes, (hipStream_t)stream, &bs);
     }
     return sscg_convs_dgrad(d, dy, wt, nullptr, dx, SSCG_ACT_NONE, 0.f, ws, ws_bytes, (hipStream_t)stream, &bs, addend);
+}
+
+extern "C" int sscg_conv2d_dgrad_bsums(const sscg_conv_desc* d, const void* dy, const void* wt, void* dx, const void* nx, const void* nz,
+                                       const void* addend, const float* mean, const float* rstd, const float* gamma, const float* beta, int G,
+                                       int64_t L, int act, float slope, void* sums, size_t sums_bytes, void* ws, size_t ws_bytes,
+                                       void* stream) {
+    return dgrad_bsums(d, dy, wt, dx, nx, nz, addend, mean, rstd, gamma, beta, G, L, act, slope, sums, sums_bytes, ws, ws_bytes, stream, false);
+}
+
+// the same launch, dx = the MASKED gradient (ReLU units, the split family): what sscg_norm_bwd_from_sums would form from dx and the mask
+// source again - that call then runs with SSCG_ACT_NONE, y = NULL, dres = NULL, and the residual's gradient is dx itself
+extern "C" int sscg_conv2d_dgrad_bsums_masked(const sscg_conv_desc* d, const void* dy, const void* wt, void* dx, const void* nx,
+                                              const void* nz, const void* addend, const float* mean, const float* rstd, const float* gamma,
+                                              const float* beta, int G, int64_t L, int act, float slope, void* sums, size_t sums_bytes,
+                                              void* ws, size_t ws_bytes, void* stream) {
+    return dgrad_bsums(d, dy, wt, dx, nx, nz, addend, mean, rstd, gamma, beta, G, L, act, slope, sums, sums_bytes, ws, ws_bytes, stream, true);
 }
 
 // dx = dgrad(dy, wt) + addend: the fan-in of a tensor with two consumers (a residual block's input: conv1 and the shortcut) joins in

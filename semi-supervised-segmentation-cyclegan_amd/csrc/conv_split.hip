@@ -99,6 +99,7 @@ struct KsParams {
     double* __restrict__ bn_sums;        // [G][bn_chunks][Ng][2]
     int bn_L, bn_G, bn_chunks, bn_act;
     float bn_slope;
+    int bn_premask;                      // dst receives the MASKED gradient gg (sscg_conv2d_dgrad_bsums_masked; ReLU only) - in the struct's padding: no offset moves
     // fused front conv (CIN > 0; PixelDiscriminator, arch/discriminators.py:70-71): the A operand is not read from memory - row m of it is
     // lrelu(fr_b1 + fr_w1 . fr_x[m]), the 1x1 conv (CIN -> Cs = 64 channels) + LeakyReLU in front of this one, formed in the prologue
     const float* __restrict__ fr_x;      // [M][CIN] fp32
@@ -978,6 +979,13 @@ __global__ __launch_bounds__(WM * WN * 64, ((KS_LB4 && TM * TN == 1) ? 4 : 2)) v
             // row the store phase waited one memory latency per row (the 128x64 data-gradient class went from 88 to 107 us)
             constexpr int PSN = BM / RPP;
             static_assert(PSN % 4 == 0, "rows per thread");
+            // (read from the argument segment HERE, not from `ep`: as one more scalar live across the k-loop the flag cost the 128x64 and
+            // 128x32 classes four and one more spilled SGPRs)
+#if defined(__HIP_DEVICE_COMPILE__)
+            const int premask = reinterpret_cast<const int*>(__builtin_amdgcn_kernarg_segment_ptr())[offsetof(KsParams, bn_premask) / 4];
+#else
+            const int premask = ep.bn_premask;
+#endif
 #pragma unroll 1
             for (int h = 0; h < PSN; h += 4) {          // (rolled: the body - twelve 16-byte loads in flight, four rows of sums - is the launch's largest block of code)
                 f32x4 av[4], yv[4], zv[4];
@@ -1001,16 +1009,23 @@ __global__ __launch_bounds__(WM * WN * 64, ((KS_LB4 && TM * TN == 1) ? 4 : 2)) v
                     const int m = m0 + r;
                     if (m >= ep.M) break;
                     const f32x4 v = *reinterpret_cast<const f32x4*>(ot + r * OLD + c4) + av[q];
-                    *reinterpret_cast<f32x4*>(ep.dst + rows[q] * ep.Ng + n) = v;
-                    if (want_bsums) {
+                    if (!want_bsums) {
+                        *reinterpret_cast<f32x4*>(ep.dst + rows[q] * ep.Ng + n) = v;
+                    } else {
+                        // the mask first, then the store: a premask launch (ReLU) leaves the MASKED gradient - what the layer's apply
+                        // pass (norm.hip act_grad) would form from v and the mask source again, +0 on the masked side - so that pass
+                        // reads neither the mask source nor writes the residual's gradient (it IS this tensor)
                         const bool lo = m < gb;
+                        f32x4 o = v;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const float xh = (yv[q][e] - (lo ? mu0[e] : mu1[e])) * (lo ? rs0[e] : rs1[e]);
                             const float ym = ep.bn_z ? zv[q][e] : xh * ga[e] + be[e];       // (sign of the output = sign of the pre-activation)
                             const float gg = ym > 0.f ? v[e] : v[e] * neg_scale;        // (ReLU: -0 for a negative masked gradient - the sums do not see the sign of a zero)
+                            if (premask) o[e] = ym > 0.f ? v[e] : 0.f;
                             if (lo) { sl[e] += gg; ql[e] = fmaf(gg, xh, ql[e]); } else { sh[e] += gg; qh[e] = fmaf(gg, xh, qh[e]); }
                         }
+                        *reinterpret_cast<f32x4*>(ep.dst + rows[q] * ep.Ng + n) = o;
                     }
                 }
             }
@@ -1408,6 +1423,8 @@ int sscg_convs_dgrad(const sscg_conv_desc* d, const void* dy, const void* wt, co
         p.bn_sums = reinterpret_cast<double*>(bs->sums); p.bn_L = (int)bs->L; p.bn_G = bs->G; p.bn_chunks = chunks;
         p.bn_act = bs->act; p.bn_slope = bs->slope;
         p.bn_z = reinterpret_cast<const float*>(bs->nz);
+        if (bs->premask && bs->act != SSCG_ACT_RELU) return SSCG_ERR_UNSUPPORTED;      // (only a 0 / 1 mask may be applied twice)
+        p.bn_premask = bs->premask ? 1 : 0;
     }
     ks_operands(p, d, true, dy, wt, bias, dx);
     set_dgrad_geometry(p, d, act, slope);

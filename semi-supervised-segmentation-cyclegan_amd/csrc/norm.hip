@@ -982,6 +982,9 @@ extern "C" int sscg_norm_bwd(const void* dy, const void* x, const void* y, const
 // Backward of y = act(norm(x) [+ residual]) (batch statistics) whose per-channel sums were already taken by the data gradient that
 // produced dy (sscg_conv2d_dgrad_bsums with descriptor d): finalize + apply only - the reduction pass over (dy, x) is gone.
 // y / dres: the unit's forward output (mask source) and the residual's gradient, for a unit a residual joined (sums taken with nz).
+// A dy that sscg_conv2d_dgrad_bsums_masked left is the masked gradient gg already: the caller passes act = SSCG_ACT_NONE, y = NULL and
+// dres = NULL, and the apply pass evaluates (gg - c1 - xhat * c2) * rstd * gamma on it - the same expression on the same values, without
+// the reads of y and the write of dres (which is dy itself).  Nothing here changes for it.
 extern "C" int sscg_norm_bwd_from_sums(const sscg_conv_desc* d, const void* sums, const void* dy, const void* x, const void* y,
                                        const float* mean, const float* rstd, const float* gamma, const float* beta, void* dx, void* dres,
                                        float* dgamma, float* dbeta, int dtype, int G, int64_t L, int C, int act, float slope, int flags,

@@ -54,6 +54,7 @@ struct sscg_bsums {
     long L;
     int act;
     float slope;
+    int premask;             // dx receives the masked gradient gg instead of the total (sscg_conv2d_dgrad_bsums_masked: ReLU, split family)
 };
 bool sscg_convs_bsums_geometry(const sscg_conv_desc* d, int G, long L, int* bm, int* wm, int* chunks);
 int sscg_convs_dgrad(const sscg_conv_desc* d, const void* dy, const void* wt, const float* bias, void* dx, int act, float slope,

@@ -413,6 +413,11 @@ FUSE_STATS = [os.environ.get("SSCG_FUSE_STATS", "1") != "0"]    # norm statistic
 _FB = os.environ.get("SSCG_FUSE_BSUMS", "1")
 FUSE_BSUMS = [_FB != "0"]            # master switch (tests flip it)
 FUSE_BSUMS_BF16 = [_FB == "1"]
+# A data gradient that takes the backward sums of a ReLU unit has that unit's mask in registers: it stores the MASKED gradient
+# (sscg_conv2d_dgrad_bsums_masked), and the unit's apply pass reads neither the mask source again nor writes the residual's gradient -
+# that is the masked gradient itself, the same tensor.  fp32 tensors, ReLU only: where the records are not honoured after all (autograd
+# accumulated into the tensor) the ordinary pass masks a second time, which a 0 / 1 mask allows bit for bit and LeakyReLU's does not.
+PREMASK = [os.environ.get("SSCG_PREMASK", "1") != "0"]          # (tests flip it)
 
 
 def set_conv_precision(mode):
@@ -851,7 +856,7 @@ def _dgrad_add_applies(d):
 
 
 def conv2d_dgrad(dy, wt, xshape, wshape, stride, pad, dil, bias=None, act=ACT_NONE, slope=0.0, out_dtype=torch.float32, bsums=None,
-                 addend=None, z=None):
+                 addend=None, z=None, premask=False):
     """dx = act(dgrad(dy, wt) + bias); `wt` is the transposed operand copy [C][R][S][K] (weight_transposed), fp32 for an
     fp32 dy, bf16 for a bf16 dy.
     bsums = (nx, mean, rstd, gamma, beta, (G, L, C), act, slope[, residual]): dx is the gradient at the output of
@@ -859,8 +864,10 @@ def conv2d_dgrad(dy, wt, xshape, wshape, stride, pad, dil, bias=None, act=ACT_NO
     off the unit's output `z`, this conv's own input).
     addend: a tensor like dx - the gradient another consumer of the same tensor left - joined in the store phase (dx = dgrad + addend;
     the sums then see the total).
+    premask (with bsums of a ReLU unit, fp32 tensors): where the sums are taken, dx is the MASKED gradient - mask ? dgrad + addend : +0,
+    what norm_bwd_from_sums would hand back as dres; that call then runs with ACT_NONE and y=None on it.
     With bsums or addend the result is (dx, records, joined): records None where the library does not fuse the geometry (the caller
-    runs the ordinary reduction pass), joined False where the addend was NOT added (the caller adds)."""
+    runs the ordinary reduction pass; dx is then the unmasked total), joined False where the addend was NOT added (the caller adds)."""
     if act == ACT_TANH and xshape[1] > 32 and dy.dtype == torch.bfloat16 and bsums is None and addend is None:
         return act_fwd(conv2d_dgrad(dy, wt, xshape, wshape, stride, pad, dil, bias, ACT_NONE, 0.0, out_dtype), ACT_TANH, 0.0)
     wdt = BF16X3 if (wt.dim() == 1 and wt.dtype == torch.bfloat16) else _dt(wt)      # the split copy is a flat tensor of three planes
@@ -882,13 +889,17 @@ def conv2d_dgrad(dy, wt, xshape, wshape, stride, pad, dil, bias=None, act=ACT_NO
         nb = _bsums_bytes(d, g, l) if (plain and c == d.C and nx.dtype == out_dtype and dy.dtype == out_dtype) else 0
         if res and not (f32 and z is not None and z.dtype == torch.float32 and z.stride() == dx.stride()):
             nb = 0
+        if premask and not (nact == ACT_RELU and f32):
+            raise _lib.SscgError("conv2d_dgrad: the masked store serves ReLU units on fp32 tensors only")
         if nb:
+            entry, name = ((lib.sscg_conv2d_dgrad_bsums_masked, "sscg_conv2d_dgrad_bsums_masked") if premask
+                           else (lib.sscg_conv2d_dgrad_bsums, "sscg_conv2d_dgrad_bsums"))
             sums = torch.empty(nb, dtype=torch.uint8, device=dy.device)
             fused_reads = dx.numel() * dx.element_size() * (1 + (1 if res else 0) + (1 if addend is not None else 0))      # nx [, z] [, addend]
-            _timed("dgrad", d, lambda: check(lib.sscg_conv2d_dgrad_bsums(
+            _timed("dgrad", d, lambda: check(entry(
                 C.byref(d), dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), nx.data_ptr(), z.data_ptr() if res else None, _ptr(addend),
                 mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta), g, l, nact, nslope, sums.data_ptr(), nb, ws.data_ptr(),
-                ws.numel(), _stream()), "sscg_conv2d_dgrad_bsums"), extra_bytes=fused_reads)
+                ws.numel(), _stream()), name), extra_bytes=fused_reads)
             return dx, (d, sums, res), joinable
     if joinable:
         _timed("dgrad", d, lambda: check(lib.sscg_conv2d_dgrad_add(C.byref(d), dy.data_ptr(), wt.data_ptr(), addend.data_ptr(), dx.data_ptr(),
@@ -901,7 +912,7 @@ def conv2d_dgrad(dy, wt, xshape, wshape, stride, pad, dil, bias=None, act=ACT_NO
 
 
 def conv2d_dgrad_param(dy, w, xshape, wshape, stride, pad, dil, bias=None, act=ACT_NONE, slope=0.0, out_dtype=torch.float32, bsums=None,
-                       addend=None, z=None):
+                       addend=None, z=None, premask=False):
     """conv2d_dgrad with the transposed operand copy of parameter `w` taken from the per-parameter cache, in the element
     type the kernel for dy reads (bf16 tiles for a bf16 dy, fp32 otherwise)."""
     if dy.dtype == torch.float32 and out_dtype == torch.float32 and bias is None and act == ACT_NONE:
@@ -917,7 +928,8 @@ def conv2d_dgrad_param(dy, w, xshape, wshape, stride, pad, dil, bias=None, act=A
             wp = _cached_copy(w, "_sscg_wpadk", lambda: _pad_filters(w.detach(), kp))       # against zero filters add nothing to dx; the
             d0 = make_desc(xshape, wshape, stride, pad, dil, xdt=F32, wdt=BF16X3, ydt=F32, prec=_prec("dgrad"))      # result has dx's own shape:
             return _timed("dgrad", d0, lambda: _unprofiled(lambda: conv2d_dgrad(      # the fused store phases (fan-in, backward sums) apply
-                resize_channels(dy, kp), _cached_wt(wp, "x3"), xshape, tuple(wp.shape), stride, pad, dil, bsums=bsums, addend=addend, z=z)))
+                resize_channels(dy, kp), _cached_wt(wp, "x3"), xshape, tuple(wp.shape), stride, pad, dil, bsums=bsums, addend=addend, z=z,
+                premask=premask)))
     if dy.dtype == torch.bfloat16:
         if wshape[0] % 64:
             raise _lib.SscgError("bf16 output gradients with %d channels: the bf16 conv kernels need a multiple of 64" % wshape[0])
@@ -927,7 +939,7 @@ def conv2d_dgrad_param(dy, w, xshape, wshape, stride, pad, dil, bias=None, act=A
         wt = _cached_wt(w, "x3")
     else:
         wt = _cached_wt(w, torch.float32)
-    return conv2d_dgrad(dy, wt, xshape, wshape, stride, pad, dil, bias, act, slope, out_dtype, bsums, addend, z)
+    return conv2d_dgrad(dy, wt, xshape, wshape, stride, pad, dil, bias, act, slope, out_dtype, bsums, addend, z, premask)
 
 
 def conv2d_wgrad(x, dy, wshape, stride, pad, dil, pad_mode=PAD_ZEROS, out=None, accumulate=False):
@@ -1937,12 +1949,16 @@ def _conv_backward(dy, x, w, wref, bref, geom, want_x, want_w, want_b, counted):
             info = getattr(x, "_sscg_norm", None) if fuse else None
         if info is not None and len(info) > 8 and info[8] and x.dtype != torch.float32:
             info = None             # (mask read off the unit's output: fp32 tensors only)
+        # A ReLU unit's sums are taken with its mask in registers: dx is stored masked (PREMASK) and the unit's apply pass skips the mask
+        # and the residual's gradient.  The flag travels with the records; without records dx is the unmasked total as before.
+        premask = PREMASK[0] and info is not None and info[6] == ACT_RELU and x.dtype == torch.float32 and dy.dtype == torch.float32
         if info is not None or addend is not None:
-            dx, rec, joined = conv2d_dgrad_param(dy, wref, x.shape, w.shape, stride, pad, dil, out_dtype=x.dtype, bsums=info, addend=addend, z=x)
+            dx, rec, joined = conv2d_dgrad_param(dy, wref, x.shape, w.shape, stride, pad, dil, out_dtype=x.dtype, bsums=info, addend=addend, z=x,
+                                                 premask=premask)
             if addend is not None and not joined:
                 rec = None          # the sums saw a partial gradient
             if rec is not None:
-                dx._sscg_bsums = (rec, dx._version)
+                dx._sscg_bsums = (rec, dx._version, premask)
             if join is not None:
                 if joined:
                     join[0].folded = (join[1], dx)
@@ -2087,7 +2103,13 @@ def _norm_backward(dy, x, y, mean, rstd, gamma, beta, gref, betaref, per_sample,
         if gacc is None or bacc is None:
             gacc = bacc = None
             ret_g, ret_b = dgamma, dbeta
-    if from_sums:
+    if from_sums and len(rec) > 2 and rec[2] and act == ACT_RELU:
+        # dy arrived masked (a ReLU unit; the data gradient that took the sums stored gg): the apply pass has no mask to form, and the
+        # residual's gradient is dy itself - no tensor allocated, nothing written.  The records are spent: the alias travels on.
+        dy._sscg_bsums = None
+        dx, _ = norm_bwd_from_sums(rec[0], dy, x, mean, rstd, gamma, beta, per_sample, ACT_NONE, 0.0, dgamma, dbeta)
+        dres = dy if want_dres else None
+    elif from_sums:
         dx, dres = norm_bwd_from_sums(rec[0], dy, x, mean, rstd, gamma, beta, per_sample, act, slope, dgamma, dbeta, y=y, want_dres=want_dres)
     else:
         dx, dres = norm_bwd(dy, x, y, mean, rstd, gamma, per_sample, act, slope, stats_grad,
