@@ -431,6 +431,55 @@ int sscg_dice_bwd(const float* x, const int64_t* labels, int N, int H, int W, in
 int sscg_upsample_head_bwd_d(const float* x, const int64_t* labels, const float* dy_soft, const float* dlogits, const float* g_ce,
                              const float* valid, const float* coef, const float* g_dice, int batch, float* dx, int N, int H, int W,
                              int C, int OH, int OW, void* stream);
+/* Hard-pixel mining (OHEM) cross entropy of the same head (opt-in; the reference has none): the cross entropy of sscg_ce_fwd_w over the
+ * hardest pixels only.  x = logits [N][H][W][C] (C <= 64), labels [N][OH][OW]; p = softmax over C of the logits resized to [OH][OW]
+ * (bilinear, align_corners=True, the pinned arithmetic of sscg_upsample_bilinear_fwd and sscg_softmax_fwd - what sscg_predict_head
+ * computes per pixel; OH == H && OW == W: p = softmax(x), the flat form on [rows][C] logits, no interpolation arithmetic).  A pixel is
+ * COUNTED when 0 <= y < C (sscg_ce_fwd's rule).  Selection:
+ *     key     k = p[y], an fp32 value in [0, 1], of every counted pixel;          V = the counted pixels of the call (the whole batch
+ *             of this rank: under data parallelism the selection is per rank, as the Dice sums are)
+ *     thresh  theta in (0, 1];     min_kept K >= 0;     min_frac f in [0, 1]
+ *     r     = clamp(max(K, ceil(f * V)), 1, V), formed on the device (the product in fp64 from the fp32 f)
+ *     m     = the r-th smallest key (1-based, exact, ties included)               tau = max(m, theta)
+ *     KEPT <=> counted and k <= tau
+ * so at least r pixels are always kept, every tie at m is kept, and nothing depends on an order among equal keys.  The comparison is
+ * <= on purpose, where HRNet's and mmsegmentation's OHEM compare with a strict <: with < a batch whose keys are all equal keeps
+ * nothing and the loss is 0 / 0.  Loss and gradient are sscg_ce_fwd_w's with "counted" replaced by "kept":
+ *     term    = (1-eps) * w[y] * (-log p[y]) + (eps/C) * sum_c w[c] * (-log p[c])
+ *     loss    = sum over the kept pixels of term / D,      D = sum over the kept pixels of w[y]
+ *     d loss / d z[c] = ((1-eps) * w[y] * (p[c] - [c==y]) + (eps/C) * (p[c] * W - w[c])) / D   at a kept pixel, 0 at every other
+ * The selection is a constant: no gradient flows through tau.  V == 0 or D == 0: the loss is NaN, the gradient zero (sscg_ce_fwd_w's
+ * rule).  NaN logits are unspecified (no access leaves the buffers).
+ * sscg_ohem_fwd: `keys` fp32 [N][OH][OW] - the key of a counted pixel, 2.0f (a sentinel above every key) elsewhere; `loss`; `valid` =
+ *   D; `thr` = tau (fp32 scalar); `counts` int64 [2] = {kept pixels, V} - all on the device, no host sync.  keys and thr are all the
+ *   backward needs.  The key pass (one thread per output pixel, no block straddles a sample) writes keys and one more fp32 per pixel
+ *   (term) in the workspace; neither the resized logits nor the probabilities reach memory.  m comes from an exact radix select over
+ *   the keys' bit patterns (a non-negative fp32 orders like its pattern; a key has 30 significant bits: three digits of ten bits,
+ *   per-block histograms in LDS, integer adds to a table the call zeroes on the stream, a one-block scan per digit), then the kept terms
+ *   are summed into per-block fp64 records and finished in a fixed order.  No sort, integer atomics only, no float atomics: the same call
+ *   twice gives the same bits, and the resized form gives the keys, thr and counts of the identity form on sscg_upsample_bilinear_fwd's
+ *   output bit for bit.  ws: sscg_ohem_workspace(N, OH, OW) bytes, contents irrelevant.
+ * sscg_ce_bwd_ohem: the flat backward (logits [rows][C], labels / keys [rows], thr / valid from an identity-size sscg_ohem_fwd):
+ *   dx = (gscale ? *gscale : 1) * w / D * d term / d z at a pixel with keys[r] <= tau, a zero row elsewhere.
+ * sscg_upsample_head_bwd_h: the WHOLE backward of the head in one launch when the cross entropy mines - sscg_upsample_head_bwd_d with
+ *   the cross-entropy gradient of the kept pixels formed in the stencil (the forward leaves none): dx = adjoint of the resize applied to
+ *   softmax_bwd(dy_soft + g_dice * (A [y == c] + B), y_soft) + [keys <= tau] * (g_ce / D) * d term / d z.  keys NULL: the cross entropy
+ *   took no part (else thr and valid are required; g_ce NULL = 1); dy_soft NULL, coef NULL: those branches unused (g_dice NULL = 1;
+ *   batch as in sscg_dice_fwd).  At least one branch is required; labels with keys or coef.  Gather form, fixed summation order.
+ * Both backwards READ the keep decision from keys and thr; it is never re-derived from recomputed probabilities.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, C outside 1..64, non-positive sizes, smoothing outside [0, 1), thresh
+ * outside (0, 1], min_kept < 0, min_frac outside [0, 1] - NaNs included - batch outside {0, 1}, keys without thr / valid),
+ * SSCG_ERR_UNSUPPORTED (N*OH*OW, N*H*W or rows >= 2^31), SSCG_ERR_WORKSPACE.
+ * (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+size_t sscg_ohem_workspace(int N, int OH, int OW);
+int sscg_ohem_fwd(const float* x, const int64_t* labels, int N, int H, int W, int C, int OH, int OW, const float* class_w, float smoothing,
+                  float thresh, int64_t min_kept, float min_frac, float* keys, float* loss, float* valid, float* thr, int64_t* counts,
+                  void* ws, size_t ws_bytes, void* stream);
+int sscg_ce_bwd_ohem(const float* logits, const int64_t* labels, const float* keys, const float* thr, int64_t rows, int C,
+                     const float* class_w, float smoothing, const float* gscale, float w, const float* valid, float* dx, void* stream);
+int sscg_upsample_head_bwd_h(const float* x, const int64_t* labels, const float* keys, const float* thr, const float* class_w,
+                             float smoothing, const float* dy_soft, const float* g_ce, const float* valid, const float* coef,
+                             const float* g_dice, int batch, float* dx, int N, int H, int W, int C, int OH, int OW, void* stream);
 /* ------------------------------------------------------------------ inference heads (ABI v18): one launch from a generator's output
  * to what its consumer keeps.  Forward only; never launched by the training step.
  *

@@ -2,7 +2,7 @@
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
---ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -44,6 +44,9 @@ class _Args(Namespace):
     dice_smooth = 1.0
     dice_skip = ""
     dice_batch = False
+    ohem_thresh = None
+    ohem_min_kept = 0
+    ohem_min_frac = 0.0625
 
 
 def get_args(argv=None):
@@ -113,7 +116,24 @@ def get_args(argv=None):
     parser.add_argument("--dice_batch", action="store_true", default=SUPPRESS,
                         help="one Dice per class over the whole batch instead of one per sample and class (per rank under data "
                              "parallelism)")
+    parser.add_argument("--ohem_thresh", type=float, default=SUPPRESS, metavar="F",
+                        help="online hard example mining of the same cross entropies: a labelled pixel takes part when the probability "
+                             "of its true class is at most F, in (0, 1], and the --ohem_min_kept / --ohem_min_frac hardest pixels of a "
+                             "batch always do (per head and per rank); the kept share is reported as lab_ohem_kept / "
+                             "gt_cycle_ohem_kept / ohem_kept (default: off, every labelled pixel takes part)")
+    parser.add_argument("--ohem_min_kept", type=int, default=SUPPRESS, metavar="N",
+                        help="with --ohem_thresh: at least N pixels of a batch are kept, N >= 0 (default: 0)")
+    parser.add_argument("--ohem_min_frac", type=float, default=SUPPRESS, metavar="F",
+                        help="with --ohem_thresh: at least the share F, in [0, 1], of a batch's labelled pixels is kept (default: 0.0625)")
     args = parser.parse_args(argv, namespace=_Args())
+    if args.ohem_thresh is not None and not 0.0 < args.ohem_thresh <= 1.0:
+        parser.error("--ohem_thresh must lie in (0, 1]")
+    if args.ohem_min_kept < 0:
+        parser.error("--ohem_min_kept must be >= 0")
+    if not 0.0 <= args.ohem_min_frac <= 1.0:
+        parser.error("--ohem_min_frac must lie in [0, 1]")
+    if args.ohem_thresh is None and ("ohem_min_kept" in vars(args) or "ohem_min_frac" in vars(args)):
+        parser.error("--ohem_min_kept / --ohem_min_frac need --ohem_thresh F")
     if not args.dice_weight >= 0.0 or args.dice_weight == float("inf"):
         parser.error("--dice_weight must be a finite number >= 0")
     if not (args.dice_smooth > 0.0 and args.dice_smooth < float("inf")):

@@ -118,6 +118,10 @@ SIGNATURES = {
     "sscg_dice_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _p, _p, _p, _sz, _p]),
     "sscg_dice_bwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _f, _p, _p]),
     "sscg_upsample_head_bwd_d": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "sscg_ohem_workspace": (_sz, [_i, _i, _i]),
+    "sscg_ohem_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _f, _f, _i64, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "sscg_ce_bwd_ohem": (_i, [_p, _p, _p, _p, _i64, _i, _p, _f, _p, _f, _p, _p, _p]),
+    "sscg_upsample_head_bwd_h": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "sscg_predict_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_predict_head_ms": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.c_uint32, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),

@@ -2697,10 +2697,17 @@ class UpsampleHeadFn(torch.autograd.Function):
         return (_label_head_backward(x, oh, ow, dy, dl, valid, g),) + (None,) * (4 + ctx.n_opt)
 
 
-def upsample_softmax_ce(x, size, labels=None, want_soft=True, weight=None, label_smoothing=0.0):
+def upsample_softmax_ce(x, size, labels=None, want_soft=True, weight=None, label_smoothing=0.0, *, ohem=None):
     """(softmax2d(interp(x)) or None, CrossEntropyLoss(interp(x), labels) or None) - fused when the resize grows the map, else the
-    three separate passes.  weight (functional.ce_weight's tensor) / label_smoothing: nn.CrossEntropyLoss's, on either path."""
+    three separate passes.  weight (functional.ce_weight's tensor) / label_smoothing: nn.CrossEntropyLoss's, on either path.
+    ohem (an OhemOptions): the cross entropy runs over the mined pixels only (sscg_ohem_fwd), on either path."""
     oh, ow = int(size[0]), int(size[1])
+    if ohem is not None and labels is not None:
+        ohem = _ohem_options(ohem)
+        if _head_applies(x, oh, ow):
+            return UpsampleHeadOhemFn.apply(x, oh, ow, labels, want_soft, weight, label_smoothing, ohem, None)[:2]
+        up = upsample_bilinear(x, size)
+        return (softmax2d(up) if want_soft else None), cross_entropy(up, labels, weight, label_smoothing, ohem=ohem)
     plain = weight is None and label_smoothing == 0.0
     if _head_applies(x, oh, ow):
         if plain:
@@ -2815,18 +2822,154 @@ class UpsampleHeadDiceFn(torch.autograd.Function):
         return (_label_head_backward(x, oh, ow, dy, dl, valid, g_ce, dice),) + (None,) * 10
 
 
-def upsample_softmax_ce_dice(x, size, labels, want_soft=True, weight=None, label_smoothing=0.0, dice=None):
+def upsample_softmax_ce_dice(x, size, labels, want_soft=True, weight=None, label_smoothing=0.0, dice=None, *, ohem=None):
     """upsample_softmax_ce plus the soft Dice loss of the same resized logits: (softmax2d(interp(x)) or None, cross entropy or None, Dice).
     dice: a DiceOptions (or a dict of its arguments; None = the defaults).  Fused when the resize grows the map - the head's forward
-    launch, the Dice statistics and their finish; one stencil launch backward - else the separate passes."""
+    launch, the Dice statistics and their finish; one stencil launch backward - else the separate passes.
+    ohem (an OhemOptions): the cross entropy - not the Dice term - runs over the mined pixels only; still one stencil launch backward."""
     if dice is None or isinstance(dice, dict):
         dice = DiceOptions(**(dice or {}))
     oh, ow = int(size[0]), int(size[1])
+    if ohem is not None:
+        ohem = _ohem_options(ohem)
+        if not dice.ce:
+            raise ValueError("ohem mines the cross entropy: DiceOptions(ce=False) leaves it nothing to mine")
+        if _head_applies(x, oh, ow):
+            return UpsampleHeadOhemFn.apply(x, oh, ow, labels, want_soft, weight, label_smoothing, ohem, dice)
+        up = upsample_bilinear(x, size)
+        return ((softmax2d(up) if want_soft else None), cross_entropy(up, labels, weight, label_smoothing, ohem=ohem),
+                dice_loss(up, labels, dice.weight, dice.smooth, dice.batch))
     if _head_applies(x, oh, ow):
         return UpsampleHeadDiceFn.apply(x, oh, ow, labels, want_soft, dice.ce, weight, label_smoothing, dice.weight, dice.smooth, dice.batch)
     up = upsample_bilinear(x, size)
     return ((softmax2d(up) if want_soft else None), (cross_entropy(up, labels, weight, label_smoothing) if dice.ce else None),
             dice_loss(up, labels, dice.weight, dice.smooth, dice.batch))
+
+
+# ----------------------------------------------------------------------------- hard-pixel mining (opt-in; include/sscg.h: sscg_ohem_fwd)
+class OhemOptions(object):
+    """Online hard example mining of a cross entropy: the loss runs over the counted pixels whose probability of the true class does
+    not exceed max(thresh, m), m = the r-th smallest such probability of the call, r = clamp(max(min_kept, ceil(min_frac * V)), 1, V)
+    of its V counted pixels.  thresh in (0, 1], min_kept an integer >= 0, min_frac in [0, 1]."""
+    __slots__ = ("thresh", "min_kept", "min_frac")
+
+    def __init__(self, thresh, min_kept=0, min_frac=0.0):
+        t, f = float(thresh), float(min_frac)
+        if not 0.0 < t <= 1.0:
+            raise ValueError("ohem thresh %r is outside (0, 1]" % (thresh,))
+        if isinstance(min_kept, float) and min_kept != int(min_kept):
+            raise ValueError("ohem min_kept %r is not an integer" % (min_kept,))
+        k = int(min_kept)
+        if k < 0 or k >= 2 ** 63:
+            raise ValueError("ohem min_kept %r is not an integer >= 0" % (min_kept,))
+        if not 0.0 <= f <= 1.0:
+            raise ValueError("ohem min_frac %r is outside [0, 1]" % (min_frac,))
+        self.thresh, self.min_kept, self.min_frac = t, k, f
+
+
+def _ohem_options(ohem):
+    if isinstance(ohem, dict):
+        ohem = OhemOptions(**ohem)
+    if not isinstance(ohem, OhemOptions):
+        raise TypeError("ohem must be a functional.OhemOptions (or a dict of its arguments), not %r" % (ohem,))
+    return ohem
+
+
+_OHEM_LAST = [None]
+
+
+def ohem_stats():
+    """(thr, kept, V) of the last mined cross entropy of this process: tau as an fp32 scalar and the two int64 counts, all on the
+    device - reading them here costs no sync.  None before the first such call."""
+    return _OHEM_LAST[0]
+
+
+def ohem_fwd(x, labels, size, ohem, weight=None, label_smoothing=0.0):
+    """sscg_ohem_fwd on channels-last fp32 logits x [N,C,H,W] and int64 labels [N,OH,OW] (size = (OH, OW); (H, W): the flat form):
+    (loss, valid = D, keys fp32 [N,OH,OW], thr, counts int64 [2] = (kept, V)).  No autograd: cross_entropy / upsample_softmax_ce wrap it."""
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    _check_labels(labels, n * oh * ow)
+    ohem = _ohem_options(ohem)
+    weight, eps, _ = _ce_options(weight, label_smoothing, c, x.device)
+    loss, valid, thr = _scalar(x.device), _scalar(x.device), _scalar(x.device)
+    keys = torch.empty((n, oh, ow), dtype=torch.float32, device=x.device)
+    counts = torch.empty((2,), dtype=torch.int64, device=x.device)
+    ws = torch.empty(lib.sscg_ohem_workspace(n, oh, ow), dtype=torch.uint8, device=x.device)
+    check(lib.sscg_ohem_fwd(x.data_ptr(), labels.data_ptr(), n, h, w, c, oh, ow, _ptr(weight), eps, ohem.thresh, ohem.min_kept,
+                            ohem.min_frac, keys.data_ptr(), loss.data_ptr(), valid.data_ptr(), thr.data_ptr(), counts.data_ptr(),
+                            ws.data_ptr(), ws.numel(), _stream()), "sscg_ohem_fwd")
+    _OHEM_LAST[0] = (thr, counts[0], counts[1])
+    return loss, valid, keys, thr, counts
+
+
+class OhemCrossEntropyFn(torch.autograd.Function):
+    """CrossEntropyFn over the mined pixels of logits [N,C,H,W] (include/sscg.h: sscg_ohem_fwd / sscg_ce_bwd_ohem)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, label_smoothing, ohem):
+        _need_hip(logits, f32_only=True)
+        logits = to_nhwc(logits)
+        labels = labels.contiguous()
+        loss, valid, keys, thr, _ = ohem_fwd(logits, labels, logits.shape[2:], ohem, weight, label_smoothing)
+        ctx.ce = (weight, float(label_smoothing))
+        ctx.save_for_backward(logits, labels, keys, thr, valid)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, keys, thr, valid = ctx.saved_tensors
+        weight, eps = ctx.ce
+        n, c, h, w = logits.shape
+        dx = torch.empty_like(logits, memory_format=CL)
+        check(lib.sscg_ce_bwd_ohem(logits.data_ptr(), labels.data_ptr(), keys.data_ptr(), thr.data_ptr(), n * h * w, c, _ptr(weight), eps,
+                                   g.data_ptr(), 1.0, valid.data_ptr(), dx.data_ptr(), _stream()), "sscg_ce_bwd_ohem")
+        return dx, None, None, None, None
+
+
+class UpsampleHeadOhemFn(torch.autograd.Function):
+    """The label head with a mined cross entropy: returns (softmax map or None, cross entropy, Dice loss or None).  Forward: the head's
+    own launch for the softmax map where it is wanted (the same entry, the same bits), sscg_ohem_fwd - keys, selection, loss - and the
+    Dice statistics when `dice` (a DiceOptions) is given; the resized logits never reach memory.  The selection couples the pixels of
+    the call, so the forward leaves no gradient: the backward is ONE stencil launch (sscg_upsample_head_bwd_h) for every live branch."""
+
+    @staticmethod
+    def forward(ctx, x, oh, ow, labels, want_soft, ce_w, eps, ohem, dice):
+        _need_hip(x, f32_only=True)
+        x = to_nhwc(x)
+        n, c = x.shape[:2]
+        labels = labels.contiguous()
+        _check_labels(labels, n * oh * ow)
+        ce_w, eps, _ = _ce_options(ce_w, eps, c, x.device)
+        y = _label_head_forward(x, oh, ow, None, True, False, None, 0.0)[0] if want_soft else None
+        loss, valid, keys, thr, _ = ohem_fwd(x, labels, (oh, ow), ohem, ce_w, eps)
+        d_loss = coef = None
+        batch = 0
+        if dice is not None:
+            d_loss, coef, _ = dice_fwd(x, labels, (oh, ow), dice.weight, dice.smooth, dice.batch)
+            batch = 1 if dice.batch else 0
+        ctx.opts = (oh, ow, ce_w, eps, batch)
+        ctx.save_for_backward(x, labels, keys, thr, valid, coef)
+        ctx.set_materialize_grads(False)
+        return y, loss, d_loss
+
+    @staticmethod
+    def backward(ctx, dy, g_ce, g_dice):
+        x, labels, keys, thr, valid, coef = ctx.saved_tensors
+        oh, ow, ce_w, eps, batch = ctx.opts
+        use_dice = g_dice is not None and coef is not None
+        if g_ce is None:          # the mined loss took no part in what was differentiated: the head's other backwards serve the rest
+            dice = (labels, coef, g_dice, batch) if use_dice else None
+            return (_label_head_backward(x, oh, ow, dy, None, None, None, dice),) + (None,) * 8
+        n, c, h, w = x.shape
+        dx = empty_nhwc(n, c, h, w, x.device)
+        if dy is not None:
+            dy = to_nhwc(dy)
+        check(lib.sscg_upsample_head_bwd_h(x.data_ptr(), labels.data_ptr(), keys.data_ptr(), thr.data_ptr(), _ptr(ce_w), eps, _ptr(dy),
+                                           g_ce.data_ptr(), valid.data_ptr(), _ptr(coef if use_dice else None),
+                                           _ptr(g_dice if use_dice else None), batch, dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
+              "sscg_upsample_head_bwd_h")
+        return (dx,) + (None,) * 8
 
 
 class MSEConstFn(torch.autograd.Function):
@@ -3078,7 +3221,9 @@ def softmax2d(x):
     return SoftmaxFn.apply(x)
 
 
-def cross_entropy(logits, labels, weight=None, label_smoothing=0.0):
+def cross_entropy(logits, labels, weight=None, label_smoothing=0.0, *, ohem=None):
+    if ohem is not None:        # hard-pixel mining (OhemOptions): the loss over the mined pixels only
+        return OhemCrossEntropyFn.apply(logits, labels, weight, label_smoothing, _ohem_options(ohem))
     if weight is None and label_smoothing == 0.0:
         return CrossEntropyFn.apply(logits, labels)
     return CrossEntropyFn.apply(logits, labels, weight, label_smoothing)

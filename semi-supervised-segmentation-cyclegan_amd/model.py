@@ -151,6 +151,7 @@ class _WeightedCE(object):
         else:
             self._ce_rule = spec
         self._init_dice(args, C)
+        self._init_ohem(args)
 
     # --dice_weight / --dice_smooth / --dice_skip / --dice_batch (opt-in; the reference has no Dice): every ground-truth cross entropy L
     # becomes L + dice_w * D inside its existing weight, D = the soft Dice loss of the same resized logits (functional.dice_loss)
@@ -172,11 +173,31 @@ class _WeightedCE(object):
         if not (self.dice_options.smooth > 0.0 and self.dice_options.smooth < float("inf")):
             raise ValueError("--dice_smooth %r must be a finite number > 0" % (getattr(args, "dice_smooth", None),))
 
-    def _head(self, logits, labels, want_soft):
-        """(softmax map or None, cross entropy, Dice loss or None) of the ground-truth head: the plain fused head by default."""
+    # --ohem_thresh / --ohem_min_kept / --ohem_min_frac (opt-in; the reference mines nothing): every ground-truth cross entropy runs over
+    # its hardest pixels only (functional.OhemOptions; per call = per head and rank)
+    ohem_options = None     # functional.OhemOptions when on: no new launch, loss key or checkpoint key otherwise
+
+    def _init_ohem(self, args):
+        thresh = getattr(args, "ohem_thresh", None)
+        if thresh is None:
+            return
+        self.ohem_options = F.OhemOptions(thresh, min_kept=getattr(args, "ohem_min_kept", 0), min_frac=getattr(args, "ohem_min_frac", 0.0625))
+
+    def _head(self, logits, labels, want_soft, kept=None):
+        """(softmax map or None, cross entropy, Dice loss or None) of the ground-truth head: the plain fused head by default.
+        --ohem_thresh: the cross entropy is the mined one, and `kept` (a dict) receives the kept share of this head under "ohem_kept"
+        - a device scalar from the counts the forward left, no sync."""
+        kw = self._ce_kwargs()
+        if self.ohem_options is not None:
+            kw = dict(kw, ohem=self.ohem_options)
         if self.dice_options is None:
-            return F.upsample_softmax_ce(logits, self.crop, labels, want_soft=want_soft, **self._ce_kwargs()) + (None,)
-        return F.upsample_softmax_ce_dice(logits, self.crop, labels, want_soft=want_soft, dice=self.dice_options, **self._ce_kwargs())
+            out = F.upsample_softmax_ce(logits, self.crop, labels, want_soft=want_soft, **kw) + (None,)
+        else:
+            out = F.upsample_softmax_ce_dice(logits, self.crop, labels, want_soft=want_soft, dice=self.dice_options, **kw)
+        if self.ohem_options is not None and kept is not None:
+            _, n_kept, n_counted = F.ohem_stats()
+            kept["ohem_kept"] = n_kept.float() / n_counted.float()
+        return out
 
     def _dice_scores(self, running):
         """--dice_weight: the per-class Dice of the confusion matrix the evaluation has just scored (utils.dice_scores), with the class
@@ -389,7 +410,8 @@ class semisuper_cycleGAN(_WeightedCE):
             gsi_second.record(main)
         # :391-392 (interp), :398 (CE of the resized logits), :401-402 (their softmax) from the low-resolution logits in one pass each:
         # the resized [B, C, crop] logits are never written (functional.UpsampleHeadFn)
-        lab_gt, lab_loss_CE, lab_loss_dice = self._head(lab_logits, labels, True)      # (plain nn.CrossEntropyLoss() by default)
+        ohem_kept = {}
+        lab_gt, lab_loss_CE, lab_loss_dice = self._head(lab_logits, labels, True, ohem_kept)   # (plain nn.CrossEntropyLoss() by default)
         fake_gt, _ = F.upsample_softmax_ce(fake_logits, self.crop)
         if fork:
             main.wait_event(gis_first)
@@ -426,6 +448,8 @@ class semisuper_cycleGAN(_WeightedCE):
             fake_img, fake_img_d, fake_img_l1 = F.split(fake_img, 3)                 # consumers: Gsi, Di, L1
             recon_logits = self.Gsi(fake_img)                                        # :410
         extra_terms, extra_weights, extras = [], [], {}
+        if ohem_kept:                                                                # --ohem_thresh: the share of counted pixels lab_loss_CE kept
+            extras["lab_ohem_kept"] = ohem_kept.pop("ohem_kept")
         if lab_loss_dice is not None:                                                # --dice_weight: inside lab_loss_CE's weight
             extras["lab_loss_dice"] = lab_loss_dice
             extra_terms.append(lab_loss_dice)
@@ -462,7 +486,9 @@ class semisuper_cycleGAN(_WeightedCE):
         img_gen_loss = F.mse_const(fake_img_dis, 1.0)                                # :445
         gt_gen_loss = F.mse_const(fake_gt_dis, 1.0)                                  # :446
         img_cycle_loss = F.mse_const(resnet_fake_img_dis, 1.0)                       # :452
-        _, gt_cycle_loss, gt_cycle_dice = self._head(recon_logits, labels, False)    # :415 (interp), :455
+        _, gt_cycle_loss, gt_cycle_dice = self._head(recon_logits, labels, False, ohem_kept)    # :415 (interp), :455
+        if ohem_kept:                                                                # --ohem_thresh: gt_cycle_loss's kept share
+            extras["gt_cycle_ohem_kept"] = ohem_kept.pop("ohem_kept")
         if gt_cycle_dice is not None:                                                # --dice_weight: inside gt_cycle_loss's weight
             extras["gt_cycle_dice"] = gt_cycle_dice
             extra_terms.append(gt_cycle_dice)
@@ -782,11 +808,14 @@ class supervised_model(_WeightedCE):
     def step(self, l_img, l_gt):
         """model.py:120-143."""
         self.gsi_optimizer.zero_grad()
-        _, loss, dice = self._head(self.Gsi(l_img), l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3]), False)
+        ohem_kept = {}
+        _, loss, dice = self._head(self.Gsi(l_img), l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3]), False, ohem_kept)
+        if ohem_kept:   # --ohem_thresh: the step returns the mined cross entropy, the kept share of the counted pixels goes to self.extras
+            self.extras = ohem_kept
         if dice is None:
             F.backward(loss)
         else:       # --dice_weight: CE + dice_w * Dice; the step still returns the cross entropy, the Dice term goes to self.extras
-            self.extras = {"dice_loss": dice.detach()}
+            self.extras = dict(ohem_kept, dice_loss=dice.detach())
             F.backward(F.weighted_sum([loss, dice], [1.0, self.dice_w]))
         if self.dp is not None:
             F.SideStream.join(l_img.device)
@@ -854,6 +883,8 @@ class supervised_model(_WeightedCE):
                     print("Epoch: (%3d) (%5d/%5d) | Crossentropy Loss:%.2e" % (epoch, i + 1, len(labeled_loader), loss))
                     if self.dice_options is not None:
                         print("Dice Loss:%.2e (weight %g)" % (float(self.extras["dice_loss"]), self.dice_w))
+                    if self.ohem_options is not None:
+                        print("OHEM kept:%.4f of the labelled pixels" % float(self.extras["ohem_kept"]))
                     if self.gsi_optimizer.last_grad_norm is not None:       # --clip_grad_norm: the norm this step's update clipped
                         print("Grad norm:%.3e (clip %.3e)" % (float(self.gsi_optimizer.last_grad_norm), self.gsi_optimizer.max_grad_norm))
                     if writer is not None:                                          # model.py:143
