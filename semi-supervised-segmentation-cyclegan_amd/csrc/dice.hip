@@ -1,4 +1,4 @@
-// Soft Dice loss of the segmentation head (include/sscg.h: sscg_dice_fwd / sscg_dice_bwd / sscg_upsample_head_bwd_d).
+// Soft Dice loss of the segmentation head (include/sscg.h: sscg_dice_fwd / sscg_dice_bwd; sscg_upsample_head_bwd_d is in head_bwd.hip).
 //
 // With p = softmax_C(resize(z)) (bilinear, align_corners=True; identity sizes: p = softmax_C(z)), a pixel COUNTED when its label y lies
 // in [0, C), groups g = the samples (batch == 0) or the whole call (batch == 1), and over the counted pixels of a group
@@ -13,9 +13,9 @@
 //                          class) with d loss / d p_c = A [y == c] + B at a counted pixel (A = -2 k / Den, B = k Num / Den^2,
 //                          k = w_c / (G sum w)).  (One block per GROUP over the records was measured first: with batch == 1 a single
 //                          block then reads every record - 1-2 MB at the step's sizes - and cost more than the statistics.)
-//   3. the backward        flat (dice_bwd_kernel: one thread per pixel) or through the adjoint of the resize (head_dice_bwd_kernel:
-//                          the gather frame of head_geom.h - one block per SOURCE pixel gathers its stencil, and the softmax-output
-//                          and cross-entropy branches of the head ride in the same launch).
+//   3. the backward        flat (dice_bwd_kernel: one thread per pixel) or through the adjoint of the resize: the DICE term of the
+//                          head's one backward kernel (head_bwd_kernel, head_bwd.hip: sscg_upsample_head_bwd_d) - one block per SOURCE
+//                          pixel gathers its stencil, and the softmax-output and cross-entropy branches ride in the same launch.
 #include "common.h"
 #include "head_common.h"
 #include "head_geom.h"
@@ -183,73 +183,6 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
     }
 }
 
-// The whole backward of the head in one launch when the Dice branch is live: head_kernel's MODE 1 (loss_optim.hip) with the Dice term.
-// One block per SOURCE pixel gathers the output pixels whose stencil touches it (head_window / head_logits / head_weight of
-// head_geom.h: the same candidates, the same weights, the same order).  Per output pixel the gradient with respect to its probabilities is
-//     q_c = g_dice * (A[c] [y == c] + B[c])   (counted pixels; 0 otherwise)   + dy_soft[c]   (SOFT)
-// then the softmax backward p_c (q_c - sum_k p_k q_k), weighted by the stencil weight.  After the block reduction the cross-entropy
-// gradient the forward left is added by the same head_store_sum: dl_ce * g_ce / valid.  The group's (A, B) rows, scaled by g_dice, sit
-// in LDS (block-uniform reads).
-template <int CT, bool SOFT>
-__global__ __launch_bounds__(256) void head_dice_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab,
-                                                            const float* __restrict__ dy_soft, const float* __restrict__ dl_ce,
-                                                            const float* __restrict__ g_ce, const float* __restrict__ valid,
-                                                            const float* __restrict__ coef, const float* __restrict__ g_dice, int batch,
-                                                            float* __restrict__ dx, HeadGeom g) {
-    __shared__ float red[4][SSCG_MAXC];
-    __shared__ float sA[SSCG_MAXC], sB[SSCG_MAXC];
-    const int C = CT ? CT : g.C;
-    const int b = blockIdx.x;
-    const HeadWindow win = head_window(g, b);
-    const int ix = win.ix, iy = win.iy, n = win.n, oy_lo = win.oy_lo, ox_lo = win.ox_lo;
-    if ((int)threadIdx.x < C) {
-        const float gd = g_dice ? *g_dice : 1.f;
-        const float* q = coef + ((size_t)(batch ? 0 : n) * C + threadIdx.x) * 2;
-        sA[threadIdx.x] = gd * q[0];
-        sB[threadIdx.x] = gd * q[1];
-    }
-    __syncthreads();
-    const int nx = win.ox_hi - ox_lo + 1, cand = (win.oy_hi - oy_lo + 1) * nx;
-    const float* xn = x + (size_t)n * g.H * g.W * C;
-    float acc[CT ? CT : SSCG_MAXC];
-#pragma unroll
-    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) acc[c] = 0.f;
-    for (int t = threadIdx.x; t < cand; t += 256) {
-        const int oy = oy_lo + t / nx, ox = ox_lo + t % nx;
-        const float wy = head_weight(g.sh, oy, iy, g.H);
-        if (wy == 0.f) continue;
-        const float wx = head_weight(g.sw, ox, ix, g.W);
-        if (wx == 0.f) continue;
-        const float w = wy * wx;
-        const size_t o = ((size_t)n * g.OH + oy) * g.OW + ox;
-        const int64_t l64 = lab[o];
-        const int l = (l64 < 0 || l64 >= C) ? -1 : (int)l64;
-        if (!SOFT && l < 0) continue;           // not counted and no softmax branch: nothing flows through this pixel
-        float v[CT ? CT : SSCG_MAXC];
-        int y0, x0;
-        head_logits<CT>(xn, g, oy, ox, C, v, &y0, &x0);
-        const float inv = sscg_softmax_exp<CT>(v, C);
-        const float* gr = SOFT ? dy_soft + o * C : nullptr;
-        float dot = 0.f;
-#pragma unroll
-        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-            if (CT || c < C) {
-                v[c] *= inv;
-                float q = l >= 0 ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
-                if (SOFT) q += gr[c];
-                dot += v[c] * q;
-            }
-#pragma unroll
-        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-            if (CT || c < C) {
-                float q = l >= 0 ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
-                if (SOFT) q += gr[c];
-                acc[c] += w * (v[c] * (q - dot));
-            }
-    }
-    head_store_sum<CT>(acc, red, C, b, dl_ce, g_ce, valid, dx);
-}
-
 int dice_bps(int OH, int OW) {
     const long npix = (long)OH * OW;
     const long b = (npix + 255) / 256;
@@ -262,22 +195,6 @@ void launch_stats(const DiceGeom& g, int N, hipStream_t st, const float* x, cons
     sscg_dispatch_classes(g.r.C, [&](auto ct) {
         hipLaunchKernelGGL((dice_stats_kernel<decltype(ct)::value, RESIZE>), grid, blk, 0, st, x, lab, part, g);
     });
-}
-
-template <bool SOFT>
-void launch_head_bwd(const HeadGeom& g, hipStream_t st, const float* x, const int64_t* lab, const float* dy_soft, const float* dl_ce,
-                     const float* g_ce, const float* valid, const float* coef, const float* g_dice, int batch, float* dx) {
-    const dim3 grid((unsigned)(g.N * g.H * g.W)), blk(256);
-    sscg_dispatch_classes(g.C, [&](auto ct) {
-        hipLaunchKernelGGL((head_dice_bwd_kernel<decltype(ct)::value, SOFT>), grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, dx, g);
-    });
-}
-
-bool sizes_ok(int N, int H, int W, int C, int OH, int OW) { return N > 0 && H > 0 && W > 0 && C > 0 && C <= SSCG_MAXC && OH > 0 && OW > 0; }
-
-bool too_large(int N, int H, int W, int OH, int OW) {
-    const size_t lim = (size_t)1 << 31;
-    return (size_t)N * OH * OW >= lim || (size_t)N * H * W >= lim;
 }
 
 }  // namespace
@@ -317,21 +234,6 @@ extern "C" int sscg_dice_bwd(const float* x, const int64_t* labels, int N, int H
     sscg_dispatch_classes(C, [&](auto ct) {
         hipLaunchKernelGGL(dice_bwd_kernel<decltype(ct)::value>, grid, blk, 0, st, x, labels, rows, C, per_group, coef, g, w, dx);
     });
-    SSCG_LAUNCH_CHECK();
-    return SSCG_OK;
-}
-
-extern "C" int sscg_upsample_head_bwd_d(const float* x, const int64_t* labels, const float* dy_soft, const float* dlogits,
-                                        const float* g_ce, const float* valid, const float* coef, const float* g_dice, int batch,
-                                        float* dx, int N, int H, int W, int C, int OH, int OW, void* stream) {
-    if (!x || !labels || !coef || !dx || !sizes_ok(N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
-    if ((batch != 0 && batch != 1) || (dlogits && !valid)) return SSCG_ERR_BAD_ARG;
-    if (too_large(N, H, W, OH, OW)) return SSCG_ERR_UNSUPPORTED;
-    HeadGeom g;
-    if (!head_geom(&g, N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dy_soft) launch_head_bwd<true>(g, st, x, labels, dy_soft, dlogits, g_ce, valid, coef, g_dice, batch, dx);
-    else launch_head_bwd<false>(g, st, x, labels, nullptr, dlogits, g_ce, valid, coef, g_dice, batch, dx);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

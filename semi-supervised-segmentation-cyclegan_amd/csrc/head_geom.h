@@ -1,8 +1,9 @@
 // The geometry of the fused label head (resize -> softmax -> losses from the low-resolution logits), shared by loss_optim.hip (the
-// cross-entropy head) and dice.hip (the Dice statistics and the head backward with Dice): the launch geometry, the resized logits
-// of one output pixel, the stencil weight of a source row / column, and the frame of a gather block - one block per SOURCE pixel: its
-// window of candidate output pixels (also upsample_bwd_kernel's, pointwise.hip) and the block sum that ends it.  Device code is not linked across translation units: this
-// header is instantiated in each, in an unnamed namespace as the kernels that use it are.
+// forward, head_kernel), head_bwd.hip (the one backward, head_bwd_kernel) and the entries of dice.hip / ohem.hip: the launch geometry
+// and the argument checks the entries share, the resized logits of one output pixel, the stencil weight of a source row / column, and
+// the frame of a gather block - one block per SOURCE pixel: its window of candidate output pixels (also upsample_bwd_kernel's,
+// pointwise.hip) and the block sum that ends it.  Device code is not linked across translation units: this header is instantiated in
+// each, in an unnamed namespace as the kernels that use it are.
 #pragma once
 #include "common.h"
 #include "head_common.h"
@@ -10,6 +11,9 @@
 namespace {
 
 struct HeadGeom { int N, H, W, C, OH, OW; float sh, sw, inv_sh, inv_sw; };
+
+// class weight of the weighted cross entropy (sscg_ce_fwd_w's formulas, loss_optim.hip); class_w == NULL: all ones
+__device__ __forceinline__ float class_weight(const float* __restrict__ class_w, int c) { return class_w ? class_w[c] : 1.f; }
 
 template <int CT>
 __device__ __forceinline__ void head_logits(const float* __restrict__ xn, const HeadGeom& g, int oy, int ox, int C, float* v,
@@ -95,8 +99,19 @@ static void head_scales(HeadGeom* g, int N, int H, int W, int C, int OH, int OW)
     g->inv_sh = sscg_resize_inv_scale(g->sh, OH); g->inv_sw = sscg_resize_inv_scale(g->sw, OW);
 }
 
+// ---- host: the argument checks the entries of the head, the Dice loss and the mined cross entropy share
+static inline bool sizes_ok(int N, int H, int W, int C, int OH, int OW) { return N > 0 && H > 0 && W > 0 && C > 0 && C <= SSCG_MAXC && OH > 0 && OW > 0; }
+
+// the kernels index source and output pixels with 32-bit integers
+static inline bool too_large(int N, int H, int W, int OH, int OW) {
+    const size_t lim = (size_t)1 << 31;
+    return (size_t)N * OH * OW >= lim || (size_t)N * H * W >= lim;
+}
+
+static inline bool smoothing_ok(float smoothing) { return smoothing >= 0.f && smoothing < 1.f; }     // (false for a NaN)
+
 static bool head_geom(HeadGeom* g, int N, int H, int W, int C, int OH, int OW) {
-    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > SSCG_MAXC || OH <= 0 || OW <= 0) return false;
+    if (!sizes_ok(N, H, W, C, OH, OW)) return false;
     if ((size_t)N * H * W >= ((size_t)1 << 31)) return false;
     head_scales(g, N, H, W, C, OH, OW);
     return true;

@@ -96,7 +96,6 @@ __global__ void label_onehot_kernel(const int64_t* __restrict__ lab, float* __re
 //     d term / d z[c] = (1-eps) * w[y] * (p[c] - [c==y]) + (eps/C) * (p[c] * W - w[c])  to the gradient (times g / D in the backward)
 // - F.cross_entropy(weight=w, label_smoothing=eps).  sum_c w[c] * (-log p[c]) = W * log(s) - sum_c w[c] * (z[c] - m) with m = max z,
 // s = sum exp(z - m): one FMA per class in the loop that forms the exponentials.  class_w == NULL: all ones.
-__device__ __forceinline__ float class_weight(const float* __restrict__ class_w, int c) { return class_w ? class_w[c] : 1.f; }
 
 template <bool WT>
 __global__ void ce_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab, size_t rows, int C,
@@ -193,14 +192,12 @@ __global__ void ce_bwd_kernel(const float* __restrict__ x, const int64_t* __rest
 //   * every block sums weight * d(loss)/d(resized logit) of its output pixels: the gradient with respect to the low-resolution
 //     logits, which for the cross entropy depends on nothing but logits and labels - so the FORWARD pass already leaves it
 //     (unscaled; the backward is an elementwise scale by g / valid).
-// MODE 0: forward (labels and / or softmax output); MODE 1: backward of the softmax output (dy_soft), plus the scaled
-// cross-entropy gradient the forward left.  WT (MODE 0 only): the class-weighted / label-smoothed cross entropy - see ce_fwd_kernel;
-// `cnt` then sums w[y], and what is left in dlo is still the gradient up to g / valid, so MODE 1 and head_scale_kernel serve it as is.
-template <int CT, int MODE, bool WT>
+// This is the forward (labels and / or softmax output); the backward is head_bwd_kernel (head_bwd.hip).  WT: the class-weighted /
+// label-smoothed cross entropy - see ce_fwd_kernel; `cnt` then sums w[y], and what is left in dlo is still the gradient up to
+// g / valid, so head_bwd_kernel and head_scale_kernel serve it as is.
+template <int CT, bool WT>
 __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab, float* __restrict__ y_soft,
-                                                   const float* __restrict__ dy_soft, float* __restrict__ dlo, const float* __restrict__ dl_ce,
-                                                   const float* __restrict__ g_ce, const float* __restrict__ valid,
-                                                   double* __restrict__ part, int nparts, HeadGeom g,
+                                                   float* __restrict__ dlo, double* __restrict__ part, int nparts, HeadGeom g,
                                                    const float* __restrict__ class_w, float smoothing) {
     __shared__ float red[4][SSCG_MAXC];
     const int C = CT ? CT : g.C;
@@ -240,7 +237,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
         for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; m = fmaxf(m, v[c]); }
         int l = -1;
         float vl = 0.f;
-        if (MODE == 0 && lab) {
+        if (lab) {
             const int64_t l64 = lab[o];
             l = (l64 < 0 || l64 >= C) ? -1 : (int)l64;
         }
@@ -254,7 +251,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
             s += v[c];
         }
         const float inv = 1.f / s;
-        if (MODE == 0 && WT) {
+        if (WT) {
             if (owner && y_soft) {
                 float* yr = y_soft + o * C;
 #pragma unroll
@@ -275,7 +272,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
                     acc[c] += w * (v[c] * inv * k - (c == l ? a : 0.f) - bs * wr[c]);
                 }
             }
-        } else if (MODE == 0) {
+        } else {
             if (owner && l >= 0) { loss += (double)(logf(s) + m - vl); cnt += 1.0; }
             if (owner && y_soft) {
                 float* yr = y_soft + o * C;
@@ -286,31 +283,15 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
 #pragma unroll
                 for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; acc[c] += w * (v[c] * inv - (c == l ? 1.f : 0.f)); }
             }
-        } else {
-            const float* gr = dy_soft + o * C;
-            float dot = 0.f;
-#pragma unroll
-            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; v[c] *= inv; dot += v[c] * gr[c]; }
-#pragma unroll
-            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) { if (CT == 0 && c >= C) break; acc[c] += w * (v[c] * (gr[c] - dot)); }
         }
     }
-    const bool want_sum = MODE == 1 || (lab && dlo);
-    if (want_sum) head_store_sum<CT>(acc, red, C, b, MODE == 1 ? dl_ce : nullptr, g_ce, valid, dlo);
-    if (MODE == 0 && lab && part) {
+    if (lab && dlo) head_store_sum<CT>(acc, red, C, b, nullptr, nullptr, nullptr, dlo);
+    if (lab && part) {
         __syncthreads();
         block_sum_to(loss, part + b);
         __syncthreads();
         block_sum_to(cnt, part + nparts + b);
     }
-}
-
-// backward of the cross entropy alone: dx = dl * g / valid
-__global__ void head_scale_kernel(const float* __restrict__ dl, const float* __restrict__ g_ce, const float* __restrict__ valid,
-                                  float* __restrict__ dx, size_t n) {
-    const float nv = valid ? *valid : 0.f;
-    const float k = (g_ce ? *g_ce : 1.f) * (nv > 0.f ? 1.f / nv : 0.f);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dx[i] = dl[i] * k;
 }
 
 // ---------------------------------------------------------------- MSE vs constant, L1
@@ -494,7 +475,6 @@ extern "C" size_t sscg_loss_workspace(int64_t n) {
 
 // The plain entries and their _w twins share one implementation each.  A _w entry refuses a smoothing outside [0, 1) first; with no
 // class weights and no smoothing (class_w == NULL, smoothing == 0: what the plain entry passes) the plain instantiation runs.
-static bool smoothing_ok(float smoothing) { return smoothing >= 0.f && smoothing < 1.f; }     // (false for a NaN)
 
 static int ce_fwd(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing, float* loss,
                   float* valid, void* ws, size_t ws_bytes, void* stream) {
@@ -523,13 +503,12 @@ extern "C" int sscg_ce_fwd_w(const float* logits, const int64_t* labels, int64_t
     return ce_fwd(logits, labels, rows, C, class_w, smoothing, loss, valid, ws, ws_bytes, stream);
 }
 
-template <int MODE, bool WT = false>
-static void launch_head(const HeadGeom& g, hipStream_t st, const float* x, const int64_t* lab, float* y_soft, const float* dy_soft,
-                        float* dlo, const float* dl_ce, const float* g_ce, const float* valid, double* part, int nparts,
-                        const float* class_w = nullptr, float smoothing = 0.f) {
+template <bool WT>
+static void launch_head(const HeadGeom& g, hipStream_t st, const float* x, const int64_t* lab, float* y_soft, float* dlo, double* part,
+                        int nparts, const float* class_w, float smoothing) {
     const dim3 grid(nparts), blk(256);
     sscg_dispatch_classes(g.C, [&](auto ct) {
-        hipLaunchKernelGGL((head_kernel<decltype(ct)::value, MODE, WT>), grid, blk, 0, st, x, lab, y_soft, dy_soft, dlo, dl_ce, g_ce, valid, part, nparts, g, class_w, smoothing);
+        hipLaunchKernelGGL((head_kernel<decltype(ct)::value, WT>), grid, blk, 0, st, x, lab, y_soft, dlo, part, nparts, g, class_w, smoothing);
     });
 }
 
@@ -548,9 +527,9 @@ static int head_fwd(const float* x, const int64_t* labels, const float* class_w,
     double* part = labels ? reinterpret_cast<double*>(ws) : nullptr;
     float* dlo = labels ? dlogits : nullptr;
     if (labels && (class_w || smoothing != 0.f))      // else nothing weighted to compute: the plain instantiations
-        launch_head<0, true>(g, st, x, labels, y_soft, nullptr, dlo, nullptr, nullptr, nullptr, part, nparts, class_w, smoothing);
+        launch_head<true>(g, st, x, labels, y_soft, dlo, part, nparts, class_w, smoothing);
     else
-        launch_head<0>(g, st, x, labels, y_soft, nullptr, dlo, nullptr, nullptr, nullptr, part, nparts);
+        launch_head<false>(g, st, x, labels, y_soft, dlo, part, nparts, nullptr, 0.f);
     if (labels) hipLaunchKernelGGL(finish_ce_kernel, dim3(1), dim3(256), 0, st, part, nparts, loss, valid);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
@@ -566,23 +545,6 @@ extern "C" int sscg_upsample_head_fwd_w(const float* x, const int64_t* labels, c
                                         size_t ws_bytes, void* stream) {
     if (!smoothing_ok(smoothing)) return SSCG_ERR_BAD_ARG;
     return head_fwd(x, labels, class_w, smoothing, y_soft, loss, valid, dlogits, N, H, W, C, OH, OW, ws, ws_bytes, stream);
-}
-
-extern "C" int sscg_upsample_head_bwd(const float* x, const float* dy_soft, const float* dlogits, const float* g_ce, const float* valid,
-                                      float* dx, int N, int H, int W, int C, int OH, int OW, void* stream) {
-    HeadGeom g;
-    if (!x || !dx || !head_geom(&g, N, H, W, C, OH, OW) || (!dy_soft && !dlogits)) return SSCG_ERR_BAD_ARG;
-    if (dlogits && !valid) return SSCG_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const int nparts = N * H * W;
-    if (dy_soft)
-        launch_head<1>(g, st, x, nullptr, nullptr, dy_soft, dx, dlogits, g_ce, valid, nullptr, nparts);
-    else {
-        const size_t n = (size_t)nparts * C;
-        hipLaunchKernelGGL(head_scale_kernel, dim3(ew_blocks(n)), dim3(256), 0, st, dlogits, g_ce, valid, dx, n);
-    }
-    SSCG_LAUNCH_CHECK();
-    return SSCG_OK;
 }
 
 static int ce_bwd(const float* logits, const int64_t* labels, int64_t rows, int C, const float* class_w, float smoothing,

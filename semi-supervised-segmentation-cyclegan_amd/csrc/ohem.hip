@@ -1,5 +1,5 @@
-// Hard-pixel mining (OHEM) cross entropy of the segmentation head (include/sscg.h: sscg_ohem_fwd / sscg_ce_bwd_ohem /
-// sscg_upsample_head_bwd_h).
+// Hard-pixel mining (OHEM) cross entropy of the segmentation head (include/sscg.h: sscg_ohem_fwd / sscg_ce_bwd_ohem;
+// sscg_upsample_head_bwd_h is in head_bwd.hip).
 //
 // With p = softmax_C(resize(z)) (bilinear, align_corners=True; identity sizes: p = softmax_C(z)) and a pixel COUNTED when its label y lies
 // in [0, C), the KEY of a counted pixel is k = p[y].  Of the V counted pixels of the call the r hardest - the r smallest keys,
@@ -17,9 +17,10 @@
 //                          Integer atomics only: the result does not depend on any order.  V, r, m and tau stay on the device;
 //   3. ohem_loss_kernel    sum of the kept terms, D = sum of the kept w[y] and the kept count: per-block fp64 records, summed in index
 //      ohem_finish_kernel  order by one block - no float atomics;
-//   4. the backward        flat (ohem_ce_bwd_kernel: one thread per pixel) or through the adjoint of the resize (head_ohem_bwd_kernel: the
-//                          gather frame of head_geom.h with the softmax-output and Dice branches in the same launch).  Both READ the keep
-//                          decision - keys[o] <= tau - and never re-derive it from recomputed probabilities.
+//   4. the backward        flat (ohem_ce_bwd_kernel: one thread per pixel) or through the adjoint of the resize: the MINED term of the
+//                          head's one backward kernel (head_bwd_kernel, head_bwd.hip: sscg_upsample_head_bwd_h), with the softmax-output
+//                          and Dice branches in the same launch.  Both READ the keep decision - keys[o] <= tau - and never re-derive
+//                          it from recomputed probabilities.
 #include "common.h"
 #include "head_common.h"
 #include "head_geom.h"
@@ -52,8 +53,6 @@ struct OhemGeom {
     int npix;      // OH * OW: output pixels of a sample
     int bps;       // key-pass blocks per sample
 };
-
-__device__ __forceinline__ float class_weight(const float* __restrict__ class_w, int c) { return class_w ? class_w[c] : 1.f; }
 
 // the tables and the state, zeroed on the stream by every call: nothing depends on what the workspace held
 __global__ __launch_bounds__(256) void ohem_zero_kernel(uint32_t* __restrict__ words, int n) {
@@ -278,94 +277,6 @@ __global__ __launch_bounds__(256) void ohem_ce_bwd_kernel(const float* __restric
     }
 }
 
-// The whole backward of the head in one launch when the cross entropy mines its pixels: head_dice_bwd_kernel (dice.hip) with the
-// cross-entropy gradient of the KEPT pixels formed here - the forward left none.  Per output pixel of the block's window, with
-// p = softmax(resized logits) and ge = g_ce / D:
-//     q_c = g_dice * (A[c] [y == c] + B[c])   (counted pixels, coef != NULL)   + dy_soft[c]   (SOFT)
-//     d_c = p_c (q_c - sum_k p_k q_k)  +  [kept] ge ((a + bs W) p_c - a [c == y] - bs w_c)          a = (1-eps) w_y, bs = eps / C
-// weighted by the stencil weight and summed over the block (head_store_sum).  Class weights and the scaled (A, B) rows sit in LDS.
-template <int CT, bool SOFT>
-__global__ __launch_bounds__(256) void head_ohem_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab,
-                                                            const float* __restrict__ keys, const float* __restrict__ thr,
-                                                            const float* __restrict__ class_w, float smoothing,
-                                                            const float* __restrict__ dy_soft, const float* __restrict__ g_ce,
-                                                            const float* __restrict__ valid, const float* __restrict__ coef,
-                                                            const float* __restrict__ g_dice, int batch, float* __restrict__ dx, HeadGeom g) {
-    __shared__ float red[4][SSCG_MAXC];
-    __shared__ float sA[SSCG_MAXC], sB[SSCG_MAXC], sW[SSCG_MAXC];
-    const int C = CT ? CT : g.C;
-    const int b = blockIdx.x;
-    const HeadWindow win = head_window(g, b);
-    const int ix = win.ix, iy = win.iy, n = win.n, oy_lo = win.oy_lo, ox_lo = win.ox_lo;
-    const bool dice = coef != nullptr, ce = keys != nullptr;
-    if ((int)threadIdx.x < C) {
-        float qa = 0.f, qb = 0.f;
-        if (dice) {
-            const float gd = g_dice ? *g_dice : 1.f;
-            const float* q = coef + ((size_t)(batch ? 0 : n) * C + threadIdx.x) * 2;
-            qa = gd * q[0]; qb = gd * q[1];
-        }
-        sA[threadIdx.x] = qa; sB[threadIdx.x] = qb;
-        sW[threadIdx.x] = class_weight(class_w, threadIdx.x);
-    }
-    __syncthreads();
-    float wsum = 0.f;
-    for (int c = 0; c < C; ++c) wsum += sW[c];
-    const float bs = smoothing / (float)C;
-    float tau = 0.f, ge = 0.f;
-    if (ce) {
-        const float nv = *valid;
-        tau = *thr;
-        ge = (g_ce ? *g_ce : 1.f) * (nv > 0.f ? 1.f / nv : 0.f);
-    }
-    const int nx = win.ox_hi - ox_lo + 1, cand = (win.oy_hi - oy_lo + 1) * nx;
-    const float* xn = x + (size_t)n * g.H * g.W * C;
-    float acc[CT ? CT : SSCG_MAXC];
-#pragma unroll
-    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) acc[c] = 0.f;
-    for (int t = threadIdx.x; t < cand; t += 256) {
-        const int oy = oy_lo + t / nx, ox = ox_lo + t % nx;
-        const float wy = head_weight(g.sh, oy, iy, g.H);
-        if (wy == 0.f) continue;
-        const float wx = head_weight(g.sw, ox, ix, g.W);
-        if (wx == 0.f) continue;
-        const float w = wy * wx;
-        const size_t o = ((size_t)n * g.OH + oy) * g.OW + ox;
-        int l = -1;
-        if (lab) {
-            const int64_t l64 = lab[o];
-            l = (l64 < 0 || l64 >= C) ? -1 : (int)l64;
-        }
-        const bool kept = ce && l >= 0 && keys[o] <= tau;
-        const bool dq = dice && l >= 0;
-        if (!SOFT && !kept && !dq) continue;         // nothing flows through this pixel
-        float v[CT ? CT : SSCG_MAXC];
-        int y0, x0;
-        head_logits<CT>(xn, g, oy, ox, C, v, &y0, &x0);
-        const float inv = sscg_softmax_exp<CT>(v, C);
-        const float* gr = SOFT ? dy_soft + o * C : nullptr;
-        float dot = 0.f;
-#pragma unroll
-        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-            if (CT || c < C) {
-                v[c] *= inv;
-                float q = dq ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
-                if (SOFT) q += gr[c];
-                dot += v[c] * q;
-            }
-        const float a = kept ? (1.f - smoothing) * sW[l] : 0.f;
-        const float gk = kept ? ge : 0.f, k = a + bs * wsum;
-#pragma unroll
-        for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
-            if (CT || c < C) {
-                float q = dq ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
-                if (SOFT) q += gr[c];
-                acc[c] += w * (v[c] * (q - dot) + gk * (v[c] * k - (c == l ? a : 0.f) - bs * sW[c]));
-            }
-    }
-    head_store_sum<CT>(acc, red, C, b, nullptr, nullptr, nullptr, dx);
-}
-
 int ohem_bps(int OH, int OW) {
     const long npix = (long)OH * OW;
     const long b = (npix + 255) / 256;
@@ -380,26 +291,6 @@ void launch_keys(const OhemGeom& g, int N, hipStream_t st, const float* x, const
         hipLaunchKernelGGL((ohem_key_kernel<decltype(ct)::value, RESIZE>), grid, blk, 0, st, x, lab, class_w, smoothing, keys, term, table0, g);
     });
 }
-
-template <bool SOFT>
-void launch_head_bwd(const HeadGeom& g, hipStream_t st, const float* x, const int64_t* lab, const float* keys, const float* thr,
-                     const float* class_w, float smoothing, const float* dy_soft, const float* g_ce, const float* valid, const float* coef,
-                     const float* g_dice, int batch, float* dx) {
-    const dim3 grid((unsigned)(g.N * g.H * g.W)), blk(256);
-    sscg_dispatch_classes(g.C, [&](auto ct) {
-        hipLaunchKernelGGL((head_ohem_bwd_kernel<decltype(ct)::value, SOFT>), grid, blk, 0, st, x, lab, keys, thr, class_w, smoothing, dy_soft, g_ce,
-                           valid, coef, g_dice, batch, dx, g);
-    });
-}
-
-bool sizes_ok(int N, int H, int W, int C, int OH, int OW) { return N > 0 && H > 0 && W > 0 && C > 0 && C <= SSCG_MAXC && OH > 0 && OW > 0; }
-
-bool too_large(int N, int H, int W, int OH, int OW) {
-    const size_t lim = (size_t)1 << 31;
-    return (size_t)N * OH * OW >= lim || (size_t)N * H * W >= lim;
-}
-
-bool smoothing_ok(float smoothing) { return smoothing >= 0.f && smoothing < 1.f; }     // (false for a NaN)
 
 }  // namespace
 
@@ -455,23 +346,6 @@ extern "C" int sscg_ce_bwd_ohem(const float* logits, const int64_t* labels, cons
         hipLaunchKernelGGL(ohem_ce_bwd_kernel<decltype(ct)::value>, grid, blk, 0, st, logits, labels, keys, thr, (size_t)rows, C, class_w, smoothing,
                            gscale, w, valid, dx);
     });
-    SSCG_LAUNCH_CHECK();
-    return SSCG_OK;
-}
-
-extern "C" int sscg_upsample_head_bwd_h(const float* x, const int64_t* labels, const float* keys, const float* thr, const float* class_w,
-                                        float smoothing, const float* dy_soft, const float* g_ce, const float* valid, const float* coef,
-                                        const float* g_dice, int batch, float* dx, int N, int H, int W, int C, int OH, int OW,
-                                        void* stream) {
-    if (!x || !dx || !sizes_ok(N, H, W, C, OH, OW) || (!keys && !dy_soft && !coef)) return SSCG_ERR_BAD_ARG;
-    if ((keys && (!thr || !valid)) || ((keys || coef) && !labels)) return SSCG_ERR_BAD_ARG;
-    if (!smoothing_ok(smoothing) || (batch != 0 && batch != 1)) return SSCG_ERR_BAD_ARG;
-    if (too_large(N, H, W, OH, OW)) return SSCG_ERR_UNSUPPORTED;
-    HeadGeom g;
-    if (!head_geom(&g, N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dy_soft) launch_head_bwd<true>(g, st, x, labels, keys, thr, class_w, smoothing, dy_soft, g_ce, valid, coef, g_dice, batch, dx);
-    else launch_head_bwd<false>(g, st, x, labels, keys, thr, class_w, smoothing, nullptr, g_ce, valid, coef, g_dice, batch, dx);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

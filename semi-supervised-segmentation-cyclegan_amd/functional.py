@@ -2573,16 +2573,16 @@ def _ce_options(weight, label_smoothing, c, device):
 
 class CrossEntropyFn(torch.autograd.Function):
     """nn.CrossEntropyLoss(weight, label_smoothing)(logits [N,C,H,W], labels [N,H,W]) - mean over the counted pixels (the sum of their
-    class weights when weighted).  Optional trailing inputs: weight (fp32 [C] on the device, or None), label_smoothing."""
+    class weights when weighted).  weight: fp32 [C] on the device, or None; label_smoothing: 0.0 for none."""
 
     @staticmethod
-    def forward(ctx, logits, labels, *opt):
+    def forward(ctx, logits, labels, weight, label_smoothing):
         _need_hip(logits, f32_only=True)
         logits = to_nhwc(logits)
         labels = labels.contiguous()
         n, c, h, w = logits.shape
         _check_labels(labels, n * h * w)
-        weight, eps, weighted = _ce_options(opt[0] if opt else None, opt[1] if len(opt) > 1 else 0.0, c, logits.device)
+        weight, eps, weighted = _ce_options(weight, label_smoothing, c, logits.device)
         loss = _scalar(logits.device)
         valid = _scalar(logits.device)      # pixels with a label in [0, C): the divisor of the mean (all of them in the reference)
         ws = _loss_ws(logits.device)
@@ -2592,14 +2592,14 @@ class CrossEntropyFn(torch.autograd.Function):
         else:
             check(lib.sscg_ce_fwd(logits.data_ptr(), labels.data_ptr(), n * h * w, c, loss.data_ptr(), valid.data_ptr(), ws.data_ptr(),
                                   ws.numel(), _stream()), "sscg_ce_fwd")
-        ctx.ce = (weight, eps, weighted, len(opt))
+        ctx.ce = (weight, eps, weighted)
         ctx.save_for_backward(logits, labels, valid)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         logits, labels, valid = ctx.saved_tensors
-        weight, eps, weighted, n_opt = ctx.ce
+        weight, eps, weighted = ctx.ce
         n, c, h, w = logits.shape
         dx = torch.empty_like(logits, memory_format=CL)
         if weighted:
@@ -2608,7 +2608,7 @@ class CrossEntropyFn(torch.autograd.Function):
         else:
             check(lib.sscg_ce_bwd(logits.data_ptr(), labels.data_ptr(), n * h * w, c, g.data_ptr(), 1.0, valid.data_ptr(),
                                   dx.data_ptr(), _stream()), "sscg_ce_bwd")
-        return (dx, None) + (None,) * n_opt
+        return dx, None, None, None
 
 
 FUSE_HEAD = [os.environ.get("SSCG_FUSE_HEAD", "1") != "0"]      # interp -> {softmax, cross entropy} without the resized logits in memory
@@ -2641,80 +2641,6 @@ def _label_head_forward(x, oh, ow, labels, want_soft, want_ce, weight, eps):
                                          n, h, w, c, oh, ow, _ptr(ws), ws.numel() if ws is not None else 0, _stream()),
               "sscg_upsample_head_fwd")
     return y, loss, valid, dl
-
-
-def _label_head_backward(x, oh, ow, dy, dl, valid, g_ce, dice=None):
-    """dx of the label head, or None where nothing was differentiated.  The cross-entropy branch is live when its loss received a
-    gradient and the forward left dl.  dice = (labels, coef, g_dice, batch) when the Dice loss received one: the one stencil launch
-    that serves every live branch; else the head's own backward."""
-    use_ce = g_ce is not None and dl is not None
-    if dy is None and not use_ce and dice is None:
-        return None
-    n, c, h, w = x.shape
-    dx = empty_nhwc(n, c, h, w, x.device)
-    if dy is not None:
-        dy = to_nhwc(dy)
-    ce = (_ptr(dl if use_ce else None), _ptr(g_ce if use_ce else None), _ptr(valid if use_ce else None))
-    if dice is None:
-        check(lib.sscg_upsample_head_bwd(x.data_ptr(), _ptr(dy), ce[0], ce[1], ce[2], dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
-              "sscg_upsample_head_bwd")
-    else:
-        labels, coef, g_dice, batch = dice
-        check(lib.sscg_upsample_head_bwd_d(x.data_ptr(), labels.data_ptr(), _ptr(dy), ce[0], ce[1], ce[2], coef.data_ptr(), g_dice.data_ptr(),
-                                           batch, dx.data_ptr(), n, h, w, c, oh, ow, _stream()), "sscg_upsample_head_bwd_d")
-    return dx
-
-
-class UpsampleHeadFn(torch.autograd.Function):
-    """interp (bilinear, align_corners=True) -> softmax2d and / or nn.CrossEntropyLoss, from the LOW-resolution logits (model.py:390-392,
-    398, 401-402, 455).  Returns (softmax map or None, loss or None).  The forward of the cross-entropy branch already leaves the
-    gradient with respect to the low-resolution logits (it depends on logits and labels only); the backward scales it.  Optional
-    trailing inputs: weight (fp32 [C] on the device, or None), label_smoothing - the class-weighted, smoothed cross entropy, for which
-    all of the above still holds (`valid` is then the sum of the counted pixels' class weights)."""
-
-    @staticmethod
-    def forward(ctx, x, oh, ow, labels, want_soft, *opt):
-        _need_hip(x, f32_only=True)
-        x = to_nhwc(x)
-        n, c = x.shape[:2]
-        if labels is not None:
-            labels = labels.contiguous()
-            _check_labels(labels, n * oh * ow)
-        weight, eps, _ = _ce_options(opt[0] if opt else None, opt[1] if len(opt) > 1 else 0.0, c, x.device)
-        y, loss, valid, dl = _label_head_forward(x, oh, ow, labels, want_soft, labels is not None, weight, eps)
-        ctx.n_opt = len(opt)
-        ctx.geom = (oh, ow)
-        ctx.save_for_backward(x, dl, valid)
-        # an output nothing differentiates (the step reads lab_gt's softmax through .detach() only): backward gets None, not a
-        # zero-filled [B, C, crop] map to gather over
-        ctx.set_materialize_grads(False)
-        return y, loss
-
-    @staticmethod
-    def backward(ctx, dy, g):
-        x, dl, valid = ctx.saved_tensors
-        oh, ow = ctx.geom
-        return (_label_head_backward(x, oh, ow, dy, dl, valid, g),) + (None,) * (4 + ctx.n_opt)
-
-
-def upsample_softmax_ce(x, size, labels=None, want_soft=True, weight=None, label_smoothing=0.0, *, ohem=None):
-    """(softmax2d(interp(x)) or None, CrossEntropyLoss(interp(x), labels) or None) - fused when the resize grows the map, else the
-    three separate passes.  weight (functional.ce_weight's tensor) / label_smoothing: nn.CrossEntropyLoss's, on either path.
-    ohem (an OhemOptions): the cross entropy runs over the mined pixels only (sscg_ohem_fwd), on either path."""
-    oh, ow = int(size[0]), int(size[1])
-    if ohem is not None and labels is not None:
-        ohem = _ohem_options(ohem)
-        if _head_applies(x, oh, ow):
-            return UpsampleHeadOhemFn.apply(x, oh, ow, labels, want_soft, weight, label_smoothing, ohem, None)[:2]
-        up = upsample_bilinear(x, size)
-        return (softmax2d(up) if want_soft else None), cross_entropy(up, labels, weight, label_smoothing, ohem=ohem)
-    plain = weight is None and label_smoothing == 0.0
-    if _head_applies(x, oh, ow):
-        if plain:
-            return UpsampleHeadFn.apply(x, oh, ow, labels, want_soft)
-        return UpsampleHeadFn.apply(x, oh, ow, labels, want_soft, weight, label_smoothing)
-    up = upsample_bilinear(x, size)
-    return (softmax2d(up) if want_soft else None), (cross_entropy(up, labels, weight, label_smoothing) if labels is not None else None)
 
 
 # ----------------------------------------------------------------------------- soft Dice (opt-in; include/sscg.h: sscg_dice_fwd)
@@ -2788,62 +2714,6 @@ def dice_loss(logits, labels, weight=None, smooth=1.0, batch=False):
     """1 - mean over (group, class) of the class-weighted soft Dice of softmax(logits) against labels; labels outside [0, C) are void.
     weight: dice_weight's tensor.  batch=False: one group per sample; True: the whole batch is one group."""
     return DiceLossFn.apply(logits, labels, weight, smooth, batch)
-
-
-class UpsampleHeadDiceFn(torch.autograd.Function):
-    """UpsampleHeadFn with the Dice branch: returns (softmax map or None, cross entropy or None, Dice loss).  Forward: the head's own
-    launch where the softmax map or the cross entropy is wanted (the same entries, the same bits), then the Dice statistics and their
-    finish - the resized logits still never reach memory.  Dice couples the pixels of a group, so its gradient cannot be left by the
-    forward: the backward is ONE stencil launch (sscg_upsample_head_bwd_d) that serves every live branch."""
-
-    @staticmethod
-    def forward(ctx, x, oh, ow, labels, want_soft, want_ce, ce_w, eps, d_w, smooth, batch):
-        _need_hip(x, f32_only=True)
-        x = to_nhwc(x)
-        n, c = x.shape[:2]
-        labels = labels.contiguous()
-        _check_labels(labels, n * oh * ow)
-        ce_w, eps, _ = _ce_options(ce_w, eps, c, x.device)
-        y = loss = valid = dl = None
-        if want_ce or want_soft:
-            y, loss, valid, dl = _label_head_forward(x, oh, ow, labels, want_soft, want_ce, ce_w, eps)
-        dice, coef, _ = dice_fwd(x, labels, (oh, ow), d_w, smooth, batch)
-        ctx.geom = (oh, ow, 1 if batch else 0)
-        ctx.save_for_backward(x, labels, dl, valid, coef)
-        ctx.set_materialize_grads(False)
-        return y, loss, dice
-
-    @staticmethod
-    def backward(ctx, dy, g_ce, g_dice):
-        x, labels, dl, valid, coef = ctx.saved_tensors
-        oh, ow, batch = ctx.geom
-        # (g_dice None: the Dice term took no part in what was differentiated)
-        dice = None if g_dice is None else (labels, coef, g_dice, batch)
-        return (_label_head_backward(x, oh, ow, dy, dl, valid, g_ce, dice),) + (None,) * 10
-
-
-def upsample_softmax_ce_dice(x, size, labels, want_soft=True, weight=None, label_smoothing=0.0, dice=None, *, ohem=None):
-    """upsample_softmax_ce plus the soft Dice loss of the same resized logits: (softmax2d(interp(x)) or None, cross entropy or None, Dice).
-    dice: a DiceOptions (or a dict of its arguments; None = the defaults).  Fused when the resize grows the map - the head's forward
-    launch, the Dice statistics and their finish; one stencil launch backward - else the separate passes.
-    ohem (an OhemOptions): the cross entropy - not the Dice term - runs over the mined pixels only; still one stencil launch backward."""
-    if dice is None or isinstance(dice, dict):
-        dice = DiceOptions(**(dice or {}))
-    oh, ow = int(size[0]), int(size[1])
-    if ohem is not None:
-        ohem = _ohem_options(ohem)
-        if not dice.ce:
-            raise ValueError("ohem mines the cross entropy: DiceOptions(ce=False) leaves it nothing to mine")
-        if _head_applies(x, oh, ow):
-            return UpsampleHeadOhemFn.apply(x, oh, ow, labels, want_soft, weight, label_smoothing, ohem, dice)
-        up = upsample_bilinear(x, size)
-        return ((softmax2d(up) if want_soft else None), cross_entropy(up, labels, weight, label_smoothing, ohem=ohem),
-                dice_loss(up, labels, dice.weight, dice.smooth, dice.batch))
-    if _head_applies(x, oh, ow):
-        return UpsampleHeadDiceFn.apply(x, oh, ow, labels, want_soft, dice.ce, weight, label_smoothing, dice.weight, dice.smooth, dice.batch)
-    up = upsample_bilinear(x, size)
-    return ((softmax2d(up) if want_soft else None), (cross_entropy(up, labels, weight, label_smoothing) if dice.ce else None),
-            dice_loss(up, labels, dice.weight, dice.smooth, dice.batch))
 
 
 # ----------------------------------------------------------------------------- hard-pixel mining (opt-in; include/sscg.h: sscg_ohem_fwd)
@@ -2927,49 +2797,114 @@ class OhemCrossEntropyFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
-class UpsampleHeadOhemFn(torch.autograd.Function):
-    """The label head with a mined cross entropy: returns (softmax map or None, cross entropy, Dice loss or None).  Forward: the head's
-    own launch for the softmax map where it is wanted (the same entry, the same bits), sscg_ohem_fwd - keys, selection, loss - and the
-    Dice statistics when `dice` (a DiceOptions) is given; the resized logits never reach memory.  The selection couples the pixels of
-    the call, so the forward leaves no gradient: the backward is ONE stencil launch (sscg_upsample_head_bwd_h) for every live branch."""
+# ----------------------------------------------------------------------------- the fused label head: one node for every option
+class LabelHeadFn(torch.autograd.Function):
+    """interp (bilinear, align_corners=True) -> softmax2d and / or the losses, from the LOW-resolution logits (model.py:390-392, 398,
+    401-402, 455): returns (softmax map or None, cross entropy or None, Dice loss or None); the resized logits never reach memory.
+    weight / eps: the class-weighted, smoothed cross entropy (None / 0.0: plain); dice: a DiceOptions or None; ohem: an OhemOptions
+    (the cross entropy runs over the mined pixels) or None.  Forward: the head's own launch where the softmax map or an unmined cross
+    entropy is wanted - that cross entropy's gradient depends on logits and labels only, so the launch already leaves it (dl, up to
+    g / valid: `valid` is the sum of the counted pixels' class weights) - then sscg_ohem_fwd (keys, selection, loss) and the Dice
+    statistics with their finish.  The selection and the Dice sums couple the pixels of the call, so those two leave no gradient.
+    Backward: ONE launch for every live branch."""
 
     @staticmethod
-    def forward(ctx, x, oh, ow, labels, want_soft, ce_w, eps, ohem, dice):
+    def forward(ctx, x, oh, ow, labels, want_soft, want_ce, weight, eps, dice, ohem):
         _need_hip(x, f32_only=True)
         x = to_nhwc(x)
         n, c = x.shape[:2]
-        labels = labels.contiguous()
-        _check_labels(labels, n * oh * ow)
-        ce_w, eps, _ = _ce_options(ce_w, eps, c, x.device)
-        y = _label_head_forward(x, oh, ow, None, True, False, None, 0.0)[0] if want_soft else None
-        loss, valid, keys, thr, _ = ohem_fwd(x, labels, (oh, ow), ohem, ce_w, eps)
-        d_loss = coef = None
-        batch = 0
+        if labels is not None:
+            labels = labels.contiguous()
+            _check_labels(labels, n * oh * ow)
+        weight, eps, _ = _ce_options(weight, eps, c, x.device)
+        mined = want_ce and ohem is not None
+        plain_ce = want_ce and not mined
+        y = loss = valid = dl = keys = thr = d_loss = coef = None
+        if want_soft or plain_ce or not (mined or dice is not None):      # (nothing wanted at all: the entry refuses the call)
+            y, loss, valid, dl = _label_head_forward(x, oh, ow, labels, want_soft, plain_ce, weight, eps)
+        if mined:
+            loss, valid, keys, thr, _ = ohem_fwd(x, labels, (oh, ow), ohem, weight, eps)
         if dice is not None:
             d_loss, coef, _ = dice_fwd(x, labels, (oh, ow), dice.weight, dice.smooth, dice.batch)
-            batch = 1 if dice.batch else 0
-        ctx.opts = (oh, ow, ce_w, eps, batch)
-        ctx.save_for_backward(x, labels, keys, thr, valid, coef)
+        ctx.opts = (oh, ow, weight, eps, 1 if dice is not None and dice.batch else 0)
+        # only what a live branch reads: the labels just where a mined or Dice branch gathers by them
+        ctx.save_for_backward(x, *((labels,) if mined or dice is not None else ()), dl, valid, coef, keys, thr)
+        # an output nothing differentiates (the step reads lab_gt's softmax through .detach() only): backward gets None, not a
+        # zero-filled [B, C, crop] map to gather over
         ctx.set_materialize_grads(False)
         return y, loss, d_loss
 
     @staticmethod
     def backward(ctx, dy, g_ce, g_dice):
-        x, labels, keys, thr, valid, coef = ctx.saved_tensors
-        oh, ow, ce_w, eps, batch = ctx.opts
+        saved = ctx.saved_tensors
+        x, labels = saved[0], (saved[1] if len(saved) == 7 else None)
+        dl, valid, coef, keys, thr = saved[-5:]
+        oh, ow, weight, eps, batch = ctx.opts
+        mined = g_ce is not None and keys is not None          # a loss that received no gradient took no part in what was differentiated
+        use_ce = g_ce is not None and dl is not None
         use_dice = g_dice is not None and coef is not None
-        if g_ce is None:          # the mined loss took no part in what was differentiated: the head's other backwards serve the rest
-            dice = (labels, coef, g_dice, batch) if use_dice else None
-            return (_label_head_backward(x, oh, ow, dy, None, None, None, dice),) + (None,) * 8
+        if dy is None and not (mined or use_ce or use_dice):
+            return (None,) * 10
         n, c, h, w = x.shape
         dx = empty_nhwc(n, c, h, w, x.device)
         if dy is not None:
             dy = to_nhwc(dy)
-        check(lib.sscg_upsample_head_bwd_h(x.data_ptr(), labels.data_ptr(), keys.data_ptr(), thr.data_ptr(), _ptr(ce_w), eps, _ptr(dy),
-                                           g_ce.data_ptr(), valid.data_ptr(), _ptr(coef if use_dice else None),
-                                           _ptr(g_dice if use_dice else None), batch, dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
-              "sscg_upsample_head_bwd_h")
-        return (dx,) + (None,) * 8
+        ce = (_ptr(dl if use_ce else None), _ptr(g_ce if use_ce else None), _ptr(valid if use_ce else None))
+        dice = (_ptr(coef if use_dice else None), _ptr(g_dice if use_dice else None), batch)
+        if mined:
+            check(lib.sscg_upsample_head_bwd_h(x.data_ptr(), labels.data_ptr(), keys.data_ptr(), thr.data_ptr(), _ptr(weight), eps, _ptr(dy),
+                                               g_ce.data_ptr(), valid.data_ptr(), dice[0], dice[1], dice[2], dx.data_ptr(), n, h, w, c, oh, ow,
+                                               _stream()), "sscg_upsample_head_bwd_h")
+        elif use_dice:
+            check(lib.sscg_upsample_head_bwd_d(x.data_ptr(), labels.data_ptr(), _ptr(dy), ce[0], ce[1], ce[2], dice[0], dice[1], dice[2],
+                                               dx.data_ptr(), n, h, w, c, oh, ow, _stream()), "sscg_upsample_head_bwd_d")
+        else:       # (dy None: the cross entropy alone - the entry scales dl)
+            check(lib.sscg_upsample_head_bwd(x.data_ptr(), _ptr(dy), ce[0], ce[1], ce[2], dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
+                  "sscg_upsample_head_bwd")
+        return (dx,) + (None,) * 9
+
+
+class UpsampleHeadFn(object):
+    """The former name of the node for the head without Dice or mining, kept for code that calls its apply(): no node of its own,
+    LabelHeadFn with the cross entropy wherever labels are given - (softmax map or None, loss or None)."""
+
+    @staticmethod
+    def apply(x, oh, ow, labels, want_soft, weight=None, label_smoothing=0.0):
+        return LabelHeadFn.apply(x, oh, ow, labels, want_soft, labels is not None, weight, label_smoothing, None, None)[:2]
+
+
+def _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem):
+    """(softmax2d(interp(x)) or None, cross entropy or None, Dice loss or None): fused (LabelHeadFn) when the resize grows the map, else
+    the separate passes.  dice: a DiceOptions or None; ohem: an OhemOptions or None."""
+    oh, ow = int(size[0]), int(size[1])
+    if _head_applies(x, oh, ow):
+        return LabelHeadFn.apply(x, oh, ow, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem)
+    up = upsample_bilinear(x, size)
+    return ((softmax2d(up) if want_soft else None),
+            (cross_entropy(up, labels, weight, label_smoothing, ohem=ohem) if want_ce else None),
+            (dice_loss(up, labels, dice.weight, dice.smooth, dice.batch) if dice is not None else None))
+
+
+def upsample_softmax_ce(x, size, labels=None, want_soft=True, weight=None, label_smoothing=0.0, *, ohem=None):
+    """(softmax2d(interp(x)) or None, CrossEntropyLoss(interp(x), labels) or None) - fused when the resize grows the map, else the
+    three separate passes.  weight (functional.ce_weight's tensor) / label_smoothing: nn.CrossEntropyLoss's, on either path.
+    ohem (an OhemOptions): the cross entropy runs over the mined pixels only (sscg_ohem_fwd), on either path."""
+    ohem = _ohem_options(ohem) if ohem is not None and labels is not None else None
+    return _label_head(x, size, labels, want_soft, labels is not None, weight, label_smoothing, None, ohem)[:2]
+
+
+def upsample_softmax_ce_dice(x, size, labels, want_soft=True, weight=None, label_smoothing=0.0, dice=None, *, ohem=None):
+    """upsample_softmax_ce plus the soft Dice loss of the same resized logits: (softmax2d(interp(x)) or None, cross entropy or None, Dice).
+    dice: a DiceOptions (or a dict of its arguments; None = the defaults).  Fused when the resize grows the map - the head's forward
+    launch, the Dice statistics and their finish; one stencil launch backward - else the separate passes.
+    ohem (an OhemOptions): the cross entropy - not the Dice term - runs over the mined pixels only; still one stencil launch backward."""
+    if dice is None or isinstance(dice, dict):
+        dice = DiceOptions(**(dice or {}))
+    if ohem is not None:
+        ohem = _ohem_options(ohem)
+        if not dice.ce:
+            raise ValueError("ohem mines the cross entropy: DiceOptions(ce=False) leaves it nothing to mine")
+    return _label_head(x, size, labels, want_soft, dice.ce, weight, label_smoothing, dice, ohem)
 
 
 class MSEConstFn(torch.autograd.Function):
@@ -3224,8 +3159,6 @@ def softmax2d(x):
 def cross_entropy(logits, labels, weight=None, label_smoothing=0.0, *, ohem=None):
     if ohem is not None:        # hard-pixel mining (OhemOptions): the loss over the mined pixels only
         return OhemCrossEntropyFn.apply(logits, labels, weight, label_smoothing, _ohem_options(ohem))
-    if weight is None and label_smoothing == 0.0:
-        return CrossEntropyFn.apply(logits, labels)
     return CrossEntropyFn.apply(logits, labels, weight, label_smoothing)
 
 
