@@ -19,7 +19,7 @@
 #include "common.h"
 #include "sscg_internal.h"
 #include "reduce_common.h"
-#include "bn_fold.h"
+#include "norm_expr.h"
 #include "conv_plan.h"
 #include <type_traits>
 
@@ -72,7 +72,7 @@ struct K16Params {
     int bn_L, bn_G, bn_chunks, bn_act;
     float bn_slope;
     FastDiv div_tn, div_hw, div_w, div_gl;   // by tiles_n, OH * OW, OW, stat_L / bn_L (launch16): tile and row decode without integer divisions (~35 VALU operations each)
-    // AFF instances only (sscg_conv2d_fwd_affine): the eval-mode BatchNorm behind this forward, applied in the store phase (bn_fold.h);
+    // AFF instances only (sscg_conv2d_fwd_affine): the eval-mode BatchNorm behind this forward, applied in the store phase (norm_expr.h);
     // `act` / `slope` are then the activation behind the norm.  Last in the struct: no other instance's argument offsets move.
     const float* __restrict__ af_mean;   // running_mean [Ng]
     const float* __restrict__ af_var;    // running_var [Ng]
@@ -574,6 +574,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && TM * TN == 2) ? 4 : 
                     const int e = 2 * w + hh;
                     const float vv = __uint_as_float(hh ? (vw[w] & 0xffff0000u) : (vw[w] << 16));
                     const float xx = __uint_as_float(hh ? (xw[w] & 0xffff0000u) : (xw[w] << 16));
+                    // (sscg_norm_xhat / sscg_norm_pre of norm_expr.h, written out: calling them reorders this kernel's schedule)
                     const float xh = (xx - bmu[e]) * brs[e];
                     const float ym = xh * bga[e] + bbe[e];
                     const float gg = ym > 0.f ? vv : vv * neg_scale;
@@ -616,7 +617,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && TM * TN == 2) ? 4 : 
         }
         // Eval-mode BatchNorm [+ residual] + activation of the staged bf16 rows (AFF): the four per-channel vectors of the thread's eight
         // channels are hoisted, rstd is formed here (no sscg_rstd_from_var launch), the residual's 16-byte row segments of every pass
-        // are requested up front like the addend's.  Per element the operations of norm.hip's apply pass in their order (bn_fold.h).
+        // are requested up front like the addend's.  Per element the operations of norm.hip's apply pass in their order (norm_expr.h).
         constexpr int NAF = AFF ? NPS : 1;
         static_assert(!AFF || NPS <= 2, "folded BatchNorm: the classes the plan uses (sscg_conv16_affine_applies)");
         uint4 fr0[NAF], fr1[NAF];
@@ -798,37 +799,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && TM * TN == 2) ? 4 : 
     }
 }
 
-// y[i] = act(sum_s part[s][i] + bias[i % Ng]) (fixed order => deterministic)
-__global__ __launch_bounds__(256) void k16_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, void* __restrict__ y,
-                                                          int out_bf16, size_t n, int Ng, int splits, int act, float slope) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < splits; ++k) s += part[(size_t)k * n + i];
-    if (bias) s += bias[(int)(i % Ng)];
-    store_out(y, i, sscg_act(s, act, slope), out_bf16);
-}
-
-// the reduction of a folded-BatchNorm launch's tail (AFF instances, bf16 tensors): per element what k16_reduce_kernel followed by
-// sscg_norm_apply computes - the sum is rounded to bf16 (the conv's stored output) and widened again in front of the affine
-__global__ __launch_bounds__(256) void k16_reduce_affine_kernel(const float* __restrict__ part, const float* __restrict__ bias, bf16* __restrict__ y,
-                                                                 size_t n, int Ng, int splits, int act, float slope, const float* __restrict__ mean,
-                                                                 const float* __restrict__ var, float eps, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, const bf16* __restrict__ res) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < splits; ++k) s += part[(size_t)k * n + i];
-    if (bias) s += bias[(int)(i % Ng)];
-    const int c = (int)(i % Ng);
-    const float x = (float)(bf16)s;
-    const float v = sscg_bn_fold(x, mean[c], sscg_bn_rstd(var[c], eps), gamma ? gamma[c] : 1.f, gamma ? beta[c] : 0.f, gamma != nullptr,
-                                 res ? (float)res[i] : 0.f, res != nullptr);
-    y[i] = (bf16)k16_act(v, act, slope);
-}
-
 // ---- host-side plan
 // tile classes: block tile, waves, copy stages (k-tiles in LDS).  The deep classes hold 2-3 tiles in flight per workgroup.
 enum { CFG_128x128 = 0, CFG_64x64 = 1, CFG_128x32 = 2, CFG_128x64 = 3, CFG_128x128_W8 = 4, CFG_256x128_W8 = 5, NCFG16 = 6 };
@@ -882,21 +852,15 @@ int launch16(const K16Params& p0, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), smem, st, p);
     SSCG_LAUNCH_CHECK();
     if (p.splits > 1) {
-        const size_t n = (size_t)(p.M - p.m_tail0) * p.Ng;
-        const size_t esz = p.out_bf16 ? 2 : 4;
-        void* yt = reinterpret_cast<char*>(p.dst) + (size_t)p.m_tail0 * p.Ng * esz;
+        SplitTail t = split_tail_of(p.part, p.bias, p.dst, p.out_bf16, p.M, p.m_tail0, p.Ng, p.splits, p.act, p.slope);
         if constexpr (AFF) {
-            hipLaunchKernelGGL(k16_reduce_affine_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, st, p.part, p.bias, reinterpret_cast<bf16*>(yt), n, p.Ng,
-                               p.splits, p.act, p.slope, p.af_mean, p.af_var, p.af_eps, p.af_gamma, p.af_beta,
-                               p.af_res ? p.af_res + (size_t)p.m_tail0 * p.Ng : nullptr);
-            SSCG_LAUNCH_CHECK();
-            return SSCG_OK;
+            t.affine = true;
+            t.mean = p.af_mean; t.var = p.af_var; t.gamma = p.af_gamma; t.beta = p.af_beta; t.eps = p.af_eps;
+            t.res = split_tail_ptr(p.af_res, t, p.m_tail0);
+        } else {
+            t.xstats = p.xstats;
         }
-        if (p.xstats)
-            return launch_split_reduce_stats(p.part, p.bias, yt, p.out_bf16, p.M - p.m_tail0, p.Ng, p.splits, p.act, p.slope, p.xstats, st);
-        hipLaunchKernelGGL(k16_reduce_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, st, p.part, p.bias, yt, p.out_bf16, n, p.Ng,
-                           p.splits, p.act, p.slope);
-        SSCG_LAUNCH_CHECK();
+        return launch_split_reduce(t, st);
     }
     return SSCG_OK;
 }

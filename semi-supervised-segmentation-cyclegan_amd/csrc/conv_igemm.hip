@@ -25,7 +25,7 @@
 // boundaries (wave-uniform branch every Cs/BK tiles) and the per-tile loader work is a pointer bump.
 #include "common.h"
 #include "sscg_internal.h"
-#include "bn_fold.h"
+#include "norm_expr.h"
 #include "reduce_common.h"
 #include "conv_plan.h"
 
@@ -65,7 +65,7 @@ struct KcParams {
     float slope;
     int tiles_n;
     int tiles;      // tiles_m * tiles_n
-    int splits;     // split-K factor of the tiles >= full_tiles (partials to `part`, reduced by kc_reduce_kernel)
+    int splits;     // split-K factor of the tiles >= full_tiles (partials to `part`, reduced by split_reduce_kernel, reduce_common.h)
     int ksplit;     // k-tiles per split
     int full_tiles; // tiles [0, full_tiles) are computed whole by one workgroup each; the rest ("tail") are split
     int m_tail0;    // first output row of the tail tiles
@@ -574,33 +574,6 @@ __global__ __launch_bounds__(256) void conv_kc_kernel(KcParams p) {
     }
 }
 
-// y[i] = act(sum_s part[s][i] + bias[i % Ng])   (fixed order => deterministic); V floats per thread
-template <int V>
-__global__ __launch_bounds__(256) void kc_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias,
-                                                         void* __restrict__ y, int out_bf16, size_t n, int Ng, int splits, int act, float slope) {
-    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
-    if (i >= n) return;
-    typedef float vec_t __attribute__((ext_vector_type(V)));
-    vec_t s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < splits; ++k) s += *reinterpret_cast<const vec_t*>(part + (size_t)k * n + i);
-    const int c = (int)(i % Ng);
-    float o[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-        float v = s[e];
-        if (bias) v += bias[c + e];     // V == 4 only when Ng % 4 == 0: the V channels are consecutive
-        o[e] = sscg_act(v, act, slope);
-    }
-    if (out_bf16) {
-        __bf16* yb = reinterpret_cast<__bf16*>(y) + i;
-        if constexpr (V == 4) st4<__bf16>(yb, o); else st1<__bf16>(yb, o[0]);
-    } else {
-        float* yf = reinterpret_cast<float*>(y) + i;
-        if constexpr (V == 4) st4<float>(yf, o); else st1<float>(yf, o[0]);
-    }
-}
-
 // ---- host-side plan: tile configuration + split-K of the tail
 // Tile choice (measured on MI355X, tools/conv_bench.py): 128x128 only when it still yields >= 2 workgroups per CU on a
 // long reduction; otherwise 64x64; a 128x32 tile for heads with a handful of output channels.  Shapes whose source
@@ -645,17 +618,9 @@ int launch_kc(const KcParams& p0, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, p);
     SSCG_LAUNCH_CHECK();
     if (p.splits > 1) {
-        size_t n = (size_t)(p.M - p.m_tail0) * p.Ng;
-        void* yt = reinterpret_cast<char*>(p.dst) + (size_t)p.m_tail0 * p.Ng * (p.out_bf16 ? 2 : 4);
-        if (p.xstats)    // the split rows' column statistics come out of their reduction pass
-            return launch_split_reduce_stats(p.part, p.bias, yt, p.out_bf16, p.M - p.m_tail0, p.Ng, p.splits, p.act, p.slope, p.xstats, st);
-        if (p.Ng % 4 == 0 && (((size_t)yt | (size_t)p.part) & 15) == 0)
-            hipLaunchKernelGGL(kc_reduce_kernel<4>, dim3(cdiv((long)(n / 4), 256)), dim3(256), 0, st, p.part, p.bias, yt, p.out_bf16, n,
-                               p.Ng, p.splits, p.act, p.slope);
-        else
-            hipLaunchKernelGGL(kc_reduce_kernel<1>, dim3(cdiv((long)n, 256)), dim3(256), 0, st, p.part, p.bias, yt, p.out_bf16, n,
-                               p.Ng, p.splits, p.act, p.slope);
-        SSCG_LAUNCH_CHECK();
+        SplitTail t = split_tail_of(p.part, p.bias, p.dst, p.out_bf16, p.M, p.m_tail0, p.Ng, p.splits, p.act, p.slope);
+        t.xstats = p.xstats;
+        return launch_split_reduce(t, st);
     }
     return SSCG_OK;
 }

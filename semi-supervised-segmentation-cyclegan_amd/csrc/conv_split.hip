@@ -25,7 +25,7 @@
 #include "common.h"
 #include "sscg_internal.h"
 #include "reduce_common.h"
-#include "bn_fold.h"
+#include "norm_expr.h"
 #include "conv_plan.h"
 #include <cstdlib>
 #include <type_traits>
@@ -109,7 +109,7 @@ struct KsParams {
     float* __restrict__ fr_h1;           // [M][Cs] or null: the front conv's output is ALSO written (a backward pass that wants it stored)
     FastDiv div_tn, div_gl;              // by tiles_n; by stat_L / bn_L (whichever the launch uses)
     FastDiv div_hw, div_w;               // by OH * OW and by OW (launch_ks): a row's (image, y, x) without integer divisions (~30 VALU operations each)
-    // AFF instances only (sscg_conv2d_fwd_affine): the eval-mode BatchNorm behind this forward, applied in the store phase (bn_fold.h);
+    // AFF instances only (sscg_conv2d_fwd_affine): the eval-mode BatchNorm behind this forward, applied in the store phase (norm_expr.h);
     // `act` / `slope` are then the activation behind the norm.  Last in the struct: no other instance's argument offsets move.
     const float* __restrict__ af_mean;   // running_mean [Ng]
     const float* __restrict__ af_var;    // running_var [Ng]
@@ -907,9 +907,9 @@ __global__ __launch_bounds__(WM * WN * 64, ((KS_LB4 && TM * TN == 1) ? 4 : 2)) v
         float* const obase = partial ? ep.part + ((long)split * (ep.M - ep.m_tail0) - ep.m_tail0) * (long)ep.Ng : ep.dst;
         if constexpr (AFF) {
             // Eval-mode BatchNorm [+ residual] + activation of the raw staged tile: y = act(((conv + bias) - mean) * rstd * gamma + beta
-            // + residual), the operations of the separate passes in their order (bn_fold.h).  The four per-channel vectors are hoisted
+            // + residual), the operations of the separate passes in their order (norm_expr.h).  The four per-channel vectors are hoisted
             // like the bias; rstd is formed here, once per thread for its four channels (no sscg_rstd_from_var launch).
-            if (n < ep.Ng && partial) {          // a split-K tail's partial sums: the reduction carries the affine (ks_reduce_affine_kernel)
+            if (n < ep.Ng && partial) {          // a split-K tail's partial sums: the reduction carries the affine (split_reduce_kernel, reduce_common.h)
 #pragma unroll
                 for (int ps = 0; ps < BM / RPP; ++ps) {
                     const int r = tid / TPR + ps * RPP;
@@ -1020,6 +1020,7 @@ __global__ __launch_bounds__(WM * WN * 64, ((KS_LB4 && TM * TN == 1) ? 4 : 2)) v
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const float xh = (yv[q][e] - (lo ? mu0[e] : mu1[e])) * (lo ? rs0[e] : rs1[e]);
+                            // (sscg_norm_xhat / sscg_norm_pre of norm_expr.h, written out: calling them reorders this kernel's schedule)
                             const float ym = ep.bn_z ? zv[q][e] : xh * ga[e] + be[e];       // (sign of the output = sign of the pre-activation)
                             const float gg = ym > 0.f ? v[e] : v[e] * neg_scale;        // (ReLU: -0 for a negative masked gradient - the sums do not see the sign of a zero)
                             if (premask) o[e] = ym > 0.f ? v[e] : 0.f;
@@ -1058,56 +1059,6 @@ __global__ __launch_bounds__(WM * WN * 64, ((KS_LB4 && TM * TN == 1) ? 4 : 2)) v
         }
     }
 
-}
-
-// y[i] = act(sum_s part[s][i] + bias[i % Ng])   (fixed order => deterministic); 4 floats per thread (Ng % 4 == 0)
-__global__ __launch_bounds__(256) void ks_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ y,
-                                                         size_t n, int Ng, int splits, int act, float slope, const float* __restrict__ addend) {
-    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= n) return;
-    f32x4 s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < splits; ++k) s += *reinterpret_cast<const f32x4*>(part + (size_t)k * n + i);
-    const int c = (int)(i % Ng);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = sscg_act(s[e] + (bias ? bias[c + e] : 0.f), act, slope);
-    if (addend) o += *reinterpret_cast<const f32x4*>(addend + i);
-    *reinterpret_cast<f32x4*>(y + i) = o;
-}
-
-// the reduction of a folded-BatchNorm launch's tail (AFF instances): y[i] = act(bn(sum_s part[s][i] + bias) + residual), per element
-// what ks_reduce_kernel followed by sscg_norm_apply computes
-__global__ __launch_bounds__(256) void ks_reduce_affine_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ y,
-                                                                size_t n, int Ng, int splits, int act, float slope, const float* __restrict__ mean,
-                                                                const float* __restrict__ var, float eps, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, const float* __restrict__ res) {
-    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= n) return;
-    f32x4 s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < splits; ++k) s += *reinterpret_cast<const f32x4*>(part + (size_t)k * n + i);
-    const int c = (int)(i % Ng);
-    f32x4 rv = 0.f, o;
-    if (res) rv = *reinterpret_cast<const f32x4*>(res + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float x = s[e] + (bias ? bias[c + e] : 0.f);
-        o[e] = ks_act(sscg_bn_fold(x, mean[c + e], sscg_bn_rstd(var[c + e], eps), gamma ? gamma[c + e] : 1.f, gamma ? beta[c + e] : 0.f,
-                                   gamma != nullptr, rv[e], res != nullptr), act, slope);
-    }
-    *reinterpret_cast<f32x4*>(y + i) = o;
-}
-
-// the same, element by element (Ng % 4 != 0: heads with 21 / 20 output channels)
-__global__ __launch_bounds__(256) void ks_reduce1_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ y,
-                                                          size_t n, int Ng, int splits, int act, float slope) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < splits; ++k) s += part[(size_t)k * n + i];
-    y[i] = sscg_act(s + (bias ? bias[(int)(i % Ng)] : 0.f), act, slope);
 }
 
 constexpr bool KS_STAGE_OUT_HOST = KS_STAGE_OUT != 0;      // the addend joins in the staged store phase
@@ -1182,23 +1133,16 @@ int launch_ks(const KsParams& p0, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), smem, st, p);
     SSCG_LAUNCH_CHECK();
     if (p.splits > 1) {
-        const size_t n = (size_t)(p.M - p.m_tail0) * p.Ng;
-        float* yt = p.dst + (size_t)p.m_tail0 * p.Ng;
+        SplitTail t = split_tail_of(p.part, p.bias, p.dst, 0, p.M, p.m_tail0, p.Ng, p.splits, p.act, p.slope);
         if constexpr (AFF) {
-            hipLaunchKernelGGL(ks_reduce_affine_kernel, dim3(cdiv((long)(n / 4), 256)), dim3(256), 0, st, p.part, p.bias, yt, n, p.Ng, p.splits, p.act,
-                               p.slope, p.af_mean, p.af_var, p.af_eps, p.af_gamma, p.af_beta,
-                               p.af_res ? p.af_res + (size_t)p.m_tail0 * p.Ng : nullptr);
-            SSCG_LAUNCH_CHECK();
-            return SSCG_OK;
+            t.affine = true;
+            t.mean = p.af_mean; t.var = p.af_var; t.gamma = p.af_gamma; t.beta = p.af_beta; t.eps = p.af_eps;
+            t.res = split_tail_ptr(p.af_res, t, p.m_tail0);
+        } else {
+            t.xstats = p.xstats;
+            t.addend = split_tail_ptr(p.addend, t, p.m_tail0);
         }
-        if (p.xstats)
-            return launch_split_reduce_stats(p.part, p.bias, yt, 0, p.M - p.m_tail0, p.Ng, p.splits, p.act, p.slope, p.xstats, st);
-        if (p.Ng & 3)
-            hipLaunchKernelGGL(ks_reduce1_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, st, p.part, p.bias, yt, n, p.Ng, p.splits, p.act, p.slope);
-        else
-            hipLaunchKernelGGL(ks_reduce_kernel, dim3(cdiv((long)(n / 4), 256)), dim3(256), 0, st, p.part, p.bias, yt, n, p.Ng, p.splits, p.act,
-                               p.slope, p.addend ? p.addend + (size_t)p.m_tail0 * p.Ng : nullptr);
-        SSCG_LAUNCH_CHECK();
+        return launch_split_reduce(t, st);
     }
     return SSCG_OK;
 }

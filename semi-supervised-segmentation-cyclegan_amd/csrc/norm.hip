@@ -10,6 +10,7 @@
 // The tensor is viewed as [G][L][C] (see sscg.h).
 #include "common.h"
 #include "sscg_internal.h"
+#include "norm_expr.h"
 #include <cstdlib>
 
 namespace {
@@ -35,13 +36,6 @@ struct RedParams {
     int act;
     float slope;
 };
-
-__device__ __forceinline__ float act_grad(float dy, float y, int act, float slope) {
-    if (act == SSCG_ACT_RELU) return y > 0.f ? dy : 0.f;
-    if (act == SSCG_ACT_LRELU) return y > 0.f ? dy : dy * slope;
-    if (act == SSCG_ACT_TANH) return dy * (1.f - y * y);
-    return dy;
-}
 
 template <typename T, int VEC> __device__ __forceinline__ void ldv(const T* p, float v[VEC]) {
     if constexpr (VEC == 8) ld8<T>(p, v);
@@ -136,10 +130,10 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(RedParams p, int CW) {
                         s0[e] += d;
                         s1[e] += d * d;
                     } else {
-                        float xh = (xv[u][e] - mu[e]) * rs[e];
+                        float xh = sscg_norm_xhat(xv[u][e], mu[e], rs[e]);
                         float ym = yv[u][e];
-                        if (remask || HEAD) ym = xh * ga[e] + be[e];      // the forward's own expression (norm_apply_kernel): same sign
-                        float gg = act_grad(dv[u][e], ym, p.act, p.slope);
+                        if (remask || HEAD) ym = sscg_norm_pre(xh, ga[e], be[e]);      // the forward's own expression (norm_expr.h): same sign
+                        float gg = sscg_act_grad(dv[u][e], ym, p.act, p.slope);
                         s0[e] += (double)gg;
                         s1[e] += (double)gg * (double)xh;
                         if constexpr (HEAD) s2[e] += (double)sscg_act(ym, p.act, p.slope) * (double)dout[u];
@@ -386,10 +380,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(ApplyParams p) {
         }
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-            float v = (xv[e] - mu[e]) * rs[e];
-            if (p.gamma) v = v * ga[e] + be[e];
-            if (p.res) v += rv[e];
-            out[e] = sscg_act(v, p.act, p.slope);
+            out[e] = sscg_act(sscg_bn_fold(xv[e], mu[e], rs[e], ga[e], be[e], p.gamma != nullptr, rv[e], p.res != nullptr), p.act, p.slope);
         }
         stv<T, VEC>(py + o, out);
     }
@@ -438,10 +429,7 @@ __global__ __launch_bounds__(256) void norm_apply_slab_kernel(ApplyParams p, int
                 float out[VEC];
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
-                    float v = (xv[u][e] - mu[e]) * rs[e];
-                    if (p.gamma) v = v * ga[e] + be[e];
-                    if (pr) v += rv[u][e];
-                    out[e] = sscg_act(v, p.act, p.slope);
+                    out[e] = sscg_act(sscg_bn_fold(xv[u][e], mu[e], rs[e], ga[e], be[e], p.gamma != nullptr, rv[u][e], pr != nullptr), p.act, p.slope);
                 }
                 stv<T, VEC>(py + (size_t)rr * p.C, out);
             }
@@ -499,6 +487,47 @@ struct BwdApplyParams {
     FastDiv div_l;
 };
 
+// the per-channel parameters of VEC consecutive channels of one group, as both backward apply kernels hold them
+template <int VEC> struct BwdChannels { float mu[VEC], rs[VEC], ga[VEC], be[VEC], c1[VEC], c2[VEC], hw[VEC]; };
+
+// s = g * C + c.  Neutral values where the launch has no such parameter (gamma 1, beta 0, constant statistics: c1 = c2 = 0)
+template <int VEC>
+__device__ __forceinline__ void load_bwd_channels(const BwdApplyParams& p, size_t s, int c, bool remask, BwdChannels<VEC>& ch) {
+    ldv<float, VEC>(p.rstd + s, ch.rs);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) { ch.ga[e] = 1.f; ch.be[e] = 0.f; ch.mu[e] = 0.f; ch.c1[e] = 0.f; ch.c2[e] = 0.f; ch.hw[e] = 0.f; }
+    if (p.gamma) ldv<float, VEC>(p.gamma + c, ch.ga);
+    if (remask && p.beta) ldv<float, VEC>(p.beta + c, ch.be);
+    if (p.coef || remask) ldv<float, VEC>(p.mean + s, ch.mu);
+    if (p.coef) {
+        if constexpr (VEC == 1) {
+            ch.c1[0] = p.coef[s * 2]; ch.c2[0] = p.coef[s * 2 + 1];
+        } else {
+            float kk[2 * VEC];          // (c1, c2) pairs of channels c .. c+VEC-1
+#pragma unroll
+            for (int q = 0; q < 2 * VEC; q += 4) ld4<float>(p.coef + s * 2 + q, kk + q);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) { ch.c1[e] = kk[2 * e]; ch.c2[e] = kk[2 * e + 1]; }
+        }
+    }
+    if (p.head_w) ldv<float, VEC>(p.head_w + c, ch.hw);
+}
+
+// (dy, x, y) of VEC channels -> (dx, the residual's gradient); yv is read only with an activation whose mask is not recomputed
+template <int VEC>
+__device__ __forceinline__ void norm_bwd_vec(int act, float slope, bool remask, bool has_c, const BwdChannels<VEC>& ch, const float (&dv)[VEC],
+                                             const float (&xv)[VEC], const float (&yv)[VEC], float (&gx)[VEC], float (&gr)[VEC]) {
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        const float xh = sscg_norm_xhat(xv[e], ch.mu[e], ch.rs[e]);
+        float ym = yv[e];
+        if (remask) ym = sscg_norm_pre(xh, ch.ga[e], ch.be[e]);
+        const float gg = act != SSCG_ACT_NONE ? sscg_act_grad(dv[e], ym, act, slope) : dv[e];
+        gr[e] = gg;
+        gx[e] = sscg_norm_bwd_elem(gg, xh, ch.c1[e], ch.c2[e], ch.rs[e], ch.ga[e], has_c);
+    }
+}
+
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(BwdApplyParams p) {
     const int CG = p.C / VEC;
@@ -507,62 +536,33 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(BwdApplyParams p) {
     const T* py = reinterpret_cast<const T*>(p.y);
     T* pdx = reinterpret_cast<T*>(p.dx);
     T* pdres = reinterpret_cast<T*>(p.dres);
+    const bool remask = p.act != SSCG_ACT_NONE && py == nullptr;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < p.total; i += gridDim.x * 256) {
         const int row = fd_div((int)i, p.div_cg);
         const int c = ((int)i - row * CG) * VEC;
         const int g = fd_div(row, p.div_l);
         const size_t o = (size_t)i * VEC;
-        const bool remask = p.act != SSCG_ACT_NONE && py == nullptr;
+        BwdChannels<VEC> ch;
+        load_bwd_channels<VEC>(p, (size_t)g * p.C + c, c, remask, ch);
         float dv[VEC], xv[VEC], yv[VEC];
         if (p.head_w) {
-            float hw[VEC];
-            ldv<float, VEC>(p.head_w + c, hw);
             const float d = p.head_dout[row];
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) dv[e] = d * hw[e];
+            for (int e = 0; e < VEC; ++e) dv[e] = d * ch.hw[e];
         } else {
             ldv<T, VEC>(pdy + o, dv);
         }
         ldv<T, VEC>(px + o, xv);
         if (p.act != SSCG_ACT_NONE && !remask) ldv<T, VEC>(py + o, yv);
         float gx[VEC], gr[VEC];
-        float mu[VEC], rsv[VEC], ga[VEC], be[VEC], c1[VEC], c2[VEC];
-        const size_t s = (size_t)g * p.C + c;
-        ldv<float, VEC>(p.rstd + s, rsv);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) { ga[e] = 1.f; be[e] = 0.f; mu[e] = 0.f; c1[e] = 0.f; c2[e] = 0.f; }
-        if (p.gamma) ldv<float, VEC>(p.gamma + c, ga);
-        if (remask && p.beta) ldv<float, VEC>(p.beta + c, be);
-        if (p.coef || remask) ldv<float, VEC>(p.mean + s, mu);
-        if (p.coef) {
-            if constexpr (VEC == 1) {
-                c1[0] = p.coef[s * 2]; c2[0] = p.coef[s * 2 + 1];
-            } else {
-                float kk[2 * VEC];          // (c1, c2) pairs of channels c .. c+VEC-1
-#pragma unroll
-                for (int q = 0; q < 2 * VEC; q += 4) ld4<float>(p.coef + s * 2 + q, kk + q);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) { c1[e] = kk[2 * e]; c2[e] = kk[2 * e + 1]; }
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const float xh = (xv[e] - mu[e]) * rsv[e];
-            float ym = yv[e];
-            if (remask) ym = xh * ga[e] + be[e];
-            float gg = p.act != SSCG_ACT_NONE ? act_grad(dv[e], ym, p.act, p.slope) : dv[e];
-            gr[e] = gg;
-            float v = gg;
-            if (p.coef) v = gg - c1[e] - xh * c2[e];
-            gx[e] = v * rsv[e] * ga[e];
-        }
+        norm_bwd_vec<VEC>(p.act, p.slope, remask, p.coef != nullptr, ch, dv, xv, yv, gx, gr);
         stv<T, VEC>(pdx + o, gx);
         if (p.dres) stv<T, VEC>(pdres + o, gr);
     }
 }
 
-// norm_bwd_apply_kernel with a thread bound to one channel group (see norm_apply_slab_kernel): the six per-channel parameter vectors
-// are loaded once per thread, U rows of (dy, x, y) in flight.  Same per-element expression.
+// norm_bwd_apply_kernel with a thread bound to one channel group (see norm_apply_slab_kernel): the per-channel parameters are loaded
+// once per thread, U rows of (dy, x, y) in flight.  The two kernels differ only in how they walk the tensor.
 template <typename T, int VEC, int U>
 __global__ __launch_bounds__(256) void norm_bwd_apply_slab_kernel(BwdApplyParams p, int cw_shift, int rows_per_chunk) {
     const int tid = threadIdx.x;
@@ -571,22 +571,8 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_slab_kernel(BwdApplyParams
     const int g = blockIdx.z;
     const bool remask = p.act != SSCG_ACT_NONE && p.y == nullptr;
     const bool has_y = p.act != SSCG_ACT_NONE && !remask;
-    float mu[VEC], rsv[VEC], ga[VEC], be[VEC], c1[VEC], c2[VEC], hw[VEC];
-    const size_t s = (size_t)g * p.C + c;
-    ldv<float, VEC>(p.rstd + s, rsv);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) { ga[e] = 1.f; be[e] = 0.f; mu[e] = 0.f; c1[e] = 0.f; c2[e] = 0.f; hw[e] = 0.f; }
-    if (p.gamma) ldv<float, VEC>(p.gamma + c, ga);
-    if (remask && p.beta) ldv<float, VEC>(p.beta + c, be);
-    if (p.coef || remask) ldv<float, VEC>(p.mean + s, mu);
-    if (p.coef) {
-        float kk[2 * VEC];          // (c1, c2) pairs of channels c .. c+VEC-1
-#pragma unroll
-        for (int q = 0; q < 2 * VEC; q += 4) ld4<float>(p.coef + s * 2 + q, kk + q);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) { c1[e] = kk[2 * e]; c2[e] = kk[2 * e + 1]; }
-    }
-    if (p.head_w) ldv<float, VEC>(p.head_w + c, hw);
+    BwdChannels<VEC> ch;
+    load_bwd_channels<VEC>(p, (size_t)g * p.C + c, c, remask, ch);
     const size_t base = (size_t)g * p.L * p.C + c;
     const T* pdy = p.head_w ? nullptr : reinterpret_cast<const T*>(p.dy) + base;
     const T* px = reinterpret_cast<const T*>(p.x) + base;
@@ -606,7 +592,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_slab_kernel(BwdApplyParams
                 if (p.head_w) {
                     const float d = pdo[rr];
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) dv[u][e] = d * hw[e];
+                    for (int e = 0; e < VEC; ++e) dv[u][e] = d * ch.hw[e];
                 } else {
                     ldv<T, VEC>(pdy + o, dv[u]);
                 }
@@ -620,17 +606,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_slab_kernel(BwdApplyParams
             if (rr < r_end) {
                 const size_t o = (size_t)rr * p.C;
                 float gx[VEC], gr[VEC];
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const float xh = (xv[u][e] - mu[e]) * rsv[e];
-                    float ym = yv[u][e];
-                    if (remask) ym = xh * ga[e] + be[e];
-                    float gg = p.act != SSCG_ACT_NONE ? act_grad(dv[u][e], ym, p.act, p.slope) : dv[u][e];
-                    gr[e] = gg;
-                    float v = gg;
-                    if (p.coef) v = gg - c1[e] - xh * c2[e];
-                    gx[e] = v * rsv[e] * ga[e];
-                }
+                norm_bwd_vec<VEC>(p.act, p.slope, remask, p.coef != nullptr, ch, dv[u], xv[u], yv[u], gx, gr);
                 stv<T, VEC>(pdx + o, gx);
                 if (pdres) stv<T, VEC>(pdres + o, gr);
             }
@@ -689,8 +665,7 @@ __global__ __launch_bounds__(256) void norm_head_fwd_kernel(HeadParams p) {
             float acc = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float v = (xv[u][e] - mu[u][e]) * rs[u][e];
-                if (p.gamma) v = v * ga[e] + be[e];
+                const float v = sscg_bn_fold(xv[u][e], mu[u][e], rs[u][e], ga[e], be[e], p.gamma != nullptr, 0.f, false);
                 acc += w[e] * sscg_act(v, p.act, p.slope);
             }
             for (int m = 1; m < lanes; m <<= 1) acc += __shfl_xor(acc, m, 64);

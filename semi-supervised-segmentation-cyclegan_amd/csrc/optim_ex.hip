@@ -4,7 +4,7 @@
 //
 // Bit contract: with a coefficient of exactly 1.0f and/or an EMA and no decay, param / both moments / shadow leave this kernel with
 // the bits adam_kernel gives them.  Left to the compiler the same expression contracts differently from kernel to kernel, so the
-// arithmetic is PINNED (as head_common.h and bn_fold.h pin theirs): contraction is switched off and the FMAs that adam_kernel
+// arithmetic is PINNED (as head_common.h and norm_expr.h pin theirs): contraction is switched off and the FMAs that adam_kernel
 // compiles to on gfx950 are written out -
 //     d     = fma(g, scale, -m)              the scaled gradient is NOT rounded on its way into the first moment
 //     m'    = fma(1 - beta1, d, m)

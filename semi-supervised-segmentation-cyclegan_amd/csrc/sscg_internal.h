@@ -29,7 +29,7 @@ size_t sscg_convs_fwd_workspace(const sscg_conv_desc* d, long stat_L);
 size_t sscg_convs_dgrad_workspace(const sscg_conv_desc* d);
 int sscg_convs_fwd(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, void* y, double* stats, long stat_L,
                    double* xstats, void* ws, size_t ws_bytes, hipStream_t st);
-// the forward with the eval-mode BatchNorm [+ residual] + activation behind it folded into the store phase (bn_fold.h)
+// the forward with the eval-mode BatchNorm [+ residual] + activation behind it folded into the store phase (norm_expr.h)
 struct sscg_bn_fold_args;
 bool sscg_convs_affine_applies(const sscg_conv_desc* d);
 int sscg_convs_fwd_affine(const sscg_conv_desc* d, const void* x, const void* w, const float* bias, const sscg_bn_fold_args& bn, void* y,

@@ -13,6 +13,7 @@ holds the distance of a plain-fp32 evaluation of the same expressions from the r
 The regimes beside each case were read off a Python mirror of plan_reduce / plan_slab (csrc/norm.hip).  A change of either planner
 has to revisit them: the cases are the smallest shapes that reach each regime, not shapes that reach them whatever the plan."""
 import functools
+import os
 
 import pytest
 import torch
@@ -299,6 +300,39 @@ def test_mask_recomputed_from_x_in_the_multi_round_regime(cid, act, F, dev):
     assert float(outs[0][0].float().abs().max()) > 0 and float(outs[0][1].abs().max()) > 0
     for a, b, name in zip(outs[0], outs[1], ("dx", "dgamma", "dbeta")):
         assert torch.equal(a, b), name
+
+
+@pytest.mark.parametrize("act", ["relu", "lrelu"])
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [64, 24, 21])
+def test_mask_recomputed_from_x_in_the_slab_flat_and_scalar_kernels(C, dtype, act, F, dev):
+    """[G][L][C] = (2, 1031, C): 64 channels run the slab kernels, 24 the flat kernels on vectors (six fp32 / three bf16 column groups:
+    no power of two), 21 the flat kernels element by element.  The backward's recomputed pre-activation and the forward's are one
+    function (csrc/norm_expr.h): dx, dgamma, dbeta with y == NULL are bitwise those of the call that reads y."""
+    G, L = 2, 1031
+    # the regime, from a mirror of vec_for / plan_slab (csrc/norm.hip): vectors of 8 (bf16, C % 8 == 0), 4 (C % 4 == 0) or 1; the slab
+    # kernels where the vectors per row are a power of two and SSCG_NORM_SLAB does not switch them off
+    vec = 8 if (dtype == BF and C % 8 == 0) else (4 if C % 4 == 0 else 1)
+    groups = C // vec
+    slab = vec >= 4 and groups & (groups - 1) == 0 and os.environ.get("SSCG_NORM_SLAB", "1").strip() != "0"
+    assert (vec, slab) == {(64, F32): (4, True), (64, BF): (8, True), (24, F32): (4, False), (24, BF): (8, False), (21, F32): (1, False),
+                           (21, BF): (1, False)}[(C, dtype)]
+    code = _act_code(F, act)
+    x = _table(G, L, C, dtype, 700 + C).to(dev).to(dtype).view(G, L, 1, C).permute(0, 3, 1, 2)
+    dy = _rnd(torch.randn(G, L, C, generator=torch.Generator().manual_seed(800 + C)), dtype).to(dev).to(dtype).view(G, L, 1, C).permute(0, 3, 1, 2)
+    gamma, beta = (t.to(dev) for t in _affine(C))
+    mean, rstd = F.norm_stats(x, True, EPS)
+    y = F.norm_apply(x, mean, rstd, gamma, beta, None, True, code, SLOPE)
+    outs = []
+    for yy in (y, None):
+        dg, db = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+        dx, _ = F.norm_bwd(dy, x, yy, mean, rstd, gamma, True, code, SLOPE, True, False, dg, db, beta=beta)
+        outs.append((dx, dg, db))
+    assert outs[0][0].dtype == dtype and float(outs[0][0].float().abs().max()) > 0 and float(outs[0][1].abs().max()) > 0
+    masked = float((y.float() <= 0).float().mean())
+    assert 0.05 < masked < 0.95, masked
+    for a, b, name in zip(outs[0], outs[1], ("dx", "dgamma", "dbeta")):
+        assert torch.equal(a, b), (name, int((a != b).sum()))
 
 
 def _row_ranges(L, rows_per_chunk, round_rows):
