@@ -533,6 +533,45 @@ int sscg_image_head(const float* x, int N, int H, int W, int C, int OH, int OW, 
 int sscg_predict_head_ms(const float* const* xs, const int* Hs, const int* Ws, int S, uint32_t flip_mask, int N, int C, int OH, int OW,
                          float* prob_sum, int64_t* index, uint8_t* label_u8, const int64_t* label_true, int64_t* hist, void* stream);
 int sscg_resize_flip(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, int flip, void* stream);
+/* ------------------------------------------------------------------ windowed dense-CRF refinement of a predicted class map: the
+ * mean-field update of the fully connected CRF that conventionally follows a DeepLab-v2 net, with the pairwise sum truncated to a
+ * dilated (2r+1)^2 window.  The reference has no CRF, so there is no call site to name; opt-in (`--crf`), forward only, never launched
+ * by the training step.  (An addition: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.)
+ *
+ * sscg_crf_head: x is, by `kind`,
+ *   SSCG_CRF_LOGITS  fp32 [N][H][W][C] low-resolution logits, resized to [OH][OW] by sscg_upsample_bilinear_fwd's arithmetic
+ *                    (OH == H && OW == W: the identity resize);
+ *   SSCG_CRF_PROBS   fp32 [N][OH][OW][C] non-negative scores, e.g. prob_sum of sscg_predict_head_ms; H == OH && W == OW required.
+ * img = the guide image, fp32 [N][OH][OW][IC], 1 <= IC <= 4, in whatever units theta_beta is given in; C <= 64.
+ * Unary, per output pixel: LOGITS u_c = (z_c - m) - logf(s) with z the resized logits, m their maximum and s = sum_c expf(z_c - m);
+ * PROBS u_c = logf(fmaxf(x_c, FLT_MIN)).  Q0 = softmax_c(u) by sscg_softmax_fwd's operations.
+ * Pairwise weight between pixel i and its tap at offset (dy * d, dx * d), dy, dx in [-r, r], centre excluded:
+ *   k = w_bilateral * expf(-(d2 * ia + c2 * ib)) + w_spatial * expf(-d2 * ig),  d2 = (dy d)^2 + (dx d)^2,
+ *   c2 = sum over the IC channels of (img_i - img_j)^2,  ia = 1 / (2 theta_alpha^2), ib = 1 / (2 theta_beta^2), ig = 1 / (2 theta_gamma^2),
+ * each formed in double and rounded to fp32 once.  A tap outside the map is skipped; nothing is renormalised.
+ * One mean-field step (Potts compatibility): msg_c(i) = sum over the taps of k * Q_c(j), the taps in row-major (dy, dx) order into one
+ * fp32 accumulator per class; Q'(i) = softmax_c(u_c(i) + msg_c(i)).  After `iterations` steps the label is the first maximum of Q
+ * (sscg_argmax_onehot's rule).  The order is part of the contract: the result depends neither on the workgroup tiling nor on N.
+ *   q_out      (nullable) fp32 [N][OH][OW][C]: Q after the last step;
+ *   index / label_u8 / label_true + hist: exactly as in sscg_predict_head (hist accumulated into, t outside [0, C) ignored).
+ * At least one output is required.  ws: sscg_crf_workspace bytes (u and two Q buffers: three [N][OH][OW][C] fp32 maps; 0 when
+ * iterations == 0), fully written before it is read.
+ * iterations == 0: no CRF launch - LOGITS is sscg_predict_head itself, PROBS the first maximum of x (what sscg_predict_head_ms takes of
+ * its sum); img and the parameters are checked but not used, q_out must be null.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null x / img / p; unknown kind; non-positive sizes; C outside 1..64; IC outside 1..4;
+ * radius outside 1..5; dilation < 1; iterations < 0; a weight that is negative or not finite; a theta that is not > 0, or so small that
+ * 1 / (2 theta^2) is not a finite fp32 number; no output; q_out with iterations == 0; label_true without hist or the reverse; PROBS
+ * with H != OH or W != OW), SSCG_ERR_UNSUPPORTED (radius * dilation > 16; N*OH*OW*C >= 2^31), SSCG_ERR_WORKSPACE. */
+#define SSCG_CRF_LOGITS 0
+#define SSCG_CRF_PROBS 1
+typedef struct sscg_crf_params {
+    int32_t radius, dilation, iterations;
+    float w_bilateral, w_spatial, theta_alpha, theta_beta, theta_gamma;
+} sscg_crf_params;
+size_t sscg_crf_workspace(int N, int C, int OH, int OW, int iterations);
+int sscg_crf_head(const float* x, int kind, int N, int H, int W, int C, int OH, int OW, const float* img, int IC,
+                  const sscg_crf_params* p, float* q_out, int64_t* index, uint8_t* label_u8, const int64_t* label_true, int64_t* hist,
+                  void* ws, size_t ws_bytes, void* stream);
 /* ------------------------------------------------------------------ per-epoch image panels: the image grids the reference sends to
  * TensorBoard at the end of every epoch (model.py:576-638; supervised_model: model.py:164-186), without the host round trip of
  * full-resolution maps, the per-pixel Python loop of utils.PIL_to_tensor (utils.py:59-94) and make_grid on the host.  Forward only;

@@ -2,7 +2,7 @@
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
---ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -47,6 +47,7 @@ class _Args(Namespace):
     ohem_thresh = None
     ohem_min_kept = 0
     ohem_min_frac = 0.0625
+    crf = ""
 
 
 def get_args(argv=None):
@@ -125,7 +126,17 @@ def get_args(argv=None):
                         help="with --ohem_thresh: at least N pixels of a batch are kept, N >= 0 (default: 0)")
     parser.add_argument("--ohem_min_frac", type=float, default=SUPPRESS, metavar="F",
                         help="with --ohem_thresh: at least the share F, in [0, 1], of a batch's labelled pixels is kept (default: 0.0625)")
+    parser.add_argument("--crf", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="refine the predicted label maps of the per-epoch evaluation, --validation and --testing with a windowed "
+                             "dense CRF guided by the input image: 'on' for the (untuned) defaults, or a comma list of key=value over "
+                             "iters, radius, dilation, wb, ws, alpha, beta, gamma (e.g. iters=5,radius=3,dilation=2,wb=4,ws=3,alpha=8,"
+                             "beta=0.5,gamma=3); with --tta it runs on the views' summed probabilities (default: off, the plain argmax)")
     args = parser.parse_args(argv, namespace=_Args())
+    if args.crf.strip():
+        try:
+            importlib.import_module(PKG + ".utils").parse_crf(args.crf)
+        except ValueError as e:
+            parser.error(str(e))
     if args.ohem_thresh is not None and not 0.0 < args.ohem_thresh <= 1.0:
         parser.error("--ohem_thresh must lie in (0, 1]")
     if args.ohem_min_kept < 0:

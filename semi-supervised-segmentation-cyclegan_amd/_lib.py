@@ -16,6 +16,7 @@ F32, BF16, BF16X3 = 0, 1, 2     # SSCG_F32 / SSCG_BF16 / SSCG_BF16X3 (split weig
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 PAD_ZEROS, PAD_REFLECT = 0, 1
 PANEL_IMAGE, PANEL_COLOUR, PANEL_GREY = 0, 1, 2     # SSCG_PANEL_*: the source kinds of sscg_panel_range / sscg_panel_grid
+CRF_LOGITS, CRF_PROBS = 0, 1                        # SSCG_CRF_*: what sscg_crf_head's x holds
 
 
 class ConvDesc(C.Structure):
@@ -32,12 +33,23 @@ class ConvDesc(C.Structure):
     ]
 
 
+class CrfParams(C.Structure):
+    """Mirror of `sscg_crf_params` (include/sscg.h)."""
+
+    _fields_ = [
+        ("radius", C.c_int32), ("dilation", C.c_int32), ("iterations", C.c_int32),
+        ("w_bilateral", C.c_float), ("w_spatial", C.c_float),
+        ("theta_alpha", C.c_float), ("theta_beta", C.c_float), ("theta_gamma", C.c_float),
+    ]
+
+
 _p = C.c_void_p
 _i = C.c_int
 _i64 = C.c_int64
 _f = C.c_float
 _sz = C.c_size_t
 _dp = C.POINTER(ConvDesc)
+_cp = C.POINTER(CrfParams)
 
 # name -> (restype, argtypes); must list every symbol of include/sscg.h (tests/test_abi.py checks)
 SIGNATURES = {
@@ -126,6 +138,8 @@ SIGNATURES = {
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_predict_head_ms": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.c_uint32, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sscg_resize_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "sscg_crf_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "sscg_crf_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _cp, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "sscg_panel_labels": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_panel_range_workspace": (_sz, [_i64, _i]),
     "sscg_panel_range": (_i, [_p, _i, _i64, _i, _f, _f, _p, _p, _p, _sz, _p]),

@@ -1388,6 +1388,109 @@ def predict_labels_ms(logits_list, flips, size, *, want_prob=False, want_index=F
     return u8, idx, hist, prob
 
 
+# Windowed dense-CRF refinement of a predicted class map (sscg_crf_head, include/sscg.h holds the definition): opt-in (`--crf`), an
+# inference call.  The defaults below are UNTUNED - no dataset was on hand to tune them; theta_beta is in the units of the guide image
+# the drivers pass, the normalised batch.
+class CrfOptions(object):
+    """iterations >= 0 mean-field steps over a dilated (2 radius + 1)^2 window (radius 1..5, dilation >= 1, radius * dilation <= 16);
+    w_bilateral / w_spatial finite and >= 0; theta_alpha / theta_beta / theta_gamma > 0."""
+    __slots__ = ("iterations", "radius", "dilation", "w_bilateral", "w_spatial", "theta_alpha", "theta_beta", "theta_gamma")
+
+    def __init__(self, iterations=5, radius=3, dilation=2, w_bilateral=4.0, w_spatial=3.0, theta_alpha=8.0, theta_beta=0.5,
+                 theta_gamma=3.0):
+        for name, val in (("iterations", iterations), ("radius", radius), ("dilation", dilation)):
+            if isinstance(val, bool) or not isinstance(val, (int, float)) or not abs(val) < 2 ** 31 or val != int(val):
+                raise ValueError("crf %s %r is not an integer" % (name, val))
+        it, r, d = int(iterations), int(radius), int(dilation)
+        if it < 0:
+            raise ValueError("crf iterations %r is not an integer >= 0" % (iterations,))
+        if not 1 <= r <= 5:
+            raise ValueError("crf radius %r is outside 1..5" % (radius,))
+        if d < 1 or r * d > 16:
+            raise ValueError("crf dilation %r: at least 1, and radius * dilation at most 16" % (dilation,))
+        ws = {}
+        for name, val in (("w_bilateral", w_bilateral), ("w_spatial", w_spatial)):
+            ws[name] = float(val)
+            if not (ws[name] >= 0.0 and ws[name] < float("inf")):
+                raise ValueError("crf %s %r is not a finite number >= 0" % (name, val))
+        for name, val in (("theta_alpha", theta_alpha), ("theta_beta", theta_beta), ("theta_gamma", theta_gamma)):
+            ws[name] = float(val)
+            if not ws[name] > 0.0:
+                raise ValueError("crf %s %r is not > 0" % (name, val))
+        self.iterations, self.radius, self.dilation = it, r, d
+        for name, val in ws.items():
+            setattr(self, name, val)
+
+    def params(self):
+        return _lib.CrfParams(self.radius, self.dilation, self.iterations, self.w_bilateral, self.w_spatial, self.theta_alpha,
+                              self.theta_beta, self.theta_gamma)
+
+    def __eq__(self, other):
+        return isinstance(other, CrfOptions) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __repr__(self):
+        return "CrfOptions(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+
+_CRF_WS_BYTES = {}
+
+
+def crf_labels(x, image, size, crf, *, probs=False, want_q=False, want_index=False, want_u8=True, label_true=None, hist=None,
+               num_classes=None):
+    """Label maps after `crf.iterations` mean-field steps of the windowed dense CRF (sscg_crf_head).  `x`: fp32 [N,C,H,W] logits,
+    resized to `size` like predict_labels' - or, with probs=True, non-negative scores already at `size` (prob_sum of predict_labels_ms).
+    `image`: the guide, fp32 [N,IC,OH,OW] at `size`, IC <= 4.  Returns (label_u8 uint8 [N,OH,OW] or None, index int64 [N,OH,OW] or None,
+    hist or None, q fp32 [N,C,OH,OW] channels-last or None = Q after the last step); `label_true` / `hist` as in predict_labels.
+    iterations == 0 is predict_labels (logits) / the first maximum of the scores, bit for bit; it has no q."""
+    if not isinstance(crf, CrfOptions):
+        raise TypeError("crf must be a functional.CrfOptions, not %r" % (crf,))
+    _need_hip(x, f32_only=True)
+    _need_hip(image, f32_only=True)
+    if x.dim() != 4 or image.dim() != 4:
+        raise _lib.SscgError("crf_labels: 4-D scores and a 4-D guide image expected")
+    _no_grad_input(x, "crf_labels")
+    _no_grad_input(image, "crf_labels")
+    xs = to_nhwc(x.detach())
+    n, c, h, w = xs.shape
+    oh, ow = int(size[0]), int(size[1])
+    if tuple(image.shape) != (n, image.shape[1], oh, ow) or not 1 <= image.shape[1] <= 4:
+        raise _lib.SscgError("crf_labels: the guide image must be [N, 1..4, OH, OW] at the output size, got %s" % (tuple(image.shape),))
+    if probs and (h, w) != (oh, ow):
+        raise _lib.SscgError("crf_labels: scores (probs=True) must already have the output size")
+    if num_classes is not None and int(num_classes) != c:
+        raise _lib.SscgError("crf_labels: %d classes asked for, the scores have %d channels" % (num_classes, c))
+    if hist is not None and label_true is None:
+        raise _lib.SscgError("crf_labels: a confusion matrix needs label_true")
+    if not (want_q or want_index or want_u8 or label_true is not None):
+        raise _lib.SscgError("crf_labels: no output asked for")
+    if want_q and crf.iterations == 0:
+        raise _lib.SscgError("crf_labels: Q is the result of a mean-field step, iterations == 0 has none")
+    guide = to_nhwc(image.detach())
+    lt = None
+    if label_true is not None:
+        if not label_true.is_cuda:
+            raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % label_true.device)
+        lt = label_true.to(torch.int64).contiguous()
+        if lt.numel() != n * oh * ow:
+            raise _lib.SscgError("crf_labels: label_true must have N*OH*OW elements")
+        if hist is None:
+            hist = torch.empty((c, c), dtype=torch.int64, device=xs.device)
+            check(lib.sscg_fill(hist.data_ptr(), 2 * hist.numel(), 0.0, _stream()), "sscg_fill")   # 2 fp32 zeros per int64 zero
+        elif not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == c * c):
+            raise _lib.SscgError("crf_labels: hist must be a contiguous int64 [C, C] tensor on the device")
+    u8 = torch.empty((n, oh, ow), dtype=torch.uint8, device=xs.device) if want_u8 else None
+    idx = torch.empty((n, oh, ow), dtype=torch.int64, device=xs.device) if want_index else None
+    q = empty_nhwc(n, c, oh, ow, xs.device) if want_q else None
+    key = (n, c, oh, ow, crf.iterations)
+    if key not in _CRF_WS_BYTES:
+        _CRF_WS_BYTES[key] = lib.sscg_crf_workspace(*key)
+    ws = _WS.get(_CRF_WS_BYTES[key], xs.device)
+    check(lib.sscg_crf_head(xs.data_ptr(), _lib.CRF_PROBS if probs else _lib.CRF_LOGITS, n, h, w, c, oh, ow, guide.data_ptr(),
+                            int(guide.shape[1]), C.byref(crf.params()), _ptr(q), _ptr(idx), _ptr(u8), _ptr(lt), _ptr(hist), ws.data_ptr(),
+                            ws.numel(), _stream()), "sscg_crf_head")
+    return u8, idx, hist, q
+
+
 # The per-epoch image panels (sscg_panel_labels / sscg_panel_range / sscg_panel_grid): the grids train() hands to the image writer,
 # built on the device.  SSCG_FUSE_PANELS=0 keeps model.panels() on the chain of separate passes and the host (an A/B aid: the bytes
 # are the same).

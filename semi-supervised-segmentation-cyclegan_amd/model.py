@@ -651,11 +651,12 @@ class semisuper_cycleGAN(_WeightedCE):
     # ------------------------------------------------------------------------------------------ evaluation (model.py:555-574)
     @_with_ema("g_optimizer")
     @torch.no_grad()
-    def evaluate(self, val_loader, first_batch=None, tta=None):
+    def evaluate(self, val_loader, first_batch=None, tta=None, crf=None):
         """`first_batch`: a list that receives the first batch's (val_img, val_gt) as they went through the network - the batch the
         panels are drawn from, without a second iterator on the loader.  `tta`: a view list of utils.parse_tta - Gsi runs once per
         view on the resized / mirrored batch and the views' probabilities are summed (multi-scale / mirrored inference; the
-        reference evaluates one view only).  None = the single forward of the reference."""
+        reference evaluates one view only).  None = the single forward of the reference.  `crf`: a F.CrfOptions (utils.parse_crf) - the
+        label is taken after its mean-field steps on the (summed) probabilities (the reference has no CRF); None = the plain first maximum."""
         self.Gsi.eval()
         self.Gis.eval()
         self.running_metrics_val.reset()
@@ -663,6 +664,11 @@ class semisuper_cycleGAN(_WeightedCE):
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
                 first_batch.extend((val_img, val_gt))
+            if crf is not None:             # the windowed dense CRF between the softmax and the first maximum, guided by the batch
+                scores, probs = utils.crf_scores(self.Gsi, val_img, self.crop, tta)
+                self.running_metrics_val.update_logits_crf(val_gt.squeeze(1), scores, utils.crf_guide(val_img, self.crop), self.crop, crf,
+                                                           probs=probs)
+                continue
             if tta:
                 self.running_metrics_val.update_logits_ms(val_gt.squeeze(1), *utils.tta_logits(self.Gsi, val_img, tta), self.crop)
                 continue
@@ -750,7 +756,8 @@ class semisuper_cycleGAN(_WeightedCE):
                 want_panels = rank0 and (writer is not None or panel_dir is not None)
                 first = [] if want_panels else None
                 with self.g_optimizer.ema_weights():    # --ema_decay: the epoch's mIoU and panels are the averaged weights' (one swap)
-                    miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
+                    miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')),
+                                                    crf=utils.parse_crf(getattr(args, 'crf', '')))
                     if rank0:
                         print("The mIoU for the epoch is: ", miou)
                         if self.dice_options is not None:
@@ -825,17 +832,23 @@ class supervised_model(_WeightedCE):
 
     @_with_ema("gsi_optimizer")
     @torch.no_grad()
-    def evaluate(self, val_loader, first_batch=None, tta=None):
+    def evaluate(self, val_loader, first_batch=None, tta=None, crf=None):
         """model.py:145-162.  The reference interpolates to a hard-coded 512x512 (`interp_val`, model.py:63,152), which only
         works for a 512x512 crop; the crop size is used here, as the semi-supervised driver does.
         `first_batch`: a list that receives the first batch's (val_img, val_gt) on the device (the batch of the panels).
-        `tta`: a view list of utils.parse_tta, as in semisuper_cycleGAN.evaluate; None = the single forward of the reference."""
+        `tta`: a view list of utils.parse_tta, `crf`: a F.CrfOptions, both as in semisuper_cycleGAN.evaluate; None = the reference's
+        single forward and plain first maximum."""
         self.Gsi.eval()
         self.running_metrics_val.reset()
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
                 first_batch.extend((val_img, val_gt))
+            if crf is not None:             # the windowed dense CRF between the softmax and the first maximum, guided by the batch
+                scores, probs = utils.crf_scores(self.Gsi, val_img, self.crop, tta)
+                self.running_metrics_val.update_logits_crf(val_gt.squeeze(1), scores, utils.crf_guide(val_img, self.crop), self.crop, crf,
+                                                           probs=probs)
+                continue
             if tta:
                 self.running_metrics_val.update_logits_ms(val_gt.squeeze(1), *utils.tta_logits(self.Gsi, val_img, tta), self.crop)
                 continue
@@ -895,7 +908,8 @@ class supervised_model(_WeightedCE):
             if val_loader is not None:                                              # model.py:145-197
                 first = [] if rank == 0 and (writer is not None or panel_dir is not None) else None
                 with self.gsi_optimizer.ema_weights():  # --ema_decay: the epoch's mIoU and panels are the averaged weights' (one swap)
-                    miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')))
+                    miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')),
+                                                    crf=utils.parse_crf(getattr(args, 'crf', '')))
                     if rank == 0:
                         print("The mIoU for the epoch is: ", miou)
                         if self.dice_options is not None:

@@ -182,6 +182,12 @@ class runningScore(object):
         self._device_hist = F.predict_labels_ms(logits_list, flips, size, want_u8=False, label_true=label_trues,
                                                 hist=self._device_hist, num_classes=self.n_classes)[2]
 
+    def update_logits_crf(self, label_trues, logits_or_probs, image, size, crf, probs=False):
+        """update_logits() with the windowed dense CRF (F.crf_labels) between the softmax and the first maximum: `image` guides it;
+        probs=True: the scores are the summed probabilities of several views (F.predict_labels_ms(want_prob=True)) at `size`."""
+        self._device_hist = F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=False, label_true=label_trues,
+                                         hist=self._device_hist, num_classes=self.n_classes)[2]
+
     def _fold_device(self):
         if self._device_hist is not None:
             self.confusion_matrix += self._device_hist.cpu().numpy().astype(np.float64)
@@ -284,6 +290,51 @@ def tta_logits(net, images, views):
     """One forward of `net` per view on F.resize_flip of the batch: (logit maps, flip flags) for F.predict_labels_ms."""
     h, w = images.shape[2:]
     return [net(F.resize_flip(images, tta_size(h, w, scale), flip)) for scale, flip in views], [flip for _, flip in views]
+
+
+_CRF_KEYS = {"iters": "iterations", "radius": "radius", "dilation": "dilation", "wb": "w_bilateral", "ws": "w_spatial",
+             "alpha": "theta_alpha", "beta": "theta_beta", "gamma": "theta_gamma"}
+
+
+def parse_crf(spec):
+    """`--crf`: the windowed dense CRF behind the evaluation's softmax.  "on" = F.CrfOptions() (untuned defaults); else a comma list of
+    key=value over iters, radius, dilation, wb, ws, alpha, beta, gamma, e.g. "iters=5,radius=3,dilation=2,wb=4,ws=3,alpha=8,beta=0.5,
+    gamma=3" - keys left out keep their defaults.  Returns a F.CrfOptions, None for "" / None.  Raises ValueError naming the bad token."""
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    if spec == "on":
+        return F.CrfOptions()
+    kw = {}
+    for tok in spec.split(","):
+        key, sep, val = tok.strip().partition("=")
+        if not sep or key not in _CRF_KEYS or _CRF_KEYS[key] in kw:
+            raise ValueError("--crf: %r is not one key=value over %s" % (tok, ", ".join(_CRF_KEYS)))
+        try:
+            kw[_CRF_KEYS[key]] = int(val) if key in ("iters", "radius", "dilation") else float(val)
+        except ValueError:
+            raise ValueError("--crf: %r is not a number%s" % (tok, " (an integer)" if key in ("iters", "radius", "dilation") else ""))
+        try:
+            F.CrfOptions(**dict({"radius": 1, "dilation": 1}, **{_CRF_KEYS[key]: kw[_CRF_KEYS[key]]}))      # the value's own range: the error names the token
+        except ValueError as e:
+            raise ValueError("--crf: %r: %s" % (tok, e))
+    try:
+        return F.CrfOptions(**kw)
+    except ValueError as e:         # what only the combination breaks: radius * dilation
+        raise ValueError("--crf: %r: %s" % (spec, e))
+
+
+def crf_guide(images, size):
+    """The CRF's guide image: the batch as the network sees it (normalised), resized to `size` when it has another."""
+    return images if tuple(images.shape[2:]) == (int(size[0]), int(size[1])) else F.upsample_bilinear(images, size)
+
+
+def crf_scores(net, images, size, tta=None):
+    """What F.crf_labels starts from, as (scores, probs): the logits of `net`'s single forward (probs=False), or with `tta` (a view list
+    of parse_tta) the summed probabilities of the views at `size` - F.predict_labels_ms asked for nothing else (probs=True)."""
+    if tta:
+        return F.predict_labels_ms(*tta_logits(net, images, tta), size, want_prob=True, want_u8=False)[3], True
+    return net(images), False
 
 
 CE_INVLOG_K = 1.02      # ENet's constant in w = 1 / ln(k + f)

@@ -39,12 +39,17 @@ def test(args, test_loader=None):
     out = os.path.join(args.results_dir, 'unsupervised' if semi else 'supervised')
     os.makedirs(out, exist_ok=True)
     tta = utils.parse_tta(getattr(args, 'tta', ''))
+    crf = utils.parse_crf(getattr(args, 'crf', ''))
     Gsi.eval()
     with torch.no_grad():
         for i, (image_test, image_name) in enumerate(test_loader):
             image_test = utils.cuda(image_test, args.gpu_ids)
             logits = None if tta else Gsi(image_test)
-            if tta:             # --tta: Gsi once per view, the views fused into one uint8 map at the images' size
+            if crf is not None:     # --crf: the windowed dense CRF, guided by the images, at the size the plain path predicts at
+                size = image_test.shape[2:] if tta else logits.shape[2:]
+                scores, probs = utils.crf_scores(Gsi, image_test, size, tta) if tta else (logits, False)
+                prediction = F.crf_labels(scores, utils.crf_guide(image_test, size), size, crf, probs=probs)[0].cpu().numpy()
+            elif tta:           # --tta: Gsi once per view, the views fused into one uint8 map at the images' size
                 prediction = F.predict_labels_ms(*utils.tta_logits(Gsi, image_test, tta), image_test.shape[2:])[0].cpu().numpy()
             elif F.FUSE_PREDICT[0]:          # softmax -> argmax on the net's own output: one launch, a uint8 map (identity resize)
                 prediction = F.predict_labels(logits, logits.shape[2:])[0].cpu().numpy()

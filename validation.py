@@ -57,13 +57,19 @@ def validation(args, val_loader=None):
     tta = utils.parse_tta(getattr(args, 'tta', ''))
     # --tta: Gsi once per view of the images, the views fused into one uint8 map (F.FUSE_TTA: in one launch)
     labels_ms = lambda x: F.predict_labels_ms(*utils.tta_logits(Gsi, x, tta), size)[0].cpu().numpy()
+    crf = utils.parse_crf(getattr(args, 'crf', ''))
+    # --crf: the windowed dense CRF, guided by the images, on Gsi's logits (with --tta: on the views' summed probabilities)
+    labels_crf = lambda x, scores, probs: F.crf_labels(scores, utils.crf_guide(x, size), size, crf, probs=probs)[0].cpu().numpy()
     img = lambda x: F.act_fwd(F.to_nhwc(F.upsample_bilinear(Gis(x), size)), F.ACT_TANH)   # Gis -> interp -> Tanh
     Gsi.eval()
     with torch.no_grad():
         for i, (image_test, real_segmentation, image_name) in enumerate(val_loader):
             image_test, real_segmentation = utils.cuda([image_test, real_segmentation], args.gpu_ids)
             logits = Gsi(image_test) if semi or not tta else None     # the image-regeneration branches stay single-view
-            prediction = labels_ms(image_test) if tta else labels(logits)
+            if crf is not None:
+                prediction = labels_crf(image_test, *(utils.crf_scores(Gsi, image_test, size, tta) if tta else (logits, False)))
+            else:
+                prediction = labels_ms(image_test) if tta else labels(logits)
             if not semi:
                 out = _mk(args.validation_dir, 'supervised')
                 for j in range(prediction.shape[0]):
