@@ -337,6 +337,27 @@ int sscg_label_lut(const uint8_t* src, int64_t* dst, int64_t n, const int64_t* l
 int sscg_augment_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H, int W, int C,
                     int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill, int label_fill,
                     void* stream);
+/* sscg_augment_u8 with a per-sample colour map between the warp and the normalisation (brightness, contrast, saturation, hue, grey,
+ * composed on the host: data_utils/augmentations.py).  colour fp32 [N][21] on the device = (A 3x3 row-major, B 3x3 row-major, b[3])
+ * of every sample; the other arguments, the warp, v and t[c] = ((float)v[c] * 2^-16) / 255, the labels and the errors are
+ * sscg_augment_u8's.  Definition, every fp32 product and sum rounded to nearest on its own (no fused multiply-add):
+ *   mean:   need_mean != 0:  S[n][c] = the sum of the integer v[c] over the sample's OH*OW output pixels, fill pixels included
+ *           (int64: exact, and the same in every run);  mu[c] = (float)((double)S[n][c] / ((double)(OH*OW) * 16711680.0)), one
+ *           rounding per fp64 operation and one for the narrowing.  need_mean == 0: mu = 0.
+ *   offset: o[c] = ((B[c][0]*mu[0] + B[c][1]*mu[1]) + B[c][2]*mu[2]) + b[c]
+ *   pixel:  u[c] = ((A[c][0]*t[0] + A[c][1]*t[1]) + A[c][2]*t[2]) + o[c];  u[c] = min(max(u[c], 0), 1);
+ *           out = (u[c] - mean[c]) / stdev[c]
+ *   C == 1: o = B[0][0]*mu[0] + b[0], u = A[0][0]*t[0] + o (only these three entries of the 21 are read).
+ * With A = I, B = 0, b = 0 every step is exact: the outputs equal sscg_augment_u8's bit for bit.  Table entries are finite.
+ * One launch; with need_mean two more in front of it, on the same stream: ws is cleared and a sum pass warps the batch once more
+ * for S (uint8 gathers, one 64-bit integer atomic per block and channel).  ws: sscg_augment_colour_workspace(N) bytes (int64
+ * [N][3]), 8-byte aligned; may be NULL without need_mean.  Errors before any HIP call: SSCG_ERR_BAD_ARG (sscg_augment_u8's cases, a
+ * NULL colour, need_mean with a NULL or misaligned ws), SSCG_ERR_UNSUPPORTED (sscg_augment_u8's size limits, C of 2 or 4, need_mean
+ * with N above 65535). */
+size_t sscg_augment_colour_workspace(int N);
+int sscg_augment_colour_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H, int W,
+                           int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill,
+                           int label_fill, const float* colour, int need_mean, void* ws, void* stream);
 
 /* ------------------------------------------------------------------ losses (K10, K11), mean reduction
  * Each forward writes one fp32 scalar to `loss` (device).  Each backward takes the upstream gradient as

@@ -75,8 +75,11 @@ def get_args(argv=None):
     parser.add_argument("--vgg_weights", type=str, default=None,
                         help="torchvision VGG16 state dict for --variants perceptual (the reference downloads vgg16(pretrained=True))")
     parser.add_argument("--augment", type=str, default="",
-                        help="comma list of geometric augmentations of the labelled and unlabelled training batches, applied in one "
-                             "launch inside the device-side batch finish: hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop (default: none)")
+                        help="comma list of geometric and colour augmentations of the labelled and unlabelled training batches, applied "
+                             "in one launch inside the device-side batch finish: hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop; "
+                             "brightness=<x>, contrast=<x>, saturation=<x> (factor in max(0,1-x)..1+x), hue=<x> (0..0.5 of a turn), "
+                             "gray=<p> - colour behind geometry, each in the order written, clamped to [0,1] once at the end; "
+                             "contrast adds a sum pass for the image mean (default: none)")
     parser.add_argument("--panels", type=str, default=None, metavar="DIR",
                         help="write the reference's per-epoch image panels (model.py:576-638) to DIR/epoch%%03d_<n>.png, and to a "
                              "tensorboardX.SummaryWriter(DIR) when that module is installed (default: off)")

@@ -2,6 +2,9 @@
 // tensors the step consumes, warped per sample by an integer (Q16) affine map.  One launch replaces image_u8_to_f32_kernel +
 // label_lut_kernel (pointwise.hip); with identity matrices the outputs equal theirs bit for bit.  The arithmetic is stated in
 // include/sscg.h (sscg_augment_u8): integers up to the last two fp32 divisions, so a host restatement agrees exactly.
+// sscg_augment_colour_u8 is the same launch with a per-sample colour table between the warp and the normalisation (COLOUR
+// instantiations of the same kernel body), in front of it - only when the table uses the image mean - a pass that sums the warped
+// integer pixels of every sample.
 #include "common.h"
 #include "sscg_internal.h"
 
@@ -29,32 +32,91 @@ __device__ __forceinline__ aug_mat aug_load_mat(const int32_t* __restrict__ mats
     return a;
 }
 
+// The colour table of one sample as the apply pass holds it: A row-major and o = B.mu + b, which no pixel changes.  One-channel images
+// are scalar: [0][0] and [0] of the [N][21] table.
+template <int C> struct aug_col { float A[C * C]; float o[C]; };
+
+// (m0*x0 + m1*x1) + m2*x2 + last, every product and sum rounded on its own.  hip's __fmul_rn / __fadd_rn are a plain * and + once
+// inlined and would fuse under the default -ffp-contract, so the expression is written here with contraction switched off.
+template <int C>
+__device__ __forceinline__ float aug_row(const float* m, const float* x, float last) {
+#pragma clang fp contract(off)
+    float s = m[0] * x[0];
+    if constexpr (C == 3) {
+        s = s + m[1] * x[1];
+        s = s + m[2] * x[2];
+    }
+    return s + last;
+}
+
+// `sums` = null: no mean (mu = 0)
+template <int C>
+__device__ __forceinline__ aug_col<C> aug_load_col(const float* __restrict__ colour, const int64_t* __restrict__ sums, int n, double denom) {
+    const float* t = colour + (size_t)n * 21;
+    float mu[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) mu[c] = sums ? (float)__ddiv_rn((double)sums[(size_t)n * 3 + c], denom) : 0.f;
+    aug_col<C> k;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+#pragma unroll
+        for (int j = 0; j < C; ++j) k.A[c * C + j] = t[c * 3 + j];
+        k.o[c] = aug_row<C>(t + 9 + c * 3, mu, t[18 + c]);
+    }
+    return k;
+}
+
+// the four taps of output pixel (n, oy, ox) at Q16 source coordinates (sx, sy): 8-bit weights, in-range flags, the upper-left address
+template <int C>
+struct aug_taps {
+    int fx, fy;
+    bool inx0, inx1, iny0, iny1;
+    const uint8_t *p00, *p10;
+
+    __device__ __forceinline__ aug_taps(const uint8_t* __restrict__ img, const aug_geom& g, size_t plane, int64_t sx, int64_t sy) {
+        const int64_t x0 = sx >> 16, y0 = sy >> 16;
+        fx = (int)(sx & 0xFFFF) >> 8, fy = (int)(sy & 0xFFFF) >> 8;
+        // a tap whose weight is zero is never read: its product is an exact 0 whatever the byte
+        inx0 = (uint64_t)x0 < (uint64_t)g.W, inx1 = fx != 0 && (uint64_t)(x0 + 1) < (uint64_t)g.W;
+        iny0 = (uint64_t)y0 < (uint64_t)g.H, iny1 = fy != 0 && (uint64_t)(y0 + 1) < (uint64_t)g.H;
+        p00 = img + (plane + (size_t)(y0 * g.W + x0)) * C;                  // dereferenced only under its in-range flags
+        p10 = p00 + (size_t)g.W * C;
+    }
+    // the integer value of channel c
+    __device__ __forceinline__ int value(int c, int image_fill) const {
+        const int v00 = (iny0 && inx0) ? p00[c] : image_fill;
+        const int v01 = (iny0 && inx1) ? p00[C + c] : image_fill;
+        const int v10 = (iny1 && inx0) ? p10[c] : image_fill;
+        const int v11 = (iny1 && inx1) ? p10[C + c] : image_fill;
+        const int top = v00 * (256 - fx) + v01 * fx;
+        const int bot = v10 * (256 - fx) + v11 * fx;
+        return top * (256 - fy) + bot * fy;                                 // < 2^24: exact in fp32
+    }
+};
+
 // one output pixel (n, oy, ox): C normalised channels into out[], the raw source label id as the return value (LABEL only)
-template <int C, bool LABEL>
-__device__ __forceinline__ int aug_pixel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ gt, const aug_mat& a, const aug_geom& g,
-                                         int n, int oy, int ox, const float* mean, const float* stdev, float* out) {
+template <int C, bool LABEL, bool COLOUR>
+__device__ __forceinline__ int aug_pixel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ gt, const aug_mat& a, const aug_col<C>& k,
+                                         const aug_geom& g, int n, int oy, int ox, const float* mean, const float* stdev, float* out) {
     const int64_t sx = (int64_t)a.m[0] * ox + (int64_t)a.m[1] * oy + a.m[2];
     const int64_t sy = (int64_t)a.m[3] * ox + (int64_t)a.m[4] * oy + a.m[5];
     const size_t plane = (size_t)n * g.H * g.W;
-    // ---- image: four taps, 8-bit weights
-    const int64_t x0 = sx >> 16, y0 = sy >> 16;
-    const int fx = (int)(sx & 0xFFFF) >> 8, fy = (int)(sy & 0xFFFF) >> 8;
-    // a tap whose weight is zero is never read: its product is an exact 0 whatever the byte
-    const bool inx0 = (uint64_t)x0 < (uint64_t)g.W, inx1 = fx != 0 && (uint64_t)(x0 + 1) < (uint64_t)g.W;
-    const bool iny0 = (uint64_t)y0 < (uint64_t)g.H, iny1 = fy != 0 && (uint64_t)(y0 + 1) < (uint64_t)g.H;
-    const uint8_t* p00 = img + (plane + (size_t)(y0 * g.W + x0)) * C;      // dereferenced only under its in-range flags
-    const uint8_t* p10 = p00 + (size_t)g.W * C;
+    // ---- image
+    const aug_taps<C> taps(img, g, plane, sx, sy);
+    float tc[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        const int v00 = (iny0 && inx0) ? p00[c] : g.image_fill;
-        const int v01 = (iny0 && inx1) ? p00[C + c] : g.image_fill;
-        const int v10 = (iny1 && inx0) ? p10[c] : g.image_fill;
-        const int v11 = (iny1 && inx1) ? p10[C + c] : g.image_fill;
-        const int top = v00 * (256 - fx) + v01 * fx;
-        const int bot = v10 * (256 - fx) + v11 * fx;
-        const int v = top * (256 - fy) + bot * fy;                          // < 2^24: exact in fp32
+        const int v = taps.value(c, g.image_fill);
         const float t = __fdiv_rn(__fmul_rn((float)v, 0x1p-16f), 255.0f);
-        out[c] = __fdiv_rn(__fsub_rn(t, mean[c]), stdev[c]);
+        if constexpr (COLOUR) tc[c] = t;
+        else out[c] = __fdiv_rn(__fsub_rn(t, mean[c]), stdev[c]);
+    }
+    if constexpr (COLOUR) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float u = fminf(fmaxf(aug_row<C>(k.A + c * C, tc, k.o[c]), 0.f), 1.f);
+            out[c] = __fdiv_rn(__fsub_rn(u, mean[c]), stdev[c]);
+        }
     }
     // ---- label: nearest source index
     int id = 0;
@@ -66,14 +128,31 @@ __device__ __forceinline__ int aug_pixel(const uint8_t* __restrict__ img, const 
     return id;
 }
 
+// what a colour launch adds to the arguments
+struct aug_colour_args {
+    const float* table;      // [N][21]
+    const int64_t* sums;     // [N][3] from the sum pass, or null = no mean
+};
+
 // Every thread owns four consecutive pixels of the flat [N * OH * OW] range (a group may straddle a row or a sample) and stores them
 // as 16-byte vectors: 4 * C floats = C stores, four labels = two stores.  `groups` = 0 sends every pixel down the scalar tail.
-template <int C, bool LABEL>
+// The colour flag is the argument pack: COL is empty - the plain launch, whose arguments and with them whose instruction stream are
+// those it had before the colour instantiations existed - or aug_colour_args, and then the sample's colour table travels with its
+// matrix and is reloaded wherever the matrix is.
+template <int C, bool LABEL, typename... COL>
 __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ gt,
                                                                  const int32_t* __restrict__ mats, float* __restrict__ out_img,
                                                                  int64_t* __restrict__ out_gt, const float* __restrict__ mean,
                                                                  const float* __restrict__ stdev, const int64_t* __restrict__ lut,
-                                                                 aug_geom g, uint32_t total, uint32_t groups) {
+                                                                 aug_geom g, uint32_t total, uint32_t groups, COL... col) {
+    constexpr bool COLOUR = sizeof...(COL) != 0;
+    const float* colour = nullptr;
+    const int64_t* sums = nullptr;
+    if constexpr (COLOUR) {
+        const aug_colour_args ca[] = {col...};
+        colour = ca[0].table;
+        sums = ca[0].sums;
+    }
     __shared__ int64_t t[256];
     if constexpr (LABEL) {
         t[threadIdx.x] = lut[threadIdx.x];
@@ -84,6 +163,8 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
     for (int c = 0; c < C; ++c) { mu[c] = mean[c]; sd[c] = stdev[c]; }
     const uint32_t hw = (uint32_t)g.OH * (uint32_t)g.OW;
     const uint32_t stride = gridDim.x * AUG_THREADS;
+    double denom = 0.0;
+    if constexpr (COLOUR) denom = __dmul_rn((double)hw, 16711680.0);
     for (uint32_t q = blockIdx.x * AUG_THREADS + threadIdx.x; q < groups; q += stride) {
         const uint32_t p0 = q * 4;
         int n = (int)(p0 / hw);
@@ -91,23 +172,26 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
         int oy = (int)(r / (uint32_t)g.OW);
         int ox = (int)(r - (uint32_t)oy * (uint32_t)g.OW);
         aug_mat a = aug_load_mat(mats, n);
+        aug_col<C> k;
+        if constexpr (COLOUR) k = aug_load_col<C>(colour, sums, n, denom);
         float v[4 * C];
         int64_t lab[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int id = aug_pixel<C, LABEL>(img, gt, a, g, n, oy, ox, mu, sd, v + e * C);
+            const int id = aug_pixel<C, LABEL, COLOUR>(img, gt, a, k, g, n, oy, ox, mu, sd, v + e * C);
             if constexpr (LABEL) lab[e] = t[id];
             if (e < 3 && ++ox == g.OW) {
                 ox = 0;
                 if (++oy == g.OH) {                 // the next pixel of the group is in range: p0 + 3 < total
                     oy = 0;
                     a = aug_load_mat(mats, ++n);
+                    if constexpr (COLOUR) k = aug_load_col<C>(colour, sums, n, denom);
                 }
             }
         }
         f32x4* o = reinterpret_cast<f32x4*>(out_img + (size_t)p0 * C);
 #pragma unroll
-        for (int k = 0; k < C; ++k) o[k] = f32x4{v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
+        for (int k4 = 0; k4 < C; ++k4) o[k4] = f32x4{v[4 * k4], v[4 * k4 + 1], v[4 * k4 + 2], v[4 * k4 + 3]};
         if constexpr (LABEL) {
             i64x2* ol = reinterpret_cast<i64x2*>(out_gt + p0);
             ol[0] = i64x2{lab[0], lab[1]};
@@ -121,11 +205,62 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
         const int oy = (int)(r / (uint32_t)g.OW);
         const int ox = (int)(r - (uint32_t)oy * (uint32_t)g.OW);
         const aug_mat a = aug_load_mat(mats, n);
+        aug_col<C> k;
+        if constexpr (COLOUR) k = aug_load_col<C>(colour, sums, n, denom);
         float v[C];
-        const int id = aug_pixel<C, LABEL>(img, gt, a, g, n, oy, ox, mu, sd, v);
+        const int id = aug_pixel<C, LABEL, COLOUR>(img, gt, a, k, g, n, oy, ox, mu, sd, v);
 #pragma unroll
         for (int c = 0; c < C; ++c) out_img[(size_t)p * C + c] = v[c];
         if constexpr (LABEL) out_gt[p] = t[id];
+    }
+}
+
+// ---- the sum pass of the image mean: sums[n][c] += the integer values v[c] of the sample's OH * OW warped pixels.  blockIdx.y is the
+// sample, so a block never straddles two; a block covers AUG_THREADS consecutive pixels per round of its loop and the grid is sized for
+// AUG_SUM_ROUNDS rounds.  Wave sum, the block's four waves through LDS, one 64-bit integer atomic per channel and block: integer
+// sums do not depend on the order, so the result is exact and the same in every run.
+constexpr int AUG_SUM_ROUNDS = 4;
+constexpr int AUG_SUM_MAX_BLOCKS = 2048;      // 8 per CU: the pass is a latency-bound gather in ~32 VGPRs, so every wave slot is used
+
+__global__ __launch_bounds__(AUG_THREADS) void augment_zero_kernel(int64_t* __restrict__ sums, int n) {
+    for (int i = blockIdx.x * AUG_THREADS + threadIdx.x; i < n; i += gridDim.x * AUG_THREADS) sums[i] = 0;
+}
+
+template <int C>
+__global__ __launch_bounds__(AUG_THREADS) void augment_sum_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ mats, aug_geom g,
+                                                                  int64_t* __restrict__ sums) {
+    __shared__ int64_t part[AUG_THREADS / 64][C];
+    const int n = blockIdx.y;
+    const aug_mat a = aug_load_mat(mats, n);
+    const size_t plane = (size_t)n * g.H * g.W;
+    const uint32_t hw = (uint32_t)g.OH * (uint32_t)g.OW;
+    int64_t s[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) s[c] = 0;
+    for (uint32_t p = blockIdx.x * AUG_THREADS + threadIdx.x; p < hw; p += gridDim.x * AUG_THREADS) {
+        const int oy = (int)(p / (uint32_t)g.OW);
+        const int ox = (int)(p - (uint32_t)oy * (uint32_t)g.OW);
+        const int64_t sx = (int64_t)a.m[0] * ox + (int64_t)a.m[1] * oy + a.m[2];
+        const int64_t sy = (int64_t)a.m[3] * ox + (int64_t)a.m[4] * oy + a.m[5];
+        const aug_taps<C> taps(img, g, plane, sx, sy);
+#pragma unroll
+        for (int c = 0; c < C; ++c) s[c] += taps.value(c, g.image_fill);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[c] += __shfl_xor((long long)s[c], o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) part[threadIdx.x >> 6][c] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < C) {
+        int64_t tot = 0;
+#pragma unroll
+        for (int w = 0; w < AUG_THREADS / 64; ++w) tot += part[w][threadIdx.x];
+        atomicAdd(reinterpret_cast<unsigned long long*>(sums + (size_t)n * 3 + threadIdx.x), (unsigned long long)tot);
     }
 }
 
@@ -141,23 +276,59 @@ void aug_launch(bool label, dim3 grid, hipStream_t st, const uint8_t* img, const
                            total, groups);
 }
 
-}  // namespace
+template <int C>
+void aug_launch_colour(bool label, dim3 grid, hipStream_t st, const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img,
+                       int64_t* out_gt, const float* mean, const float* stdev, const int64_t* lut, const aug_geom& g, uint32_t total,
+                       uint32_t groups, const float* colour, int64_t* sums, int N) {
+    if (sums) {
+        const uint32_t hw = (uint32_t)g.OH * (uint32_t)g.OW;
+        const int cap = AUG_SUM_MAX_BLOCKS / N > 0 ? AUG_SUM_MAX_BLOCKS / N : 1;
+        int bx = cdiv((long)hw, (long)AUG_THREADS * AUG_SUM_ROUNDS);
+        if (bx > cap) bx = cap;
+        hipLaunchKernelGGL(augment_zero_kernel, dim3(ew_blocks((size_t)N * 3, 64)), dim3(AUG_THREADS), 0, st, sums, N * 3);
+        hipLaunchKernelGGL(augment_sum_kernel<C>, dim3(bx, N), dim3(AUG_THREADS), 0, st, img, mats, g, sums);
+    }
+    const aug_colour_args ca = {colour, sums};
+    if (label)
+        hipLaunchKernelGGL((augment_u8_kernel<C, true, aug_colour_args>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean, stdev, lut,
+                           g, total, groups, ca);
+    else
+        hipLaunchKernelGGL((augment_u8_kernel<C, false, aug_colour_args>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean, stdev,
+                           lut, g, total, groups, ca);
+}
 
-extern "C" int sscg_augment_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H,
-                               int W, int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill,
-                               int label_fill, void* stream) {
+// the argument rules both entries share; 0 = go on
+int aug_check(const uint8_t* img, const uint8_t* gt, const int32_t* mats, const float* out_img, const int64_t* out_gt, int N, int H, int W,
+              int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill, int label_fill) {
     if (!img || !mats || !out_img || !mean || !stdev) return SSCG_ERR_BAD_ARG;
     if (C < 1 || C > 4 || N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return SSCG_ERR_BAD_ARG;
     if (image_fill < 0 || image_fill > 255 || label_fill < 0 || label_fill > 255) return SSCG_ERR_BAD_ARG;
     if (gt ? (!lut256 || !out_gt) : out_gt != nullptr) return SSCG_ERR_BAD_ARG;
     const int64_t total = (int64_t)N * OH * OW;
     if (total >= ((int64_t)1 << 31) || H > 32767 || W > 32767) return SSCG_ERR_UNSUPPORTED;
+    return SSCG_OK;
+}
+
+// groups of four and the grid of the apply pass
+uint32_t aug_plan(const float* out_img, const int64_t* out_gt, int64_t total, uint32_t* groups) {
     // the 16-byte stores need 16-byte aligned outputs (every group starts a multiple of 16 bytes behind them)
     const bool aligned = (((size_t)out_img | (size_t)out_gt) & 15) == 0;
-    const uint32_t groups = aligned ? (uint32_t)(total / 4) : 0u;
-    const uint32_t work = groups ? groups + (uint32_t)(total - (int64_t)groups * 4 > 0) : (uint32_t)total;
+    *groups = aligned ? (uint32_t)(total / 4) : 0u;
+    const uint32_t work = *groups ? *groups + (uint32_t)(total - (int64_t)*groups * 4 > 0) : (uint32_t)total;
     uint32_t blocks = (work + AUG_THREADS - 1) / AUG_THREADS;
-    if (blocks > AUG_MAX_BLOCKS) blocks = AUG_MAX_BLOCKS;
+    return blocks > AUG_MAX_BLOCKS ? AUG_MAX_BLOCKS : blocks;
+}
+
+}  // namespace
+
+extern "C" int sscg_augment_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H,
+                               int W, int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill,
+                               int label_fill, void* stream) {
+    const int bad = aug_check(img, gt, mats, out_img, out_gt, N, H, W, C, OH, OW, mean, stdev, lut256, image_fill, label_fill);
+    if (bad) return bad;
+    const int64_t total = (int64_t)N * OH * OW;
+    uint32_t groups;
+    const uint32_t blocks = aug_plan(out_img, out_gt, total, &groups);
     const aug_geom g = {H, W, OH, OW, image_fill, label_fill};
     const hipStream_t st = (hipStream_t)stream;
     const bool label = gt != nullptr;
@@ -167,6 +338,32 @@ extern "C" int sscg_augment_u8(const uint8_t* img, const uint8_t* gt, const int3
         case 3: aug_launch<3>(label, dim3(blocks), st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, (uint32_t)total, groups); break;
         default: aug_launch<4>(label, dim3(blocks), st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, (uint32_t)total, groups); break;
     }
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
+extern "C" size_t sscg_augment_colour_workspace(int N) { return N > 0 ? (size_t)N * 3 * sizeof(int64_t) : 0; }
+
+extern "C" int sscg_augment_colour_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N,
+                                      int H, int W, int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256,
+                                      int image_fill, int label_fill, const float* colour, int need_mean, void* ws, void* stream) {
+    const int bad = aug_check(img, gt, mats, out_img, out_gt, N, H, W, C, OH, OW, mean, stdev, lut256, image_fill, label_fill);
+    if (bad == SSCG_ERR_BAD_ARG) return bad;
+    if (!colour || (need_mean && (!ws || ((size_t)ws & 7) != 0))) return SSCG_ERR_BAD_ARG;
+    if (bad) return bad;
+    // the sum pass takes the sample from blockIdx.y
+    if (C == 2 || C == 4 || (need_mean && N > 65535)) return SSCG_ERR_UNSUPPORTED;
+    const int64_t total = (int64_t)N * OH * OW;
+    uint32_t groups;
+    const uint32_t blocks = aug_plan(out_img, out_gt, total, &groups);
+    const aug_geom g = {H, W, OH, OW, image_fill, label_fill};
+    const hipStream_t st = (hipStream_t)stream;
+    const bool label = gt != nullptr;
+    int64_t* sums = need_mean ? reinterpret_cast<int64_t*>(ws) : nullptr;
+    if (C == 1)
+        aug_launch_colour<1>(label, dim3(blocks), st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, (uint32_t)total, groups, colour, sums, N);
+    else
+        aug_launch_colour<3>(label, dim3(blocks), st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, (uint32_t)total, groups, colour, sums, N);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

@@ -14,8 +14,10 @@ Augmentation (`augmentations.py`; the reference has the module and never uses it
 `build_loaders` reading `args.augment` - and only for the 'label' and 'unlabel' sets.  Its ops are affine maps, not pixel
 code: in `device_finish` mode `DeviceLoader(..., augmentation=)` draws one map per sample on the host, uploads the int32
 matrices with the batch and finishes the batch with ONE `sscg_augment_u8` launch (warp + ToTensor + Normalize + label table)
-instead of the two passes above; in host mode the same maps go through PIL as the datasets' `augmentation=`.  Without an
-augmentation nothing changes: the same two launches as before."""
+instead of the two passes above; in host mode the same maps go through PIL as the datasets' `augmentation=`.  Colour items
+(brightness, contrast, saturation, hue, gray) compose into one small table per sample that the same launch applies
+(`sscg_augment_colour_u8`; a contrast item adds a sum pass for the image mean).  Without an augmentation nothing changes: the same
+two launches as before."""
 import numpy as np
 import torch
 from PIL import Image
@@ -179,13 +181,16 @@ class DeviceLoader:
     'test' split.  Batches cross PCIe as uint8 from pinned memory; the float conversion is one HIP launch per batch.
     `augmentation` (an `augmentations.Compose`, default None = nothing changes): every sample is warped by an affine map of its own
     inside the finish - the maps of a batch are drawn on the host from `RandomState(seed)`, in batch order, uploaded with the batch
-    and applied by one `functional.augment_batch` launch that replaces the two passes."""
+    and applied by one `functional.augment_batch` launch that replaces the two passes.  When the augmentation has colour ops, their
+    per-sample table is drawn from a second generator, `RandomState(seed + augmentations.COLOUR_SEED_OFFSET)`, and travels with the
+    maps; the geometric draws of a seed do not depend on it."""
 
     def __init__(self, loader, transformation, device, augmentation=None, seed=0):
         if not transformation.get('device_finish'):
             raise ValueError("DeviceLoader needs get_transformation(..., device_finish=True)")
         self.loader, self.device = loader, device
         self.augmentation, self.rng = augmentation, np.random.RandomState(seed)
+        self.colour_rng = np.random.RandomState(seed + augmentations.COLOUR_SEED_OFFSET)
         self.lut = transformation['lut'].to(device)
         self.mean = torch.tensor(transformation['mean'], dtype=torch.float32, device=device)
         self.std = torch.tensor(transformation['std'], dtype=torch.float32, device=device)
@@ -212,11 +217,15 @@ class DeviceLoader:
 
     def _augmented(self, F, batch):
         aug = self.augmentation
-        b, h, w, _ = batch[0].shape
+        b, h, w, c = batch[0].shape
         mats = self._up(torch.from_numpy(aug.matrices(self.rng, b, w, h)))
         gt = self._up(batch[1]) if len(batch) == 3 else None
+        colour = {}
+        if aug.colour_ops:
+            table, need_mean = aug.colours(self.colour_rng, b, c)
+            colour = {"colour": self._up(torch.from_numpy(table)), "need_mean": need_mean}
         img, gt = F.augment_batch(self._up(batch[0]), gt, mats, aug.out_size or (h, w), self.mean, self.std, self.lut,
-                                  image_fill=aug.image_fill, label_fill=aug.label_fill)
+                                  image_fill=aug.image_fill, label_fill=aug.label_fill, **colour)
         return (img, batch[1]) if gt is None else (img, gt, batch[2])
 
 

@@ -1,4 +1,4 @@
-"""Geometric augmentations as affine maps.  The class names and constructor arguments are those of the reference's
+"""Geometric and colour augmentations as affine maps.  The class names and constructor arguments are those of the reference's
 `data_utils/augmentations.py` (RandomCrop, CenterCrop, RandomRotate, Scale, RandomSizedCrop, RandomSized, Compose, plus
 RandomHorizontallyFlip and RandomScale); the implementation is not: no op touches a pixel.  Every op only answers
 
@@ -18,13 +18,33 @@ back ends:
 The two agree exactly on maps that land on pixel centres (identity, flips, integer crops and pads).  Elsewhere they differ by
 design: the device path is bilinear with 8-bit weights, treats every tap outside the source as the fill colour (PIL extends the
 edge pixel half a pixel outwards) and, like PIL's AFFINE transform, does not antialias when it minifies.  Labels agree wherever the
-nearest source index is not a tie.  There is no photometric jitter here."""
+nearest source index is not a tie.
+
+Colour jitter has the same structure.  Brightness, saturation, hue rotation and random grey are linear maps of RGB and contrast is
+affine in the pixel and the image mean, so every colour op only answers
+
+    colour(rng, channels) -> (M, None)  a linear map of the channels,  or  (None, c)  a contrast factor
+
+and `Compose` folds the colour ops of a pipeline, in the order written and after the geometry, into one state (A, B, b) per sample:
+
+    x = A.v + B.mu + b          v the warped pixel in [0, 1], mu the mean of v over the sample's whole output (fill included)
+
+`Compose.colours(rng, n, channels)` draws a batch of states as the float32 [n, 21] table that sscg_augment_colour_u8 applies inside
+the same launch that warps; `Compose.__call__` applies the same float32 formula in numpy behind the PIL transform.  Not
+torchvision's ColorJitter, by design: values are clamped to [0, 1] once, at the end, not after every op, and the ops apply in the
+order written, not in a random one.  Colour draws come from a generator of their own (`seed + COLOUR_SEED_OFFSET`), so the geometric
+maps of a seed are the same with and without colour items.  One-channel images: the state is scalar (luma = the channel);
+saturation, hue and grey are the identity."""
 import math
 
 import numpy as np
 from PIL import Image
 
 Q16 = 65536
+LUMA = (0.299, 0.587, 0.114)
+YIQ = np.array([[.299, .587, .114], [.596, -.274, -.322], [.211, -.523, .312]], dtype=np.float64)   # NTSC; row 0 is LUMA, rows 1, 2 sum to 0
+YIQ_INV = np.linalg.inv(YIQ)
+COLOUR_SEED_OFFSET = 500
 
 
 def _pair(size):
@@ -165,21 +185,123 @@ class RandomSized:
         return m.dot(m2).dot(m3), out
 
 
+def _luma(channels):
+    return np.array(LUMA if channels == 3 else (1.0,), dtype=np.float64)
+
+
+def _factor(rng, x):
+    return rng.uniform(max(0.0, 1.0 - x), 1.0 + x)
+
+
+class RandomBrightness:
+    """Pixel times a factor uniform in [max(0, 1-x), 1+x]."""
+
+    def __init__(self, x):
+        self.x = float(x)
+
+    def colour(self, rng, channels):
+        return _factor(rng, self.x) * np.eye(channels), None
+
+
+class RandomContrast:
+    """x' = c.x + (1-c).mean_luma(x), c uniform in [max(0, 1-x), 1+x]: the one op that needs the image mean."""
+
+    def __init__(self, x):
+        self.x = float(x)
+
+    def colour(self, rng, channels):
+        return None, _factor(rng, self.x)
+
+
+class RandomSaturation:
+    """Blend with the pixel's luma: f.I + (1-f).1w', f uniform in [max(0, 1-x), 1+x]."""
+
+    def __init__(self, x):
+        self.x = float(x)
+
+    def colour(self, rng, channels):
+        f = _factor(rng, self.x)
+        if channels != 3:
+            return np.eye(channels), None
+        return f * np.eye(3) + (1.0 - f) * np.outer(np.ones(3), _luma(3)), None
+
+
+class RandomHue:
+    """Rotation of the I/Q plane of NTSC YIQ by 2.pi.h, h uniform in [-x, x], 0 <= x <= 0.5: keeps luma and grey pixels."""
+
+    def __init__(self, x):
+        self.x = float(x)
+
+    def colour(self, rng, channels):
+        t = 2.0 * math.pi * rng.uniform(-self.x, self.x)
+        if channels != 3:
+            return np.eye(channels), None
+        co, si = math.cos(t), math.sin(t)
+        R = np.array([[1.0, 0.0, 0.0], [0.0, co, -si], [0.0, si, co]], dtype=np.float64)
+        return YIQ_INV.dot(R).dot(YIQ), None
+
+
+class RandomGrayscale:
+    """With probability p every channel becomes the pixel's luma."""
+
+    def __init__(self, p=0.1):
+        self.p = float(p)
+
+    def colour(self, rng, channels):
+        grey = rng.random_sample() < self.p
+        if channels != 3 or not grey:
+            return np.eye(channels), None
+        return np.outer(np.ones(3), _luma(3)), None
+
+
+def colour_table_row(A, B, b):
+    """One row of the [n, 21] table of sscg_augment_colour_u8: A row-major, B row-major, b, rounded from float64.  A scalar state
+    (one channel) sits at [0][0] and [0]; the rest of the row is the identity state."""
+    k = A.shape[0]
+    fa, fb, fv = np.eye(3), np.zeros((3, 3)), np.zeros(3)
+    fa[:k, :k], fb[:k, :k], fv[:k] = A, B, b
+    return np.concatenate([fa.reshape(-1), fb.reshape(-1), fv]).astype(np.float32)
+
+
+def apply_colour(px, row, need_mean):
+    """The colour stage of sscg_augment_colour_u8 on uint8 pixels [h, w, channels] of a finished warp, in numpy float32 with one
+    rounding per operation: t = px / 255, mu from the integer sum, u = clamp(A.t + (B.mu + b)); -> uint8 rint(255 u)."""
+    h, w, k = px.shape
+    f = np.float32
+    A, B, b = row[:9].reshape(3, 3), row[9:18].reshape(3, 3), row[18:21]
+    t = px.astype(f) / f(255)
+    mu = np.zeros(k, dtype=f)
+    if need_mean:
+        S = px.reshape(-1, k).astype(np.int64).sum(axis=0) * Q16
+        mu = (S.astype(np.float64) / (np.float64(h * w) * np.float64(16711680.0))).astype(f)
+    out = np.empty((h, w, k), dtype=f)
+    for c in range(k):
+        o, u = B[c, 0] * mu[0], A[c, 0] * t[..., 0]
+        for j in range(1, k):
+            o, u = o + B[c, j] * mu[j], u + A[c, j] * t[..., j]
+        out[..., c] = np.minimum(np.maximum(u + (o + b[c]), f(0)), f(1))
+    return np.rint(f(255) * out).astype(np.uint8)
+
+
 class Compose:
     """The product of the ops' maps.  `out_size` = (height, width): a centre crop (or pad) is appended when the ops end elsewhere,
     so every sample of a batch leaves with the same shape.  `image_fill` / `label_fill` (0..255) colour what lies outside the
-    source; the label fill is a raw id (the label transforms behind it see it like any pixel).  `seed` seeds the generator of the
-    host path (`__call__`); the device path is handed its generator by the caller."""
+    source; the label fill is a raw id (the label transforms behind it see it like any pixel).  `seed` seeds the generators of the
+    host path (`__call__`); the device path is handed its generators by the caller.  Geometric ops (those with `.matrix`) and
+    colour ops (those with `.colour`) may be mixed in `ops`: each kind keeps its order, the colour runs after the geometry."""
 
     def __init__(self, ops, out_size=None, image_fill=0, label_fill=0, seed=None):
         self.ops = list(ops)
+        self.geometric_ops = [op for op in self.ops if hasattr(op, "matrix")]
+        self.colour_ops = [op for op in self.ops if hasattr(op, "colour")]
         self.out_size = _pair(out_size) if out_size is not None else None
         self.image_fill, self.label_fill = int(image_fill), int(label_fill)
         self.rng = np.random.RandomState(seed)
+        self.colour_rng = np.random.RandomState(seed + COLOUR_SEED_OFFSET if seed is not None else None)
 
     def matrix(self, rng, w, h):
         M = _affine()
-        for op in self.ops:
+        for op in self.geometric_ops:
             m, (w, h) = op.matrix(rng, w, h)
             M = M.dot(m)
         if self.out_size is not None and (h, w) != self.out_size:
@@ -191,21 +313,55 @@ class Compose:
         """int32 [n, 6]: one drawn map per sample of a batch of (w, h) images, as sscg_augment_u8 reads them."""
         return np.stack([to_q16(self.matrix(rng, w, h)[0]) for _ in range(n)]).astype(np.int32)
 
+    def colour_state(self, rng, channels):
+        """(A, B, b) in float64, [channels, channels] twice and [channels]: the drawn colour ops folded in the order written."""
+        w, one = _luma(channels), np.ones(channels)
+        A, B, b = np.eye(channels), np.zeros((channels, channels)), np.zeros(channels)
+        for op in self.colour_ops:
+            M, c = op.colour(rng, channels)
+            if M is not None:
+                A, B, b = M.dot(A), M.dot(B), M.dot(b)
+            else:
+                A, B, b = c * A, c * B + (1.0 - c) * np.outer(one, w.dot(A + B)), c * b + (1.0 - c) * one * w.dot(b)
+        return A, B, b
+
+    @property
+    def need_mean(self):
+        return any(isinstance(op, RandomContrast) for op in self.colour_ops)
+
+    def colours(self, rng, n, channels):
+        """(float32 [n, 21], need_mean): one drawn colour state per sample as sscg_augment_colour_u8 reads them; need_mean is true
+        iff an op is a contrast."""
+        return np.stack([colour_table_row(*self.colour_state(rng, channels)) for _ in range(n)]), self.need_mean
+
     def __call__(self, img, mask=None):
         w, h = img.size
         assert mask is None or mask.size == img.size
         M, out = self.matrix(self.rng, w, h)
         coef = tuple(float(v) for v in M[:2].reshape(-1))
-        fill = self.image_fill if len(img.getbands()) == 1 else (self.image_fill,) * len(img.getbands())
+        bands = len(img.getbands())
+        fill = self.image_fill if bands == 1 else (self.image_fill,) * bands
         img = img.transform(out, Image.AFFINE, coef, Image.BILINEAR, fillcolor=fill)
+        if self.colour_ops:
+            if bands not in (1, 3) or img.mode not in ("L", "RGB"):
+                raise ValueError("colour augmentation takes 8-bit images of one or three channels, given mode %r" % img.mode)
+            row = colour_table_row(*self.colour_state(self.colour_rng, bands))
+            px = apply_colour(np.asarray(img).reshape(out[1], out[0], bands), row, self.need_mean)
+            img = Image.fromarray(px if bands == 3 else px[:, :, 0])
         if mask is None:
             return img
         return img, mask.transform(out, Image.AFFINE, coef, Image.NEAREST, fillcolor=self.label_fill)
 
 
+COLOUR_ITEMS = {"brightness": RandomBrightness, "contrast": RandomContrast, "saturation": RandomSaturation, "hue": RandomHue,
+                "gray": RandomGrayscale}
+
+
 def from_spec(spec, size, image_fill=0, label_fill=0, out_size=None, seed=None):
     """The augmentation a `--augment` value names, or None for an empty one: a comma list of `hflip`, `rotate=<deg>`,
-    `scale=<lo>:<hi>` and `sizedcrop` (RandomSizedCrop to `size` = (height, width)), applied in the order written."""
+    `scale=<lo>:<hi>` and `sizedcrop` (RandomSizedCrop to `size` = (height, width)), and of the colour items `brightness=<x>`,
+    `contrast=<x>`, `saturation=<x>` (factor in max(0, 1-x)..1+x), `hue=<x>` (0..0.5 of a turn) and `gray=<p>` (a probability) -
+    geometry and colour each applied in the order written, colour behind geometry."""
     ops = []
     for item in (s.strip() for s in (spec or "").split(",")):
         if not item:
@@ -222,6 +378,13 @@ def from_spec(spec, size, image_fill=0, label_fill=0, out_size=None, seed=None):
             ops.append(RandomScale(lo, hi))
         elif key == "sizedcrop" and not val:
             ops.append(RandomSizedCrop(size))
+        elif key in COLOUR_ITEMS and val:
+            x = float(val)
+            top = {"hue": 0.5, "gray": 1.0}.get(key, float("inf"))
+            if not 0.0 <= x <= top:                       # (false for a NaN)
+                raise ValueError("--augment %s=<x> needs 0 <= x%s, given %r" % (key, " <= %g" % top if top < float("inf") else "", item))
+            ops.append(COLOUR_ITEMS[key](x))
         else:
-            raise ValueError("--augment: unknown item %r (hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop)" % item)
+            raise ValueError("--augment: unknown item %r (hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop, brightness=<x>, "
+                             "contrast=<x>, saturation=<x>, hue=<x>, gray=<p>)" % item)
     return Compose(ops, out_size=out_size, image_fill=image_fill, label_fill=label_fill, seed=seed) if ops else None

@@ -1599,11 +1599,14 @@ def label_lut(gt_u8, lut):
     return dst.unsqueeze(1)
 
 
-def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, label_fill=0):
+def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, label_fill=0, colour=None, need_mean=False):
     """Batched affine augmentation fused into the batch finish (sscg_augment_u8, one launch): uint8 [N,H,W,C] pixels, uint8 [N,H,W]
     label ids (or None) and one int32 Q16 map per sample (`mats` [N,6], data_utils.augmentations.to_q16) -> what image_u8_to_f32 and
     label_lut return for the warped batch: fp32 logical [N,C,OH,OW] channels-last, int64 [N,1,OH,OW] (or None).  Outside the source:
-    `image_fill` per tap, the raw id `label_fill` through the table.  Identity maps reproduce the two passes bit for bit."""
+    `image_fill` per tap, the raw id `label_fill` through the table.  Identity maps reproduce the two passes bit for bit.
+    `colour` (fp32 [N,21] on the device, data_utils.augmentations.Compose.colours; C of 1 or 3): the samples' colour maps, applied to
+    the warped pixels inside the same launch (sscg_augment_colour_u8); `need_mean`: the maps use the image mean (a contrast op), which
+    costs a sum pass in front of the launch.  None = the plain entry, as before."""
     if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or img_u8.dim() != 4:
         raise _lib.SscgError("augment_batch: uint8 [N,H,W,C] tensor on the MI355X expected")
     n, h, w, c = img_u8.shape
@@ -1612,15 +1615,22 @@ def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, l
     if gt_u8 is not None and (not gt_u8.is_cuda or gt_u8.dtype != torch.uint8 or tuple(gt_u8.shape) != (n, h, w)
                               or lut is None or lut.dtype != torch.int64 or lut.numel() != 256):
         raise _lib.SscgError("augment_batch: uint8 [N,H,W] labels on the MI355X and an int64 table of 256 entries expected")
+    if colour is not None and (not colour.is_cuda or colour.dtype != torch.float32 or tuple(colour.shape) != (n, 21)):
+        raise _lib.SscgError("augment_batch: fp32 [N,21] colour table on the MI355X expected")
     oh, ow = int(out_size[0]), int(out_size[1])
     src, m = img_u8.contiguous(), mats.contiguous()
     dst = torch.empty((n, oh, ow, c), dtype=torch.float32, device=src.device)
     gsrc = gt_u8.contiguous() if gt_u8 is not None else None
     gdst = torch.empty((n, oh, ow), dtype=torch.int64, device=src.device) if gt_u8 is not None else None
-    check(lib.sscg_augment_u8(src.data_ptr(), gsrc.data_ptr() if gsrc is not None else None, m.data_ptr(), dst.data_ptr(),
-                              gdst.data_ptr() if gdst is not None else None, n, h, w, c, oh, ow, mean.data_ptr(), std.data_ptr(),
-                              lut.data_ptr() if gsrc is not None else None, int(image_fill), int(label_fill), _stream()),
-          "sscg_augment_u8")
+    args = (src.data_ptr(), gsrc.data_ptr() if gsrc is not None else None, m.data_ptr(), dst.data_ptr(),
+            gdst.data_ptr() if gdst is not None else None, n, h, w, c, oh, ow, mean.data_ptr(), std.data_ptr(),
+            lut.data_ptr() if gsrc is not None else None, int(image_fill), int(label_fill))
+    if colour is None:
+        check(lib.sscg_augment_u8(*args, _stream()), "sscg_augment_u8")
+    else:
+        table = colour.contiguous()
+        ws = _WS.get(lib.sscg_augment_colour_workspace(n), src.device) if need_mean else None
+        check(lib.sscg_augment_colour_u8(*args, table.data_ptr(), int(bool(need_mean)), _ptr(ws), _stream()), "sscg_augment_colour_u8")
     return dst.permute(0, 3, 1, 2), (gdst.unsqueeze(1) if gdst is not None else None)
 
 

@@ -4,9 +4,14 @@
   (b) the fused launch with a drawn rotate + scale batch            HIP events
   (c) sscg_image_u8_to_f32 + sscg_label_lut on the same bytes       HIP events   (writes the bytes (a) writes)
   (d) the PIL path (Compose.__call__) over the same batch            host wall time, one process, no workers
+and the colour table of sscg_augment_colour_u8 against the plain launch, all three at the drawn maps of (b), interleaved among themselves:
+  (e) the plain fused launch                                         HIP events
+  (f) the colour launch, table without a contrast (no mean)          HIP events
+  (g) the colour launch with the image mean (clear + sum pass + launch)   HIP events
 Same process, warm-up first, the variants interleaved repetition by repetition, medians reported, with bytes written over kernel time
-beside the device figures.  (a) is compared with (c) bit for bit before anything is timed.
-usage: python tools/augment_bench.py [--reps 30] [--warmup 3] [--configs voc,cityscapes] [--spec rotate=10,scale=0.5:2] [--out FILE]"""
+beside the device figures.  (a) is compared with (c), and the colour launch with the identity table with (e), bit for bit before anything is timed.
+usage: python tools/augment_bench.py [--reps 30] [--warmup 3] [--configs voc,cityscapes] [--spec rotate=10,scale=0.5:2]
+                                     [--colour brightness=0.4,contrast=0.4,saturation=0.4,hue=0.1] [--out FILE]"""
 import argparse
 import importlib
 import os
@@ -52,6 +57,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--configs", default="voc,cityscapes")
     ap.add_argument("--spec", default="rotate=10,scale=0.5:2")
+    ap.add_argument("--colour", default="brightness=0.4,contrast=0.4,saturation=0.4,hue=0.1")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -101,6 +107,31 @@ def main():
             med["(a) fused, identity maps"] / med["(c) image_u8_to_f32 + label_lut"],
             med["(b) fused, drawn maps"] / med["(c) image_u8_to_f32 + label_lut"],
             med["(d) PIL Compose.__call__ per sample (host)"] / med["(b) fused, drawn maps"]))
+        # ---- the colour table, at the same maps
+        ccomp = du.augmentations.from_spec(a.colour, (H, W))
+        table = torch.from_numpy(ccomp.colours(np.random.RandomState(511), B, 3)[0]).to(dev)
+        eye = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1] + [0] * 12, dtype=torch.float32).repeat(B, 1).to(dev)
+        colour = lambda t, m: F.augment_batch(d_img, d_gt, drawn, (H, W), mean, std, lut, label_fill=comp.label_fill, colour=t, need_mean=m)
+        (i0, g0) = fused(drawn)
+        same = all(torch.equal(i0, i) and torch.equal(g0, g) for i, g in (colour(eye, False), colour(eye, True)))
+        lines += ["    colour table %s; the identity table bit-identical to (e): %s" % (a.colour, same)]
+        if not same:
+            sys.exit("\n".join(lines + ["the colour launch with the identity table does not reproduce the plain launch: nothing timed"]))
+        variants = [("(e) fused, drawn maps, plain entry", lambda: fused(drawn)), ("(f) colour table, no mean", lambda: colour(table, False)),
+                    ("(g) colour table + mean (clear, sum pass)", lambda: colour(table, True))]
+        for _ in range(a.warmup):
+            for _, fn in variants:
+                fn()
+        torch.cuda.synchronize()
+        ms = {name: [] for name, _ in variants}
+        for _ in range(a.reps):
+            for name, fn in variants:
+                ms[name].append(timed(fn))
+        for name, _ in variants:
+            lines.append("    " + row(name, ms[name], nbytes))
+        med = {n: statistics.median(v) for n, v in ms.items()}
+        lines.append("    (f) / (e) = %.2f    (g) / (e) = %.2f" % (med["(f) colour table, no mean"] / med["(e) fused, drawn maps, plain entry"],
+                                                               med["(g) colour table + mean (clear, sum pass)"] / med["(e) fused, drawn maps, plain entry"]))
     text = "\n".join(lines)
     print(text)
     if a.out:
