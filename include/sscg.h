@@ -593,6 +593,32 @@ size_t sscg_crf_workspace(int N, int C, int OH, int OW, int iterations);
 int sscg_crf_head(const float* x, int kind, int N, int H, int W, int C, int OH, int OW, const float* img, int IC,
                   const sscg_crf_params* p, float* q_out, int64_t* index, uint8_t* label_u8, const int64_t* label_true, int64_t* hist,
                   void* ws, size_t ws_bytes, void* stream);
+/* ------------------------------------------------------------------ contour scores of the evaluation: the counts behind the Boundary
+ * IoU (Cheng et al., CVPR 2021) and the trimap mIoU of the DeepLab papers, beside the confusion matrix of runningScore (utils.py:357-412,
+ * the call site whose evaluation this extends; the reference has neither score).  Opt-in (`--boundary`), forward only, never launched by
+ * the training step.  (An addition: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.)
+ *
+ * sscg_boundary_counts: label_true int64 [N][H][W] (any values), label_pred uint8 [N][H][W], 1 <= C <= 64, width 1 <= d <= 32 in
+ * pixels of the chessboard metric (the published Boundary IoU erodes d times with a 3x3 element).  With
+ *   t(p) = label_true(p) inside [0, C), else VOID;  r(p) = label_pred(p) - a byte >= C takes part in the comparisons, is counted in
+ *          no bin and indexes no memory;
+ *   Win_d(p) = the (2d+1) x (2d+1) window around p CLIPPED to the image;
+ *   in_t(p) = some q in Win_d(p) has t(q) != t(p) (VOID is a label like any other);  in_r(p) = the same on r;
+ *   out(p) = the unclipped window leaves the image: y < d || y >= H - d || x < d || x >= W - d;
+ *   valid(p) = t(p) != VOID;  E_t = valid & (in_t | out);  E_r = valid & (in_r | out);  band = valid & in_t
+ * (the image border is a contour, as in the published code, which pads with zeros before eroding; alone it puts no pixel into the
+ * trimap band), counts is int64 [3 C + C C] on the device, ACCUMULATED into:
+ *   counts[c]               bt[c]     += #{p : E_t(p), t(p) = c}
+ *   counts[C + c]           bp[c]     += #{p : E_r(p), r(p) = c}
+ *   counts[2 C + c]         bi[c]     += #{p : E_t(p) & E_r(p), t(p) = r(p) = c}
+ *   counts[3 C + C c + k]   tri[c][k] += #{p : band(p), t(p) = c, r(p) = k}
+ * Boundary IoU of class c = bi / (bt + bp - bi); the trimap IoU is the confusion-matrix IoU of tri.  One launch; per-workgroup LDS
+ * bins, then 64-bit integer atomics: exact and independent of scheduling, as sscg_confusion_hist.  The work per pixel grows with d,
+ * not d^2 (a window is uniform iff each of its clipped row segments is uniform with the same value).
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, non-positive sizes, C outside 1..64, d outside 1..32),
+ * SSCG_ERR_UNSUPPORTED (N*H*W >= 2^31). */
+int sscg_boundary_counts(const int64_t* label_true, const uint8_t* label_pred, int N, int H, int W, int C, int d, int64_t* counts,
+                         void* stream);
 /* ------------------------------------------------------------------ per-epoch image panels: the image grids the reference sends to
  * TensorBoard at the end of every epoch (model.py:576-638; supervised_model: model.py:164-186), without the host round trip of
  * full-resolution maps, the per-pixel Python loop of utils.PIL_to_tensor (utils.py:59-94) and make_grid on the host.  Forward only;

@@ -2,7 +2,7 @@
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
---ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -48,6 +48,7 @@ class _Args(Namespace):
     ohem_min_kept = 0
     ohem_min_frac = 0.0625
     crf = ""
+    boundary = ""
 
 
 def get_args(argv=None):
@@ -134,10 +135,20 @@ def get_args(argv=None):
                              "dense CRF guided by the input image: 'on' for the (untuned) defaults, or a comma list of key=value over "
                              "iters, radius, dilation, wb, ws, alpha, beta, gamma (e.g. iters=5,radius=3,dilation=2,wb=4,ws=3,alpha=8,"
                              "beta=0.5,gamma=3); with --tta it runs on the views' summed probabilities (default: off, the plain argmax)")
+    parser.add_argument("--boundary", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="also score the per-epoch evaluation's label maps near object contours: the Boundary IoU (Cheng et al., "
+                             "CVPR 2021) and the trimap mIoU of the DeepLab papers, printed beside the mIoU; 'on' for the published "
+                             "width (0.02 of the image diagonal), d=N for N pixels (1..32), or ratio=F of the diagonal; combines with "
+                             "--tta, --crf and --ema_decay (default: off, region scores only)")
     args = parser.parse_args(argv, namespace=_Args())
     if args.crf.strip():
         try:
             importlib.import_module(PKG + ".utils").parse_crf(args.crf)
+        except ValueError as e:
+            parser.error(str(e))
+    if args.boundary.strip():
+        try:
+            importlib.import_module(PKG + ".utils").parse_boundary(args.boundary)
         except ValueError as e:
             parser.error(str(e))
     if args.ohem_thresh is not None and not 0.0 < args.ohem_thresh <= 1.0:

@@ -1491,6 +1491,71 @@ def crf_labels(x, image, size, crf, *, probs=False, want_q=False, want_index=Fal
     return u8, idx, hist, q
 
 
+# Contour scores of the evaluation (sscg_boundary_counts, include/sscg.h holds the definitions): opt-in (`--boundary`).
+BOUNDARY_MAX_D = 32
+
+
+class BoundaryOptions(object):
+    """The contour width of the Boundary IoU / trimap mIoU: `d` pixels (1..32, chessboard metric) given directly, or `ratio` of the
+    image diagonal (in (0, 1]; the published default 0.02) - one of the two, never both."""
+    __slots__ = ("d", "ratio")
+
+    def __init__(self, d=None, ratio=None):
+        if d is not None and ratio is not None:
+            raise ValueError("boundary: d and ratio are two ways to give one width, got both")
+        if d is not None:
+            if isinstance(d, bool) or not isinstance(d, (int, float)) or d != d or d != int(d) or not 1 <= int(d) <= BOUNDARY_MAX_D:
+                raise ValueError("boundary d %r is not an integer in 1..%d" % (d, BOUNDARY_MAX_D))
+            d = int(d)
+        else:
+            ratio = 0.02 if ratio is None else ratio
+            if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < float(ratio) <= 1.0:
+                raise ValueError("boundary ratio %r is not a number in (0, 1]" % (ratio,))
+            ratio = float(ratio)
+        self.d, self.ratio = d, ratio
+
+    def width(self, h, w):
+        """The width in pixels on an h x w map: d itself, or max(1, int(ratio * diagonal + 0.5)); above 32 is refused."""
+        if self.d is not None:
+            return self.d
+        d = max(1, int(self.ratio * (float(h) * h + float(w) * w) ** 0.5 + 0.5))
+        if d > BOUNDARY_MAX_D:
+            raise ValueError("boundary width d = %d (ratio %g of the diagonal of a %d x %d map) is above %d" % (
+                d, self.ratio, h, w, BOUNDARY_MAX_D))
+        return d
+
+    def __eq__(self, other):
+        return isinstance(other, BoundaryOptions) and (self.d, self.ratio) == (other.d, other.ratio)
+
+    def __repr__(self):
+        return "BoundaryOptions(d=%r, ratio=%r)" % (self.d, self.ratio)
+
+
+def boundary_counts(label_true, label_pred, num_classes, d, counts=None):
+    """The counts behind the Boundary IoU and the trimap mIoU of a batch (sscg_boundary_counts): label_true [N,H,W] (any integer
+    type, values outside [0, C) are void), label_pred [N,H,W] class ids as bytes, width d in 1..32.  Returns `counts`, int64
+    [3 C + C C] on the device = bt | bp | bi | tri, accumulated into (None = a new zeroed one)."""
+    if not (label_true.is_cuda and label_pred.is_cuda):
+        raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % label_true.device)
+    if isinstance(d, bool) or not isinstance(d, int) or not 1 <= d <= BOUNDARY_MAX_D:
+        raise ValueError("boundary_counts: d = %r is not an integer in 1..%d" % (d, BOUNDARY_MAX_D))
+    c = int(num_classes)
+    if label_true.dim() != 3 or tuple(label_true.shape) != tuple(label_pred.shape):
+        raise _lib.SscgError("boundary_counts: two [N, H, W] label maps of one shape expected, got %s and %s" % (
+            tuple(label_true.shape), tuple(label_pred.shape)))
+    lt = label_true.to(torch.int64).contiguous()
+    lp = label_pred.to(torch.uint8).contiguous()
+    nb = 3 * c + c * c
+    if counts is None:
+        counts = torch.empty((nb,), dtype=torch.int64, device=lt.device)
+        check(lib.sscg_fill(counts.data_ptr(), 2 * counts.numel(), 0.0, _stream()), "sscg_fill")   # 2 fp32 zeros per int64 zero
+    elif not (counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == nb):
+        raise _lib.SscgError("boundary_counts: counts must be a contiguous int64 [3 C + C C] tensor on the device")
+    n, h, w = lt.shape
+    check(lib.sscg_boundary_counts(lt.data_ptr(), lp.data_ptr(), n, h, w, c, d, counts.data_ptr(), _stream()), "sscg_boundary_counts")
+    return counts
+
+
 # The per-epoch image panels (sscg_panel_labels / sscg_panel_range / sscg_panel_grid): the grids train() hands to the image writer,
 # built on the device.  SSCG_FUSE_PANELS=0 keeps model.panels() on the chain of separate passes and the host (an A/B aid: the bytes
 # are the same).

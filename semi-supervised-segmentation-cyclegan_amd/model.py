@@ -205,6 +205,15 @@ class _WeightedCE(object):
         if self.dice_options is not None:
             self.eval_dice = running.get_dice()
 
+    def _boundary_scores(self, running):
+        """--boundary: the contour scores of the evaluation that has just run (runningScore.get_boundary_scores), kept in
+        `self.eval_boundary` = {"boundary_iou", "class_boundary_iou", "trimap_iou", "class_trimap_iou"}.  Off: the attribute is absent."""
+        scores = running.get_boundary_scores()
+        if scores is not None:
+            self.eval_boundary = scores
+        elif hasattr(self, "eval_boundary"):
+            del self.eval_boundary
+
     def _ce_device(self):
         ids = getattr(self.args, "gpu_ids", None)
         return torch.device("cuda", int(ids[0])) if ids else torch.device("cpu")
@@ -651,15 +660,18 @@ class semisuper_cycleGAN(_WeightedCE):
     # ------------------------------------------------------------------------------------------ evaluation (model.py:555-574)
     @_with_ema("g_optimizer")
     @torch.no_grad()
-    def evaluate(self, val_loader, first_batch=None, tta=None, crf=None):
+    def evaluate(self, val_loader, first_batch=None, tta=None, crf=None, boundary=None):
         """`first_batch`: a list that receives the first batch's (val_img, val_gt) as they went through the network - the batch the
         panels are drawn from, without a second iterator on the loader.  `tta`: a view list of utils.parse_tta - Gsi runs once per
         view on the resized / mirrored batch and the views' probabilities are summed (multi-scale / mirrored inference; the
         reference evaluates one view only).  None = the single forward of the reference.  `crf`: a F.CrfOptions (utils.parse_crf) - the
-        label is taken after its mean-field steps on the (summed) probabilities (the reference has no CRF); None = the plain first maximum."""
+        label is taken after its mean-field steps on the (summed) probabilities (the reference has no CRF); None = the plain first maximum.
+        `boundary`: a F.BoundaryOptions (utils.parse_boundary) - the Boundary IoU and the trimap mIoU of the same label maps are kept in
+        `self.eval_boundary` (utils.boundary_scores); None = neither is computed, nothing more is launched.  The return value is the same."""
         self.Gsi.eval()
         self.Gis.eval()
         self.running_metrics_val.reset()
+        self.running_metrics_val.set_boundary(boundary)
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
@@ -680,6 +692,7 @@ class semisuper_cycleGAN(_WeightedCE):
             self.running_metrics_val.update_device(val_gt.squeeze(1), F.argmax_index(outputs))   # :566-569 without the host round trip
         score, class_iou = self.running_metrics_val.get_scores()
         self._dice_scores(self.running_metrics_val)
+        self._boundary_scores(self.running_metrics_val)
         self.Gsi.train()
         self.Gis.train()
         return score["Mean IoU : \t"], class_iou
@@ -757,11 +770,14 @@ class semisuper_cycleGAN(_WeightedCE):
                 first = [] if want_panels else None
                 with self.g_optimizer.ema_weights():    # --ema_decay: the epoch's mIoU and panels are the averaged weights' (one swap)
                     miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')),
-                                                    crf=utils.parse_crf(getattr(args, 'crf', '')))
+                                                    crf=utils.parse_crf(getattr(args, 'crf', '')),
+                                                    boundary=utils.parse_boundary(getattr(args, 'boundary', '')))
                     if rank0:
                         print("The mIoU for the epoch is: ", miou)
                         if self.dice_options is not None:
                             print("The mean Dice for the epoch is: ", self.eval_dice["mean_dice"])
+                        if hasattr(self, "eval_boundary"):
+                            print("The Boundary IoU / trimap mIoU for the epoch are: ", self.eval_boundary["boundary_iou"], self.eval_boundary["trimap_iou"])
                     if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank0:                                 # model.py:641-655
@@ -832,14 +848,16 @@ class supervised_model(_WeightedCE):
 
     @_with_ema("gsi_optimizer")
     @torch.no_grad()
-    def evaluate(self, val_loader, first_batch=None, tta=None, crf=None):
+    def evaluate(self, val_loader, first_batch=None, tta=None, crf=None, boundary=None):
         """model.py:145-162.  The reference interpolates to a hard-coded 512x512 (`interp_val`, model.py:63,152), which only
         works for a 512x512 crop; the crop size is used here, as the semi-supervised driver does.
         `first_batch`: a list that receives the first batch's (val_img, val_gt) on the device (the batch of the panels).
         `tta`: a view list of utils.parse_tta, `crf`: a F.CrfOptions, both as in semisuper_cycleGAN.evaluate; None = the reference's
-        single forward and plain first maximum."""
+        single forward and plain first maximum.  `boundary`: a F.BoundaryOptions, as in semisuper_cycleGAN.evaluate (the scores are
+        kept in `self.eval_boundary`); None = off."""
         self.Gsi.eval()
         self.running_metrics_val.reset()
+        self.running_metrics_val.set_boundary(boundary)
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
@@ -860,6 +878,7 @@ class supervised_model(_WeightedCE):
             self.running_metrics_val.update_device(val_gt.squeeze(1), F.argmax_index(outputs))
         score, class_iou = self.running_metrics_val.get_scores()
         self._dice_scores(self.running_metrics_val)
+        self._boundary_scores(self.running_metrics_val)
         self.running_metrics_val.reset()
         self.Gsi.train()
         return score["Mean IoU : \t"], class_iou
@@ -909,11 +928,14 @@ class supervised_model(_WeightedCE):
                 first = [] if rank == 0 and (writer is not None or panel_dir is not None) else None
                 with self.gsi_optimizer.ema_weights():  # --ema_decay: the epoch's mIoU and panels are the averaged weights' (one swap)
                     miou, class_iou = self.evaluate(val_loader, first_batch=first, tta=utils.parse_tta(getattr(args, 'tta', '')),
-                                                    crf=utils.parse_crf(getattr(args, 'crf', '')))
+                                                    crf=utils.parse_crf(getattr(args, 'crf', '')),
+                                                    boundary=utils.parse_boundary(getattr(args, 'boundary', '')))
                     if rank == 0:
                         print("The mIoU for the epoch is: ", miou)
                         if self.dice_options is not None:
                             print("The mean Dice for the epoch is: ", self.eval_dice["mean_dice"])
+                        if hasattr(self, "eval_boundary"):
+                            print("The Boundary IoU / trimap mIoU for the epoch are: ", self.eval_boundary["boundary_iou"], self.eval_boundary["trimap_iou"])
                     if first:                                                       # model.py:164-186
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank == 0:

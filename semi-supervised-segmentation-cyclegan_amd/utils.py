@@ -164,29 +164,69 @@ class runningScore(object):
         self.n_classes, self.dataset = n_classes, dataset
         self.confusion_matrix = np.zeros((n_classes, n_classes))
         self._device_hist = None     # int64 [C, C] accumulated by sscg_confusion_hist; folded in by get_scores()
+        self._boundary = None        # set_boundary(): a F.BoundaryOptions, or None = no contour scores, no launch for them
+        self._boundary_counts = None    # int64 [3 C + C C] accumulated by sscg_boundary_counts while the option is set
+
+    def set_boundary(self, boundary):
+        """The contour scores (Boundary IoU, trimap mIoU) as STATE of the score keeper: a F.BoundaryOptions (utils.parse_boundary), or an
+        integer width d, or None = off.  While set, every update_* on device tensors also asks its head for the uint8 label map and
+        hands it to F.boundary_counts; while off, every method launches exactly what it launches without the option."""
+        if boundary is not None and not isinstance(boundary, F.BoundaryOptions):
+            boundary = F.BoundaryOptions(d=boundary)
+        if boundary != self._boundary:
+            self._boundary_counts = None
+        self._boundary = boundary
+
+    def get_boundary(self):
+        return self._boundary
+
+    def _count_boundary(self, label_trues, label_u8):
+        self._boundary_counts = F.boundary_counts(label_trues.reshape(label_u8.shape), label_u8, self.n_classes,
+                                                  self._boundary.width(*label_u8.shape[-2:]), self._boundary_counts)
 
     def update_device(self, label_trues, label_preds):
         """Same counts as update(), for label / prediction tensors that already live on the MI355X: no
         device->host copy of the maps per batch (model.py:568-569 moves both to numpy)."""
         self._device_hist = F.confusion_hist(label_trues, label_preds, self.n_classes, self._device_hist)
+        if self._boundary is not None:
+            self._count_boundary(label_trues, label_preds.to(torch.uint8))
 
     def update_logits(self, label_trues, logits, size):
         """update_device() from the network's low-resolution logits: resize -> softmax -> argmax -> counts in one launch
-        (F.predict_labels); neither the resized logits nor a predicted label map reach memory."""
-        self._device_hist = F.predict_labels(logits, size, want_u8=False, label_true=label_trues, hist=self._device_hist,
-                                             num_classes=self.n_classes)[2]
+        (F.predict_labels); neither the resized logits nor a predicted label map reach memory (with set_boundary(): the uint8 map
+        does, for F.boundary_counts)."""
+        want = self._boundary is not None
+        u8, _, self._device_hist = F.predict_labels(logits, size, want_u8=want, label_true=label_trues, hist=self._device_hist,
+                                                    num_classes=self.n_classes)
+        if want:
+            self._count_boundary(label_trues, u8)
 
     def update_logits_ms(self, label_trues, logits_list, flips, size):
         """update_logits() over several views of the batch (multi-scale / mirrored inference): the views' probabilities are summed
         and the counts taken in one launch (F.predict_labels_ms)."""
-        self._device_hist = F.predict_labels_ms(logits_list, flips, size, want_u8=False, label_true=label_trues,
-                                                hist=self._device_hist, num_classes=self.n_classes)[2]
+        want = self._boundary is not None
+        u8, _, self._device_hist = F.predict_labels_ms(logits_list, flips, size, want_u8=want, label_true=label_trues,
+                                                       hist=self._device_hist, num_classes=self.n_classes)[:3]
+        if want:
+            self._count_boundary(label_trues, u8)
 
     def update_logits_crf(self, label_trues, logits_or_probs, image, size, crf, probs=False):
         """update_logits() with the windowed dense CRF (F.crf_labels) between the softmax and the first maximum: `image` guides it;
         probs=True: the scores are the summed probabilities of several views (F.predict_labels_ms(want_prob=True)) at `size`."""
-        self._device_hist = F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=False, label_true=label_trues,
-                                         hist=self._device_hist, num_classes=self.n_classes)[2]
+        want = self._boundary is not None
+        u8, _, self._device_hist = F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=want, label_true=label_trues,
+                                                hist=self._device_hist, num_classes=self.n_classes)[:3]
+        if want:
+            self._count_boundary(label_trues, u8)
+
+    def get_boundary_scores(self):
+        """boundary_scores() of the counts accumulated since the last reset(); None while the option is off.  One device -> host copy
+        of 3 C + C C integers."""
+        if self._boundary is None:
+            return None
+        c = self.n_classes
+        counts = np.zeros(3 * c + c * c, dtype=np.int64) if self._boundary_counts is None else self._boundary_counts.cpu().numpy()
+        return boundary_scores(counts, c, self.dataset)
 
     def _fold_device(self):
         if self._device_hist is not None:
@@ -206,8 +246,7 @@ class runningScore(object):
         with np.errstate(divide="ignore", invalid="ignore"):
             acc = np.diag(h).sum() / h.sum()
             acc_cls = np.nanmean(np.diag(h) / h.sum(axis=1))
-            sub = h[1:, 1:] if self.dataset == "voc2012" else (h[:n - 1, :n - 1] if self.dataset == "cityscapes" else h)
-            iu = np.diag(sub) / (sub.sum(axis=1) + sub.sum(axis=0) - np.diag(sub))
+            iu = kept_iou(h, n, self.dataset)
         cls_iu = dict(zip(range(len(iu)), iu))
         return {"Overall Acc: \t": acc, "Mean Acc : \t": acc_cls, "Mean IoU : \t": np.nanmean(iu)}, cls_iu
 
@@ -215,7 +254,8 @@ class runningScore(object):
         """{"mean_dice", "class_dice"} of the accumulated confusion matrix (dice_scores), over the classes get_scores() keeps."""
         self._fold_device()
         h, n = self.confusion_matrix, self.n_classes
-        sub = h[1:, 1:] if self.dataset == "voc2012" else (h[:n - 1, :n - 1] if self.dataset == "cityscapes" else h)
+        k = kept_classes(n, self.dataset)
+        sub = h[k, k]
         d = dice_scores(sub)
         with np.errstate(invalid="ignore"):
             mean = float(np.nanmean(d)) if np.isfinite(d).any() else float("nan")
@@ -224,6 +264,66 @@ class runningScore(object):
     def reset(self):
         self.confusion_matrix = np.zeros((self.n_classes, self.n_classes))
         self._device_hist = None
+        self._boundary_counts = None
+
+
+def kept_classes(n_classes, dataset):
+    """The classes the mean scores run over, as a slice: VOC ignores class 0, Cityscapes the last class, ACDC none (utils.py:398-405)."""
+    return slice(1, n_classes) if dataset == "voc2012" else (slice(0, n_classes - 1) if dataset == "cityscapes" else slice(0, n_classes))
+
+
+def kept_iou(hist, n_classes, dataset):
+    """Per-class IoU TP / (TP + FP + FN) of the kept classes' block of a confusion matrix hist[true][predicted] (NaN on an empty
+    denominator): runningScore.get_scores()'s arithmetic, which the trimap mIoU applies to its band-restricted matrix."""
+    k = kept_classes(n_classes, dataset)
+    sub = hist[k, k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.diag(sub) / (sub.sum(axis=1) + sub.sum(axis=0) - np.diag(sub))
+
+
+def _nanmean(v):
+    with np.errstate(invalid="ignore"):
+        return float(np.nanmean(v)) if np.isfinite(v).any() else float("nan")
+
+
+def boundary_scores(counts, n_classes, dataset):
+    """The contour scores of F.boundary_counts' vector bt | bp | bi | tri (include/sscg.h: sscg_boundary_counts):
+    class_boundary_iou[c] = bi / (bt + bp - bi) (Cheng et al.; NaN on an empty denominator), class_trimap_iou = kept_iou(tri) (the
+    DeepLab papers' trimap: the confusion matrix restricted to the band around the ground-truth label changes), boundary_iou /
+    trimap_iou = their nanmean - all over the classes runningScore.get_scores() keeps for the dataset."""
+    c = int(n_classes)
+    v = np.asarray(counts).reshape(-1)
+    if v.size != 3 * c + c * c:
+        raise ValueError("boundary_scores: %d counts, 3 C + C C = %d expected" % (v.size, 3 * c + c * c))
+    v = v.astype(np.float64)
+    bt, bp, bi, tri = v[:c], v[c:2 * c], v[2 * c:3 * c], v[3 * c:].reshape(c, c)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        biou = np.where(bt + bp - bi > 0, bi / (bt + bp - bi), np.nan)[kept_classes(c, dataset)]
+    tiou = kept_iou(tri, c, dataset)
+    return {"boundary_iou": _nanmean(biou), "class_boundary_iou": dict(zip(range(len(biou)), biou)),
+            "trimap_iou": _nanmean(tiou), "class_trimap_iou": dict(zip(range(len(tiou)), tiou))}
+
+
+def parse_boundary(spec):
+    """`--boundary`: the contour scores of the evaluation.  "on" = F.BoundaryOptions() (the published width: 0.02 of the image
+    diagonal); "d=N" = N pixels, 1..32; "ratio=F" = F of the diagonal, in (0, 1].  Returns a F.BoundaryOptions, None for "" / None.
+    Raises ValueError naming the bad token."""
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    if spec == "on":
+        return F.BoundaryOptions()
+    key, sep, val = spec.partition("=")
+    if not sep or key not in ("d", "ratio"):
+        raise ValueError("--boundary: %r is not 'on', d=N or ratio=F" % spec)
+    try:
+        num = int(val) if key == "d" else float(val)
+    except ValueError:
+        raise ValueError("--boundary: %r is not a number%s" % (spec, " (an integer)" if key == "d" else ""))
+    try:
+        return F.BoundaryOptions(**{key: num})
+    except ValueError as e:
+        raise ValueError("--boundary: %r: %s" % (spec, e))
 
 
 def dice_scores(hist):
