@@ -619,6 +619,38 @@ int sscg_crf_head(const float* x, int kind, int N, int H, int W, int C, int OH, 
  * SSCG_ERR_UNSUPPORTED (N*H*W >= 2^31). */
 int sscg_boundary_counts(const int64_t* label_true, const uint8_t* label_pred, int N, int H, int W, int C, int d, int64_t* counts,
                          void* stream);
+/* ------------------------------------------------------------------ surface distances of the evaluation: the per-case records behind
+ * the Hausdorff distance (HD), its percentile (HD95), the average symmetric surface distance (ASSD) and the normalised surface Dice (NSD)
+ * of a ground-truth / predicted pair of label maps - the second metric of the ACDC challenge beside Dice, which no width-limited contour
+ * band can give (the reference has none of them).  Opt-in (`--surface`), forward only, never launched by the training step.  (An
+ * addition: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.)
+ *
+ * sscg_surface_stats: label_true int64 [N][H][W] (any values), label_pred uint8 [N][H][W], 1 <= C <= 64, unit pixel spacing.  With
+ *   T_c = {label_true == c}, P_c = {label_pred == c} (a true label outside [0, C) and a predicted byte >= C belong to no class);
+ *   S(M) = the pixels of M with a 4-neighbour that is not in M or lies outside the image (M minus its erosion by the cross, border
+ *          value 0: the edge definition of MONAI and medpy);
+ *   direction 0 (T->P): D2 = { min over q in S(P_c) of |r - q|^2 : r in S(T_c) };  direction 1 (P->T) the other way round - integers;
+ * per direction dir, sample n and class c, OVERWRITTEN (nothing is accumulated, nothing depends on what ws, stats or sums held):
+ *   stats[dir][n][c][0]  cnt     number of source surface pixels (reported whenever the source surface exists)
+ *   stats[dir][n][c][1]  within  number with d^2 <= tol2 (tol2 = floor(tol^2): for an integer d^2 exactly d <= tol)
+ *   stats[dir][n][c][2]  max2    the largest d^2
+ *   stats[dir][n][c][3]  v_lo    the d^2 of ascending zero-based rank lo = ((cnt - 1) * pct) / 100 (integer arithmetic)
+ *   stats[dir][n][c][4]  v_hi    the d^2 of rank hi = min(lo + 1, cnt - 1)
+ *   sums[dir][n][c]      sum     the sum of sqrt(d^2) in fp64
+ * When the source or the target surface is empty: within = 0, max2 = v_lo = v_hi = -1, sum = 0.  From these the host forms
+ *   hd = sqrt(max of the two max2),  hd95 = max over the directions of a + (b - a) * (((cnt - 1) * pct) % 100) / 100 with a = sqrt(v_lo),
+ *   b = sqrt(v_hi) (numpy's linear percentile, per direction),  assd = (sum0 + sum1) / (cnt0 + cnt1),  nsd = (within0 + within1) /
+ *   (cnt0 + cnt1) (utils.surface_scores).
+ * The distances are exact at any separation (a column pass and a row pass of the squared Euclidean distance transform, no window);
+ * cnt / within / max2 are integer atomics, v_lo / v_hi an exact radix select over three ten-bit digits, sum is added from per-row fp64
+ * records in a fixed order: the integers are independent of scheduling and the sums reproduce bit for bit.  Everything stays on the
+ * stream.  ws: sscg_surface_workspace(N, H, W, C) bytes (0 for sizes sscg_surface_stats refuses), 256-byte aligned - about
+ * 10 + 4 min(C, 8) bytes per pixel of the batch plus 2 N C (4112 + 8 H) bytes.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (a null pointer, non-positive sizes, C outside 1..64, tol2 < 0, pct outside 1..100),
+ * SSCG_ERR_UNSUPPORTED (N*H*W >= 2^31; (H-1)^2 + (W-1)^2 >= 2^30, the largest d^2 the selection's digits cover), SSCG_ERR_WORKSPACE. */
+size_t sscg_surface_workspace(int N, int H, int W, int C);
+int sscg_surface_stats(const int64_t* label_true, const uint8_t* label_pred, int N, int H, int W, int C, int tol2, int pct,
+                       int64_t* stats, double* sums, void* ws, size_t ws_bytes, void* stream);
 /* ------------------------------------------------------------------ per-epoch image panels: the image grids the reference sends to
  * TensorBoard at the end of every epoch (model.py:576-638; supervised_model: model.py:164-186), without the host round trip of
  * full-resolution maps, the per-pixel Python loop of utils.PIL_to_tensor (utils.py:59-94) and make_grid on the host.  Forward only;

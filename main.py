@@ -2,7 +2,7 @@
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
---ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -49,6 +49,7 @@ class _Args(Namespace):
     ohem_min_frac = 0.0625
     crf = ""
     boundary = ""
+    surface = ""
 
 
 def get_args(argv=None):
@@ -140,6 +141,11 @@ def get_args(argv=None):
                              "CVPR 2021) and the trimap mIoU of the DeepLab papers, printed beside the mIoU; 'on' for the published "
                              "width (0.02 of the image diagonal), d=N for N pixels (1..32), or ratio=F of the diagonal; combines with "
                              "--tta, --crf and --ema_decay (default: off, region scores only)")
+    parser.add_argument("--surface", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="also score the per-epoch evaluation's label maps by their surface distances per sample and class: the "
+                             "Hausdorff distance, its percentile (HD95), the average symmetric surface distance and the normalised "
+                             "surface Dice, in pixels, printed beside the mIoU; 'on' for tol=2,pct=95, or a comma list over tol=F (the "
+                             "NSD tolerance) and pct=N (1..100); combines with --tta, --crf, --boundary and --ema_decay (default: off)")
     args = parser.parse_args(argv, namespace=_Args())
     if args.crf.strip():
         try:
@@ -149,6 +155,11 @@ def get_args(argv=None):
     if args.boundary.strip():
         try:
             importlib.import_module(PKG + ".utils").parse_boundary(args.boundary)
+        except ValueError as e:
+            parser.error(str(e))
+    if args.surface.strip():
+        try:
+            importlib.import_module(PKG + ".utils").parse_surface(args.surface)
         except ValueError as e:
             parser.error(str(e))
     if args.ohem_thresh is not None and not 0.0 < args.ohem_thresh <= 1.0:

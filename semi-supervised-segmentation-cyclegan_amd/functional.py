@@ -10,7 +10,7 @@ Tensors keep the reference's logical NCHW shapes; physically they are channels-l
 what every kernel assumes.  There is no fallback: a non-HIP tensor raises.
 """
 import ctypes as C
-
+import math
 import os
 import weakref
 
@@ -1554,6 +1554,68 @@ def boundary_counts(label_true, label_pred, num_classes, d, counts=None):
     n, h, w = lt.shape
     check(lib.sscg_boundary_counts(lt.data_ptr(), lp.data_ptr(), n, h, w, c, d, counts.data_ptr(), _stream()), "sscg_boundary_counts")
     return counts
+
+
+# Surface distances of the evaluation (sscg_surface_stats, include/sscg.h holds the definitions): opt-in (`--surface`).
+class SurfaceOptions(object):
+    """The two parameters of the surface distances: `tol`, the tolerance of the normalised surface Dice in pixels (finite, >= 0; a
+    surface pixel is within it when d <= tol, i.e. d^2 <= floor(tol^2) for the integer d^2), and `pct`, the percentile of HD95 (an
+    integer in 1..100; 100 makes it the Hausdorff distance)."""
+    __slots__ = ("tol", "pct")
+
+    def __init__(self, tol=2.0, pct=95):
+        if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not 0.0 <= float(tol) < float("inf"):
+            raise ValueError("surface tol %r is not a finite number >= 0" % (tol,))
+        if isinstance(pct, bool) or not isinstance(pct, int) or not 1 <= pct <= 100:
+            raise ValueError("surface pct %r is not an integer in 1..100" % (pct,))
+        self.tol, self.pct = float(tol), pct
+
+    @property
+    def tol2(self):
+        """floor(tol^2), capped at the largest d^2 an image the kernel accepts can hold."""
+        return int(min(math.floor(self.tol * self.tol), 2 ** 30))
+
+    def __eq__(self, other):
+        return isinstance(other, SurfaceOptions) and (self.tol, self.pct) == (other.tol, other.pct)
+
+    def __repr__(self):
+        return "SurfaceOptions(tol=%r, pct=%r)" % (self.tol, self.pct)
+
+
+_SURFACE_WS_BYTES = {}
+
+
+def surface_stats(label_true, label_pred, num_classes, options, *, stats=None, sums=None):
+    """The per-case records of the surface distances of a batch (sscg_surface_stats): label_true [N,H,W] (any integer type, values
+    outside [0, C) belong to no class), label_pred [N,H,W] class ids as bytes.  Returns (stats int64 [2,N,C,5] = cnt, within, max2,
+    v_lo, v_hi per direction (0: true -> predicted), sample and class; sums float64 [2,N,C]) on the device, overwritten.  `stats`,
+    `sums`: tensors to use instead of new ones."""
+    if not (label_true.is_cuda and label_pred.is_cuda):
+        raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % label_true.device)
+    if not isinstance(options, SurfaceOptions):
+        raise TypeError("options must be a functional.SurfaceOptions, not %r" % (options,))
+    c = int(num_classes)
+    if label_true.dim() != 3 or tuple(label_true.shape) != tuple(label_pred.shape):
+        raise _lib.SscgError("surface_stats: two [N, H, W] label maps of one shape expected, got %s and %s" % (
+            tuple(label_true.shape), tuple(label_pred.shape)))
+    lt = label_true.to(torch.int64).contiguous()
+    lp = label_pred.to(torch.uint8).contiguous()
+    n, h, w = lt.shape
+    if stats is None:
+        stats = torch.empty((2, n, c, 5), dtype=torch.int64, device=lt.device)
+    elif not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape) == (2, n, c, 5)):
+        raise _lib.SscgError("surface_stats: stats must be a contiguous int64 [2, N, C, 5] tensor on the device")
+    if sums is None:
+        sums = torch.empty((2, n, c), dtype=torch.float64, device=lt.device)
+    elif not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and tuple(sums.shape) == (2, n, c)):
+        raise _lib.SscgError("surface_stats: sums must be a contiguous float64 [2, N, C] tensor on the device")
+    key = (n, h, w, c)
+    if key not in _SURFACE_WS_BYTES:
+        _SURFACE_WS_BYTES[key] = lib.sscg_surface_workspace(*key)
+    ws = _WS.get(_SURFACE_WS_BYTES[key], lt.device)
+    check(lib.sscg_surface_stats(lt.data_ptr(), lp.data_ptr(), n, h, w, c, options.tol2, options.pct, stats.data_ptr(), sums.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), _stream()), "sscg_surface_stats")
+    return stats, sums
 
 
 # The per-epoch image panels (sscg_panel_labels / sscg_panel_range / sscg_panel_grid): the grids train() hands to the image writer,

@@ -214,6 +214,20 @@ class _WeightedCE(object):
         elif hasattr(self, "eval_boundary"):
             del self.eval_boundary
 
+    def set_surface(self, opts):
+        """--surface: a F.SurfaceOptions (utils.parse_surface), or None = off, handed to the score keeper (runningScore.set_surface):
+        evaluate()'s parameter list stays as it is, the option is state like the Dice and OHEM options."""
+        self.running_metrics_val.set_surface(opts)
+
+    def _surface_scores(self, running):
+        """--surface: the surface distances of the evaluation that has just run (runningScore.get_surface_scores), kept in
+        `self.eval_surface` = {"hd", "hd95", "assd", "nsd", "class_*", "cases", "missing"}.  Off: the attribute is absent."""
+        scores = running.get_surface_scores()
+        if scores is not None:
+            self.eval_surface = scores
+        elif hasattr(self, "eval_surface"):
+            del self.eval_surface
+
     def _ce_device(self):
         ids = getattr(self.args, "gpu_ids", None)
         return torch.device("cuda", int(ids[0])) if ids else torch.device("cpu")
@@ -693,6 +707,7 @@ class semisuper_cycleGAN(_WeightedCE):
         score, class_iou = self.running_metrics_val.get_scores()
         self._dice_scores(self.running_metrics_val)
         self._boundary_scores(self.running_metrics_val)
+        self._surface_scores(self.running_metrics_val)
         self.Gsi.train()
         self.Gis.train()
         return score["Mean IoU : \t"], class_iou
@@ -735,6 +750,7 @@ class semisuper_cycleGAN(_WeightedCE):
         rank0 = self.dp is None or self.dp.rank == 0
         done = 0
         history = []
+        self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
         for epoch in range(self.start_epoch, args.epochs):
             if rank0:
                 print('learning rate = %.7f' % self.g_optimizer.param_groups[0]['lr'])
@@ -778,6 +794,9 @@ class semisuper_cycleGAN(_WeightedCE):
                             print("The mean Dice for the epoch is: ", self.eval_dice["mean_dice"])
                         if hasattr(self, "eval_boundary"):
                             print("The Boundary IoU / trimap mIoU for the epoch are: ", self.eval_boundary["boundary_iou"], self.eval_boundary["trimap_iou"])
+                        if hasattr(self, "eval_surface"):
+                            print("The HD / HD%d / ASSD / NSD for the epoch are: " % self.running_metrics_val.get_surface().pct,
+                                  self.eval_surface["hd"], self.eval_surface["hd95"], self.eval_surface["assd"], self.eval_surface["nsd"])
                     if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank0:                                 # model.py:641-655
@@ -879,6 +898,7 @@ class supervised_model(_WeightedCE):
         score, class_iou = self.running_metrics_val.get_scores()
         self._dice_scores(self.running_metrics_val)
         self._boundary_scores(self.running_metrics_val)
+        self._surface_scores(self.running_metrics_val)
         self.running_metrics_val.reset()
         self.Gsi.train()
         return score["Mean IoU : \t"], class_iou
@@ -905,6 +925,7 @@ class supervised_model(_WeightedCE):
         self.resolve_ce_weights(labeled_loader)
         val_loader = loaders[2] if len(loaders) > 2 else None
         history, done = [], 0
+        self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
         for epoch in range(self.start_epoch, args.epochs):
             self.Gsi.train()
             for i, (l_img, l_gt, _) in enumerate(labeled_loader):
@@ -936,6 +957,9 @@ class supervised_model(_WeightedCE):
                             print("The mean Dice for the epoch is: ", self.eval_dice["mean_dice"])
                         if hasattr(self, "eval_boundary"):
                             print("The Boundary IoU / trimap mIoU for the epoch are: ", self.eval_boundary["boundary_iou"], self.eval_boundary["trimap_iou"])
+                        if hasattr(self, "eval_surface"):
+                            print("The HD / HD%d / ASSD / NSD for the epoch are: " % self.running_metrics_val.get_surface().pct,
+                                  self.eval_surface["hd"], self.eval_surface["hd95"], self.eval_surface["assd"], self.eval_surface["nsd"])
                     if first:                                                       # model.py:164-186
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank == 0:

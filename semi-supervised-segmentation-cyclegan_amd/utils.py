@@ -166,6 +166,8 @@ class runningScore(object):
         self._device_hist = None     # int64 [C, C] accumulated by sscg_confusion_hist; folded in by get_scores()
         self._boundary = None        # set_boundary(): a F.BoundaryOptions, or None = no contour scores, no launch for them
         self._boundary_counts = None    # int64 [3 C + C C] accumulated by sscg_boundary_counts while the option is set
+        self._surface = None         # set_surface(): a F.SurfaceOptions, or None = no surface distances, no launch for them
+        self._surface_records = []   # per update_* call (stats int64 [2, N, C, 5], sums float64 [2, N, C]) on the device
 
     def set_boundary(self, boundary):
         """The contour scores (Boundary IoU, trimap mIoU) as STATE of the score keeper: a F.BoundaryOptions (utils.parse_boundary), or an
@@ -180,22 +182,39 @@ class runningScore(object):
     def get_boundary(self):
         return self._boundary
 
+    def set_surface(self, surface):
+        """The surface distances (HD, HD95, ASSD, NSD) as STATE of the score keeper: a F.SurfaceOptions (utils.parse_surface), or None =
+        off.  While set, every update_* on device tensors also asks its head for the uint8 label map and keeps the call's two small
+        record tensors of F.surface_stats; while off, every method launches exactly what it launches without the option."""
+        if surface is not None and not isinstance(surface, F.SurfaceOptions):
+            raise TypeError("set_surface: a functional.SurfaceOptions or None expected, not %r" % (surface,))
+        if surface != self._surface:
+            self._surface_records = []
+        self._surface = surface
+
+    def get_surface(self):
+        return self._surface
+
     def _count_boundary(self, label_trues, label_u8):
-        self._boundary_counts = F.boundary_counts(label_trues.reshape(label_u8.shape), label_u8, self.n_classes,
-                                                  self._boundary.width(*label_u8.shape[-2:]), self._boundary_counts)
+        """What the contour options ask of one batch's uint8 label map: the boundary counts and / or the surface records."""
+        if self._boundary is not None:
+            self._boundary_counts = F.boundary_counts(label_trues.reshape(label_u8.shape), label_u8, self.n_classes,
+                                                      self._boundary.width(*label_u8.shape[-2:]), self._boundary_counts)
+        if self._surface is not None:
+            self._surface_records.append(F.surface_stats(label_trues.reshape(label_u8.shape), label_u8, self.n_classes, self._surface))
 
     def update_device(self, label_trues, label_preds):
         """Same counts as update(), for label / prediction tensors that already live on the MI355X: no
         device->host copy of the maps per batch (model.py:568-569 moves both to numpy)."""
         self._device_hist = F.confusion_hist(label_trues, label_preds, self.n_classes, self._device_hist)
-        if self._boundary is not None:
+        if self._boundary is not None or self._surface is not None:
             self._count_boundary(label_trues, label_preds.to(torch.uint8))
 
     def update_logits(self, label_trues, logits, size):
         """update_device() from the network's low-resolution logits: resize -> softmax -> argmax -> counts in one launch
         (F.predict_labels); neither the resized logits nor a predicted label map reach memory (with set_boundary(): the uint8 map
         does, for F.boundary_counts)."""
-        want = self._boundary is not None
+        want = self._boundary is not None or self._surface is not None
         u8, _, self._device_hist = F.predict_labels(logits, size, want_u8=want, label_true=label_trues, hist=self._device_hist,
                                                     num_classes=self.n_classes)
         if want:
@@ -204,7 +223,7 @@ class runningScore(object):
     def update_logits_ms(self, label_trues, logits_list, flips, size):
         """update_logits() over several views of the batch (multi-scale / mirrored inference): the views' probabilities are summed
         and the counts taken in one launch (F.predict_labels_ms)."""
-        want = self._boundary is not None
+        want = self._boundary is not None or self._surface is not None
         u8, _, self._device_hist = F.predict_labels_ms(logits_list, flips, size, want_u8=want, label_true=label_trues,
                                                        hist=self._device_hist, num_classes=self.n_classes)[:3]
         if want:
@@ -213,7 +232,7 @@ class runningScore(object):
     def update_logits_crf(self, label_trues, logits_or_probs, image, size, crf, probs=False):
         """update_logits() with the windowed dense CRF (F.crf_labels) between the softmax and the first maximum: `image` guides it;
         probs=True: the scores are the summed probabilities of several views (F.predict_labels_ms(want_prob=True)) at `size`."""
-        want = self._boundary is not None
+        want = self._boundary is not None or self._surface is not None
         u8, _, self._device_hist = F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=want, label_true=label_trues,
                                                 hist=self._device_hist, num_classes=self.n_classes)[:3]
         if want:
@@ -227,6 +246,22 @@ class runningScore(object):
         c = self.n_classes
         counts = np.zeros(3 * c + c * c, dtype=np.int64) if self._boundary_counts is None else self._boundary_counts.cpu().numpy()
         return boundary_scores(counts, c, self.dataset)
+
+    def get_surface_scores(self):
+        """surface_scores() of the records kept since the last reset(); None while the option is off.  The list is concatenated once
+        and copied to the host once: 2 N C (5 integers + 1 double) per evaluated sample."""
+        if self._surface is None:
+            return None
+        c = self.n_classes
+        if self._surface_records:
+            stats = torch.cat([r[0] for r in self._surface_records], dim=1)
+            sums = torch.cat([r[1] for r in self._surface_records], dim=1)
+            packed = torch.cat([stats.reshape(-1), sums.reshape(-1).view(torch.int64)]).cpu().numpy()
+            stats = packed[:stats.numel()].reshape(tuple(stats.shape))
+            sums = packed[stats.size:].view(np.float64).reshape(tuple(sums.shape))
+        else:
+            stats, sums = np.zeros((2, 0, c, 5), dtype=np.int64), np.zeros((2, 0, c), dtype=np.float64)
+        return surface_scores(stats, sums, c, self.dataset, self._surface.pct)
 
     def _fold_device(self):
         if self._device_hist is not None:
@@ -265,6 +300,7 @@ class runningScore(object):
         self.confusion_matrix = np.zeros((self.n_classes, self.n_classes))
         self._device_hist = None
         self._boundary_counts = None
+        self._surface_records = []
 
 
 def kept_classes(n_classes, dataset):
@@ -324,6 +360,68 @@ def parse_boundary(spec):
         return F.BoundaryOptions(**{key: num})
     except ValueError as e:
         raise ValueError("--boundary: %r: %s" % (spec, e))
+
+
+def surface_scores(stats, sums, n_classes, dataset, pct):
+    """The surface distances of F.surface_stats' records (include/sscg.h: sscg_surface_stats): stats int64 [2, M, C, 5] = cnt, within,
+    max2, v_lo, v_hi and sums float64 [2, M, C] per direction, case sample and class.  A case (sample, class) is DEFINED when both
+    surfaces exist, MISSING when exactly one does, not counted when neither does.  Per defined case, in fp64:
+    hd = sqrt(max of the two max2); hd95 = the larger of the two directions' a + (b - a) * (((cnt - 1) * pct) % 100) / 100 with
+    a = sqrt(v_lo), b = sqrt(v_hi) - numpy's linear percentile written with integer ranks, so that the device selects two order
+    statistics and no rank is ever formed in floating point; assd = (sum0 + sum1) / (cnt0 + cnt1); nsd = (within0 + within1) /
+    (cnt0 + cnt1).  class_* = the mean over the class's defined cases (NaN without one), cases / missing = their numbers, hd / hd95 /
+    assd / nsd = the nanmean over the classes runningScore.get_scores() keeps for the dataset."""
+    c = int(n_classes)
+    st = np.asarray(stats, dtype=np.int64)
+    sm = np.asarray(sums, dtype=np.float64)
+    if st.ndim != 4 or st.shape[0] != 2 or st.shape[2:] != (c, 5) or sm.shape != st.shape[:3]:
+        raise ValueError("surface_scores: stats [2, M, %d, 5] and sums [2, M, %d] expected, got %s and %s" % (c, c, st.shape, sm.shape))
+    cnt, within, max2, vlo, vhi = (st[..., k] for k in range(5))
+    defined = (cnt[0] > 0) & (cnt[1] > 0)                                   # [M, C]
+    missing = (cnt[0] > 0) ^ (cnt[1] > 0)
+    frac = (((cnt - 1) * int(pct)) % 100).astype(np.float64) / 100.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a, b = np.sqrt(vlo.astype(np.float64)), np.sqrt(vhi.astype(np.float64))
+        per_dir = a + (b - a) * frac
+        total = (cnt[0] + cnt[1]).astype(np.float64)
+        case = {"hd": np.sqrt(np.maximum(max2[0], max2[1]).astype(np.float64)), "hd95": np.maximum(per_dir[0], per_dir[1]),
+                "assd": (sm[0] + sm[1]) / total, "nsd": (within[0] + within[1]).astype(np.float64) / total}
+    k = kept_classes(c, dataset)
+    n_def = defined.sum(axis=0)
+    out = {}
+    for name, v in case.items():
+        with np.errstate(invalid="ignore", divide="ignore"):
+            cls = np.where(n_def > 0, np.where(defined, v, 0.0).sum(axis=0) / n_def, np.nan)[k]
+        out[name] = _nanmean(cls)
+        out["class_" + name] = dict(zip(range(len(cls)), cls))
+    out["cases"] = dict(zip(range(len(n_def[k])), (int(v) for v in n_def[k])))
+    out["missing"] = dict(zip(range(len(n_def[k])), (int(v) for v in missing.sum(axis=0)[k])))
+    return out
+
+
+def parse_surface(spec):
+    """`--surface`: the surface distances of the evaluation.  "on" = F.SurfaceOptions() (tol 2 pixels, the 95th percentile); else a
+    comma list over tol=F (the NSD tolerance in pixels, >= 0) and pct=N (the percentile, an integer in 1..100) - keys left out keep
+    their defaults.  Returns a F.SurfaceOptions, None for "" / None.  Raises ValueError naming the bad token."""
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    if spec == "on":
+        return F.SurfaceOptions()
+    kw = {}
+    for tok in spec.split(","):
+        key, sep, val = tok.strip().partition("=")
+        if not sep or key not in ("tol", "pct") or key in kw:
+            raise ValueError("--surface: %r is not 'on' or one key=value over tol, pct" % tok)
+        try:
+            kw[key] = int(val) if key == "pct" else float(val)
+        except ValueError:
+            raise ValueError("--surface: %r is not a number%s" % (tok, " (an integer)" if key == "pct" else ""))
+        try:
+            F.SurfaceOptions(**{key: kw[key]})
+        except ValueError as e:
+            raise ValueError("--surface: %r: %s" % (tok, e))
+    return F.SurfaceOptions(**kw)
 
 
 def dice_scores(hist):
