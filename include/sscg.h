@@ -651,6 +651,41 @@ int sscg_boundary_counts(const int64_t* label_true, const uint8_t* label_pred, i
 size_t sscg_surface_workspace(int N, int H, int W, int C);
 int sscg_surface_stats(const int64_t* label_true, const uint8_t* label_pred, int N, int H, int W, int C, int tol2, int pct,
                        int64_t* stats, double* sums, void* ws, size_t ws_bytes, void* stream);
+/* ------------------------------------------------------------------ connected-component filtering of predicted label maps: the
+ * post-processing of the ACDC / nnU-Net style pipelines - label the connected components of every predicted class, keep the largest one
+ * per sample and / or the ones of at least min_area pixels, relabel the rest - without which one stray speckle far from its structure
+ * sets the Hausdorff distance of --surface (the reference has no such step: its validation scores the argmax as it is).  Opt-in
+ * (`--components`), forward only, never launched by the training step.  (An addition: no existing entry changes meaning, so
+ * SSCG_ABI_VERSION stays 18.)
+ *
+ * sscg_components_filter: label_pred uint8 [N][H][W] (the map the heads write), 1 <= C <= 64, conn = 4 or 8, largest = 0 or 1,
+ * min_area >= 0, 0 <= fill < C; bit c of exempt_mask exempts class c, the fill class is always exempt.
+ *   COMPONENT of class c in sample n: a maximal conn-connected set of pixels of sample n with label_pred == c.  Connectivity never
+ *     crosses a sample or the image border.  A byte >= C belongs to no component, joins nothing and is copied through unchanged.
+ *   ANCHOR of a component: its smallest row-major pixel index within the sample;  AREA: its pixel count.
+ *   A component of a non-exempt class c is KEPT iff area >= min_area and, if largest, it is the component of (n, c) with the largest
+ *     area, ties going to the smallest anchor.  Components of exempt classes are always kept.
+ *   label_out[p] = label_pred[p] on kept components and on bytes >= C, fill otherwise; every byte is written; label_out == label_pred
+ *     (in place) is allowed.
+ *   hist (non-null only together with label_true int64 [N][H][W]): int64 [C][C], ACCUMULATED, hist[t][label_out] under exactly
+ *     sscg_confusion_hist's rules (a true label outside [0, C) and a byte >= C are counted nowhere) - equal to calling that entry on
+ *     label_out.
+ *   stats (nullable): int64 [N][C][4], OVERWRITTEN: the number of components, the number of kept components, the pixels of the class
+ *     before filtering, the pixels after (for the fill class "after" includes what was relabelled into it).
+ * Nothing depends on what ws, label_out or stats held, or on scheduling: all results are integers formed by order-free atomics and
+ * reproduce bit for bit.  A block-based union-find (csrc/components.hip): one int32 parent and one int32 area per pixel of the batch,
+ * unions by minimum index inside 32x32 tiles in LDS, then across the tile seams by global atomicMin, so that the root of a component
+ * is its anchor; one 64-bit key (area << 32 | ~anchor) per (sample, class) selects the largest.  Five launches on the stream, no host
+ * synchronisation, no copy.  ws: sscg_components_workspace(N, H, W, C) bytes (0 for sizes sscg_components_filter refuses), 256-byte
+ * aligned - 8 bytes per pixel of the batch plus 8 N C.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (label_pred / label_out / ws null, non-positive sizes, C outside 1..64, conn not 4 or 8,
+ * largest not 0 or 1, min_area < 0, fill outside [0, C), hist without label_true, exempt_mask bits at or above C),
+ * SSCG_ERR_UNSUPPORTED (N*H*W >= 2^31), SSCG_ERR_WORKSPACE. */
+size_t sscg_components_workspace(int N, int H, int W, int C);
+int sscg_components_filter(const uint8_t* label_pred, const int64_t* label_true /*nullable*/, int N, int H, int W, int C,
+                           int conn, int largest, int min_area, int fill, uint64_t exempt_mask,
+                           uint8_t* label_out, int64_t* hist /*nullable, accumulated*/, int64_t* stats /*nullable, overwritten*/,
+                           void* ws, size_t ws_bytes, void* stream);
 /* ------------------------------------------------------------------ per-epoch image panels: the image grids the reference sends to
  * TensorBoard at the end of every epoch (model.py:576-638; supervised_model: model.py:164-186), without the host round trip of
  * full-resolution maps, the per-pixel Python loop of utils.PIL_to_tensor (utils.py:59-94) and make_grid on the host.  Forward only;

@@ -2,7 +2,7 @@
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
---ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -50,6 +50,7 @@ class _Args(Namespace):
     crf = ""
     boundary = ""
     surface = ""
+    components = ""
 
 
 def get_args(argv=None):
@@ -146,6 +147,13 @@ def get_args(argv=None):
                              "Hausdorff distance, its percentile (HD95), the average symmetric surface distance and the normalised "
                              "surface Dice, in pixels, printed beside the mIoU; 'on' for tol=2,pct=95, or a comma list over tol=F (the "
                              "NSD tolerance) and pct=N (1..100); combines with --tta, --crf, --boundary and --ema_decay (default: off)")
+    parser.add_argument("--components", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="filter the predicted label maps of the evaluation, validation and testing by connected components "
+                             "before they are scored or saved: per sample and class keep only the largest component ('largest') and / "
+                             "or the components of at least N pixels ('min_area=N'), relabel the rest as class K ('fill=K', default 0); "
+                             "'conn=4|8' (default 8), 'skip=a:b:c' for classes never filtered; 'on' for min_area=64 (an untuned "
+                             "default); e.g. largest,min_area=16,skip=3; combines with --tta, --crf, --boundary, --surface and "
+                             "--ema_decay (default: off, the maps are scored as predicted)")
     args = parser.parse_args(argv, namespace=_Args())
     if args.crf.strip():
         try:
@@ -162,6 +170,12 @@ def get_args(argv=None):
             importlib.import_module(PKG + ".utils").parse_surface(args.surface)
         except ValueError as e:
             parser.error(str(e))
+    if args.components.strip():
+        try:
+            importlib.import_module(PKG + ".utils").parse_components(args.components).exempt_mask(
+                {"voc2012": 21, "cityscapes": 20, "acdc": 4}[args.dataset])
+        except ValueError as e:
+            parser.error("--components: %s" % e if not str(e).startswith("--components") else str(e))
     if args.ohem_thresh is not None and not 0.0 < args.ohem_thresh <= 1.0:
         parser.error("--ohem_thresh must lie in (0, 1]")
     if args.ohem_min_kept < 0:

@@ -1618,6 +1618,117 @@ def surface_stats(label_true, label_pred, num_classes, options, *, stats=None, s
     return stats, sums
 
 
+# Connected-component filtering of predicted label maps (sscg_components_filter, include/sscg.h holds the definitions): opt-in
+# (`--components`).
+class ComponentOptions(object):
+    """What the component filter keeps: `largest` = only the largest component of each (sample, class), ties to the one that starts
+    first in row-major order; `min_area` = only components of at least that many pixels (0 = no threshold); both may be set.  `conn` =
+    4 or 8 (pixel connectivity), `fill` = the class a removed component becomes, `skip` = class ids that are never filtered (the fill
+    class never is)."""
+    __slots__ = ("largest", "min_area", "conn", "fill", "skip")
+
+    def __init__(self, largest=False, min_area=0, conn=8, fill=0, skip=()):
+        if not isinstance(largest, (bool, int)) or largest not in (0, 1):
+            raise ValueError("components largest %r is not a bool" % (largest,))
+        if isinstance(min_area, bool) or not isinstance(min_area, int) or not 0 <= min_area < 2 ** 31:
+            raise ValueError("components min_area %r is not an integer in 0..2^31-1" % (min_area,))
+        if isinstance(conn, bool) or conn not in (4, 8):
+            raise ValueError("components conn %r is not 4 or 8" % (conn,))
+        if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill < 64:
+            raise ValueError("components fill %r is not a class id in 0..63" % (fill,))
+        try:
+            skip = tuple(sorted(set(skip)))
+        except TypeError:
+            raise ValueError("components skip %r is not a list of class ids" % (skip,))
+        if any(isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < 64 for s in skip):
+            raise ValueError("components skip %r holds something that is not a class id in 0..63" % (skip,))
+        self.largest, self.min_area, self.conn, self.fill, self.skip = bool(largest), min_area, conn, fill, skip
+
+    def exempt_mask(self, num_classes):
+        """Bit c set = class c is never filtered: the skip list and the fill class, checked against the class count."""
+        c = int(num_classes)
+        if not 1 <= c <= 64:
+            raise ValueError("components: %d classes, 1..64 expected" % c)
+        if self.fill >= c:
+            raise ValueError("components fill=%d is not a class of %d" % (self.fill, c))
+        if any(s >= c for s in self.skip):
+            raise ValueError("components skip=%s names a class that is not one of %d" % (":".join(str(s) for s in self.skip), c))
+        mask = 1 << self.fill
+        for s in self.skip:
+            mask |= 1 << s
+        return mask
+
+    def _key(self):
+        return (self.largest, self.min_area, self.conn, self.fill, self.skip)
+
+    def __eq__(self, other):
+        return isinstance(other, ComponentOptions) and self._key() == other._key()
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "ComponentOptions(largest=%r, min_area=%r, conn=%r, fill=%r, skip=%r)" % self._key()
+
+
+_COMPONENTS_WS_BYTES = {}
+
+
+def component_filter(label_pred, num_classes, options, *, label_true=None, hist=None, out=None, stats=False):
+    """The component filter on a batch of predicted label maps (sscg_components_filter): label_pred [N,H,W] class ids as bytes.
+    Returns (label_u8 uint8 [N,H,W], hist or None, stats or None).  `label_true` ([N,H,W], any integer type; values outside [0, C) are
+    void) adds the FILTERED maps to the confusion matrix `hist` (int64 [C,C] on the device, accumulated; None = a new zeroed one);
+    `out`: a uint8 [N,H,W] tensor to write instead of a new one (label_pred itself = in place); `stats`: True = a new int64 [N,C,4]
+    tensor (components, kept components, pixels before, pixels after per sample and class), or such a tensor, overwritten."""
+    if not label_pred.is_cuda or (label_true is not None and not label_true.is_cuda):
+        raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % (
+            label_pred.device if not label_pred.is_cuda else label_true.device))
+    if not isinstance(options, ComponentOptions):
+        raise TypeError("options must be a functional.ComponentOptions, not %r" % (options,))
+    c = int(num_classes)
+    try:
+        mask = options.exempt_mask(c)
+    except ValueError as e:
+        raise _lib.SscgError("component_filter: %s" % e)
+    if label_pred.dim() != 3:
+        raise _lib.SscgError("component_filter: an [N, H, W] label map expected, got %s" % (tuple(label_pred.shape),))
+    if hist is not None and label_true is None:
+        raise _lib.SscgError("component_filter: a confusion matrix needs label_true")
+    lp = label_pred.to(torch.uint8).contiguous()
+    n, h, w = lp.shape
+    lt = None
+    if label_true is not None:
+        lt = label_true.to(torch.int64).contiguous()
+        if lt.numel() != lp.numel():
+            raise _lib.SscgError("component_filter: label_true must have N*H*W elements")
+        if hist is None:
+            hist = torch.empty((c, c), dtype=torch.int64, device=lp.device)
+            check(lib.sscg_fill(hist.data_ptr(), 2 * hist.numel(), 0.0, _stream()), "sscg_fill")   # 2 fp32 zeros per int64 zero
+        elif not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == c * c):
+            raise _lib.SscgError("component_filter: hist must be a contiguous int64 [C, C] tensor on the device")
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=lp.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, h, w)):
+        raise _lib.SscgError("component_filter: out must be a contiguous uint8 [N, H, W] tensor on the device")
+    if stats is True:
+        stats = torch.empty((n, c, 4), dtype=torch.int64, device=lp.device)
+    elif stats is False or stats is None:
+        stats = None
+    elif not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape) == (n, c, 4)):
+        raise _lib.SscgError("component_filter: stats must be a contiguous int64 [N, C, 4] tensor on the device")
+    key = (n, h, w, c)
+    if key not in _COMPONENTS_WS_BYTES:
+        _COMPONENTS_WS_BYTES[key] = lib.sscg_components_workspace(*key)
+    ws = _WS.get(_COMPONENTS_WS_BYTES[key], lp.device)
+    check(lib.sscg_components_filter(lp.data_ptr(), _ptr(lt), n, h, w, c, options.conn, int(options.largest), options.min_area,
+                                     options.fill, mask, out.data_ptr(), _ptr(hist), _ptr(stats), ws.data_ptr(), ws.numel(), _stream()),
+          "sscg_components_filter")
+    return out, hist, stats
+
+
 # The per-epoch image panels (sscg_panel_labels / sscg_panel_range / sscg_panel_grid): the grids train() hands to the image writer,
 # built on the device.  SSCG_FUSE_PANELS=0 keeps model.panels() on the chain of separate passes and the host (an A/B aid: the bytes
 # are the same).

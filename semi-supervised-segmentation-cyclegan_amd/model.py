@@ -228,6 +228,20 @@ class _WeightedCE(object):
         elif hasattr(self, "eval_surface"):
             del self.eval_surface
 
+    def set_components(self, opts):
+        """--components: a F.ComponentOptions (utils.parse_components), or None = off, handed to the score keeper
+        (runningScore.set_components): evaluate()'s parameter list stays as it is, the option is state like the surface option."""
+        self.running_metrics_val.set_components(opts)
+
+    def _component_scores(self, running):
+        """--components: what the component filter did in the evaluation that has just run (runningScore.get_component_scores), kept
+        in `self.eval_components` = {"components", "kept_components", "removed_pixels", "class_*"}.  Off: the attribute is absent."""
+        scores = running.get_component_scores()
+        if scores is not None:
+            self.eval_components = scores
+        elif hasattr(self, "eval_components"):
+            del self.eval_components
+
     def _ce_device(self):
         ids = getattr(self.args, "gpu_ids", None)
         return torch.device("cuda", int(ids[0])) if ids else torch.device("cpu")
@@ -708,6 +722,7 @@ class semisuper_cycleGAN(_WeightedCE):
         self._dice_scores(self.running_metrics_val)
         self._boundary_scores(self.running_metrics_val)
         self._surface_scores(self.running_metrics_val)
+        self._component_scores(self.running_metrics_val)
         self.Gsi.train()
         self.Gis.train()
         return score["Mean IoU : \t"], class_iou
@@ -751,6 +766,7 @@ class semisuper_cycleGAN(_WeightedCE):
         done = 0
         history = []
         self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
+        self.set_components(utils.parse_components(getattr(args, 'components', '')))
         for epoch in range(self.start_epoch, args.epochs):
             if rank0:
                 print('learning rate = %.7f' % self.g_optimizer.param_groups[0]['lr'])
@@ -797,6 +813,9 @@ class semisuper_cycleGAN(_WeightedCE):
                         if hasattr(self, "eval_surface"):
                             print("The HD / HD%d / ASSD / NSD for the epoch are: " % self.running_metrics_val.get_surface().pct,
                                   self.eval_surface["hd"], self.eval_surface["hd95"], self.eval_surface["assd"], self.eval_surface["nsd"])
+                        if hasattr(self, "eval_components"):
+                            print("The components found / kept and the pixels relabelled for the epoch are: ", self.eval_components["components"],
+                                  self.eval_components["kept_components"], self.eval_components["removed_pixels"])
                     if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank0:                                 # model.py:641-655
@@ -899,6 +918,7 @@ class supervised_model(_WeightedCE):
         self._dice_scores(self.running_metrics_val)
         self._boundary_scores(self.running_metrics_val)
         self._surface_scores(self.running_metrics_val)
+        self._component_scores(self.running_metrics_val)
         self.running_metrics_val.reset()
         self.Gsi.train()
         return score["Mean IoU : \t"], class_iou
@@ -926,6 +946,7 @@ class supervised_model(_WeightedCE):
         val_loader = loaders[2] if len(loaders) > 2 else None
         history, done = [], 0
         self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
+        self.set_components(utils.parse_components(getattr(args, 'components', '')))
         for epoch in range(self.start_epoch, args.epochs):
             self.Gsi.train()
             for i, (l_img, l_gt, _) in enumerate(labeled_loader):
@@ -960,6 +981,9 @@ class supervised_model(_WeightedCE):
                         if hasattr(self, "eval_surface"):
                             print("The HD / HD%d / ASSD / NSD for the epoch are: " % self.running_metrics_val.get_surface().pct,
                                   self.eval_surface["hd"], self.eval_surface["hd95"], self.eval_surface["assd"], self.eval_surface["nsd"])
+                        if hasattr(self, "eval_components"):
+                            print("The components found / kept and the pixels relabelled for the epoch are: ", self.eval_components["components"],
+                                  self.eval_components["kept_components"], self.eval_components["removed_pixels"])
                     if first:                                                       # model.py:164-186
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank == 0:

@@ -168,6 +168,8 @@ class runningScore(object):
         self._boundary_counts = None    # int64 [3 C + C C] accumulated by sscg_boundary_counts while the option is set
         self._surface = None         # set_surface(): a F.SurfaceOptions, or None = no surface distances, no launch for them
         self._surface_records = []   # per update_* call (stats int64 [2, N, C, 5], sums float64 [2, N, C]) on the device
+        self._components = None      # set_components(): a F.ComponentOptions, or None = the label maps are scored as predicted
+        self._component_stats = []   # per update_* call F.component_filter's stats int64 [N, C, 4] on the device
 
     def set_boundary(self, boundary):
         """The contour scores (Boundary IoU, trimap mIoU) as STATE of the score keeper: a F.BoundaryOptions (utils.parse_boundary), or an
@@ -195,6 +197,36 @@ class runningScore(object):
     def get_surface(self):
         return self._surface
 
+    def set_components(self, components):
+        """The component filter (F.component_filter) as STATE of the score keeper: a F.ComponentOptions (utils.parse_components), or
+        None = off.  While set, every update_* on device tensors asks its head for the uint8 label map ONLY (no label_true, no
+        confusion matrix), filters it, and takes the confusion matrix (inside the filter's last launch), the contour counts and the
+        surface records from the FILTERED map; the call's small stats tensor is kept.  While off, every method launches exactly what
+        it launches without the option."""
+        if components is not None and not isinstance(components, F.ComponentOptions):
+            raise TypeError("set_components: a functional.ComponentOptions or None expected, not %r" % (components,))
+        if components is not None:
+            try:
+                components.exempt_mask(self.n_classes)
+            except ValueError as e:
+                raise ValueError("set_components: %s" % e)
+        if components != self._components:
+            self._component_stats = []
+        self._components = components
+
+    def get_components(self):
+        return self._components
+
+    def _filter_components(self, label_trues, label_u8):
+        """The component filter on one batch's uint8 label map: the confusion matrix, the contour options and the kept stats all see
+        the filtered map, which is returned."""
+        u8, self._device_hist, stats = F.component_filter(label_u8, self.n_classes, self._components, label_true=label_trues,
+                                                          hist=self._device_hist, stats=True)
+        self._component_stats.append(stats)
+        if self._boundary is not None or self._surface is not None:
+            self._count_boundary(label_trues, u8)
+        return u8
+
     def _count_boundary(self, label_trues, label_u8):
         """What the contour options ask of one batch's uint8 label map: the boundary counts and / or the surface records."""
         if self._boundary is not None:
@@ -206,6 +238,9 @@ class runningScore(object):
     def update_device(self, label_trues, label_preds):
         """Same counts as update(), for label / prediction tensors that already live on the MI355X: no
         device->host copy of the maps per batch (model.py:568-569 moves both to numpy)."""
+        if self._components is not None:
+            self._filter_components(label_trues, label_preds.to(torch.uint8))
+            return
         self._device_hist = F.confusion_hist(label_trues, label_preds, self.n_classes, self._device_hist)
         if self._boundary is not None or self._surface is not None:
             self._count_boundary(label_trues, label_preds.to(torch.uint8))
@@ -214,6 +249,9 @@ class runningScore(object):
         """update_device() from the network's low-resolution logits: resize -> softmax -> argmax -> counts in one launch
         (F.predict_labels); neither the resized logits nor a predicted label map reach memory (with set_boundary(): the uint8 map
         does, for F.boundary_counts)."""
+        if self._components is not None:
+            self._filter_components(label_trues, F.predict_labels(logits, size, want_u8=True, num_classes=self.n_classes)[0])
+            return
         want = self._boundary is not None or self._surface is not None
         u8, _, self._device_hist = F.predict_labels(logits, size, want_u8=want, label_true=label_trues, hist=self._device_hist,
                                                     num_classes=self.n_classes)
@@ -223,6 +261,10 @@ class runningScore(object):
     def update_logits_ms(self, label_trues, logits_list, flips, size):
         """update_logits() over several views of the batch (multi-scale / mirrored inference): the views' probabilities are summed
         and the counts taken in one launch (F.predict_labels_ms)."""
+        if self._components is not None:
+            self._filter_components(label_trues, F.predict_labels_ms(logits_list, flips, size, want_u8=True,
+                                                                     num_classes=self.n_classes)[0])
+            return
         want = self._boundary is not None or self._surface is not None
         u8, _, self._device_hist = F.predict_labels_ms(logits_list, flips, size, want_u8=want, label_true=label_trues,
                                                        hist=self._device_hist, num_classes=self.n_classes)[:3]
@@ -232,6 +274,10 @@ class runningScore(object):
     def update_logits_crf(self, label_trues, logits_or_probs, image, size, crf, probs=False):
         """update_logits() with the windowed dense CRF (F.crf_labels) between the softmax and the first maximum: `image` guides it;
         probs=True: the scores are the summed probabilities of several views (F.predict_labels_ms(want_prob=True)) at `size`."""
+        if self._components is not None:
+            self._filter_components(label_trues, F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=True,
+                                                              num_classes=self.n_classes)[0])
+            return
         want = self._boundary is not None or self._surface is not None
         u8, _, self._device_hist = F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=want, label_true=label_trues,
                                                 hist=self._device_hist, num_classes=self.n_classes)[:3]
@@ -262,6 +308,24 @@ class runningScore(object):
         else:
             stats, sums = np.zeros((2, 0, c, 5), dtype=np.int64), np.zeros((2, 0, c), dtype=np.float64)
         return surface_scores(stats, sums, c, self.dataset, self._surface.pct)
+
+    def get_component_scores(self):
+        """What the component filter did since the last reset(), summed over the evaluated samples; None while the option is off.
+        class_components / class_kept_components = the components found / kept per class, class_removed_pixels = the pixels a class
+        lost (0 for the fill class, which only gains), components / kept_components / removed_pixels = their sums over the classes.
+        One device -> host copy of 4 C integers."""
+        if self._components is None:
+            return None
+        c = self.n_classes
+        if self._component_stats:
+            st = torch.cat(self._component_stats, dim=0).sum(dim=0).cpu().numpy()
+        else:
+            st = np.zeros((c, 4), dtype=np.int64)
+        removed = np.where(np.arange(c) == self._components.fill, 0, st[:, 2] - st[:, 3])
+        return {"components": int(st[:, 0].sum()), "kept_components": int(st[:, 1].sum()), "removed_pixels": int(removed.sum()),
+                "class_components": dict(zip(range(c), (int(v) for v in st[:, 0]))),
+                "class_kept_components": dict(zip(range(c), (int(v) for v in st[:, 1]))),
+                "class_removed_pixels": dict(zip(range(c), (int(v) for v in removed)))}
 
     def _fold_device(self):
         if self._device_hist is not None:
@@ -301,6 +365,7 @@ class runningScore(object):
         self._device_hist = None
         self._boundary_counts = None
         self._surface_records = []
+        self._component_stats = []
 
 
 def kept_classes(n_classes, dataset):
@@ -422,6 +487,38 @@ def parse_surface(spec):
         except ValueError as e:
             raise ValueError("--surface: %r: %s" % (tok, e))
     return F.SurfaceOptions(**kw)
+
+
+def parse_components(spec):
+    """`--components`: the connected-component filter of the evaluation's label maps.  "on" = min_area=64 with 8-connectivity and
+    fill=0 (an untuned default, not a published one); else a comma list over `largest` (keep only the largest component of each sample
+    and class), min_area=N (keep components of at least N pixels), conn=4|8, fill=K (the class removed pixels get) and skip=a:b:c
+    (classes never filtered) - at least one of largest / min_area has to be named, keys left out keep their defaults.  Returns a
+    F.ComponentOptions, None for "" / None.  Raises ValueError naming the bad token."""
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    if spec == "on":
+        return F.ComponentOptions(min_area=64)
+    kw = {}
+    for tok in spec.split(","):
+        key, sep, val = tok.strip().partition("=")
+        if key in kw or not ((key == "largest" and not sep) or (key in ("min_area", "conn", "fill", "skip") and sep)):
+            raise ValueError("--components: %r is not 'on', largest or one key=value over min_area, conn, fill, skip" % tok)
+        if key == "largest":
+            kw[key] = True
+            continue
+        try:
+            kw[key] = tuple(int(v) for v in val.split(":")) if key == "skip" else int(val)
+        except ValueError:
+            raise ValueError("--components: %r is not an integer%s" % (tok, " list a:b:c" if key == "skip" else ""))
+        try:
+            F.ComponentOptions(**{key: kw[key]})
+        except ValueError as e:
+            raise ValueError("--components: %r: %s" % (tok, e))
+    if "largest" not in kw and "min_area" not in kw:
+        raise ValueError("--components: %r names neither largest nor min_area: nothing would be filtered" % spec)
+    return F.ComponentOptions(**kw)
 
 
 def dice_scores(hist):

@@ -40,6 +40,9 @@ def test(args, test_loader=None):
     os.makedirs(out, exist_ok=True)
     tta = utils.parse_tta(getattr(args, 'tta', ''))
     crf = utils.parse_crf(getattr(args, 'crf', ''))
+    comp = utils.parse_components(getattr(args, 'components', ''))
+    # --components: the predicted label maps go through the connected-component filter on the device before they are copied and saved
+    filt = lambda t: t if comp is None else F.component_filter(t, n_channels, comp)[0]
     Gsi.eval()
     with torch.no_grad():
         for i, (image_test, image_name) in enumerate(test_loader):
@@ -48,13 +51,13 @@ def test(args, test_loader=None):
             if crf is not None:     # --crf: the windowed dense CRF, guided by the images, at the size the plain path predicts at
                 size = image_test.shape[2:] if tta else logits.shape[2:]
                 scores, probs = utils.crf_scores(Gsi, image_test, size, tta) if tta else (logits, False)
-                prediction = F.crf_labels(scores, utils.crf_guide(image_test, size), size, crf, probs=probs)[0].cpu().numpy()
+                prediction = filt(F.crf_labels(scores, utils.crf_guide(image_test, size), size, crf, probs=probs)[0]).cpu().numpy()
             elif tta:           # --tta: Gsi once per view, the views fused into one uint8 map at the images' size
-                prediction = F.predict_labels_ms(*utils.tta_logits(Gsi, image_test, tta), image_test.shape[2:])[0].cpu().numpy()
+                prediction = filt(F.predict_labels_ms(*utils.tta_logits(Gsi, image_test, tta), image_test.shape[2:])[0]).cpu().numpy()
             elif F.FUSE_PREDICT[0]:          # softmax -> argmax on the net's own output: one launch, a uint8 map (identity resize)
-                prediction = F.predict_labels(logits, logits.shape[2:])[0].cpu().numpy()
+                prediction = filt(F.predict_labels(logits, logits.shape[2:])[0]).cpu().numpy()
             else:
-                prediction = F.argmax_index(F.softmax2d(logits)).cpu().numpy()
+                prediction = filt(F.argmax_index(F.softmax2d(logits))).cpu().numpy()
             for j in range(prediction.shape[0]):
                 utils.colorize_mask(prediction[j], args.dataset).save(os.path.join(out, image_name[j] + '.png'))
             print('Epoch-', str(i + 1), ' Done!')

@@ -50,16 +50,19 @@ def validation(args, val_loader=None):
     except Exception:
         print(' [*] No checkpoint!')
 
+    comp = utils.parse_components(getattr(args, 'components', ''))
+    # --components: every predicted label map goes through the connected-component filter on the device before it is copied and saved
+    filt = lambda t: t if comp is None else F.component_filter(t, n_channels, comp)[0]
     fused = F.FUSE_PREDICT[0]                     # SSCG_FUSE_PREDICT=0: the chain of separate passes (same bits)
     soft = lambda lg: F.softmax2d(F.upsample_bilinear(lg, size))                    # interp -> Softmax2d
     # Gsi's logits -> interp -> Softmax2d -> argmax: uint8 label maps from one launch, or the int64 maps of the separate passes
-    labels = (lambda lg: F.predict_labels(lg, size)[0].cpu().numpy()) if fused else (lambda lg: F.argmax_index(soft(lg)).cpu().numpy())
+    labels = (lambda lg: filt(F.predict_labels(lg, size)[0]).cpu().numpy()) if fused else (lambda lg: filt(F.argmax_index(soft(lg))).cpu().numpy())
     tta = utils.parse_tta(getattr(args, 'tta', ''))
     # --tta: Gsi once per view of the images, the views fused into one uint8 map (F.FUSE_TTA: in one launch)
-    labels_ms = lambda x: F.predict_labels_ms(*utils.tta_logits(Gsi, x, tta), size)[0].cpu().numpy()
+    labels_ms = lambda x: filt(F.predict_labels_ms(*utils.tta_logits(Gsi, x, tta), size)[0]).cpu().numpy()
     crf = utils.parse_crf(getattr(args, 'crf', ''))
     # --crf: the windowed dense CRF, guided by the images, on Gsi's logits (with --tta: on the views' summed probabilities)
-    labels_crf = lambda x, scores, probs: F.crf_labels(scores, utils.crf_guide(x, size), size, crf, probs=probs)[0].cpu().numpy()
+    labels_crf = lambda x, scores, probs: filt(F.crf_labels(scores, utils.crf_guide(x, size), size, crf, probs=probs)[0]).cpu().numpy()
     img = lambda x: F.act_fwd(F.to_nhwc(F.upsample_bilinear(Gis(x), size)), F.ACT_TANH)   # Gis -> interp -> Tanh
     Gsi.eval()
     with torch.no_grad():
