@@ -501,6 +501,63 @@ int sscg_ce_bwd_ohem(const float* logits, const int64_t* labels, const float* ke
 int sscg_upsample_head_bwd_h(const float* x, const int64_t* labels, const float* keys, const float* thr, const float* class_w,
                              float smoothing, const float* dy_soft, const float* g_ce, const float* valid, const float* coef,
                              const float* g_dice, int batch, float* dx, int N, int H, int W, int C, int OH, int OW, void* stream);
+/* Boundary loss on signed distance maps of the same head (opt-in; the reference has none): Kervadec et al., "Boundary loss for highly
+ * unbalanced segmentation" (MIDL 2019).  Labels are [N][OH][OW] int64; a pixel is COUNTED when 0 <= y < C (sscg_ce_fwd's rule: 255,
+ * -100 and any id >= C are void).
+ * Signed squared distance map  sdm[n][oy][ox][c], int32, class innermost (the layout the head's stencil reads):
+ *   - for sample n and class c the MEMBERS are the pixels with y == c; void pixels are non-members of every class;
+ *   - d2 = the squared Euclidean distance, in pixels, from a pixel to the nearest pixel of the opposite membership in the same sample:
+ *     exact at any separation, no window, never across samples;
+ *   - sdm = +d2 at a non-member, -d2 at a member;
+ *   - sdm = 0 everywhere in the plane when the class has no member in the sample (Kervadec's one_hot2dist leaves zeros for an absent
+ *     class) or every pixel of the sample is a member (pinned to zero: there is no opposite pixel to measure to).
+ * Level set  phi, fp32, formed from sdm wherever it is needed and never stored:
+ *     s > 0: phi = sqrt_rn((float)s)        s < 0: phi = 1 - sqrt_rn((float)(-s))        s == 0: phi = 0
+ *   which is distance(neg) * neg - (distance(pos) - 1) * pos; every step is correctly rounded, so sqrt on the fp32 cast gives the same
+ *   bits on the host.
+ * Loss: p = softmax over C of the logits resized to [OH][OW] (the pinned arithmetic of sscg_upsample_bilinear_fwd and
+ *   sscg_softmax_fwd, as in sscg_dice_fwd; OH == H && OW == W: the flat form, no interpolation arithmetic); class_w [C] fp32 >= 0
+ *   (NULL = all ones), Wsum = sum_c w_c, V = the counted pixels of the call;
+ *     loss = (1 / (V * Wsum)) * sum over counted pixels, sum_c w_c p_c phi_c
+ *   V == 0: loss 0, gradient zero (no 0 / 0).  The host refuses Wsum == 0.  The loss may be negative: a perfect prediction sits at
+ *   its minimum.  Under data parallelism V is per rank.
+ * Gradient: d loss / d p_c = k w_c phi_c at a counted pixel, k = 1 / (V * Wsum); it enters the head's backward as one more term of q_c
+ *   in d_c = p_c (q_c - sum_k p_k q_k), beside dy_soft and the Dice term.  The forward leaves k on the device (`coef`).
+ * sscg_sdm: a presence pass (members per (n, c): integer atomics through LDS bins), then per chunk of 16 classes a column pass (the
+ *   vertical distance to the nearest pixel of the opposite membership, lanes on consecutive columns) and a row pass (a row's column
+ *   distances of one class staged in LDS, per pixel the exact minimum of dx^2 + g[x']^2 by a walk outwards that stops when
+ *   dx^2 >= best) over EVERY pixel.  Every loop's bound is known at launch, no workgroup waits on another, nothing spins on a value.
+ *   Every element of sdm is written (the planes without a contour as zeros); nothing is read from what sdm or the workspace held.
+ *   ws: sscg_sdm_workspace(N, H, W, C) bytes: 4 N C for the counts + 2 min(C, 16) bytes per label pixel, 256-byte aligned parts.
+ *   sdm itself is 4 C bytes per label pixel.
+ * sscg_boundary_loss_fwd: `loss` (fp32 scalar), `sums` (nullable) [N][C] fp64 = per sample and class the sum of p_c phi_c over the
+ *   counted pixels (unweighted), `counted` (nullable) = V, `coef` = k (fp32 scalar).  One thread per output pixel, per-block fp64
+ *   records, fixed-order reduction, a one-block finish; no float atomics: the same call twice gives the same bits, and the resized form
+ *   gives the bits of the identity form on sscg_upsample_bilinear_fwd's output.  Neither the resized logits nor the probabilities are
+ *   written.  ws: sscg_boundary_loss_workspace(N, OH, OW, C) bytes.
+ * sscg_boundary_loss_bwd: the flat backward (logits [N][H][W][C], labels and sdm at the same size, coef of an identity-size forward):
+ *   dx = (g ? *g : 1) * w * p_c (q_c - sum_k p_k q_k), q_c = k w_c phi_c; a zero row for a pixel that is not counted.
+ * sscg_upsample_head_bwd_b: the WHOLE backward of the head in one stencil launch when the boundary branch is live - the arguments of
+ *   sscg_upsample_head_bwd_h plus sdm, bnd_coef (k), bnd_w (the class weights of the boundary term, NULL = ones) and g_bnd (NULL = 1).
+ *   With sdm: labels and bnd_coef are required; the cross entropy is live when `valid` is given - over the pixels with keys <= tau when
+ *   keys (and thr) are given, over every counted pixel otherwise (the unmined cross entropy of sscg_ce_fwd_w formed in the stencil, D =
+ *   valid) - dy_soft and coef as in _bwd_h.  With sdm == NULL it runs sscg_upsample_head_bwd_h itself (the same kernels, the same
+ *   bits), except that valid without keys is refused there: that entry would drop the cross entropy.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, C outside 1..64, non-positive sizes, what _bwd_h refuses),
+ * SSCG_ERR_UNSUPPORTED (N*OH*OW or N*H*W >= 2^31, (OH-1)^2 + (OW-1)^2 >= 2^30), SSCG_ERR_WORKSPACE; the workspace queries return 0 for
+ * sizes the entries refuse.  (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+size_t sscg_sdm_workspace(int N, int H, int W, int C);
+int sscg_sdm(const int64_t* labels, int N, int H, int W, int C, int32_t* sdm, void* ws, size_t ws_bytes, void* stream);
+size_t sscg_boundary_loss_workspace(int N, int OH, int OW, int C);
+int sscg_boundary_loss_fwd(const float* x, const int64_t* labels, const int32_t* sdm, int N, int H, int W, int C, int OH, int OW,
+                           const float* class_w, float* loss, double* sums, int64_t* counted, float* coef, void* ws, size_t ws_bytes,
+                           void* stream);
+int sscg_boundary_loss_bwd(const float* x, const int64_t* labels, const int32_t* sdm, int N, int H, int W, int C, const float* class_w,
+                           const float* coef, const float* g, float w, float* dx, void* stream);
+int sscg_upsample_head_bwd_b(const float* x, const int64_t* labels, const float* keys, const float* thr, const float* class_w,
+                             float smoothing, const float* dy_soft, const float* g_ce, const float* valid, const float* coef,
+                             const float* g_dice, int batch, float* dx, int N, int H, int W, int C, int OH, int OW, const int32_t* sdm,
+                             const float* bnd_coef, const float* bnd_w, const float* g_bnd, void* stream);
 /* ------------------------------------------------------------------ inference heads (ABI v18): one launch from a generator's output
  * to what its consumer keeps.  Forward only; never launched by the training step.
  *

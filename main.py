@@ -2,7 +2,8 @@
 """Command line of the reference (main.py:10-87) driving the MI355X build: same flags, same defaults, same
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
---ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
+--boundary_loss, --boundary_loss_skip, --boundary_loss_ramp.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -51,6 +52,9 @@ class _Args(Namespace):
     boundary = ""
     surface = ""
     components = ""
+    boundary_loss = 0.0
+    boundary_loss_skip = ""
+    boundary_loss_ramp = 0
 
 
 def get_args(argv=None):
@@ -154,6 +158,18 @@ def get_args(argv=None):
                              "'conn=4|8' (default 8), 'skip=a:b:c' for classes never filtered; 'on' for min_area=64 (an untuned "
                              "default); e.g. largest,min_area=16,skip=3; combines with --tta, --crf, --boundary, --surface and "
                              "--ema_decay (default: off, the maps are scored as predicted)")
+    parser.add_argument("--boundary_loss", type=float, default=SUPPRESS, metavar="F",
+                        help="add F times the boundary loss of Kervadec et al. (MIDL 2019) to every ground-truth cross entropy "
+                             "(lab_loss_CE, gt_cycle_loss, the supervised loss), inside that term's own weight: the softmax "
+                             "probabilities times the signed distance to the ground-truth contour of each class, computed on the "
+                             "device; reported as lab_loss_boundary / gt_cycle_boundary / boundary_loss (it may be negative); "
+                             "combines with --ce_weights, --label_smoothing, --dice_weight and --ohem_thresh; F >= 0, 0 = off "
+                             "(default: off, the reference's losses)")
+    parser.add_argument("--boundary_loss_skip", type=str, default=SUPPRESS, metavar="LIST",
+                        help="comma list of class ids the boundary loss leaves out (weight 0), as --dice_skip (default: none)")
+    parser.add_argument("--boundary_loss_ramp", type=int, default=SUPPRESS, metavar="N",
+                        help="raise the boundary term's weight linearly over the first N epochs, F * min(1, epoch / N); N >= 0, "
+                             "0 = constant (default: 0)")
     args = parser.parse_args(argv, namespace=_Args())
     if args.crf.strip():
         try:
@@ -193,6 +209,15 @@ def get_args(argv=None):
         n_cls = {"voc2012": 21, "cityscapes": 20, "acdc": 4}[args.dataset]
         if not all(t.isdigit() and int(t) < n_cls for t in toks) or len(set(int(t) for t in toks)) >= n_cls:
             parser.error("--dice_skip must be a comma list of class ids in [0, %d) that leaves a class over" % n_cls)
+    if not args.boundary_loss >= 0.0 or args.boundary_loss == float("inf"):
+        parser.error("--boundary_loss must be a finite number >= 0")
+    if args.boundary_loss_ramp < 0:
+        parser.error("--boundary_loss_ramp must be an integer >= 0")
+    if args.boundary_loss_skip.strip():
+        toks = [t.strip() for t in args.boundary_loss_skip.split(",")]
+        n_cls = {"voc2012": 21, "cityscapes": 20, "acdc": 4}[args.dataset]
+        if not all(t.isdigit() and int(t) < n_cls for t in toks) or len(set(int(t) for t in toks)) >= n_cls:
+            parser.error("--boundary_loss_skip must be a comma list of class ids in [0, %d) that leaves a class over" % n_cls)
     if args.adamw and not args.weight_decay > 0.0:
         parser.error("--adamw decouples the weight decay from the gradient: it needs --weight_decay F with F > 0")
     if args.weight_decay < 0.0 or args.weight_decay != args.weight_decay:

@@ -136,6 +136,12 @@ SIGNATURES = {
     "sscg_ohem_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _f, _f, _i64, _f, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "sscg_ce_bwd_ohem": (_i, [_p, _p, _p, _p, _i64, _i, _p, _f, _p, _f, _p, _p, _p]),
     "sscg_upsample_head_bwd_h": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "sscg_sdm_workspace": (_sz, [_i, _i, _i, _i]),
+    "sscg_sdm": (_i, [_p, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "sscg_boundary_loss_workspace": (_sz, [_i, _i, _i, _i]),
+    "sscg_boundary_loss_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "sscg_boundary_loss_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p]),
+    "sscg_upsample_head_bwd_b": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sscg_predict_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_predict_head_ms": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.c_uint32, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),

@@ -1,8 +1,10 @@
-// The backward of the fused label head (include/sscg.h: sscg_upsample_head_bwd / _bwd_d / _bwd_h): ONE gather kernel for every branch
-// that can be live - the softmax map's upstream gradient, the cross entropy (plain or mined) and the Dice loss - through the adjoint
-// of the resize.  One block per SOURCE pixel walks the output pixels whose stencil touches it (head_window / head_weight / head_logits
-// of head_geom.h: the forward's candidates, weights and order).  Per output pixel, with p = softmax(resized logits):
+// The backward of the fused label head (include/sscg.h: sscg_upsample_head_bwd / _bwd_d / _bwd_h / _bwd_b): ONE gather kernel for every
+// branch that can be live - the softmax map's upstream gradient, the cross entropy (plain or mined), the Dice loss and the boundary
+// loss - through the adjoint of the resize.  One block per SOURCE pixel walks the output pixels whose stencil touches it (head_window /
+// head_weight / head_logits of head_geom.h: the forward's candidates, weights and order).  Per output pixel, with p = softmax(resized
+// logits):
 //     q_c = dy_soft[c]   (SOFT)   + g_dice * (A[c] [y == c] + B[c])   (DICE; counted pixels: y in [0, C))
+//                                 + g_bnd * k * wb_c * phi_c            (BND; counted pixels; phi = sscg_level_set(sdm[o][c]), sdm.hip)
 //     d_c = p_c (q_c - sum_k p_k q_k)  +  [kept] ge ((a + bs W) p_c - a [c == y] - bs w_c)          (MINED; a = (1-eps) w_y, bs = eps / C,
 //                                                                                                   ge = g_ce / D, kept: keys <= tau)
 // weighted by the stencil weight and summed over the block by head_store_sum, which - !MINED - adds the cross-entropy gradient the
@@ -18,25 +20,32 @@ namespace {
 // MINED only.  A MINED instantiation serves every call of sscg_upsample_head_bwd_h and so keeps its two loss branches as RUN-TIME
 // tests (`dice`: coef given, `ce`: keys given) - with a branch off it still adds that branch's zero, which a compile-time flag would
 // drop, and the sum's signed zeros with it.
-template <int CT, bool SOFT, bool DICE, bool MINED>
+// BND: the boundary term of sscg_upsample_head_bwd_b, on top of a MINED instantiation.  There the cross entropy is live when `valid`
+// is given and mined when `keys` is given too: without keys every counted pixel is kept, which is the unmined cross entropy formed in
+// the stencil (that entry takes no gradient the forward left).  Per touched pixel it reads the C contiguous int32 of sdm.
+struct HeadBnd { const int32_t* sdm; const float* coef; const float* w; const float* g; };
+
+template <int CT, bool SOFT, bool DICE, bool MINED, bool BND = false>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab,
                                                        const float* __restrict__ dy_soft, const float* __restrict__ dl_ce,
                                                        const float* __restrict__ g_ce, const float* __restrict__ valid,
                                                        const float* __restrict__ coef, const float* __restrict__ g_dice, int batch,
                                                        const float* __restrict__ keys, const float* __restrict__ thr,
-                                                       const float* __restrict__ class_w, float smoothing, float* __restrict__ dx, HeadGeom g) {
+                                                       const float* __restrict__ class_w, float smoothing, float* __restrict__ dx, HeadGeom g,
+                                                       HeadBnd bnd) {
     static_assert(SOFT || DICE, "an instantiation with nothing to gather");
     static_assert(DICE || !MINED, "the mined instantiations carry the Dice branch as a run-time test");
+    static_assert(MINED || !BND, "the boundary instantiations are mined ones with one more term");
     // the run-time class count without a loss branch keeps its class loops rolled (a `break`, as head_logits): unrolled and predicated
     // that instance needs 168 registers instead of 104 and loses a wave per SIMD; the instances with a loss branch do not
     constexpr bool ROLLED = CT == 0 && !DICE;
     __shared__ float red[4][SSCG_MAXC];
-    __shared__ float sA[SSCG_MAXC], sB[SSCG_MAXC], sW[SSCG_MAXC];
+    __shared__ float sA[SSCG_MAXC], sB[SSCG_MAXC], sW[SSCG_MAXC], sQ[SSCG_MAXC];
     const int C = CT ? CT : g.C;
     const int b = blockIdx.x;
     const HeadWindow win = head_window(g, b);
     const int ix = win.ix, iy = win.iy, n = win.n, oy_lo = win.oy_lo, ox_lo = win.ox_lo;
-    const bool dice = DICE && (!MINED || coef != nullptr), ce = MINED && keys != nullptr;
+    const bool dice = DICE && (!MINED || coef != nullptr), ce = MINED && (BND ? valid != nullptr : keys != nullptr);
     float wsum = 0.f, bs = 0.f, tau = 0.f, ge = 0.f;
     if constexpr (DICE) {
         if ((int)threadIdx.x < C) {
@@ -48,6 +57,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
             }
             sA[threadIdx.x] = qa; sB[threadIdx.x] = qb;
             if constexpr (MINED) sW[threadIdx.x] = class_weight(class_w, threadIdx.x);
+            if constexpr (BND) sQ[threadIdx.x] = (bnd.g ? *bnd.g : 1.f) * *bnd.coef * class_weight(bnd.w, threadIdx.x);
         }
         __syncthreads();
     }
@@ -56,7 +66,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
         bs = smoothing / (float)C;
         if (ce) {
             const float nv = *valid;
-            tau = *thr;
+            if constexpr (BND) tau = keys ? *thr : 0.f;
+            else tau = *thr;
             ge = (g_ce ? *g_ce : 1.f) * (nv > 0.f ? 1.f / nv : 0.f);
         }
     }
@@ -78,18 +89,33 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
             const int64_t l64 = lab[o];
             l = (l64 < 0 || l64 >= C) ? -1 : (int)l64;
         }
-        const bool kept = ce && l >= 0 && keys[o] <= tau;
+        bool kept;
+        if constexpr (BND) kept = ce && l >= 0 && (keys == nullptr || keys[o] <= tau);
+        else kept = ce && l >= 0 && keys[o] <= tau;
         const bool dq = dice && l >= 0;
-        if (!SOFT && !kept && !dq) continue;         // nothing flows through this pixel
+        if (!SOFT && !kept && !dq && !(BND && l >= 0)) continue;         // nothing flows through this pixel
         float v[CT ? CT : SSCG_MAXC];
         int y0, x0;
         head_logits<CT>(xn, g, oy, ox, C, v, &y0, &x0);
         const float inv = sscg_softmax_exp<CT>(v, C);
         const float* gr = SOFT ? dy_soft + o * C : nullptr;
+        // The boundary term of q_c is used twice per class.  HOLD: formed once and held in registers.  Beside v and acc that costs the
+        // instantiations of 20 / 21 classes without dy_soft (the training step's) their second wave per SIMD - 290 registers against
+        // 254 - so those form it where it is used instead: the second read of sdm hits the cache (measured: profiles/boundary_loss.txt).
+        constexpr bool HOLD = BND && !(CT >= 16 && !SOFT);
+        const int32_t* sr = BND ? bnd.sdm + o * C : nullptr;
+        float qb[HOLD ? (CT ? CT : SSCG_MAXC) : 1];
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
+                if (CT || c < C) qb[c] = l >= 0 ? sQ[c] * sscg_level_set(sr[c]) : 0.f;
+        }
         const auto upstream = [&](int c) {           // q_c
             if constexpr (!DICE) return gr[c];
             else {
-                const float q = dq ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
+                float q = dq ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
+                if constexpr (HOLD) q += qb[c];
+                else if constexpr (BND) q += l >= 0 ? sQ[c] * sscg_level_set(sr[c]) : 0.f;
                 if constexpr (SOFT) return q + gr[c];
                 else return q;
             }
@@ -134,14 +160,15 @@ __global__ void head_scale_kernel(const float* __restrict__ dl, const float* __r
 // dice / mined: the entry's branches; SOFT follows dy_soft.  The argument order is the kernel's.
 void launch_head_bwd(const HeadGeom& g, hipStream_t st, bool dice, bool mined, const float* x, const int64_t* lab, const float* dy_soft,
                      const float* dl_ce, const float* g_ce, const float* valid, const float* coef, const float* g_dice, int batch,
-                     const float* keys, const float* thr, const float* class_w, float smoothing, float* dx) {
+                     const float* keys, const float* thr, const float* class_w, float smoothing, float* dx, const HeadBnd& bnd = HeadBnd()) {
     const dim3 grid((unsigned)(g.N * g.H * g.W)), blk(256);
     sscg_dispatch_classes(g.C, [&](auto ct) {
         constexpr int CT = decltype(ct)::value;
         const auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, keys, thr, class_w, smoothing, dx, g);
+            hipLaunchKernelGGL(kernel, grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, keys, thr, class_w, smoothing, dx, g, bnd);
         };
-        if (mined) dy_soft ? go(head_bwd_kernel<CT, true, true, true>) : go(head_bwd_kernel<CT, false, true, true>);
+        if (bnd.sdm) dy_soft ? go(head_bwd_kernel<CT, true, true, true, true>) : go(head_bwd_kernel<CT, false, true, true, true>);
+        else if (mined) dy_soft ? go(head_bwd_kernel<CT, true, true, true>) : go(head_bwd_kernel<CT, false, true, true>);
         else if (dice) dy_soft ? go(head_bwd_kernel<CT, true, true, false>) : go(head_bwd_kernel<CT, false, true, false>);
         else go(head_bwd_kernel<CT, true, false, false>);
     });
@@ -191,6 +218,31 @@ extern "C" int sscg_upsample_head_bwd_h(const float* x, const int64_t* labels, c
     if (!head_geom(&g, N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
     launch_head_bwd(g, (hipStream_t)stream, true, true, x, labels, dy_soft, nullptr, g_ce, valid, coef, g_dice, batch, keys, thr, class_w, smoothing,
                     dx);
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
+extern "C" int sscg_upsample_head_bwd_b(const float* x, const int64_t* labels, const float* keys, const float* thr, const float* class_w,
+                                        float smoothing, const float* dy_soft, const float* g_ce, const float* valid, const float* coef,
+                                        const float* g_dice, int batch, float* dx, int N, int H, int W, int C, int OH, int OW,
+                                        const int32_t* sdm, const float* bnd_coef, const float* bnd_w, const float* g_bnd, void* stream) {
+    if (!sdm) {
+        // the unmined cross entropy exists in the boundary instantiations only: here it would be dropped without a word
+        if (!keys && valid) return SSCG_ERR_BAD_ARG;
+        return sscg_upsample_head_bwd_h(x, labels, keys, thr, class_w, smoothing, dy_soft, g_ce, valid, coef, g_dice, batch, dx, N, H, W, C,
+                                        OH, OW, stream);
+    }
+    if (!x || !dx || !labels || !bnd_coef || !sizes_ok(N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
+    if (keys && (!thr || !valid)) return SSCG_ERR_BAD_ARG;
+    if (!smoothing_ok(smoothing) || (batch != 0 && batch != 1)) return SSCG_ERR_BAD_ARG;
+    if (too_large(N, H, W, OH, OW)) return SSCG_ERR_UNSUPPORTED;
+    const uint64_t ey = (uint64_t)(OH - 1), ex = (uint64_t)(OW - 1);
+    if (ey * ey + ex * ex >= ((uint64_t)1 << 30)) return SSCG_ERR_UNSUPPORTED;      // sscg_sdm's range
+    HeadGeom g;
+    if (!head_geom(&g, N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
+    const HeadBnd bnd = {sdm, bnd_coef, bnd_w, g_bnd};
+    launch_head_bwd(g, (hipStream_t)stream, true, true, x, labels, dy_soft, nullptr, g_ce, valid, coef, g_dice, batch, keys, thr, class_w, smoothing,
+                    dx, bnd);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

@@ -164,6 +164,15 @@ __device__ __forceinline__ int sscg_first_max(const float* a, int C) {
     return bi;
 }
 
+// The level set of the boundary loss from one signed squared distance (include/sscg.h: sscg_sdm): sqrt(s) outside the class,
+// 1 - sqrt(-s) inside, 0 on a plane without a contour.  The conversion, the square root and the subtraction are each rounded once:
+// the bits of numpy's sqrt on the fp32 cast.  Nothing here can contract.
+__device__ __forceinline__ float sscg_level_set(int s) {
+    if (s > 0) return __fsqrt_rn((float)s);
+    if (s < 0) return 1.f - __fsqrt_rn((float)(-s));
+    return 0.f;
+}
+
 // ---- the [C][C] confusion counts of one workgroup of 256 threads in LDS (nb = C * C bins; nb == 0, block-uniform: no histogram asked
 // for, nothing happens): clear, count while the pixels are walked, flush with one 64-bit atomic per bin that was hit.  Integer sums:
 // the result does not depend on the order.

@@ -3148,6 +3148,97 @@ class OhemCrossEntropyFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
+# ----------------------------------------------------------------------------- boundary loss (opt-in; include/sscg.h: sscg_sdm)
+def boundary_weight(values, num_classes, device):
+    """The class-weight operand of the boundary loss, as dice_weight: C numbers, finite, >= 0, not all zero (the loss divides by
+    their sum), sent to `device` as fp32 [C]."""
+    w = ce_weight(values, num_classes, torch.device("cpu"))
+    if not float(w.sum()) > 0.0:
+        raise ValueError("boundary weights: every entry is 0 (the loss divides by their sum)")
+    return w.to(device)
+
+
+class BoundaryLossOptions(object):
+    """The boundary branch of upsample_softmax_losses: weight (boundary_weight's tensor, or None = all ones)."""
+    __slots__ = ("weight",)
+
+    def __init__(self, weight=None):
+        self.weight = weight
+
+
+def _boundary_options(boundary):
+    if isinstance(boundary, dict):
+        boundary = BoundaryLossOptions(**boundary)
+    if not isinstance(boundary, BoundaryLossOptions):
+        raise TypeError("boundary must be a functional.BoundaryLossOptions (or a dict of its arguments), not %r" % (boundary,))
+    return boundary
+
+
+def signed_distance_maps(labels, num_classes):
+    """sscg_sdm: int64 labels [N,H,W] on the device -> int32 [N,H,W,C], per class +d2 outside it and -d2 inside, d2 = the exact squared
+    Euclidean distance to the nearest pixel of the opposite membership in the sample; a class absent from a sample (or filling it)
+    has a zero plane.  Labels outside [0, C) belong to no class."""
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int64 and labels.dim() == 3):
+        raise _lib.SscgError("signed_distance_maps: labels must be an int64 [N, H, W] tensor on the GPU")
+    labels = labels.contiguous()
+    n, h, w = labels.shape
+    c = int(num_classes)
+    sdm = torch.empty((n, h, w, c), dtype=torch.int32, device=labels.device)
+    ws = torch.empty(lib.sscg_sdm_workspace(n, h, w, c), dtype=torch.uint8, device=labels.device)
+    check(lib.sscg_sdm(labels.data_ptr(), n, h, w, c, sdm.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sscg_sdm")
+    return sdm
+
+
+def boundary_loss_fwd(x, labels, size, sdm, weight=None, want_sums=False):
+    """sscg_boundary_loss_fwd on channels-last fp32 logits x [N,C,H,W], int64 labels [N,OH,OW] and their signed_distance_maps
+    (size = (OH, OW); (H, W): the flat form): (loss, coef = k, sums [N,C] fp64 or None, counted int64 scalar or None).  No autograd."""
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    _check_labels(labels, n * oh * ow)
+    _class_weight_ok(weight, c, x.device, "boundary")
+    if sdm.dtype != torch.int32 or sdm.numel() != n * oh * ow * c or not sdm.is_contiguous() or sdm.device != x.device:
+        raise _lib.SscgError("sdm must be a contiguous int32 [N, OH, OW, C] tensor on %s (functional.signed_distance_maps makes one)" % x.device)
+    loss, coef = _scalar(x.device), _scalar(x.device)
+    sums = torch.empty((n, c), dtype=torch.float64, device=x.device) if want_sums else None
+    counted = torch.empty((), dtype=torch.int64, device=x.device) if want_sums else None
+    ws = torch.empty(lib.sscg_boundary_loss_workspace(n, oh, ow, c), dtype=torch.uint8, device=x.device)
+    check(lib.sscg_boundary_loss_fwd(x.data_ptr(), labels.data_ptr(), sdm.data_ptr(), n, h, w, c, oh, ow, _ptr(weight), loss.data_ptr(),
+                                     _ptr(sums), _ptr(counted), coef.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "sscg_boundary_loss_fwd")
+    return loss, coef, sums, counted
+
+
+class BoundaryLossFn(torch.autograd.Function):
+    """Boundary loss of logits [N,C,H,W] against labels [N,H,W] (include/sscg.h: sscg_sdm, sscg_boundary_loss_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight):
+        _need_hip(logits, f32_only=True)
+        logits = to_nhwc(logits)
+        labels = labels.contiguous()
+        sdm = signed_distance_maps(labels, logits.shape[1])
+        loss, coef, _, _ = boundary_loss_fwd(logits, labels, logits.shape[2:], sdm, weight)
+        ctx.weight = weight
+        ctx.save_for_backward(logits, labels, sdm, coef)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, sdm, coef = ctx.saved_tensors
+        n, c, h, w = logits.shape
+        dx = torch.empty_like(logits, memory_format=CL)
+        check(lib.sscg_boundary_loss_bwd(logits.data_ptr(), labels.data_ptr(), sdm.data_ptr(), n, h, w, c, _ptr(ctx.weight), coef.data_ptr(),
+                                         g.data_ptr(), 1.0, dx.data_ptr(), _stream()), "sscg_boundary_loss_bwd")
+        return dx, None, None
+
+
+def boundary_loss(logits, labels, weight=None):
+    """Kervadec's boundary loss: the mean over the counted pixels of sum_c w_c softmax(logits)_c phi_c / sum_c w_c, phi the level set
+    of the labels' signed distance maps (signed_distance_maps; computed here, on the device).  It may be negative.  weight:
+    boundary_weight's tensor."""
+    return BoundaryLossFn.apply(logits, labels, weight)
+
+
 # ----------------------------------------------------------------------------- the fused label head: one node for every option
 class LabelHeadFn(torch.autograd.Function):
     """interp (bilinear, align_corners=True) -> softmax2d and / or the losses, from the LOW-resolution logits (model.py:390-392, 398,
@@ -3157,10 +3248,13 @@ class LabelHeadFn(torch.autograd.Function):
     entropy is wanted - that cross entropy's gradient depends on logits and labels only, so the launch already leaves it (dl, up to
     g / valid: `valid` is the sum of the counted pixels' class weights) - then sscg_ohem_fwd (keys, selection, loss) and the Dice
     statistics with their finish.  The selection and the Dice sums couple the pixels of the call, so those two leave no gradient.
+    boundary: a BoundaryLossOptions or None - given, the node returns a fourth value, the boundary loss (sscg_sdm on the labels, then
+    sscg_boundary_loss_fwd), and every live branch of its backward rides in sscg_upsample_head_bwd_b; not given, the node is the one
+    it always was, three values included.
     Backward: ONE launch for every live branch."""
 
     @staticmethod
-    def forward(ctx, x, oh, ow, labels, want_soft, want_ce, weight, eps, dice, ohem):
+    def forward(ctx, x, oh, ow, labels, want_soft, want_ce, weight, eps, dice, ohem, boundary=None):
         _need_hip(x, f32_only=True)
         x = to_nhwc(x)
         n, c = x.shape[:2]
@@ -3170,14 +3264,23 @@ class LabelHeadFn(torch.autograd.Function):
         weight, eps, _ = _ce_options(weight, eps, c, x.device)
         mined = want_ce and ohem is not None
         plain_ce = want_ce and not mined
-        y = loss = valid = dl = keys = thr = d_loss = coef = None
-        if want_soft or plain_ce or not (mined or dice is not None):      # (nothing wanted at all: the entry refuses the call)
+        y = loss = valid = dl = keys = thr = d_loss = coef = b_loss = sdm = b_coef = None
+        if want_soft or plain_ce or not (mined or dice is not None or boundary is not None):      # (nothing wanted at all: the entry refuses the call)
             y, loss, valid, dl = _label_head_forward(x, oh, ow, labels, want_soft, plain_ce, weight, eps)
         if mined:
             loss, valid, keys, thr, _ = ohem_fwd(x, labels, (oh, ow), ohem, weight, eps)
         if dice is not None:
             d_loss, coef, _ = dice_fwd(x, labels, (oh, ow), dice.weight, dice.smooth, dice.batch)
         ctx.opts = (oh, ow, weight, eps, 1 if dice is not None and dice.batch else 0)
+        if boundary is not None:
+            sdm = signed_distance_maps(labels.view(n, oh, ow), c)
+            b_loss, b_coef, _, _ = boundary_loss_fwd(x, labels, (oh, ow), sdm, boundary.weight)
+            # the boundary backward forms the unmined cross entropy in its stencil: the gradient the forward launch left is not kept
+            ctx.boundary = (boundary.weight, want_ce)
+            ctx.save_for_backward(x, labels, valid, coef, keys, thr, sdm, b_coef)
+            ctx.set_materialize_grads(False)
+            return y, loss, d_loss, b_loss
+        ctx.boundary = None
         # only what a live branch reads: the labels just where a mined or Dice branch gathers by them
         ctx.save_for_backward(x, *((labels,) if mined or dice is not None else ()), dl, valid, coef, keys, thr)
         # an output nothing differentiates (the step reads lab_gt's softmax through .detach() only): backward gets None, not a
@@ -3186,7 +3289,9 @@ class LabelHeadFn(torch.autograd.Function):
         return y, loss, d_loss
 
     @staticmethod
-    def backward(ctx, dy, g_ce, g_dice):
+    def backward(ctx, dy, g_ce, g_dice, g_bnd=None):
+        if ctx.boundary is not None:
+            return LabelHeadFn._backward_b(ctx, dy, g_ce, g_dice, g_bnd)
         saved = ctx.saved_tensors
         x, labels = saved[0], (saved[1] if len(saved) == 7 else None)
         dl, valid, coef, keys, thr = saved[-5:]
@@ -3214,6 +3319,32 @@ class LabelHeadFn(torch.autograd.Function):
                   "sscg_upsample_head_bwd")
         return (dx,) + (None,) * 9
 
+    @staticmethod
+    def _backward_b(ctx, dy, g_ce, g_dice, g_bnd):
+        """The backward of a node with the boundary branch: one sscg_upsample_head_bwd_b launch for whatever received a gradient (a
+        boundary loss that received none leaves sdm out, and the entry runs sscg_upsample_head_bwd_h itself)."""
+        x, labels, valid, coef, keys, thr, sdm, b_coef = ctx.saved_tensors
+        oh, ow, weight, eps, batch = ctx.opts
+        b_weight, want_ce = ctx.boundary
+        use_ce = g_ce is not None and want_ce
+        use_dice = g_dice is not None and coef is not None
+        use_bnd = g_bnd is not None
+        if dy is None and not (use_ce or use_dice or use_bnd):
+            return (None,) * 11
+        n, c, h, w = x.shape
+        dx = empty_nhwc(n, c, h, w, x.device)
+        if dy is not None:
+            dy = to_nhwc(dy)
+        if not use_bnd and use_ce and keys is None:
+            # the unmined cross entropy is formed by the boundary instantiations only (no dl was kept): that branch rides along at zero
+            g_bnd, use_bnd = torch.zeros((), dtype=torch.float32, device=x.device), True
+        check(lib.sscg_upsample_head_bwd_b(x.data_ptr(), labels.data_ptr(), _ptr(keys if use_ce else None), _ptr(thr if use_ce else None),
+                                           _ptr(weight), eps, _ptr(dy), _ptr(g_ce if use_ce else None), _ptr(valid if use_ce else None),
+                                           _ptr(coef if use_dice else None), _ptr(g_dice if use_dice else None), batch, dx.data_ptr(),
+                                           n, h, w, c, oh, ow, _ptr(sdm if use_bnd else None), _ptr(b_coef), _ptr(b_weight),
+                                           _ptr(g_bnd if use_bnd else None), _stream()), "sscg_upsample_head_bwd_b")
+        return (dx,) + (None,) * 10
+
 
 class UpsampleHeadFn(object):
     """The former name of the node for the head without Dice or mining, kept for code that calls its apply(): no node of its own,
@@ -3224,16 +3355,20 @@ class UpsampleHeadFn(object):
         return LabelHeadFn.apply(x, oh, ow, labels, want_soft, labels is not None, weight, label_smoothing, None, None)[:2]
 
 
-def _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem):
-    """(softmax2d(interp(x)) or None, cross entropy or None, Dice loss or None): fused (LabelHeadFn) when the resize grows the map, else
-    the separate passes.  dice: a DiceOptions or None; ohem: an OhemOptions or None."""
+def _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, boundary=None):
+    """(softmax2d(interp(x)) or None, cross entropy or None, Dice loss or None[, boundary loss]): fused (LabelHeadFn) when the resize
+    grows the map, else the separate passes.  dice: a DiceOptions or None; ohem: an OhemOptions or None; boundary: a
+    BoundaryLossOptions (then there is a fourth value) or None."""
     oh, ow = int(size[0]), int(size[1])
     if _head_applies(x, oh, ow):
+        if boundary is not None:
+            return LabelHeadFn.apply(x, oh, ow, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, boundary)
         return LabelHeadFn.apply(x, oh, ow, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem)
     up = upsample_bilinear(x, size)
-    return ((softmax2d(up) if want_soft else None),
-            (cross_entropy(up, labels, weight, label_smoothing, ohem=ohem) if want_ce else None),
-            (dice_loss(up, labels, dice.weight, dice.smooth, dice.batch) if dice is not None else None))
+    out = ((softmax2d(up) if want_soft else None),
+           (cross_entropy(up, labels, weight, label_smoothing, ohem=ohem) if want_ce else None),
+           (dice_loss(up, labels, dice.weight, dice.smooth, dice.batch) if dice is not None else None))
+    return out if boundary is None else out + (boundary_loss(up, labels, boundary.weight),)
 
 
 def upsample_softmax_ce(x, size, labels=None, want_soft=True, weight=None, label_smoothing=0.0, *, ohem=None):
@@ -3256,6 +3391,26 @@ def upsample_softmax_ce_dice(x, size, labels, want_soft=True, weight=None, label
         if not dice.ce:
             raise ValueError("ohem mines the cross entropy: DiceOptions(ce=False) leaves it nothing to mine")
     return _label_head(x, size, labels, want_soft, dice.ce, weight, label_smoothing, dice, ohem)
+
+
+def upsample_softmax_losses(x, size, labels, *, want_soft=True, weight=None, label_smoothing=0.0, dice=None, ohem=None, boundary=None,
+                            want_ce=True):
+    """The label head with every loss it knows: (softmax2d(interp(x)) or None, cross entropy or None, Dice or None, boundary loss or
+    None) of the same resized logits - None for what was not asked.  weight / label_smoothing / ohem: the cross entropy's, as in
+    upsample_softmax_ce; dice: a DiceOptions (or a dict of its arguments), its `ce` flag and want_ce both gate the cross entropy;
+    boundary: a BoundaryLossOptions (or a dict).  Fused when the resize grows the map - still one autograd node: the existing forward
+    entries, then sscg_sdm and sscg_boundary_loss_fwd; ONE sscg_upsample_head_bwd_b launch backward - else the separate passes on
+    upsample_bilinear's output."""
+    if isinstance(dice, dict):
+        dice = DiceOptions(**dice)
+    want_ce = bool(want_ce) and (dice is None or dice.ce)
+    if ohem is not None:
+        ohem = _ohem_options(ohem)
+        if not want_ce:
+            raise ValueError("ohem mines the cross entropy: without it there is nothing to mine")
+    if boundary is None:
+        return _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem) + (None,)
+    return _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, _boundary_options(boundary))
 
 
 class MSEConstFn(torch.autograd.Function):

@@ -152,6 +152,7 @@ class _WeightedCE(object):
             self._ce_rule = spec
         self._init_dice(args, C)
         self._init_ohem(args)
+        self._init_boundary_loss(args, C)
 
     # --dice_weight / --dice_smooth / --dice_skip / --dice_batch (opt-in; the reference has no Dice): every ground-truth cross entropy L
     # becomes L + dice_w * D inside its existing weight, D = the soft Dice loss of the same resized logits (functional.dice_loss)
@@ -183,14 +184,52 @@ class _WeightedCE(object):
             return
         self.ohem_options = F.OhemOptions(thresh, min_kept=getattr(args, "ohem_min_kept", 0), min_frac=getattr(args, "ohem_min_frac", 0.0625))
 
+    # --boundary_loss / --boundary_loss_skip / --boundary_loss_ramp (opt-in; the reference has no boundary loss): every ground-truth
+    # cross entropy L becomes L + b * Boundary inside its existing weight, Boundary = Kervadec's loss of the same resized logits on the
+    # labels' signed distance maps (functional.boundary_loss), b = boundary_w * min(1, epoch / ramp): a host scalar per epoch
+    boundary_w = 0.0                # 0 = off: no launch, no loss key, no checkpoint key
+    boundary_ramp = 0               # epochs over which b rises linearly from 0 to boundary_w; 0 = constant
+    boundary_loss_options = None    # functional.BoundaryLossOptions when on
+    _boundary_b = 0.0               # the weight of the current epoch (set_boundary_epoch)
+
+    def _init_boundary_loss(self, args, C):
+        self.boundary_w = float(getattr(args, "boundary_loss", 0.0) or 0.0)
+        if not (self.boundary_w >= 0.0 and self.boundary_w < float("inf")):
+            raise ValueError("--boundary_loss %r must be a finite number >= 0" % (getattr(args, "boundary_loss", None),))
+        if self.boundary_w == 0.0:
+            return
+        ramp = getattr(args, "boundary_loss_ramp", 0) or 0
+        if isinstance(ramp, bool) or ramp != int(ramp) or int(ramp) < 0:
+            raise ValueError("--boundary_loss_ramp %r must be an integer >= 0" % (ramp,))
+        self.boundary_ramp = int(ramp)
+        weight = None
+        skip = utils.parse_boundary_loss_skip(getattr(args, "boundary_loss_skip", ""), C)
+        if skip:
+            weight = F.boundary_weight([0.0 if c in skip else 1.0 for c in range(C)], C, self._ce_device())
+        self.boundary_loss_options = F.BoundaryLossOptions(weight=weight)
+        self.set_boundary_epoch(0)
+
+    def set_boundary_epoch(self, epoch):
+        """--boundary_loss_ramp: the boundary term's weight for `epoch` (utils.boundary_loss_schedule); train() calls it once per epoch.
+        Off: nothing changes."""
+        if self.boundary_loss_options is not None:
+            self._boundary_b = utils.boundary_loss_schedule(self.boundary_w, self.boundary_ramp, epoch)
+        return self._boundary_b
+
     def _head(self, logits, labels, want_soft, kept=None):
         """(softmax map or None, cross entropy, Dice loss or None) of the ground-truth head: the plain fused head by default.
         --ohem_thresh: the cross entropy is the mined one, and `kept` (a dict) receives the kept share of this head under "ohem_kept"
-        - a device scalar from the counts the forward left, no sync."""
+        - a device scalar from the counts the forward left, no sync.  --boundary_loss: `kept` also receives the boundary loss of this
+        head under "boundary" (without a dict the term is not computed)."""
         kw = self._ce_kwargs()
         if self.ohem_options is not None:
             kw = dict(kw, ohem=self.ohem_options)
-        if self.dice_options is None:
+        if self.boundary_loss_options is not None and kept is not None:
+            out = F.upsample_softmax_losses(logits, self.crop, labels, want_soft=want_soft, dice=self.dice_options,
+                                            boundary=self.boundary_loss_options, **kw)
+            kept["boundary"] = out[3]
+            out = out[:3]
+        elif self.dice_options is None:
             out = F.upsample_softmax_ce(logits, self.crop, labels, want_soft=want_soft, **kw) + (None,)
         else:
             out = F.upsample_softmax_ce_dice(logits, self.crop, labels, want_soft=want_soft, dice=self.dice_options, **kw)
@@ -485,12 +524,16 @@ class semisuper_cycleGAN(_WeightedCE):
             fake_img, fake_img_d, fake_img_l1 = F.split(fake_img, 3)                 # consumers: Gsi, Di, L1
             recon_logits = self.Gsi(fake_img)                                        # :410
         extra_terms, extra_weights, extras = [], [], {}
-        if ohem_kept:                                                                # --ohem_thresh: the share of counted pixels lab_loss_CE kept
+        if "ohem_kept" in ohem_kept:                                                 # --ohem_thresh: the share of counted pixels lab_loss_CE kept
             extras["lab_ohem_kept"] = ohem_kept.pop("ohem_kept")
         if lab_loss_dice is not None:                                                # --dice_weight: inside lab_loss_CE's weight
             extras["lab_loss_dice"] = lab_loss_dice
             extra_terms.append(lab_loss_dice)
             extra_weights.append(a.lab_CE_weight * self.dice_w)
+        if "boundary" in ohem_kept:                                                  # --boundary_loss: inside lab_loss_CE's weight
+            extras["lab_loss_boundary"] = ohem_kept.pop("boundary")
+            extra_terms.append(extras["lab_loss_boundary"])
+            extra_weights.append(a.lab_CE_weight * self._boundary_b)
         if "l1_cycle" in self.variants:                                              # :453 (commented out in the reference)
             recon_img, recon_img_l1 = F.split(recon_img, 2)
             extras["img_cycle_l1"] = F.l1_loss(recon_img_l1, unl_img)
@@ -524,12 +567,16 @@ class semisuper_cycleGAN(_WeightedCE):
         gt_gen_loss = F.mse_const(fake_gt_dis, 1.0)                                  # :446
         img_cycle_loss = F.mse_const(resnet_fake_img_dis, 1.0)                       # :452
         _, gt_cycle_loss, gt_cycle_dice = self._head(recon_logits, labels, False, ohem_kept)    # :415 (interp), :455
-        if ohem_kept:                                                                # --ohem_thresh: gt_cycle_loss's kept share
+        if "ohem_kept" in ohem_kept:                                                 # --ohem_thresh: gt_cycle_loss's kept share
             extras["gt_cycle_ohem_kept"] = ohem_kept.pop("ohem_kept")
         if gt_cycle_dice is not None:                                                # --dice_weight: inside gt_cycle_loss's weight
             extras["gt_cycle_dice"] = gt_cycle_dice
             extra_terms.append(gt_cycle_dice)
             extra_weights.append(a.lamda_gt * self.dice_w)
+        if "boundary" in ohem_kept:                                                  # --boundary_loss: inside gt_cycle_loss's weight
+            extras["gt_cycle_boundary"] = ohem_kept.pop("boundary")
+            extra_terms.append(extras["gt_cycle_boundary"])
+            extra_weights.append(a.lamda_gt * self._boundary_b)
         lab_loss_MSE = F.l1_loss(fake_img_l1, l_img)                                 # :461
         # :464-468  gen_loss = CE_w*CE + MSE_w*L1 + adv_w*(img_gen + gt_gen) + img_cycle + lamda_gt*gt_cycle
         gen_loss = F.weighted_sum(
@@ -768,6 +815,7 @@ class semisuper_cycleGAN(_WeightedCE):
         self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
         self.set_components(utils.parse_components(getattr(args, 'components', '')))
         for epoch in range(self.start_epoch, args.epochs):
+            self.set_boundary_epoch(epoch)
             if rank0:
                 print('learning rate = %.7f' % self.g_optimizer.param_groups[0]['lr'])
             self.Gsi.train()
@@ -871,13 +919,22 @@ class supervised_model(_WeightedCE):
         self.gsi_optimizer.zero_grad()
         ohem_kept = {}
         _, loss, dice = self._head(self.Gsi(l_img), l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3]), False, ohem_kept)
+        bnd = ohem_kept.pop("boundary", None)
         if ohem_kept:   # --ohem_thresh: the step returns the mined cross entropy, the kept share of the counted pixels goes to self.extras
             self.extras = ohem_kept
-        if dice is None:
+        if dice is None and bnd is None:
             F.backward(loss)
-        else:       # --dice_weight: CE + dice_w * Dice; the step still returns the cross entropy, the Dice term goes to self.extras
+        elif bnd is None:       # --dice_weight: CE + dice_w * Dice; the step still returns the cross entropy, the Dice term goes to self.extras
             self.extras = dict(ohem_kept, dice_loss=dice.detach())
             F.backward(F.weighted_sum([loss, dice], [1.0, self.dice_w]))
+        else:       # --boundary_loss: CE [+ dice_w * Dice] + b * Boundary, the terms reported the same way
+            terms, weights = [loss, bnd], [1.0, self._boundary_b]
+            self.extras = dict(ohem_kept, boundary_loss=bnd.detach())
+            if dice is not None:
+                terms.append(dice)
+                weights.append(self.dice_w)
+                self.extras["dice_loss"] = dice.detach()
+            F.backward(F.weighted_sum(terms, weights))
         if self.dp is not None:
             F.SideStream.join(l_img.device)
             self.dp.sync_grads(self.gsi_optimizer)
@@ -948,6 +1005,7 @@ class supervised_model(_WeightedCE):
         self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
         self.set_components(utils.parse_components(getattr(args, 'components', '')))
         for epoch in range(self.start_epoch, args.epochs):
+            self.set_boundary_epoch(epoch)
             self.Gsi.train()
             for i, (l_img, l_gt, _) in enumerate(labeled_loader):
                 l_img, l_gt = utils.cuda([l_img, l_gt], args.gpu_ids)
@@ -957,6 +1015,8 @@ class supervised_model(_WeightedCE):
                     print("Epoch: (%3d) (%5d/%5d) | Crossentropy Loss:%.2e" % (epoch, i + 1, len(labeled_loader), loss))
                     if self.dice_options is not None:
                         print("Dice Loss:%.2e (weight %g)" % (float(self.extras["dice_loss"]), self.dice_w))
+                    if self.boundary_loss_options is not None:
+                        print("Boundary Loss:%.2e (weight %g)" % (float(self.extras["boundary_loss"]), self._boundary_b))
                     if self.ohem_options is not None:
                         print("OHEM kept:%.4f of the labelled pixels" % float(self.extras["ohem_kept"]))
                     if self.gsi_optimizer.last_grad_norm is not None:       # --clip_grad_norm: the norm this step's update clipped

@@ -548,6 +548,32 @@ def parse_dice_skip(spec, n_classes):
     return sorted(ids)
 
 
+def parse_boundary_loss_skip(spec, n_classes):
+    """--boundary_loss_skip: a comma list of class ids the boundary loss gives weight 0, in parse_dice_skip's grammar -> a sorted list
+    of distinct ids in [0, n_classes); "" / None -> [].  Skipping every class is refused (the loss divides by the sum of the weights).
+    Raises ValueError naming the bad token."""
+    if spec is None or not str(spec).strip():
+        return []
+    ids = set()
+    for tok in str(spec).split(","):
+        t = tok.strip()
+        if not (t.isdigit() and int(t) < int(n_classes)):
+            raise ValueError("--boundary_loss_skip: %r is not a class id in [0, %d)" % (t, n_classes))
+        ids.add(int(t))
+    if len(ids) >= int(n_classes):
+        raise ValueError("--boundary_loss_skip: %r skips every class" % (spec,))
+    return sorted(ids)
+
+
+def boundary_loss_schedule(weight, ramp, epoch):
+    """--boundary_loss F with --boundary_loss_ramp N: the weight of the boundary term in `epoch` (0-based), b = F * min(1, epoch / N);
+    N == 0: F from the first epoch on.  A host scalar: no kernel sees it."""
+    weight, ramp, epoch = float(weight), int(ramp), int(epoch)
+    if ramp <= 0:
+        return weight
+    return weight * min(1.0, max(epoch, 0) / float(ramp))
+
+
 MAX_TTA_VIEWS = 8
 
 
