@@ -797,6 +797,33 @@ int sscg_mse_bwd(const float* a, const float* b, int64_t n, const float* gscale,
 /* nn.L1Loss (model.py:271; call :461) */
 int sscg_l1_fwd(const float* a, const float* b, int64_t n, float* loss, void* ws, size_t ws_bytes, void* stream);
 int sscg_l1_bwd(const float* a, const float* b, int64_t n, const float* gscale, float w, float* da, void* stream);
+/* Structural similarity fused with that L1 term (`--ssim_weight`; the reference has no such term: its image terms are the plain L1 of
+ * model.py:461 and the commented-out :453).  a (the prediction, gets the gradient) and b (the data) are fp32 [N][H][W][C], C <= 4.
+ * Window: win x win, win odd in 3..11, separable, g[i] = exp(-(i - (win-1)/2)^2 / (2 sigma^2)) normalised to sum 1 in fp64 on the
+ *   host, rounded to fp32 once.  "Valid": the map has H' = H - win + 1 by W' = W - win + 1 positions, no padding.
+ * Per (n, c, p), with the window's weighted moments mu_a, mu_b, E[a^2], E[b^2], E[ab]:
+ *     va = E[a^2] - mu_a^2    vb = E[b^2] - mu_b^2    cov = E[ab] - mu_a mu_b
+ *     A1 = 2 mu_a mu_b + c1   A2 = 2 cov + c2         B1 = mu_a^2 + mu_b^2 + c1    B2 = va + vb + c2        S = A1 A2 / (B1 B2)
+ *   ssim_loss = 1 - mean S over M = N C H' W' positions; per_sample (nullable) [N] = the mean S of a sample; l1 (nullable) = mean |a - b|
+ *   over N C H W, taken in the same launch, every input pixel once.  c1 = (0.01 L)^2, c2 = (0.03 L)^2 for a data range L.
+ * Gradient: with P1 = 2 mu_b (A2 - A1) / (B1 B2) - 2 mu_a S (1 / B1 - 1 / B2), P2 = -S / B2, P3 = 2 A1 / (B1 B2) per position and G^T
+ *   the adjoint of the valid filter (a full correlation; border pixels receive fewer windows),
+ *     d ssim_loss / d a(q) = -(1 / M) [ (G^T P1)(q) + 2 a(q) (G^T P2)(q) + b(q) (G^T P3)(q) ].
+ * sscg_l1_ssim_fwd: one tiled stencil launch (16 x 16 positions per workgroup, the tile of a and b with its win-1 halo staged in LDS, a
+ *   row pass and a column pass of the five moments) and a one-block finish; fp64 block records in a fixed order, no float atomics: the
+ *   same call twice gives the same bits, whatever the workspace held.  coef (nullable; wanted with a gradient) receives P1, P2, P3 as
+ *   [3][N][H'][W'][C] fp32.  ws: sscg_ssim_workspace(N, H, W, C, win) bytes, 8-byte aligned.
+ * sscg_l1_ssim_bwd: one stencil launch that writes every element of
+ *     da = (*g_ssim) w_ssim d ssim_loss / d a + (*g_l1) w_l1 sign(a - b) / (N C H W);
+ *   a NULL g_l1 or g_ssim drops its term (both NULL: refused).  With g_ssim == NULL coef is not read and da has sscg_l1_bwd's bits.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, win even or outside 3..11, sigma <= 0, H < win or W < win, c1 or c2 < 0,
+ * non-positive sizes), SSCG_ERR_UNSUPPORTED (C outside 1..4, N H W C >= 2^31), SSCG_ERR_WORKSPACE; sscg_ssim_workspace returns 0 for
+ * sizes the entries refuse.  (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+size_t sscg_ssim_workspace(int N, int H, int W, int C, int win);
+int sscg_l1_ssim_fwd(const float* a, const float* b, int N, int H, int W, int C, int win, float sigma, float c1, float c2, float* l1,
+                     float* ssim_loss, float* per_sample, float* coef, void* ws, size_t ws_bytes, void* stream);
+int sscg_l1_ssim_bwd(const float* a, const float* b, const float* coef, int N, int H, int W, int C, int win, float sigma,
+                     const float* g_l1, float w_l1, const float* g_ssim, float w_ssim, float* da, void* stream);
 /* out = sum_i w[i] * (*terms[i]) for up to 16 device scalars (gen_loss / discriminator_loss, model.py:464-468,538) */
 int sscg_weighted_sum(const float* const* terms, const float* w, int n, float* out, void* stream);
 

@@ -3,7 +3,7 @@
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
---boundary_loss, --boundary_loss_skip, --boundary_loss_ramp.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -55,6 +55,9 @@ class _Args(Namespace):
     boundary_loss = 0.0
     boundary_loss_skip = ""
     boundary_loss_ramp = 0
+    ssim_weight = 0.0
+    ssim_window = 11
+    ssim_sigma = 1.5
 
 
 def get_args(argv=None):
@@ -170,6 +173,15 @@ def get_args(argv=None):
     parser.add_argument("--boundary_loss_ramp", type=int, default=SUPPRESS, metavar="N",
                         help="raise the boundary term's weight linearly over the first N epochs, F * min(1, epoch / N); N >= 0, "
                              "0 = constant (default: 0)")
+    parser.add_argument("--ssim_weight", type=float, default=SUPPRESS, metavar="F",
+                        help="add F times the structural-similarity loss 1 - mean SSIM (Wang et al. 2004) to every image L1 term "
+                             "(lab_loss_MSE; img_cycle_l1 under --variants l1_cycle), inside that term's own weight, from the same "
+                             "forward and backward launch as the L1; reported as lab_loss_ssim / img_cycle_ssim; the supervised "
+                             "model has no image term and ignores it; F >= 0, 0 = off (default: off, the reference's losses)")
+    parser.add_argument("--ssim_window", type=int, default=SUPPRESS, metavar="N",
+                        help="side of the SSIM term's Gaussian window: odd, 3..11, at most the crop (default: 11)")
+    parser.add_argument("--ssim_sigma", type=float, default=SUPPRESS, metavar="F",
+                        help="standard deviation of the SSIM term's Gaussian window, > 0 (default: 1.5)")
     args = parser.parse_args(argv, namespace=_Args())
     if args.crf.strip():
         try:
@@ -218,6 +230,12 @@ def get_args(argv=None):
         n_cls = {"voc2012": 21, "cityscapes": 20, "acdc": 4}[args.dataset]
         if not all(t.isdigit() and int(t) < n_cls for t in toks) or len(set(int(t) for t in toks)) >= n_cls:
             parser.error("--boundary_loss_skip must be a comma list of class ids in [0, %d) that leaves a class over" % n_cls)
+    if not args.ssim_weight >= 0.0 or args.ssim_weight == float("inf"):
+        parser.error("--ssim_weight must be a finite number >= 0")
+    if not 3 <= args.ssim_window <= 11 or args.ssim_window % 2 == 0:
+        parser.error("--ssim_window must be an odd integer in 3..11")
+    if not (args.ssim_sigma > 0.0 and args.ssim_sigma < float("inf")):
+        parser.error("--ssim_sigma must be a finite number > 0")
     if args.adamw and not args.weight_decay > 0.0:
         parser.error("--adamw decouples the weight decay from the gradient: it needs --weight_decay F with F > 0")
     if args.weight_decay < 0.0 or args.weight_decay != args.weight_decay:

@@ -163,6 +163,9 @@ SIGNATURES = {
     "sscg_mse_bwd": (_i, [_p, _p, _i64, _p, _f, _p, _p, _p]),
     "sscg_l1_fwd": (_i, [_p, _p, _i64, _p, _p, _sz, _p]),
     "sscg_l1_bwd": (_i, [_p, _p, _i64, _p, _f, _p, _p]),
+    "sscg_ssim_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "sscg_l1_ssim_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p]),
+    "sscg_l1_ssim_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _f, _p, _f, _p, _p]),
     "sscg_weighted_sum": (_i, [C.POINTER(_p), C.POINTER(_f), _i, _p, _p]),
     "sscg_adam_step": (_i, [_p, _p, _p, _p, _p, _i, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _i, _f, _p]),
     "sscg_grad_norm_workspace": (_sz, [_i64]),

@@ -3461,6 +3461,92 @@ class L1Fn(torch.autograd.Function):
         return da, None
 
 
+class SsimOptions(object):
+    """The structural-similarity term of l1_ssim_loss / ssim_loss / ssim (include/sscg.h: sscg_l1_ssim_fwd): a window x window
+    Gaussian of `sigma` (window odd, 3..11), data_range L = max - min of the images ([-1, 1] after Normalize(.5, .5): 2), which sets
+    c1 = (0.01 L)^2 and c2 = (0.03 L)^2."""
+    __slots__ = ("window", "sigma", "data_range")
+
+    def __init__(self, window=11, sigma=1.5, data_range=2.0):
+        if isinstance(window, bool) or int(window) != window or not (3 <= int(window) <= 11) or int(window) % 2 == 0:
+            raise ValueError("ssim window %r must be an odd integer in 3..11" % (window,))
+        if not (float(sigma) > 0.0 and math.isfinite(float(sigma))):
+            raise ValueError("ssim sigma %r must be a finite number > 0" % (sigma,))
+        if not (float(data_range) > 0.0 and math.isfinite(float(data_range))):
+            raise ValueError("ssim data_range %r must be a finite number > 0" % (data_range,))
+        self.window, self.sigma, self.data_range = int(window), float(sigma), float(data_range)
+
+    @property
+    def c1(self):
+        return (0.01 * self.data_range) ** 2
+
+    @property
+    def c2(self):
+        return (0.03 * self.data_range) ** 2
+
+
+def _ssim_options(ssim):
+    if ssim is None:
+        return SsimOptions()
+    if isinstance(ssim, dict):
+        ssim = SsimOptions(**ssim)
+    if not isinstance(ssim, SsimOptions):
+        raise TypeError("ssim must be a functional.SsimOptions (or a dict of its arguments), not %r" % (ssim,))
+    return ssim
+
+
+def _ssim_operands(a, b, opts):
+    _need_hip(a, f32_only=True)
+    _need_hip(b, f32_only=True)
+    if a.dim() != 4 or a.shape != b.shape:
+        raise _lib.SscgError("ssim: two [N, C, H, W] tensors of one shape expected, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if min(a.shape[2], a.shape[3]) < opts.window:
+        raise _lib.SscgError("ssim: a %dx%d image is smaller than the %d-pixel window" % (a.shape[2], a.shape[3], opts.window))
+    return to_nhwc(a), to_nhwc(b)
+
+
+def l1_ssim_fwd(a, b, opts, want_l1=True, want_coef=False, want_per_sample=False):
+    """sscg_l1_ssim_fwd on channels-last fp32 a, b [N,C,H,W]: (l1 or None, ssim_loss, per_sample [N] or None, coef or None), coef =
+    the backward's three coefficient maps [3,N,H',W',C].  No autograd."""
+    n, c, h, w = a.shape
+    k = opts.window
+    dev = a.device
+    l1 = _scalar(dev) if want_l1 else None
+    loss = _scalar(dev)
+    per = torch.empty((n,), dtype=torch.float32, device=dev) if want_per_sample else None
+    coef = torch.empty((3, n, h - k + 1, w - k + 1, c), dtype=torch.float32, device=dev) if want_coef else None
+    ws = _WS.get(lib.sscg_ssim_workspace(n, h, w, c, k), dev)
+    check(lib.sscg_l1_ssim_fwd(a.data_ptr(), b.data_ptr(), n, h, w, c, k, opts.sigma, opts.c1, opts.c2, _ptr(l1), loss.data_ptr(),
+                               _ptr(per), _ptr(coef), ws.data_ptr(), ws.numel(), _stream()), "sscg_l1_ssim_fwd")
+    return l1, loss, per, coef
+
+
+class L1SsimFn(torch.autograd.Function):
+    """nn.L1Loss()(a, b) and 1 - mean SSIM(a, b) from one forward launch; one backward launch writes the whole gradient of both to `a`
+    (b is data).  want_l1 False: the SSIM term alone."""
+
+    @staticmethod
+    def forward(ctx, a, b, opts, want_l1):
+        a, b = _ssim_operands(a, b, opts)
+        need = ctx.needs_input_grad[0]
+        l1, loss, _, coef = l1_ssim_fwd(a, b, opts, want_l1=want_l1, want_coef=need)
+        ctx.opts, ctx.want_l1 = opts, want_l1
+        ctx.set_materialize_grads(False)             # an output nothing reads arrives as None: its term is not formed
+        if need:
+            ctx.save_for_backward(a, b, coef)
+        return (l1, loss) if want_l1 else loss
+
+    @staticmethod
+    def backward(ctx, *gs):
+        a, b, coef = ctx.saved_tensors
+        g_l1, g_ssim = gs if ctx.want_l1 else (None, gs[0])
+        n, c, h, w = a.shape
+        da = torch.empty_like(a, memory_format=CL)
+        check(lib.sscg_l1_ssim_bwd(a.data_ptr(), b.data_ptr(), coef.data_ptr(), n, h, w, c, ctx.opts.window, ctx.opts.sigma, _ptr(g_l1), 1.0,
+                                   _ptr(g_ssim), 1.0, da.data_ptr(), _stream()), "sscg_l1_ssim_bwd")
+        return da, None, None, None
+
+
 class MseFn(torch.autograd.Function):
     """nn.MSELoss()(a, b) between two tensors (utils.perceptual_loss, utils.py:205-206); gradients to both."""
 
@@ -3674,6 +3760,25 @@ def mse_const(x, target):
 
 def l1_loss(a, b):
     return L1Fn.apply(a, b)
+
+
+def l1_ssim_loss(a, b, ssim=None):
+    """(nn.L1Loss()(a, b), 1 - mean SSIM(a, b)) as one autograd node: one forward launch reads a and b once for both, one backward
+    launch writes the gradient of both to `a`.  ssim: a SsimOptions (None = the defaults)."""
+    return L1SsimFn.apply(a, b, _ssim_options(ssim), True)
+
+
+def ssim_loss(a, b, ssim=None):
+    """1 - mean SSIM(a, b): l1_ssim_loss without the L1 output."""
+    return L1SsimFn.apply(a, b, _ssim_options(ssim), False)
+
+
+def ssim(a, b, ssim=None):
+    """The mean SSIM of each sample, [N] fp32.  No gradient."""
+    opts = _ssim_options(ssim)
+    with torch.no_grad():
+        a, b = _ssim_operands(a.detach(), b.detach(), opts)
+        return l1_ssim_fwd(a, b, opts, want_l1=False, want_per_sample=True)[2]
 
 
 def weighted_sum(terms, weights):

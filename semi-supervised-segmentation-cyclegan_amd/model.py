@@ -367,6 +367,7 @@ class semisuper_cycleGAN(_WeightedCE):
         self.overlap_d = bool(getattr(args, "overlap_d", False))
         self.dp = data_parallel
         self._init_ce(args, C)
+        self._init_ssim(args)
 
         self.g_optimizer = FusedAdam(itertools.chain(self.Gis.parameters(), self.Gsi.parameters()), lr=args.lr, betas=(0.5, 0.999),
                                      **_optim_options(args, ema=True))
@@ -397,6 +398,35 @@ class semisuper_cycleGAN(_WeightedCE):
             print(' [*] No checkpoint!')
             self.start_epoch = 0
             self.best_iou = -100
+
+    # --ssim_weight / --ssim_window / --ssim_sigma (opt-in; the reference's image terms are plain L1): every image L1 term gains
+    # ssim_w * (1 - mean SSIM) inside its own weight, from the L1's own forward and backward launch (functional.l1_ssim_loss)
+    ssim_w = 0.0                    # 0 = off: no launch, no loss key, no checkpoint key
+    ssim_options = None             # functional.SsimOptions when on
+
+    def _init_ssim(self, args):
+        self.ssim_w = float(getattr(args, "ssim_weight", 0.0) or 0.0)
+        if not (self.ssim_w >= 0.0 and self.ssim_w < float("inf")):
+            raise ValueError("--ssim_weight %r must be a finite number >= 0" % (getattr(args, "ssim_weight", None),))
+        if self.ssim_w == 0.0:
+            return
+        window, sigma = getattr(args, "ssim_window", 11), getattr(args, "ssim_sigma", 1.5)
+        try:
+            opts = F.SsimOptions(window=window, sigma=sigma, data_range=2.0)         # Normalize(.5, .5): images in [-1, 1]
+        except ValueError as e:
+            raise ValueError("--ssim_window / --ssim_sigma: %s" % e)
+        if opts.window > min(self.crop):
+            raise ValueError("--ssim_window %d is larger than the %dx%d crop" % (opts.window, self.crop[0], self.crop[1]))
+        self.ssim_options = opts
+
+    def _image_l1(self, pred, img, extras, key, weight, extra_terms, extra_weights):
+        """An image L1 term; with --ssim_weight the SSIM term of the same pair joins the extras under `key` with `weight` * ssim_w."""
+        if self.ssim_options is None:
+            return F.l1_loss(pred, img)
+        l1, extras[key] = F.l1_ssim_loss(pred, img, self.ssim_options)
+        extra_terms.append(extras[key])
+        extra_weights.append(weight * self.ssim_w)
+        return l1
 
     # ------------------------------------------------------------------------------------------ one iteration
     def _mark(self, name, stream=None):
@@ -536,7 +566,7 @@ class semisuper_cycleGAN(_WeightedCE):
             extra_weights.append(a.lab_CE_weight * self._boundary_b)
         if "l1_cycle" in self.variants:                                              # :453 (commented out in the reference)
             recon_img, recon_img_l1 = F.split(recon_img, 2)
-            extras["img_cycle_l1"] = F.l1_loss(recon_img_l1, unl_img)
+            extras["img_cycle_l1"] = self._image_l1(recon_img_l1, unl_img, extras, "img_cycle_ssim", a.lamda_img, extra_terms, extra_weights)
             extra_terms.append(extras["img_cycle_l1"])
             extra_weights.append(a.lamda_img)
         if "perceptual" in self.variants:                                            # :454,:462 (commented out; weights main.py:23,28)
@@ -577,7 +607,7 @@ class semisuper_cycleGAN(_WeightedCE):
             extras["gt_cycle_boundary"] = ohem_kept.pop("boundary")
             extra_terms.append(extras["gt_cycle_boundary"])
             extra_weights.append(a.lamda_gt * self._boundary_b)
-        lab_loss_MSE = F.l1_loss(fake_img_l1, l_img)                                 # :461
+        lab_loss_MSE = self._image_l1(fake_img_l1, l_img, extras, "lab_loss_ssim", a.lab_MSE_weight, extra_terms, extra_weights)   # :461
         # :464-468  gen_loss = CE_w*CE + MSE_w*L1 + adv_w*(img_gen + gt_gen) + img_cycle + lamda_gt*gt_cycle
         gen_loss = F.weighted_sum(
             [lab_loss_CE, lab_loss_MSE, img_gen_loss, gt_gen_loss, img_cycle_loss, gt_cycle_loss] + extra_terms,
@@ -828,9 +858,13 @@ class semisuper_cycleGAN(_WeightedCE):
                 if (i % log_every == 0) and rank0:
                     self.sync_losses()
                     norms = [o.last_grad_norm for o in (self.g_optimizer, self.d_optimizer) if o.last_grad_norm is not None]
-                    vals = torch.stack([losses[k] for k in LOSS_KEYS] + norms).cpu().tolist()   # the only host sync of the step
+                    ssim_keys = [k for k in ("lab_loss_ssim", "img_cycle_ssim") if k in losses]          # --ssim_weight
+                    vals = torch.stack([losses[k] for k in LOSS_KEYS + tuple(ssim_keys)] + norms).cpu().tolist()   # the only host sync of the step
                     rec = dict(zip(LOSS_KEYS, vals))
                     history.append(rec)
+                    if ssim_keys:
+                        print("SSIM Loss (weight %g): " % self.ssim_w + " ".join(
+                            "%s:%.2e" % (k, v) for k, v in zip(ssim_keys, vals[len(LOSS_KEYS):])))
                     if norms:       # --clip_grad_norm: the norms the two updates of this step clipped
                         print("Grad norm G:%.3e D:%.3e (clip %.3e)" % (vals[-2], vals[-1], self.g_optimizer.max_grad_norm))
                     print("Epoch: (%3d) (%5d/%5d) | Dis Loss:%.2e | Unlab Gen Loss:%.2e | Lab Gen loss:%.2e" % (
@@ -898,6 +932,8 @@ class supervised_model(_WeightedCE):
         if self.dp is not None:
             self.dp.attach_one(self.gsi_optimizer, [self.Gsi])
         self._init_ce(args, self.n_channels)
+        if float(getattr(args, "ssim_weight", 0.0) or 0.0) != 0.0:
+            print("--ssim_weight is ignored: the supervised model has no image term")
         self.running_metrics_val = utils.runningScore(self.n_channels, args.dataset)
         if not os.path.isdir(args.checkpoint_dir):
             os.makedirs(args.checkpoint_dir, exist_ok=True)
