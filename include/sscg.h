@@ -558,6 +558,43 @@ int sscg_upsample_head_bwd_b(const float* x, const int64_t* labels, const float*
                              float smoothing, const float* dy_soft, const float* g_ce, const float* valid, const float* coef,
                              const float* g_dice, int batch, float* dx, int N, int H, int W, int C, int OH, int OW, const int32_t* sdm,
                              const float* bnd_coef, const float* bnd_w, const float* g_bnd, void* stream);
+/* The losses of the UNLABELLED head (opt-in; the reference has none): entropy minimisation (Grandvalet & Bengio 2004; ADVENT's MinEnt, Vu
+ * et al., CVPR 2019), the maximum-squares loss (Chen et al., ICCV 2019) and the confidence-thresholded pseudo-label cross entropy
+ * (self-training, Lee 2013) of the model's own prediction.  x = logits [N][H][W][C] (C <= 64); z = x resized to [OH][OW] (bilinear,
+ * align_corners=True, the pinned arithmetic of sscg_upsample_bilinear_fwd and sscg_softmax_fwd as in sscg_dice_fwd; OH == H && OW == W:
+ * z = x, the flat form, no interpolation arithmetic).  Per output pixel u_c = z_c - max_k z_k, s = sum_c exp(u_c), p_c = exp(u_c) / s;
+ * V = N * OH * OW, every pixel of the call (there is no void on this side; under data parallelism V is per rank):
+ *     H     = ln s - sum_c p_c u_c                         L_ent = sum_o H / (V ln C)  in [0, 1]   (C == 1: the divisor is V, H is 0)
+ *     L_msq = -sum_o sum_c p_c^2 / (2 V)                   in [-1/2, -1/(2C)]
+ *     y*    = the first maximum of p (sscg_argmax_onehot's rule), conf = p[y*];  KEPT <=> conf >= tau;  K = the kept pixels
+ *     L_pl  = sum over the kept pixels of (ln s - u[y*]) / max(K, 1)             (K == 0: loss 0, gradient 0)
+ * u_c is the logit difference held before the exponentiation, never the logarithm of p_c: a vanished p_c adds exactly 0, not NaN.
+ * y* and the keep decision are constants: no gradient flows through them.  With g_e, g_m, g_p the upstream scalars of the three losses:
+ *     q_c = dy_soft[c] - (g_e / (V ln C)) u_c - (g_m / V) p_c
+ *     d loss / d z_c = p_c (q_c - sum_k p_k q_k) + [kept] (g_p / max(K, 1)) (p_c - [c == y*])
+ * sscg_unl_fwd: `losses` fp32 [3] = (L_ent, L_msq, L_pl); `sums` fp64 [4] = (sum H in nats, sum sum p^2, the kept cross entropies' sum,
+ *   K) - K is what the backward divides by; `pseudo` (nullable) uint8 [N][OH][OW] = y* of a kept pixel, 255 of a dropped one; thresh =
+ *   tau in [0, 1].  One thread per output pixel (no block straddles a sample; K per wave by ballot), one fp64 record per block in the
+ *   workspace, a reduce step in index order and a one-block finish: no float atomics - the same call twice gives the same bits, and the
+ *   resized form gives the bits of the identity form on sscg_upsample_bilinear_fwd's output (losses, sums and map).  Neither the resized
+ *   logits nor the probabilities are written.  ws: sscg_unl_workspace(N, OH, OW) bytes, contents irrelevant.
+ * sscg_unl_bwd: the flat backward (logits [N][H][W][C], pseudo / sums from an identity-size sscg_unl_fwd): dx = d loss / d z above
+ *   without dy_soft.  g_ent / g_msq / g_pl: device scalars, NULL = that loss took no part (at least one is required; pseudo with g_pl).
+ * sscg_upsample_head_bwd_u: the WHOLE backward of the unlabelled head in one stencil launch - sscg_upsample_head_bwd's softmax-map branch
+ *   (dy_soft, nullable) plus whichever of the three losses received a gradient, through the adjoint of the resize; pseudo may be NULL
+ *   when g_pl is.  Both backwards READ y* and the keep decision from `pseudo`: they are never re-derived from recomputed logits, whose
+ *   last bit may differ from the forward's.  With g_ent, g_msq and g_pl all NULL it runs sscg_upsample_head_bwd itself (the same
+ *   kernels, the same bits).  Gather form, fixed summation order.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, C outside 1..64, non-positive sizes, thresh outside [0, 1] or NaN, g_pl
+ * without pseudo), SSCG_ERR_UNSUPPORTED (N*OH*OW or N*H*W >= 2^31), SSCG_ERR_WORKSPACE; the workspace query returns 0 for sizes the
+ * entries refuse.  (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+size_t sscg_unl_workspace(int N, int OH, int OW);
+int sscg_unl_fwd(const float* x, int N, int H, int W, int C, int OH, int OW, float thresh, float* losses, double* sums, uint8_t* pseudo,
+                 void* ws, size_t ws_bytes, void* stream);
+int sscg_unl_bwd(const float* x, const uint8_t* pseudo, int N, int H, int W, int C, const float* g_ent, const float* g_msq,
+                 const float* g_pl, const double* sums, float* dx, void* stream);
+int sscg_upsample_head_bwd_u(const float* x, const uint8_t* pseudo, const float* dy_soft, const float* g_ent, const float* g_msq,
+                             const float* g_pl, const double* sums, float* dx, int N, int H, int W, int C, int OH, int OW, void* stream);
 /* ------------------------------------------------------------------ inference heads (ABI v18): one launch from a generator's output
  * to what its consumer keeps.  Forward only; never launched by the training step.
  *

@@ -3,7 +3,7 @@
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
---boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -58,6 +58,11 @@ class _Args(Namespace):
     ssim_weight = 0.0
     ssim_window = 11
     ssim_sigma = 1.5
+    unl_entropy = 0.0
+    unl_maxsq = 0.0
+    unl_pseudo = 0.0
+    unl_pseudo_thresh = None        # 0.9 once --unl_pseudo is given
+    unl_ramp = 0
 
 
 def get_args(argv=None):
@@ -182,6 +187,23 @@ def get_args(argv=None):
                         help="side of the SSIM term's Gaussian window: odd, 3..11, at most the crop (default: 11)")
     parser.add_argument("--ssim_sigma", type=float, default=SUPPRESS, metavar="F",
                         help="standard deviation of the SSIM term's Gaussian window, > 0 (default: 1.5)")
+    parser.add_argument("--unl_entropy", type=float, default=SUPPRESS, metavar="F",
+                        help="add F times the entropy of the UNLABELLED batch's prediction to the generator loss (entropy "
+                             "minimisation, Grandvalet & Bengio 2004; ADVENT's MinEnt): the mean over its pixels of the softmax "
+                             "entropy divided by ln C, from the unlabelled head's own forward and backward; reported as unl_entropy; "
+                             "the supervised model has no unlabelled batch and ignores it; F >= 0, 0 = off (default: off)")
+    parser.add_argument("--unl_maxsq", type=float, default=SUPPRESS, metavar="F",
+                        help="add F times the maximum-squares loss (Chen et al., ICCV 2019) of the same prediction, the mean of "
+                             "-sum_c p_c^2 / 2; reported as unl_maxsq; F >= 0, 0 = off (default: off)")
+    parser.add_argument("--unl_pseudo", type=float, default=SUPPRESS, metavar="F",
+                        help="add F times the cross entropy of the same prediction against its own argmax, over the pixels whose "
+                             "maximum probability is at least --unl_pseudo_thresh (self-training, Lee 2013; per rank); reported as "
+                             "unl_pseudo_ce, the kept share as unl_pseudo_kept; F >= 0, 0 = off (default: off)")
+    parser.add_argument("--unl_pseudo_thresh", type=float, default=SUPPRESS, metavar="T",
+                        help="with --unl_pseudo: the confidence threshold, in [0, 1] (default: 0.9)")
+    parser.add_argument("--unl_ramp", type=int, default=SUPPRESS, metavar="N",
+                        help="raise the three --unl_* weights linearly over the first N epochs, F * min(1, epoch / N); N >= 0, "
+                             "0 = constant (default: 0)")
     args = parser.parse_args(argv, namespace=_Args())
     if args.crf.strip():
         try:
@@ -236,6 +258,16 @@ def get_args(argv=None):
         parser.error("--ssim_window must be an odd integer in 3..11")
     if not (args.ssim_sigma > 0.0 and args.ssim_sigma < float("inf")):
         parser.error("--ssim_sigma must be a finite number > 0")
+    for key in ("unl_entropy", "unl_maxsq", "unl_pseudo"):
+        if not getattr(args, key) >= 0.0 or getattr(args, key) == float("inf"):
+            parser.error("--%s must be a finite number >= 0" % key)
+    if args.unl_pseudo_thresh is not None:
+        if not args.unl_pseudo > 0.0:
+            parser.error("--unl_pseudo_thresh needs --unl_pseudo F with F > 0")
+        if not 0.0 <= args.unl_pseudo_thresh <= 1.0:
+            parser.error("--unl_pseudo_thresh must lie in [0, 1]")
+    if args.unl_ramp < 0:
+        parser.error("--unl_ramp must be an integer >= 0")
     if args.adamw and not args.weight_decay > 0.0:
         parser.error("--adamw decouples the weight decay from the gradient: it needs --weight_decay F with F > 0")
     if args.weight_decay < 0.0 or args.weight_decay != args.weight_decay:

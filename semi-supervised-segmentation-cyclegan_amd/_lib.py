@@ -142,6 +142,10 @@ SIGNATURES = {
     "sscg_boundary_loss_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "sscg_boundary_loss_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p]),
     "sscg_upsample_head_bwd_b": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "sscg_unl_workspace": (_sz, [_i, _i, _i]),
+    "sscg_unl_fwd": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "sscg_unl_bwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "sscg_upsample_head_bwd_u": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "sscg_predict_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_predict_head_ms": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.c_uint32, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),

@@ -1,4 +1,4 @@
-// The backward of the fused label head (include/sscg.h: sscg_upsample_head_bwd / _bwd_d / _bwd_h / _bwd_b): ONE gather kernel for every
+// The backward of the fused label head (include/sscg.h: sscg_upsample_head_bwd / _bwd_d / _bwd_h / _bwd_b / _bwd_u): ONE gather kernel for every
 // branch that can be live - the softmax map's upstream gradient, the cross entropy (plain or mined), the Dice loss and the boundary
 // loss - through the adjoint of the resize.  One block per SOURCE pixel walks the output pixels whose stencil touches it (head_window /
 // head_weight / head_logits of head_geom.h: the forward's candidates, weights and order).  Per output pixel, with p = softmax(resized
@@ -9,6 +9,9 @@
 //                                                                                                   ge = g_ce / D, kept: keys <= tau)
 // weighted by the stencil weight and summed over the block by head_store_sum, which - !MINED - adds the cross-entropy gradient the
 // forward left (dl_ce * g_ce / valid): that gradient depends on the pixel alone, the mined one on the selection, so it is formed here.
+// The UNLABELLED head (sscg_upsample_head_bwd_u; the losses of unl.hip) is the same kernel without a label branch:
+//     q_c = dy_soft[c]   (SOFT)   - ke u_c - km p_c                       (UNL; u_c = z_c - max z, the factors of unl_coef, head_geom.h)
+//     d_c = p_c (q_c - sum_k p_k q_k)  +  [kept] kp (p_c - [c == y*])     (kept and y*: the byte of the forward's pseudo-label map)
 #include "common.h"
 #include "head_geom.h"
 #include "sscg_internal.h"
@@ -24,16 +27,20 @@ namespace {
 // is given and mined when `keys` is given too: without keys every counted pixel is kept, which is the unmined cross entropy formed in
 // the stencil (that entry takes no gradient the forward left).  Per touched pixel it reads the C contiguous int32 of sdm.
 struct HeadBnd { const int32_t* sdm; const float* coef; const float* w; const float* g; };
+// UNL: the entropy, max-squares and pseudo-label terms of the unlabelled head, with or without SOFT and with no label branch.  Each of
+// the three is a RUN-TIME factor (0 where its upstream scalar is NULL), as the loss branches of a MINED instantiation are.
+struct HeadUnl { const uint8_t* pseudo; const float* g_ent; const float* g_msq; const float* g_pl; const double* sums; };
 
-template <int CT, bool SOFT, bool DICE, bool MINED, bool BND = false>
+template <int CT, bool SOFT, bool DICE, bool MINED, bool BND = false, bool UNL = false>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab,
                                                        const float* __restrict__ dy_soft, const float* __restrict__ dl_ce,
                                                        const float* __restrict__ g_ce, const float* __restrict__ valid,
                                                        const float* __restrict__ coef, const float* __restrict__ g_dice, int batch,
                                                        const float* __restrict__ keys, const float* __restrict__ thr,
                                                        const float* __restrict__ class_w, float smoothing, float* __restrict__ dx, HeadGeom g,
-                                                       HeadBnd bnd) {
-    static_assert(SOFT || DICE, "an instantiation with nothing to gather");
+                                                       HeadBnd bnd, HeadUnl unl) {
+    static_assert(SOFT || DICE || UNL, "an instantiation with nothing to gather");
+    static_assert(!UNL || !DICE, "the unlabelled head has no label branch");
     static_assert(DICE || !MINED, "the mined instantiations carry the Dice branch as a run-time test");
     static_assert(MINED || !BND, "the boundary instantiations are mined ones with one more term");
     // the run-time class count without a loss branch keeps its class loops rolled (a `break`, as head_logits): unrolled and predicated
@@ -71,6 +78,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
             ge = (g_ce ? *g_ce : 1.f) * (nv > 0.f ? 1.f / nv : 0.f);
         }
     }
+    UnlCoef uk = {0.f, 0.f, 0.f};
+    if constexpr (UNL) uk = unl_coef(unl.g_ent, unl.g_msq, unl.g_pl, unl.sums, (double)g.N * g.OH * g.OW, C);
     const int nx = win.ox_hi - ox_lo + 1, cand = (win.oy_hi - oy_lo + 1) * nx;
     const float* xn = x + (size_t)n * g.H * g.W * C;
     float acc[CT ? CT : SSCG_MAXC];
@@ -93,10 +102,28 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
         if constexpr (BND) kept = ce && l >= 0 && (keys == nullptr || keys[o] <= tau);
         else kept = ce && l >= 0 && keys[o] <= tau;
         const bool dq = dice && l >= 0;
-        if (!SOFT && !kept && !dq && !(BND && l >= 0)) continue;         // nothing flows through this pixel
+        if constexpr (!UNL)
+            if (!SOFT && !kept && !dq && !(BND && l >= 0)) continue;     // nothing flows through this pixel
         float v[CT ? CT : SSCG_MAXC];
         int y0, x0;
         head_logits<CT>(xn, g, oy, ox, C, v, &y0, &x0);
+        // UNL: u_c = z_c - max z, HELD beside v and acc before v becomes exp(u_c) (the register tables: profiles/unl.txt)
+        float u[UNL ? (CT ? CT : SSCG_MAXC) : 1];
+        int ys = UNL_DROPPED;
+        if constexpr (UNL) {
+            float m = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) {
+                if (ROLLED && c >= C) break;
+                if (CT || c < C) m = fmaxf(m, v[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) {
+                if (ROLLED && c >= C) break;
+                if (CT || c < C) u[c] = v[c] - m;
+            }
+            if (unl.g_pl) ys = unl.pseudo[o];
+        }
         const float inv = sscg_softmax_exp<CT>(v, C);
         const float* gr = SOFT ? dy_soft + o * C : nullptr;
         // The boundary term of q_c is used twice per class.  HOLD: formed once and held in registers.  Beside v and acc that costs the
@@ -111,7 +138,11 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
                 if (CT || c < C) qb[c] = l >= 0 ? sQ[c] * sscg_level_set(sr[c]) : 0.f;
         }
         const auto upstream = [&](int c) {           // q_c
-            if constexpr (!DICE) return gr[c];
+            if constexpr (UNL) {
+                const float q = unl_upstream(uk, u[c], v[c]);
+                if constexpr (SOFT) return q + gr[c];
+                else return q;
+            } else if constexpr (!DICE) return gr[c];
             else {
                 float q = dq ? (c == l ? sA[c] : 0.f) + sB[c] : 0.f;
                 if constexpr (HOLD) q += qb[c];
@@ -135,6 +166,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
             gk = kept ? ge : 0.f;
             k = a + bs * wsum;
         }
+        const float kpl = UNL && ys != UNL_DROPPED ? uk.kp : 0.f;       // the kept pixel's pseudo-label cross entropy
         const auto mined = [&](int c) { return gk * (v[c] * k - (c == l ? a : 0.f) - bs * sW[c]); };      // the kept pixel's cross entropy
 #pragma unroll
         for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c) {
@@ -142,11 +174,12 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
             if (CT || c < C) {
                 float d = v[c] * (upstream(c) - dot);
                 if constexpr (MINED) d += mined(c);
+                if constexpr (UNL) d += kpl * (v[c] - (c == ys ? 1.f : 0.f));
                 acc[c] += w * d;
             }
         }
     }
-    head_store_sum<CT>(acc, red, C, b, MINED ? nullptr : dl_ce, g_ce, valid, dx);
+    head_store_sum<CT>(acc, red, C, b, (MINED || UNL) ? nullptr : dl_ce, g_ce, valid, dx);
 }
 
 // backward of the cross entropy alone: dx = dl * g / valid
@@ -161,16 +194,31 @@ __global__ void head_scale_kernel(const float* __restrict__ dl, const float* __r
 void launch_head_bwd(const HeadGeom& g, hipStream_t st, bool dice, bool mined, const float* x, const int64_t* lab, const float* dy_soft,
                      const float* dl_ce, const float* g_ce, const float* valid, const float* coef, const float* g_dice, int batch,
                      const float* keys, const float* thr, const float* class_w, float smoothing, float* dx, const HeadBnd& bnd = HeadBnd()) {
+    const HeadUnl unl = HeadUnl();
     const dim3 grid((unsigned)(g.N * g.H * g.W)), blk(256);
     sscg_dispatch_classes(g.C, [&](auto ct) {
         constexpr int CT = decltype(ct)::value;
         const auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, keys, thr, class_w, smoothing, dx, g, bnd);
+            hipLaunchKernelGGL(kernel, grid, blk, 0, st, x, lab, dy_soft, dl_ce, g_ce, valid, coef, g_dice, batch, keys, thr, class_w, smoothing, dx, g, bnd, unl);
         };
         if (bnd.sdm) dy_soft ? go(head_bwd_kernel<CT, true, true, true, true>) : go(head_bwd_kernel<CT, false, true, true, true>);
         else if (mined) dy_soft ? go(head_bwd_kernel<CT, true, true, true>) : go(head_bwd_kernel<CT, false, true, true>);
         else if (dice) dy_soft ? go(head_bwd_kernel<CT, true, true, false>) : go(head_bwd_kernel<CT, false, true, false>);
         else go(head_bwd_kernel<CT, true, false, false>);
+    });
+}
+
+// the unlabelled head: SOFT follows dy_soft, every label argument is absent
+void launch_head_bwd_unl(const HeadGeom& g, hipStream_t st, const float* x, const float* dy_soft, float* dx, const HeadUnl& unl) {
+    const dim3 grid((unsigned)(g.N * g.H * g.W)), blk(256);
+    sscg_dispatch_classes(g.C, [&](auto ct) {
+        constexpr int CT = decltype(ct)::value;
+        const auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, blk, 0, st, x, (const int64_t*)nullptr, dy_soft, (const float*)nullptr, (const float*)nullptr,
+                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr,
+                               (const float*)nullptr, (const float*)nullptr, 0.f, dx, g, HeadBnd(), unl);
+        };
+        dy_soft ? go(head_bwd_kernel<CT, true, false, false, false, true>) : go(head_bwd_kernel<CT, false, false, false, false, true>);
     });
 }
 
@@ -243,6 +291,21 @@ extern "C" int sscg_upsample_head_bwd_b(const float* x, const int64_t* labels, c
     const HeadBnd bnd = {sdm, bnd_coef, bnd_w, g_bnd};
     launch_head_bwd(g, (hipStream_t)stream, true, true, x, labels, dy_soft, nullptr, g_ce, valid, coef, g_dice, batch, keys, thr, class_w, smoothing,
                     dx, bnd);
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
+extern "C" int sscg_upsample_head_bwd_u(const float* x, const uint8_t* pseudo, const float* dy_soft, const float* g_ent, const float* g_msq,
+                                        const float* g_pl, const double* sums, float* dx, int N, int H, int W, int C, int OH, int OW,
+                                        void* stream) {
+    // no loss received a gradient: the plain head's backward itself (the same kernels, the same bits)
+    if (!g_ent && !g_msq && !g_pl) return sscg_upsample_head_bwd(x, dy_soft, nullptr, nullptr, nullptr, dx, N, H, W, C, OH, OW, stream);
+    if (!x || !dx || !sums || !sizes_ok(N, H, W, C, OH, OW) || (g_pl && !pseudo)) return SSCG_ERR_BAD_ARG;
+    if (too_large(N, H, W, OH, OW)) return SSCG_ERR_UNSUPPORTED;
+    HeadGeom g;
+    if (!head_geom(&g, N, H, W, C, OH, OW)) return SSCG_ERR_BAD_ARG;
+    const HeadUnl unl = {pseudo, g_ent, g_msq, g_pl, sums};
+    launch_head_bwd_unl(g, (hipStream_t)stream, x, dy_soft, dx, unl);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

@@ -1,5 +1,5 @@
 // The geometry of the fused label head (resize -> softmax -> losses from the low-resolution logits), shared by loss_optim.hip (the
-// forward, head_kernel), head_bwd.hip (the one backward, head_bwd_kernel) and the entries of dice.hip / ohem.hip: the launch geometry
+// forward, head_kernel), head_bwd.hip (the one backward, head_bwd_kernel) and the entries of dice.hip / ohem.hip / unl.hip: the launch geometry
 // and the argument checks the entries share, the resized logits of one output pixel, the stencil weight of a source row / column, and
 // the frame of a gather block - one block per SOURCE pixel: its window of candidate output pixels (also upsample_bwd_kernel's,
 // pointwise.hip) and the block sum that ends it.  Device code is not linked across translation units: this header is instantiated in
@@ -89,6 +89,29 @@ __device__ __forceinline__ void head_store_sum(const float (&acc)[CT ? CT : SSCG
         out[(size_t)b * C + c] = r;
     }
 }
+
+// ---- the losses of the unlabelled head (unl.hip's flat backward and the UNL term of head_bwd_kernel share these)
+constexpr int UNL_DROPPED = 255;   // the pseudo-label map's value of a pixel below the threshold (C <= 64: never a class id)
+
+// the per-call factors of the three gradients: ke = g_ent / (V ln C) (C == 1: / V), km = g_msq / V, kp = g_pl / max(K, 1), K = sums[3];
+// a NULL upstream scalar: that loss took no part, its factor is 0
+struct UnlCoef { float ke, km, kp; };
+
+__device__ __forceinline__ UnlCoef unl_coef(const float* __restrict__ g_ent, const float* __restrict__ g_msq, const float* __restrict__ g_pl,
+                                            const double* __restrict__ sums, double V, int C) {
+    UnlCoef k;
+    k.ke = g_ent ? (float)((double)*g_ent / (V * (C > 1 ? log((double)C) : 1.0))) : 0.f;
+    k.km = g_msq ? (float)((double)*g_msq / V) : 0.f;
+    k.kp = 0.f;
+    if (g_pl) {
+        const double K = sums[3];
+        k.kp = (float)((double)*g_pl / (K > 1.0 ? K : 1.0));
+    }
+    return k;
+}
+
+// q_c without the softmax map's gradient: -ke u_c - km p_c (u_c = z_c - max z: finite where p_c has vanished, so p_c q_c is 0, not NaN)
+__device__ __forceinline__ float unl_upstream(const UnlCoef& k, float u, float p) { return -(k.ke * u) - k.km * p; }
 
 }  // namespace
 

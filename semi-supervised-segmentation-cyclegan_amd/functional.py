@@ -3413,6 +3413,156 @@ def upsample_softmax_losses(x, size, labels, *, want_soft=True, weight=None, lab
     return _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, _boundary_options(boundary))
 
 
+# ----------------------------------------------------------------------------- the unlabelled head (opt-in; include/sscg.h: sscg_unl_fwd)
+class UnlabelledOptions(object):
+    """The losses of the unlabelled head: the weights of the entropy, the max-squares loss and the pseudo-label cross entropy (each
+    finite and >= 0; 0 = that term is not used) and the confidence threshold of the pseudo labels, in [0, 1].  The functions below
+    return the three losses unweighted: the weights are the caller's (model.step adds them to its weighted sum), and `pseudo` > 0 is
+    what makes the forward keep the pseudo-label map its cross entropy's backward reads."""
+    __slots__ = ("entropy", "maxsq", "pseudo", "thresh")
+
+    def __init__(self, entropy=0.0, maxsq=0.0, pseudo=0.0, thresh=0.9):
+        import math
+        vals = []
+        for name, v in (("entropy", entropy), ("maxsq", maxsq), ("pseudo", pseudo)):
+            f = float(v)
+            if not (math.isfinite(f) and f >= 0.0):
+                raise ValueError("unlabelled %s weight %r is not a finite number >= 0" % (name, v))
+            vals.append(f)
+        t = float(thresh)
+        if not 0.0 <= t <= 1.0:
+            raise ValueError("unlabelled pseudo-label thresh %r is outside [0, 1]" % (thresh,))
+        self.entropy, self.maxsq, self.pseudo = vals
+        self.thresh = t
+
+    @property
+    def any(self):
+        return self.entropy > 0.0 or self.maxsq > 0.0 or self.pseudo > 0.0
+
+
+def _unl_options(unl):
+    if unl is None or isinstance(unl, dict):
+        unl = UnlabelledOptions(**(unl or {}))
+    if not isinstance(unl, UnlabelledOptions):
+        raise TypeError("unl must be a functional.UnlabelledOptions (or a dict of its arguments), not %r" % (unl,))
+    return unl
+
+
+def unl_fwd(x, size, thresh, want_pseudo=True):
+    """sscg_unl_fwd on channels-last fp32 logits x [N,C,H,W] (size = (OH, OW); (H, W): the flat form): (losses fp32 [3] = (entropy,
+    max-squares, pseudo-label cross entropy), sums fp64 [4] = (sum H, sum sum p^2, sum of the kept cross entropies, K), the pseudo-label
+    map uint8 [N,OH,OW] - 255 = dropped - or None).  No autograd: unlabelled_losses / upsample_softmax_unl wrap it."""
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    losses = torch.empty((3,), dtype=torch.float32, device=x.device)
+    sums = torch.empty((4,), dtype=torch.float64, device=x.device)
+    pseudo = torch.empty((n, oh, ow), dtype=torch.uint8, device=x.device) if want_pseudo else None
+    ws = torch.empty(lib.sscg_unl_workspace(n, oh, ow), dtype=torch.uint8, device=x.device)
+    check(lib.sscg_unl_fwd(x.data_ptr(), n, h, w, c, oh, ow, float(thresh), losses.data_ptr(), sums.data_ptr(), _ptr(pseudo),
+                           ws.data_ptr(), ws.numel(), _stream()), "sscg_unl_fwd")
+    return losses, sums, pseudo
+
+
+def _unl_outputs(ctx, losses, sums, pseudo):
+    """What both nodes return behind the softmax map: the three losses, then the sums and the map as constants.  Without the map the
+    pseudo-label cross entropy is a value only: its backward has no labels to read."""
+    l_ent, l_msq, l_pl = losses.unbind(0)
+    ctx.mark_non_differentiable(sums, *((pseudo,) if pseudo is not None else (l_pl,)))
+    # a loss nothing differentiates: backward gets None and passes NULL, that branch adds nothing
+    ctx.set_materialize_grads(False)
+    return l_ent, l_msq, l_pl, sums, pseudo
+
+
+class UnlabelledLossFn(torch.autograd.Function):
+    """The three losses of full-resolution logits [N,C,H,W] (include/sscg.h: sscg_unl_fwd / sscg_unl_bwd): (entropy, max-squares,
+    pseudo-label cross entropy, sums, pseudo-label map or None)."""
+
+    @staticmethod
+    def forward(ctx, logits, thresh, keep_map):
+        _need_hip(logits, f32_only=True)
+        logits = to_nhwc(logits)
+        losses, sums, pseudo = unl_fwd(logits, logits.shape[2:], thresh, keep_map)
+        ctx.save_for_backward(logits, sums, pseudo)
+        return _unl_outputs(ctx, losses, sums, pseudo)
+
+    @staticmethod
+    def backward(ctx, g_ent, g_msq, g_pl, _sums=None, _map=None):
+        logits, sums, pseudo = ctx.saved_tensors
+        if pseudo is None:
+            g_pl = None
+        if g_ent is None and g_msq is None and g_pl is None:
+            return None, None, None
+        n, c, h, w = logits.shape
+        dx = torch.empty_like(logits, memory_format=CL)
+        check(lib.sscg_unl_bwd(logits.data_ptr(), _ptr(pseudo), n, h, w, c, _ptr(g_ent), _ptr(g_msq), _ptr(g_pl), sums.data_ptr(),
+                               dx.data_ptr(), _stream()), "sscg_unl_bwd")
+        return dx, None, None
+
+
+class UnlabelledHeadFn(torch.autograd.Function):
+    """interp (bilinear, align_corners=True) -> softmax2d and the three losses of the UNLABELLED prediction, from the LOW-resolution
+    logits: (softmax map or None, entropy, max-squares, pseudo-label cross entropy, sums, pseudo-label map or None); the resized logits
+    never reach memory.  Forward: the label head's own launch for the softmax map (_label_head_forward without labels - the bits of
+    upsample_softmax_ce's map), then sscg_unl_fwd.  Backward: ONE sscg_upsample_head_bwd_u launch for the map's upstream gradient and
+    every loss that received one.  No branch of this node can coexist with a label branch of LabelHeadFn: the two are separate nodes."""
+
+    @staticmethod
+    def forward(ctx, x, oh, ow, want_soft, thresh, keep_map):
+        _need_hip(x, f32_only=True)
+        x = to_nhwc(x)
+        y = _label_head_forward(x, oh, ow, None, True, False, None, 0.0)[0] if want_soft else None
+        losses, sums, pseudo = unl_fwd(x, (oh, ow), thresh, keep_map)
+        ctx.size = (oh, ow)
+        ctx.save_for_backward(x, sums, pseudo)
+        return (y,) + _unl_outputs(ctx, losses, sums, pseudo)
+
+    @staticmethod
+    def backward(ctx, dy, g_ent, g_msq, g_pl, _sums=None, _map=None):
+        x, sums, pseudo = ctx.saved_tensors
+        if pseudo is None:
+            g_pl = None
+        if dy is None and g_ent is None and g_msq is None and g_pl is None:
+            return (None,) * 6
+        oh, ow = ctx.size
+        n, c, h, w = x.shape
+        dx = empty_nhwc(n, c, h, w, x.device)
+        if dy is not None:
+            dy = to_nhwc(dy)
+        check(lib.sscg_upsample_head_bwd_u(x.data_ptr(), _ptr(pseudo if g_pl is not None else None), _ptr(dy), _ptr(g_ent), _ptr(g_msq),
+                                           _ptr(g_pl), sums.data_ptr(), dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
+              "sscg_upsample_head_bwd_u")
+        return (dx,) + (None,) * 5
+
+
+def unlabelled_losses(logits, unl=None, want_pseudo=False):
+    """(entropy / ln C, max-squares loss, pseudo-label cross entropy, stats) of logits [N,C,H,W] - the model's own prediction, no labels:
+    the mean over every pixel of the softmax entropy divided by ln C (in [0, 1]); -sum_c p_c^2 / 2 averaged the same way; and the cross
+    entropy against the first maximum of p over the pixels where that maximum is at least unl.thresh (0 when none is).  Unweighted: the
+    weights of `unl` (an UnlabelledOptions or a dict of its arguments) are the caller's.  stats = {"sums": fp64 [4] on the device = (sum
+    of the entropies in nats, sum sum p^2, sum of the kept cross entropies, the kept pixels K), "pseudo": the uint8 label map with 255
+    for a dropped pixel when want_pseudo, else None}.  The pseudo-label term is differentiable when unl.pseudo > 0 or want_pseudo."""
+    unl = _unl_options(unl)
+    l_ent, l_msq, l_pl, sums, pseudo = UnlabelledLossFn.apply(logits, unl.thresh, bool(want_pseudo) or unl.pseudo > 0.0)
+    return l_ent, l_msq, l_pl, {"sums": sums, "pseudo": pseudo if want_pseudo else None}
+
+
+def upsample_softmax_unl(x, size, unl=None, want_soft=True, want_pseudo=False):
+    """(softmax2d(interp(x)) or None, entropy, max-squares, pseudo-label cross entropy, stats) of the unlabelled prediction's
+    low-resolution logits: unlabelled_losses of the resized logits plus upsample_softmax_ce's softmax map (the same bits).  Fused when
+    the resize grows the map - the head's forward launch, sscg_unl_fwd, ONE stencil launch backward - else the separate passes on
+    upsample_bilinear's output."""
+    unl = _unl_options(unl)
+    oh, ow = int(size[0]), int(size[1])
+    keep = bool(want_pseudo) or unl.pseudo > 0.0
+    if _head_applies(x, oh, ow):
+        soft, l_ent, l_msq, l_pl, sums, pseudo = UnlabelledHeadFn.apply(x, oh, ow, bool(want_soft), unl.thresh, keep)
+    else:
+        up = upsample_bilinear(x, size)
+        soft = softmax2d(up) if want_soft else None
+        l_ent, l_msq, l_pl, sums, pseudo = UnlabelledLossFn.apply(up, unl.thresh, keep)
+    return soft, l_ent, l_msq, l_pl, {"sums": sums, "pseudo": pseudo if want_pseudo else None}
+
+
 class MSEConstFn(torch.autograd.Function):
     """nn.MSELoss()(x, full_like(x, target)) - the LSGAN terms."""
 

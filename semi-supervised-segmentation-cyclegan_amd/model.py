@@ -317,7 +317,62 @@ class _WeightedCE(object):
         return {"weight": self.ce_weight, "label_smoothing": self.ce_smoothing}
 
 
-class semisuper_cycleGAN(_WeightedCE):
+class _UnlabelledLosses(object):
+    # --unl_entropy / --unl_maxsq / --unl_pseudo / --unl_pseudo_thresh / --unl_ramp (opt-in; the reference's unlabelled batch reaches Gsi
+    # through the cycle and adversarial terms only): the entropy, the max-squares loss and the thresholded pseudo-label cross entropy of
+    # the unlabelled prediction join the generator loss as terms of their own, weight F * min(1, epoch / ramp) each
+    # (functional.upsample_softmax_unl: the unlabelled head's forward plus one statistics pass, the same single backward launch)
+    unl_options = None              # functional.UnlabelledOptions when a weight is > 0: no launch, loss key or checkpoint key otherwise
+    unl_ramp = 0                    # epochs over which the three weights rise linearly from 0; 0 = constant
+    _unl_scale = 1.0                # min(1, epoch / ramp) of the current epoch (set_unl_epoch)
+
+    def _init_unl(self, args):
+        w = {}
+        for key in ("unl_entropy", "unl_maxsq", "unl_pseudo"):
+            w[key] = float(getattr(args, key, 0.0) or 0.0)
+            if not (w[key] >= 0.0 and w[key] < float("inf")):
+                raise ValueError("--%s %r must be a finite number >= 0" % (key, getattr(args, key, None)))
+        thresh = getattr(args, "unl_pseudo_thresh", None)
+        if thresh is not None and not w["unl_pseudo"] > 0.0:
+            raise ValueError("--unl_pseudo_thresh needs --unl_pseudo F with F > 0")
+        thresh = 0.9 if thresh is None else float(thresh)
+        if not 0.0 <= thresh <= 1.0:
+            raise ValueError("--unl_pseudo_thresh %r is outside [0, 1]" % (thresh,))
+        ramp = getattr(args, "unl_ramp", 0) or 0
+        if isinstance(ramp, bool) or ramp != int(ramp) or int(ramp) < 0:
+            raise ValueError("--unl_ramp %r must be an integer >= 0" % (ramp,))
+        if not any(v > 0.0 for v in w.values()):
+            return
+        self.unl_ramp = int(ramp)
+        self.unl_options = F.UnlabelledOptions(entropy=w["unl_entropy"], maxsq=w["unl_maxsq"], pseudo=w["unl_pseudo"], thresh=thresh)
+        self.set_unl_epoch(0)
+
+    def set_unl_epoch(self, epoch):
+        """--unl_ramp: the factor on the three unlabelled weights for `epoch` (utils.boundary_loss_schedule's arithmetic); train() calls
+        it once per epoch.  Off: nothing changes."""
+        if self.unl_options is not None:
+            self._unl_scale = utils.boundary_loss_schedule(1.0, self.unl_ramp, epoch)
+        return self._unl_scale
+
+    def _unl_head(self, fake_logits, extras, extra_terms, extra_weights):
+        """The softmax map of the unlabelled prediction (:401-402): the plain fused head by default.  With an --unl_* weight the head
+        also returns the enabled losses: each joins the extras under its own key with its own ramped weight, and --unl_pseudo reports
+        the kept share K / V - a device scalar from the sums the forward left, no sync."""
+        o = self.unl_options
+        if o is None:
+            return F.upsample_softmax_ce(fake_logits, self.crop)[0]
+        fake_gt, l_ent, l_msq, l_pl, stats = F.upsample_softmax_unl(fake_logits, self.crop, o)
+        for key, term, w in (("unl_entropy", l_ent, o.entropy), ("unl_maxsq", l_msq, o.maxsq), ("unl_pseudo_ce", l_pl, o.pseudo)):
+            if w > 0.0:
+                extras[key] = term
+                extra_terms.append(term)
+                extra_weights.append(w * self._unl_scale)
+        if o.pseudo > 0.0:
+            extras["unl_pseudo_kept"] = (stats["sums"][3] / float(fake_gt.shape[0] * self.crop[0] * self.crop[1])).float()
+        return fake_gt
+
+
+class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
     def __init__(self, args, data_parallel=None):
         self.args = args
         _select_device(args)
@@ -368,6 +423,7 @@ class semisuper_cycleGAN(_WeightedCE):
         self.dp = data_parallel
         self._init_ce(args, C)
         self._init_ssim(args)
+        self._init_unl(args)
 
         self.g_optimizer = FusedAdam(itertools.chain(self.Gis.parameters(), self.Gsi.parameters()), lr=args.lr, betas=(0.5, 0.999),
                                      **_optim_options(args, ema=True))
@@ -518,7 +574,8 @@ class semisuper_cycleGAN(_WeightedCE):
         # the resized [B, C, crop] logits are never written (functional.UpsampleHeadFn)
         ohem_kept = {}
         lab_gt, lab_loss_CE, lab_loss_dice = self._head(lab_logits, labels, True, ohem_kept)   # (plain nn.CrossEntropyLoss() by default)
-        fake_gt, _ = F.upsample_softmax_ce(fake_logits, self.crop)
+        extra_terms, extra_weights, extras = [], [], {}
+        fake_gt = self._unl_head(fake_logits, extras, extra_terms, extra_weights)    # (--unl_*: plus the enabled losses)
         if fork:
             main.wait_event(gis_first)
         # (Gis(onehot_gt) and Gis(fake_gt) as ONE grouped-BatchNorm pass on the main lane was built in round 4 and measured slower than
@@ -553,7 +610,6 @@ class semisuper_cycleGAN(_WeightedCE):
             fake_img_all = fake_img
             fake_img, fake_img_d, fake_img_l1 = F.split(fake_img, 3)                 # consumers: Gsi, Di, L1
             recon_logits = self.Gsi(fake_img)                                        # :410
-        extra_terms, extra_weights, extras = [], [], {}
         if "ohem_kept" in ohem_kept:                                                 # --ohem_thresh: the share of counted pixels lab_loss_CE kept
             extras["lab_ohem_kept"] = ohem_kept.pop("ohem_kept")
         if lab_loss_dice is not None:                                                # --dice_weight: inside lab_loss_CE's weight
@@ -846,6 +902,7 @@ class semisuper_cycleGAN(_WeightedCE):
         self.set_components(utils.parse_components(getattr(args, 'components', '')))
         for epoch in range(self.start_epoch, args.epochs):
             self.set_boundary_epoch(epoch)
+            self.set_unl_epoch(epoch)
             if rank0:
                 print('learning rate = %.7f' % self.g_optimizer.param_groups[0]['lr'])
             self.Gsi.train()
@@ -934,6 +991,8 @@ class supervised_model(_WeightedCE):
         self._init_ce(args, self.n_channels)
         if float(getattr(args, "ssim_weight", 0.0) or 0.0) != 0.0:
             print("--ssim_weight is ignored: the supervised model has no image term")
+        if any(float(getattr(args, k, 0.0) or 0.0) != 0.0 for k in ("unl_entropy", "unl_maxsq", "unl_pseudo")):
+            print("--unl_entropy / --unl_maxsq / --unl_pseudo are ignored: the supervised model has no unlabelled batch")
         self.running_metrics_val = utils.runningScore(self.n_channels, args.dataset)
         if not os.path.isdir(args.checkpoint_dir):
             os.makedirs(args.checkpoint_dir, exist_ok=True)
