@@ -595,6 +595,54 @@ int sscg_unl_bwd(const float* x, const uint8_t* pseudo, int N, int H, int W, int
                  const float* g_pl, const double* sums, float* dx, void* stream);
 int sscg_upsample_head_bwd_u(const float* x, const uint8_t* pseudo, const float* dy_soft, const float* g_ent, const float* g_msq,
                              const float* g_pl, const double* sums, float* dx, int N, int H, int W, int C, int OH, int OW, void* stream);
+/* Segmented stable radix sort (no reference counterpart): S segments of L uint32 keys each, [S][L].  out_keys: every segment in
+ * DESCENDING order; out_index: the position (0 .. L-1, int32) each key had in its segment; equal keys keep ascending index.  upper:
+ * every key is below it (0: no bound) - a pass over eight-bit digits that are zero in every key is skipped; keys at or above a
+ * non-zero `upper` are ordered by their low digits only.  Least significant digit first, three launches per pass (per-block digit
+ * histograms in LDS, an exclusive scan of the [digit][block] table, a stable scatter); no block waits for another block of its
+ * launch.  Integer arithmetic only, and nothing is read from the workspace before the call wrote it: the same bits from call to
+ * call.  The entry reads `keys` and writes the two output planes and `ws` (sscg_sort_ws_bytes(S, L) bytes, 4-byte aligned: two
+ * planes of S * L words and the tables) - nothing else.  sscg_sort_chunk: the keys one block of the histogram and scatter passes
+ * serves.  Errors before any HIP call: SSCG_ERR_BAD_ARG (null or misaligned pointers, out_keys == keys, non-positive sizes),
+ * SSCG_ERR_UNSUPPORTED (S * L >= 2^31, or a table of 2^31 entries; the query then returns 0), SSCG_ERR_WORKSPACE.
+ * (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+int sscg_sort_chunk(void);
+size_t sscg_sort_ws_bytes(int64_t S, int64_t L);
+int sscg_sort_u32_desc(const uint32_t* keys, int S, int L, uint32_t upper, uint32_t* out_keys, int32_t* out_index, void* ws,
+                       size_t ws_bytes, void* stream);
+/* Lovasz-softmax loss of the label head (opt-in; the reference has none): Berman, Triki, Blaschko (CVPR 2018).  x = logits
+ * [N][H][W][C] (C <= 64), labels [N][OH][OW]; p = softmax over C of the logits resized to [OH][OW] (bilinear, align_corners=True, the
+ * arithmetic of sscg_upsample_bilinear_fwd; OH == H && OW == W: the logits themselves, the flat form).  A pixel is COUNTED when its
+ * label lies in [0, C).  A SEGMENT is the whole call (per_image == 0) or one sample.  For a segment s and a class c:
+ *     f_i = [y_i == c]   e_i = |f_i - p_i,c| in fp32   G = sum_i f_i   over the V counted pixels i of the segment;
+ *     the pixels ordered by e descending, ties by ascending pixel index; for rank j = 1 .. V: F_j = the foreground pixels among the
+ *     first j, I_j = G - F_j, U_j = G + j - F_j, J_j = 1 - I_j / U_j, J_0 = 0, g_j = J_j - J_{j-1};   loss_{s,c} = sum_j e_(j) g_j.
+ *   g_j is formed in closed form from exact integers in fp64: 1 / U_j at a foreground pixel, I_j / (U_j (U_j - 1)) at a background
+ *   pixel, 1 / (G + 1) at a background pixel of rank 1 (which covers an absent class: G = 0, J_1 = 1).
+ *   The segment's loss is the mean of loss_{s,c} over the classes that take part: never a class of skip_mask (bit c set: class c is
+ *   skipped); with classes_all == 0 ("present") only classes with G > 0 - a segment with none gives 0 - with classes_all == 1 every
+ *   class that is not skipped.  The loss is the mean over the segments; with per_image only samples with a counted pixel enter it,
+ *   with none the loss is 0.  Ignored pixels take no rank, shift no rank, and get gradient 0.
+ * sscg_lovasz_fwd: keys [segments][C][pixels of a segment] uint32 (N * C * OH * OW words): bits(e) + 1 for a counted pixel, 0 for an
+ *   ignored one; loss: the scalar; per_class (fp32 [C], nullable): per class the mean of loss_{s,c} over the live segments in which
+ *   the class took part; coef fp32 [N][OH][OW][C]: d loss / d p with g held constant, (f ? -1 : +1) * g_rank / (classes of the segment
+ *   * live segments), exactly 0 at ignored pixels and at classes that take no part - the layout and the meaning of the dy_soft operand
+ *   of sscg_upsample_head_bwd[_d|_h|_b] and of dy in sscg_softmax_bwd, which are the loss's backward: no stencil of its own.  Every
+ *   element of keys and coef is written.  The key pass (one thread per output pixel; G and V through LDS bins and integer atomics),
+ *   sscg_sort_u32_desc, a multi-block integer scan of the foreground flags in sorted order, one pass that forms g_j, adds e_(j) g_j
+ *   into fixed-order fp64 block records and scatters the coefficients, a one-block finish.  No float atomics; neither the resized
+ *   logits nor the probabilities reach memory; the same bits from call to call.  ws: sscg_lovasz_workspace bytes, 8-byte aligned -
+ *   the sorted keys, their pixels and the sort's two planes (4 * N * C * OH * OW bytes each) and the tables.
+ * sscg_lovasz_scale_add: out[i] = (dy_soft ? dy_soft[i] : 0) + *g * coef[i], n elements: the upstream gradient of the softmax map
+ *   the backward entries receive (g: the loss's upstream scalar on the device; out may be dy_soft).
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null tensors, C outside 1..64, non-positive sizes, flags outside {0, 1}, a skip bit
+ * at or above C, classes_all with every class skipped), SSCG_ERR_UNSUPPORTED (N * C * OH * OW >= 2^31, N*H*W >= 2^31; the query
+ * then returns 0), SSCG_ERR_WORKSPACE.  (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+size_t sscg_lovasz_workspace(int N, int OH, int OW, int C, int per_image);
+int sscg_lovasz_fwd(const float* x, const int64_t* labels, int N, int H, int W, int C, int OH, int OW, int classes_all, int per_image,
+                    uint64_t skip_mask, uint32_t* keys, float* coef, float* loss, float* per_class, void* ws, size_t ws_bytes,
+                    void* stream);
+int sscg_lovasz_scale_add(const float* coef, const float* g, const float* dy_soft, float* out, int64_t n, void* stream);
 /* ------------------------------------------------------------------ inference heads (ABI v18): one launch from a generator's output
  * to what its consumer keeps.  Forward only; never launched by the training step.
  *

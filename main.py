@@ -3,7 +3,8 @@
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
---boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp,
+--lovasz_weight, --lovasz_per_image, --lovasz_classes, --lovasz_skip.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
 import os
@@ -63,6 +64,10 @@ class _Args(Namespace):
     unl_pseudo = 0.0
     unl_pseudo_thresh = None        # 0.9 once --unl_pseudo is given
     unl_ramp = 0
+    lovasz_weight = 0.0
+    lovasz_per_image = False
+    lovasz_classes = "present"
+    lovasz_skip = ""
 
 
 def get_args(argv=None):
@@ -204,6 +209,20 @@ def get_args(argv=None):
     parser.add_argument("--unl_ramp", type=int, default=SUPPRESS, metavar="N",
                         help="raise the three --unl_* weights linearly over the first N epochs, F * min(1, epoch / N); N >= 0, "
                              "0 = constant (default: 0)")
+    parser.add_argument("--lovasz_weight", type=float, default=SUPPRESS, metavar="F",
+                        help="add F times the Lovasz-softmax loss (Berman et al., CVPR 2018), the mIoU surrogate, to every "
+                             "ground-truth cross entropy (lab_loss_CE, gt_cycle_loss, the supervised loss), inside that term's own "
+                             "weight: per class the errors |[y == c] - p_c| sorted on the device and weighted by the gradient of the "
+                             "Jaccard index; reported as lab_loss_lovasz / gt_cycle_lovasz / lovasz_loss; per rank under data "
+                             "parallelism; combines with --ce_weights, --label_smoothing, --dice_weight, --ohem_thresh and "
+                             "--boundary_loss; F >= 0, 0 = off (default: off, the reference's losses)")
+    parser.add_argument("--lovasz_per_image", action="store_true", default=SUPPRESS,
+                        help="one Lovasz loss per sample, averaged over the samples with a labelled pixel (default: the batch is "
+                             "one segment)")
+    parser.add_argument("--lovasz_classes", type=str, choices=["present", "all"], default=SUPPRESS,
+                        help="average the Lovasz loss over the classes present in the segment, or over all (default: present)")
+    parser.add_argument("--lovasz_skip", type=str, default=SUPPRESS, metavar="LIST",
+                        help="comma list of class ids the Lovasz loss leaves out, as --dice_skip (default: none)")
     args = parser.parse_args(argv, namespace=_Args())
     if args.crf.strip():
         try:
@@ -268,6 +287,13 @@ def get_args(argv=None):
             parser.error("--unl_pseudo_thresh must lie in [0, 1]")
     if args.unl_ramp < 0:
         parser.error("--unl_ramp must be an integer >= 0")
+    if not args.lovasz_weight >= 0.0 or args.lovasz_weight == float("inf"):
+        parser.error("--lovasz_weight must be a finite number >= 0")
+    if args.lovasz_skip.strip():
+        toks = [t.strip() for t in args.lovasz_skip.split(",")]
+        n_cls = {"voc2012": 21, "cityscapes": 20, "acdc": 4}[args.dataset]
+        if not all(t.isdigit() and int(t) < n_cls for t in toks) or len(set(int(t) for t in toks)) >= n_cls:
+            parser.error("--lovasz_skip must be a comma list of class ids in [0, %d) that leaves a class over" % n_cls)
     if args.adamw and not args.weight_decay > 0.0:
         parser.error("--adamw decouples the weight decay from the gradient: it needs --weight_decay F with F > 0")
     if args.weight_decay < 0.0 or args.weight_decay != args.weight_decay:

@@ -146,6 +146,12 @@ SIGNATURES = {
     "sscg_unl_fwd": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
     "sscg_unl_bwd": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sscg_upsample_head_bwd_u": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "sscg_sort_chunk": (_i, []),
+    "sscg_sort_ws_bytes": (_sz, [_i64, _i64]),
+    "sscg_sort_u32_desc": (_i, [_p, _i, _i, C.c_uint32, _p, _p, _p, _sz, _p]),
+    "sscg_lovasz_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "sscg_lovasz_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _p, _p, _p, _p, _p, _sz, _p]),
+    "sscg_lovasz_scale_add": (_i, [_p, _p, _p, _p, _i64, _p]),
     "sscg_predict_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_predict_head_ms": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.c_uint32, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),

@@ -3239,6 +3239,127 @@ def boundary_loss(logits, labels, weight=None):
     return BoundaryLossFn.apply(logits, labels, weight)
 
 
+# ----------------------------------------------------------------------------- Lovasz-softmax (opt-in; include/sscg.h: sscg_lovasz_fwd)
+def sort_u32_desc(keys, upper=None):
+    """sscg_sort_u32_desc: the rows of `keys` ([S, L] or [L]; int32 or uint32 on the device, read as unsigned 32-bit words) in
+    descending order and, int32, the position each key had in its row - equal keys keep ascending position.  upper: every key is
+    below it (None: no bound), which lets the sort skip the passes over digits that are zero in every key."""
+    if not (isinstance(keys, torch.Tensor) and keys.is_cuda and keys.dtype in (torch.int32, torch.uint32) and keys.dim() in (1, 2)):
+        raise _lib.SscgError("sort_u32_desc: keys must be an int32 / uint32 [S, L] or [L] tensor on the GPU")
+    keys = keys.contiguous()
+    s, l = (1, keys.shape[0]) if keys.dim() == 1 else keys.shape
+    up = 0 if upper is None else int(upper)
+    if not 0 <= up < 2 ** 32:
+        raise ValueError("sort_u32_desc: upper %r is outside [0, 2^32)" % (upper,))
+    out = torch.empty_like(keys)
+    index = torch.empty(keys.shape, dtype=torch.int32, device=keys.device)
+    if keys.numel() == 0:
+        return out, index
+    ws = torch.empty(lib.sscg_sort_ws_bytes(s, l), dtype=torch.uint8, device=keys.device)
+    check(lib.sscg_sort_u32_desc(keys.data_ptr(), s, l, up, out.data_ptr(), index.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "sscg_sort_u32_desc")
+    return out, index
+
+
+class LovaszOptions(object):
+    """The Lovasz-softmax loss (include/sscg.h: sscg_lovasz_fwd): classes ("present": the mean runs over the classes with a
+    foreground pixel in the segment; "all": over every class), per_image (False: the call is one segment; True: one per sample, the
+    mean over the samples with a counted pixel), skip (class ids that never take part, under either setting of `classes`)."""
+    __slots__ = ("classes", "per_image", "skip")
+
+    def __init__(self, classes="present", per_image=False, skip=()):
+        if classes not in ("present", "all"):
+            raise ValueError("lovasz classes %r is neither 'present' nor 'all'" % (classes,))
+        ids = []
+        for v in skip:
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < MAX_CLASSES:
+                raise ValueError("lovasz skip: %r is not a class id in [0, %d)" % (v, MAX_CLASSES))
+            if v in ids:
+                raise ValueError("lovasz skip: class %d is listed twice" % v)
+            ids.append(v)
+        self.classes, self.per_image, self.skip = classes, bool(per_image), tuple(sorted(ids))
+
+    def skip_mask(self, c):
+        """The skip list as the entry's bit mask, checked against the class count."""
+        mask = 0
+        for v in self.skip:
+            if v >= c:
+                raise ValueError("lovasz skip: class %d of %d classes" % (v, c))
+            mask |= 1 << v
+        if self.classes == "all" and mask == (1 << c) - 1:
+            raise ValueError("lovasz: classes='all' with every class skipped leaves nothing to average")
+        return mask
+
+
+def _lovasz_options(lovasz):
+    if lovasz is None:
+        return LovaszOptions()
+    if isinstance(lovasz, dict):
+        lovasz = LovaszOptions(**lovasz)
+    if not isinstance(lovasz, LovaszOptions):
+        raise TypeError("lovasz must be a functional.LovaszOptions (or a dict of its arguments), not %r" % (lovasz,))
+    return lovasz
+
+
+def lovasz_fwd(x, labels, size, lovasz=None, want_class=False):
+    """sscg_lovasz_fwd on channels-last fp32 logits x [N,C,H,W] and int64 labels [N,OH,OW] (size = (OH, OW); (H, W): the flat form):
+    (loss, coef fp32 [N,OH,OW,C] = d loss / d softmax, keys int32 [segments,C,pixels] = bits(e) + 1, per-class losses [C] or None).
+    No autograd: lovasz_softmax / upsample_softmax_losses wrap it."""
+    n, c, h, w = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    _check_labels(labels, n * oh * ow)
+    lovasz = _lovasz_options(lovasz)
+    mask = lovasz.skip_mask(c)
+    per_image = 1 if lovasz.per_image else 0
+    nws = lib.sscg_lovasz_workspace(n, oh, ow, c, per_image)
+    if nws == 0:
+        raise _lib.SscgError("lovasz: N * C * OH * OW = %d is not below 2^31" % (n * c * oh * ow))
+    segs = n if per_image else 1
+    keys = torch.empty((segs, c, n * oh * ow // segs), dtype=torch.int32, device=x.device)
+    coef = torch.empty((n, oh, ow, c), dtype=torch.float32, device=x.device)
+    loss = _scalar(x.device)
+    per_class = torch.empty((c,), dtype=torch.float32, device=x.device) if want_class else None
+    ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+    check(lib.sscg_lovasz_fwd(x.data_ptr(), labels.data_ptr(), n, h, w, c, oh, ow, 1 if lovasz.classes == "all" else 0, per_image, mask,
+                              keys.data_ptr(), coef.data_ptr(), loss.data_ptr(), _ptr(per_class), ws.data_ptr(), ws.numel(), _stream()),
+          "sscg_lovasz_fwd")
+    return loss, coef, keys, per_class
+
+
+def _lovasz_upstream(coef, g, dy):
+    """g * coef [+ dy]: the upstream gradient of the softmax map the backward entries receive, channels-last [N,C,OH,OW]."""
+    n, oh, ow, c = coef.shape
+    out = empty_nhwc(n, c, oh, ow, coef.device)
+    check(lib.sscg_lovasz_scale_add(coef.data_ptr(), g.data_ptr(), _ptr(dy), out.data_ptr(), coef.numel(), _stream()),
+          "sscg_lovasz_scale_add")
+    return out
+
+
+class LovaszSoftmaxFn(torch.autograd.Function):
+    """Lovasz-softmax loss of logits [N,C,H,W] against labels [N,H,W], the flat form (include/sscg.h: sscg_lovasz_fwd): the forward
+    leaves d loss / d softmax, the backward is sscg_softmax_bwd on it."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, lovasz):
+        _need_hip(logits, f32_only=True)
+        logits = to_nhwc(logits)
+        labels = labels.contiguous()
+        loss, coef, _, _ = lovasz_fwd(logits, labels, logits.shape[2:], lovasz)
+        ctx.save_for_backward(logits, coef)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, coef = ctx.saved_tensors
+        return softmax_bwd(_lovasz_upstream(coef, g.contiguous(), None), softmax_fwd(logits)), None, None
+
+
+def lovasz_softmax(logits, labels, lovasz=None):
+    """The Lovasz-softmax loss (Berman et al., CVPR 2018) of softmax(logits) against labels; labels outside [0, C) are void.
+    lovasz: a LovaszOptions (or a dict of its arguments; None = the defaults)."""
+    return LovaszSoftmaxFn.apply(logits, labels, _lovasz_options(lovasz))
+
+
 # ----------------------------------------------------------------------------- the fused label head: one node for every option
 class LabelHeadFn(torch.autograd.Function):
     """interp (bilinear, align_corners=True) -> softmax2d and / or the losses, from the LOW-resolution logits (model.py:390-392, 398,
@@ -3251,10 +3372,13 @@ class LabelHeadFn(torch.autograd.Function):
     boundary: a BoundaryLossOptions or None - given, the node returns a fourth value, the boundary loss (sscg_sdm on the labels, then
     sscg_boundary_loss_fwd), and every live branch of its backward rides in sscg_upsample_head_bwd_b; not given, the node is the one
     it always was, three values included.
+    lovasz: a LovaszOptions or None - given, the node returns one more value, the last: the Lovasz-softmax loss (sscg_lovasz_fwd, which
+    leaves d loss / d softmax as a coefficient map).  Its backward is no branch of the stencil: g * coef is added to the upstream
+    gradient of the softmax map (sscg_lovasz_scale_add) and whichever entry the other live branches select carries it.
     Backward: ONE launch for every live branch."""
 
     @staticmethod
-    def forward(ctx, x, oh, ow, labels, want_soft, want_ce, weight, eps, dice, ohem, boundary=None):
+    def forward(ctx, x, oh, ow, labels, want_soft, want_ce, weight, eps, dice, ohem, boundary=None, lovasz=None):
         _need_hip(x, f32_only=True)
         x = to_nhwc(x)
         n, c = x.shape[:2]
@@ -3265,34 +3389,46 @@ class LabelHeadFn(torch.autograd.Function):
         mined = want_ce and ohem is not None
         plain_ce = want_ce and not mined
         y = loss = valid = dl = keys = thr = d_loss = coef = b_loss = sdm = b_coef = None
-        if want_soft or plain_ce or not (mined or dice is not None or boundary is not None):      # (nothing wanted at all: the entry refuses the call)
+        if want_soft or plain_ce or not (mined or dice is not None or boundary is not None or lovasz is not None):      # (nothing wanted at all: the entry refuses the call)
             y, loss, valid, dl = _label_head_forward(x, oh, ow, labels, want_soft, plain_ce, weight, eps)
         if mined:
             loss, valid, keys, thr, _ = ohem_fwd(x, labels, (oh, ow), ohem, weight, eps)
         if dice is not None:
             d_loss, coef, _ = dice_fwd(x, labels, (oh, ow), dice.weight, dice.smooth, dice.batch)
         ctx.opts = (oh, ow, weight, eps, 1 if dice is not None and dice.batch else 0)
+        # the Lovasz branch: its loss is one more value at the end, its coefficient map one more saved tensor at the end
+        ctx.lovasz = lovasz is not None
+        ctx.nin = 10 + (1 if boundary is not None or ctx.lovasz else 0) + (1 if ctx.lovasz else 0)
+        l_out = l_saved = ()
+        if ctx.lovasz:
+            l_loss, l_coef, _, _ = lovasz_fwd(x, labels, (oh, ow), lovasz)
+            l_out, l_saved = (l_loss,), (l_coef,)
         if boundary is not None:
             sdm = signed_distance_maps(labels.view(n, oh, ow), c)
             b_loss, b_coef, _, _ = boundary_loss_fwd(x, labels, (oh, ow), sdm, boundary.weight)
             # the boundary backward forms the unmined cross entropy in its stencil: the gradient the forward launch left is not kept
             ctx.boundary = (boundary.weight, want_ce)
-            ctx.save_for_backward(x, labels, valid, coef, keys, thr, sdm, b_coef)
+            ctx.save_for_backward(x, labels, valid, coef, keys, thr, sdm, b_coef, *l_saved)
             ctx.set_materialize_grads(False)
-            return y, loss, d_loss, b_loss
+            return (y, loss, d_loss, b_loss) + l_out
         ctx.boundary = None
         # only what a live branch reads: the labels just where a mined or Dice branch gathers by them
-        ctx.save_for_backward(x, *((labels,) if mined or dice is not None else ()), dl, valid, coef, keys, thr)
+        ctx.save_for_backward(x, *((labels,) if mined or dice is not None else ()), dl, valid, coef, keys, thr, *l_saved)
         # an output nothing differentiates (the step reads lab_gt's softmax through .detach() only): backward gets None, not a
         # zero-filled [B, C, crop] map to gather over
         ctx.set_materialize_grads(False)
-        return y, loss, d_loss
+        return (y, loss, d_loss) + l_out
 
     @staticmethod
-    def backward(ctx, dy, g_ce, g_dice, g_bnd=None):
-        if ctx.boundary is not None:
-            return LabelHeadFn._backward_b(ctx, dy, g_ce, g_dice, g_bnd)
+    def backward(ctx, dy, g_ce, g_dice, *g_rest):
         saved = ctx.saved_tensors
+        if ctx.lovasz:
+            # g_lovasz * coef joins (or is) the upstream gradient of the softmax map: the entries below see one more live dy_soft
+            g_lov, g_rest, l_coef, saved = g_rest[-1], g_rest[:-1], saved[-1], saved[:-1]
+            if g_lov is not None:
+                dy = _lovasz_upstream(l_coef, g_lov.contiguous(), to_nhwc(dy) if dy is not None else None)
+        if ctx.boundary is not None:
+            return LabelHeadFn._backward_b(ctx, saved, dy, g_ce, g_dice, g_rest[0] if g_rest else None)
         x, labels = saved[0], (saved[1] if len(saved) == 7 else None)
         dl, valid, coef, keys, thr = saved[-5:]
         oh, ow, weight, eps, batch = ctx.opts
@@ -3300,7 +3436,7 @@ class LabelHeadFn(torch.autograd.Function):
         use_ce = g_ce is not None and dl is not None
         use_dice = g_dice is not None and coef is not None
         if dy is None and not (mined or use_ce or use_dice):
-            return (None,) * 10
+            return (None,) * ctx.nin
         n, c, h, w = x.shape
         dx = empty_nhwc(n, c, h, w, x.device)
         if dy is not None:
@@ -3317,20 +3453,20 @@ class LabelHeadFn(torch.autograd.Function):
         else:       # (dy None: the cross entropy alone - the entry scales dl)
             check(lib.sscg_upsample_head_bwd(x.data_ptr(), _ptr(dy), ce[0], ce[1], ce[2], dx.data_ptr(), n, h, w, c, oh, ow, _stream()),
                   "sscg_upsample_head_bwd")
-        return (dx,) + (None,) * 9
+        return (dx,) + (None,) * (ctx.nin - 1)
 
     @staticmethod
-    def _backward_b(ctx, dy, g_ce, g_dice, g_bnd):
+    def _backward_b(ctx, saved, dy, g_ce, g_dice, g_bnd):
         """The backward of a node with the boundary branch: one sscg_upsample_head_bwd_b launch for whatever received a gradient (a
         boundary loss that received none leaves sdm out, and the entry runs sscg_upsample_head_bwd_h itself)."""
-        x, labels, valid, coef, keys, thr, sdm, b_coef = ctx.saved_tensors
+        x, labels, valid, coef, keys, thr, sdm, b_coef = saved
         oh, ow, weight, eps, batch = ctx.opts
         b_weight, want_ce = ctx.boundary
         use_ce = g_ce is not None and want_ce
         use_dice = g_dice is not None and coef is not None
         use_bnd = g_bnd is not None
         if dy is None and not (use_ce or use_dice or use_bnd):
-            return (None,) * 11
+            return (None,) * ctx.nin
         n, c, h, w = x.shape
         dx = empty_nhwc(n, c, h, w, x.device)
         if dy is not None:
@@ -3343,7 +3479,7 @@ class LabelHeadFn(torch.autograd.Function):
                                            _ptr(coef if use_dice else None), _ptr(g_dice if use_dice else None), batch, dx.data_ptr(),
                                            n, h, w, c, oh, ow, _ptr(sdm if use_bnd else None), _ptr(b_coef), _ptr(b_weight),
                                            _ptr(g_bnd if use_bnd else None), _stream()), "sscg_upsample_head_bwd_b")
-        return (dx,) + (None,) * 10
+        return (dx,) + (None,) * (ctx.nin - 1)
 
 
 class UpsampleHeadFn(object):
@@ -3355,11 +3491,22 @@ class UpsampleHeadFn(object):
         return LabelHeadFn.apply(x, oh, ow, labels, want_soft, labels is not None, weight, label_smoothing, None, None)[:2]
 
 
-def _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, boundary=None):
-    """(softmax2d(interp(x)) or None, cross entropy or None, Dice loss or None[, boundary loss]): fused (LabelHeadFn) when the resize
-    grows the map, else the separate passes.  dice: a DiceOptions or None; ohem: an OhemOptions or None; boundary: a
-    BoundaryLossOptions (then there is a fourth value) or None."""
+def _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, boundary=None, lovasz=None):
+    """(softmax2d(interp(x)) or None, cross entropy or None, Dice loss or None[, boundary loss][, Lovasz loss]): fused (LabelHeadFn)
+    when the resize grows the map, else the separate passes.  dice: a DiceOptions or None; ohem: an OhemOptions or None; boundary: a
+    BoundaryLossOptions (then there is a fourth value) or None; lovasz: a LovaszOptions (then its loss is one more value, the last)
+    or None."""
     oh, ow = int(size[0]), int(size[1])
+    if lovasz is not None:
+        if _head_applies(x, oh, ow):
+            return LabelHeadFn.apply(x, oh, ow, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, boundary, lovasz)
+        up = upsample_bilinear(x, size)
+        out = ((softmax2d(up) if want_soft else None),
+               (cross_entropy(up, labels, weight, label_smoothing, ohem=ohem) if want_ce else None),
+               (dice_loss(up, labels, dice.weight, dice.smooth, dice.batch) if dice is not None else None))
+        if boundary is not None:
+            out = out + (boundary_loss(up, labels, boundary.weight),)
+        return out + (lovasz_softmax(up, labels, lovasz),)
     if _head_applies(x, oh, ow):
         if boundary is not None:
             return LabelHeadFn.apply(x, oh, ow, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, boundary)
@@ -3394,13 +3541,14 @@ def upsample_softmax_ce_dice(x, size, labels, want_soft=True, weight=None, label
 
 
 def upsample_softmax_losses(x, size, labels, *, want_soft=True, weight=None, label_smoothing=0.0, dice=None, ohem=None, boundary=None,
-                            want_ce=True):
+                            want_ce=True, lovasz=None):
     """The label head with every loss it knows: (softmax2d(interp(x)) or None, cross entropy or None, Dice or None, boundary loss or
     None) of the same resized logits - None for what was not asked.  weight / label_smoothing / ohem: the cross entropy's, as in
     upsample_softmax_ce; dice: a DiceOptions (or a dict of its arguments), its `ce` flag and want_ce both gate the cross entropy;
     boundary: a BoundaryLossOptions (or a dict).  Fused when the resize grows the map - still one autograd node: the existing forward
     entries, then sscg_sdm and sscg_boundary_loss_fwd; ONE sscg_upsample_head_bwd_b launch backward - else the separate passes on
-    upsample_bilinear's output."""
+    upsample_bilinear's output.  lovasz: a LovaszOptions (or a dict) - given, and only then, there is a fifth value, the
+    Lovasz-softmax loss (sscg_lovasz_fwd); its gradient reaches the same backward launch as an upstream gradient of the softmax map."""
     if isinstance(dice, dict):
         dice = DiceOptions(**dice)
     want_ce = bool(want_ce) and (dice is None or dice.ce)
@@ -3408,6 +3556,13 @@ def upsample_softmax_losses(x, size, labels, *, want_soft=True, weight=None, lab
         ohem = _ohem_options(ohem)
         if not want_ce:
             raise ValueError("ohem mines the cross entropy: without it there is nothing to mine")
+    if lovasz is not None:
+        # one more value, the last: the Lovasz-softmax loss (its gradient rides in the same backward launch as dy_soft)
+        lovasz = _lovasz_options(lovasz)
+        if boundary is None:
+            out = _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, None, lovasz)
+            return out[:3] + (None,) + out[3:]
+        return _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, _boundary_options(boundary), lovasz)
     if boundary is None:
         return _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem) + (None,)
     return _label_head(x, size, labels, want_soft, want_ce, weight, label_smoothing, dice, ohem, _boundary_options(boundary))

@@ -153,6 +153,7 @@ class _WeightedCE(object):
         self._init_dice(args, C)
         self._init_ohem(args)
         self._init_boundary_loss(args, C)
+        self._init_lovasz(args, C)
 
     # --dice_weight / --dice_smooth / --dice_skip / --dice_batch (opt-in; the reference has no Dice): every ground-truth cross entropy L
     # becomes L + dice_w * D inside its existing weight, D = the soft Dice loss of the same resized logits (functional.dice_loss)
@@ -216,15 +217,40 @@ class _WeightedCE(object):
             self._boundary_b = utils.boundary_loss_schedule(self.boundary_w, self.boundary_ramp, epoch)
         return self._boundary_b
 
+    # --lovasz_weight / --lovasz_per_image / --lovasz_classes / --lovasz_skip (opt-in; the reference has no IoU surrogate): every
+    # ground-truth cross entropy L becomes L + lovasz_w * Lovasz inside its existing weight, Lovasz = the Lovasz-softmax loss of the same
+    # resized logits (functional.lovasz_softmax; per call = per head and rank, as the Dice statistics are)
+    lovasz_w = 0.0              # 0 = off: no launch, no loss key, no checkpoint key
+    lovasz_options = None       # functional.LovaszOptions when on
+
+    def _init_lovasz(self, args, C):
+        self.lovasz_w = float(getattr(args, "lovasz_weight", 0.0) or 0.0)
+        if not (self.lovasz_w >= 0.0 and self.lovasz_w < float("inf")):
+            raise ValueError("--lovasz_weight %r must be a finite number >= 0" % (getattr(args, "lovasz_weight", None),))
+        if self.lovasz_w == 0.0:
+            return
+        self.lovasz_options = F.LovaszOptions(classes=getattr(args, "lovasz_classes", "present") or "present",
+                                              per_image=bool(getattr(args, "lovasz_per_image", False)),
+                                              skip=utils.parse_lovasz_skip(getattr(args, "lovasz_skip", ""), C))
+        self.lovasz_options.skip_mask(C)        # (refuses classes='all' with every class skipped here, not at the first step)
+
     def _head(self, logits, labels, want_soft, kept=None):
         """(softmax map or None, cross entropy, Dice loss or None) of the ground-truth head: the plain fused head by default.
         --ohem_thresh: the cross entropy is the mined one, and `kept` (a dict) receives the kept share of this head under "ohem_kept"
         - a device scalar from the counts the forward left, no sync.  --boundary_loss: `kept` also receives the boundary loss of this
-        head under "boundary" (without a dict the term is not computed)."""
+        head under "boundary" (without a dict the term is not computed).  --lovasz_weight: likewise the Lovasz-softmax loss under
+        "lovasz"."""
         kw = self._ce_kwargs()
         if self.ohem_options is not None:
             kw = dict(kw, ohem=self.ohem_options)
-        if self.boundary_loss_options is not None and kept is not None:
+        if self.lovasz_options is not None and kept is not None:
+            out = F.upsample_softmax_losses(logits, self.crop, labels, want_soft=want_soft, dice=self.dice_options,
+                                            boundary=self.boundary_loss_options, lovasz=self.lovasz_options, **kw)
+            if self.boundary_loss_options is not None:
+                kept["boundary"] = out[3]
+            kept["lovasz"] = out[4]
+            out = out[:3]
+        elif self.boundary_loss_options is not None and kept is not None:
             out = F.upsample_softmax_losses(logits, self.crop, labels, want_soft=want_soft, dice=self.dice_options,
                                             boundary=self.boundary_loss_options, **kw)
             kept["boundary"] = out[3]
@@ -620,6 +646,10 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
             extras["lab_loss_boundary"] = ohem_kept.pop("boundary")
             extra_terms.append(extras["lab_loss_boundary"])
             extra_weights.append(a.lab_CE_weight * self._boundary_b)
+        if "lovasz" in ohem_kept:                                                    # --lovasz_weight: inside lab_loss_CE's weight
+            extras["lab_loss_lovasz"] = ohem_kept.pop("lovasz")
+            extra_terms.append(extras["lab_loss_lovasz"])
+            extra_weights.append(a.lab_CE_weight * self.lovasz_w)
         if "l1_cycle" in self.variants:                                              # :453 (commented out in the reference)
             recon_img, recon_img_l1 = F.split(recon_img, 2)
             extras["img_cycle_l1"] = self._image_l1(recon_img_l1, unl_img, extras, "img_cycle_ssim", a.lamda_img, extra_terms, extra_weights)
@@ -663,6 +693,10 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
             extras["gt_cycle_boundary"] = ohem_kept.pop("boundary")
             extra_terms.append(extras["gt_cycle_boundary"])
             extra_weights.append(a.lamda_gt * self._boundary_b)
+        if "lovasz" in ohem_kept:                                                    # --lovasz_weight: inside gt_cycle_loss's weight
+            extras["gt_cycle_lovasz"] = ohem_kept.pop("lovasz")
+            extra_terms.append(extras["gt_cycle_lovasz"])
+            extra_weights.append(a.lamda_gt * self.lovasz_w)
         lab_loss_MSE = self._image_l1(fake_img_l1, l_img, extras, "lab_loss_ssim", a.lab_MSE_weight, extra_terms, extra_weights)   # :461
         # :464-468  gen_loss = CE_w*CE + MSE_w*L1 + adv_w*(img_gen + gt_gen) + img_cycle + lamda_gt*gt_cycle
         gen_loss = F.weighted_sum(
@@ -1015,16 +1049,25 @@ class supervised_model(_WeightedCE):
         ohem_kept = {}
         _, loss, dice = self._head(self.Gsi(l_img), l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3]), False, ohem_kept)
         bnd = ohem_kept.pop("boundary", None)
+        lov = ohem_kept.pop("lovasz", None)
         if ohem_kept:   # --ohem_thresh: the step returns the mined cross entropy, the kept share of the counted pixels goes to self.extras
             self.extras = ohem_kept
-        if dice is None and bnd is None:
+        if dice is None and bnd is None and lov is None:
             F.backward(loss)
-        elif bnd is None:       # --dice_weight: CE + dice_w * Dice; the step still returns the cross entropy, the Dice term goes to self.extras
+        elif bnd is None and lov is None:       # --dice_weight: CE + dice_w * Dice; the step still returns the cross entropy, the Dice term goes to self.extras
             self.extras = dict(ohem_kept, dice_loss=dice.detach())
             F.backward(F.weighted_sum([loss, dice], [1.0, self.dice_w]))
-        else:       # --boundary_loss: CE [+ dice_w * Dice] + b * Boundary, the terms reported the same way
-            terms, weights = [loss, bnd], [1.0, self._boundary_b]
-            self.extras = dict(ohem_kept, boundary_loss=bnd.detach())
+        else:       # --boundary_loss / --lovasz_weight: CE [+ dice_w * Dice] [+ b * Boundary] [+ lovasz_w * Lovasz], reported the same way
+            terms, weights = [loss], [1.0]
+            self.extras = dict(ohem_kept)
+            if bnd is not None:
+                terms.append(bnd)
+                weights.append(self._boundary_b)
+                self.extras["boundary_loss"] = bnd.detach()
+            if lov is not None:
+                terms.append(lov)
+                weights.append(self.lovasz_w)
+                self.extras["lovasz_loss"] = lov.detach()
             if dice is not None:
                 terms.append(dice)
                 weights.append(self.dice_w)
@@ -1112,6 +1155,8 @@ class supervised_model(_WeightedCE):
                         print("Dice Loss:%.2e (weight %g)" % (float(self.extras["dice_loss"]), self.dice_w))
                     if self.boundary_loss_options is not None:
                         print("Boundary Loss:%.2e (weight %g)" % (float(self.extras["boundary_loss"]), self._boundary_b))
+                    if self.lovasz_options is not None:
+                        print("Lovasz Loss:%.2e (weight %g)" % (float(self.extras["lovasz_loss"]), self.lovasz_w))
                     if self.ohem_options is not None:
                         print("OHEM kept:%.4f of the labelled pixels" % float(self.extras["ohem_kept"]))
                     if self.gsi_optimizer.last_grad_norm is not None:       # --clip_grad_norm: the norm this step's update clipped

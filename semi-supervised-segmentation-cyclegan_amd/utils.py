@@ -565,6 +565,22 @@ def parse_boundary_loss_skip(spec, n_classes):
     return sorted(ids)
 
 
+def parse_lovasz_skip(spec, n_classes):
+    """--lovasz_skip: a comma list of class ids the Lovasz-softmax loss leaves out, in parse_dice_skip's grammar -> a sorted tuple of
+    distinct ids in [0, n_classes); "" / None -> ().  Skipping every class is refused.  Raises ValueError naming the bad token."""
+    if spec is None or not str(spec).strip():
+        return ()
+    ids = set()
+    for tok in str(spec).split(","):
+        t = tok.strip()
+        if not (t.isdigit() and int(t) < int(n_classes)):
+            raise ValueError("--lovasz_skip: %r is not a class id in [0, %d)" % (t, n_classes))
+        ids.add(int(t))
+    if len(ids) >= int(n_classes):
+        raise ValueError("--lovasz_skip: %r skips every class" % (spec,))
+    return tuple(sorted(ids))
+
+
 def boundary_loss_schedule(weight, ramp, epoch):
     """--boundary_loss F with --boundary_loss_ramp N: the weight of the boundary term in `epoch` (0-based), b = F * min(1, epoch / N);
     N == 0: F from the first epoch on.  A host scalar: no kernel sees it."""
