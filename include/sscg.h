@@ -358,6 +358,32 @@ size_t sscg_augment_colour_workspace(int N);
 int sscg_augment_colour_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H, int W,
                            int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill,
                            int label_fill, const float* colour, int need_mean, void* ws, void* stream);
+/* sscg_augment_colour_u8 with an elastic (free-form) deformation added to the affine source coordinate: a uniform cubic B-spline over
+ * a coarse lattice of control nodes per sample, evaluated per output pixel in integers.  colour may be NULL = no colour stage (then
+ * need_mean and ws are ignored and every C in 1..4 is taken); the other arguments of sscg_augment_colour_u8 mean what they mean there.
+ *   lattice: nodes int32 [N][GH][GW][2] on the device, grid >= 4 the node spacing in OUTPUT pixels, GH = (OH-1)/grid + 4,
+ *            GW = (OW-1)/grid + 4 (integer division).  Component 0 is the x, component 1 the y displacement, in SOURCE pixels, Q16:
+ *            the host has multiplied the 2x2 linear part of the sample's affine map into its lattice (the interpolation is linear in
+ *            the nodes, so that is exact up to the rounding of the nodes).  |node| < 2^26.
+ *   cell:    for output pixel (oy, ox): cx = ox / grid, tx = ((ox - cx*grid) * 256) / grid; cy, ty likewise from oy.
+ *   weights: the four B-spline weights at t in 0..255 are the integer numerators over D = 6 * 2^24
+ *              n0 = (256-t)^3    n1 = 3t^3 - 6*256 t^2 + 4*256^3    n2 = -3t^3 + 3*256 t^2 + 3*256^2 t + 256^3    n3 = t^3
+ *            (non-negative, each below 2^31, the four sum to D exactly).
+ *   y pass, then x pass, per component, in int64 with FLOOR division (negative values too; every sum stays below 2^53):
+ *              c_j = floor((sum_i n_i(ty) * node[cy+i][cx+j] + D/2) / D)   j = 0..3
+ *              d   = floor((sum_j n_j(tx) * c_j + D/2) / D)
+ *   sample:  sx = m0*ox + m1*oy + m2 + d_x    sy = m3*ox + m4*oy + m5 + d_y; everything behind (sx, sy) is sscg_augment_u8's and
+ *            sscg_augment_colour_u8's: taps and fill, the nearest label index, the tables, the two fp32 divisions - and the sum pass
+ *            of need_mean sums the DISPLACED pixels.
+ * An all-zero lattice gives the bits of the affine entries; a constant lattice (a, b) those of the affine entries with m2 + a and
+ * m5 + b (the weights sum to D).  Errors before any HIP call: SSCG_ERR_BAD_ARG (sscg_augment_u8's cases, a NULL nodes, grid < 4, GH or
+ * GW other than the formula's, with a colour table need_mean with a NULL or misaligned ws), SSCG_ERR_UNSUPPORTED (sscg_augment_u8's
+ * size limits, grid above 2^22; with a colour table C of 2 or 4 and need_mean with N above 65535).
+ * (An addition: no existing entry changes meaning or bits, so SSCG_ABI_VERSION stays 18.) */
+int sscg_augment_elastic_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H, int W,
+                            int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill,
+                            int label_fill, const float* colour, int need_mean, void* ws, const int32_t* nodes, int grid, int GH, int GW,
+                            void* stream);
 
 /* ------------------------------------------------------------------ losses (K10, K11), mean reduction
  * Each forward writes one fp32 scalar to `loss` (device).  Each backward takes the upstream gradient as

@@ -96,7 +96,9 @@ def get_args(argv=None):
                         help="torchvision VGG16 state dict for --variants perceptual (the reference downloads vgg16(pretrained=True))")
     parser.add_argument("--augment", type=str, default="",
                         help="comma list of geometric and colour augmentations of the labelled and unlabelled training batches, applied "
-                             "in one launch inside the device-side batch finish: hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop; "
+                             "in one launch inside the device-side batch finish: hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop, "
+                             "elastic=<alpha>[:<grid>] (a B-spline deformation of the output: control nodes every <grid> output pixels, "
+                             "default 32, untuned, each moved by up to <alpha> pixels; alpha <= 0.4 * grid, at most one such item); "
                              "brightness=<x>, contrast=<x>, saturation=<x> (factor in max(0,1-x)..1+x), hue=<x> (0..0.5 of a turn), "
                              "gray=<p> - colour behind geometry, each in the order written, clamped to [0,1] once at the end; "
                              "contrast adds a sum pass for the image mean (default: none)")

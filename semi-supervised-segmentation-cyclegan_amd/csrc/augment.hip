@@ -5,6 +5,10 @@
 // sscg_augment_colour_u8 is the same launch with a per-sample colour table between the warp and the normalisation (COLOUR
 // instantiations of the same kernel body), in front of it - only when the table uses the image mean - a pass that sums the warped
 // integer pixels of every sample.
+// sscg_augment_elastic_u8 adds a free-form deformation to the affine source coordinate (ELASTIC instantiations of the same three
+// kernels): a cubic B-spline over a coarse lattice of int32 control nodes per sample, integers throughout.
+#include <type_traits>
+
 #include "common.h"
 #include "sscg_internal.h"
 
@@ -94,12 +98,118 @@ struct aug_taps {
     }
 };
 
+// ---- the elastic term (include/sscg.h, sscg_augment_elastic_u8): what an elastic launch adds to the arguments, and its arithmetic
+struct aug_elastic_args {
+    const int32_t* nodes;    // [N][GH][GW][2]
+    int grid, GH, GW;
+};
+
+// the displacement of one pixel, Q16 source pixels (zero in the launches without a lattice, where it folds away)
+struct aug_disp { int32_t x, y; };
+
+// the four B-spline numerators at t in 0..255, over D = 6 * 2^24: non-negative, each below 2^27
+__device__ __forceinline__ void aug_bspline(int t, int32_t* n) {
+    const int u = 256 - t, t2 = t * t, t3 = t2 * t;
+    n[0] = u * u * u;
+    n[1] = 3 * t3 - 1536 * t2 + (4 << 24);
+    n[2] = -3 * t3 + 768 * t2 + 196608 * t + (1 << 24);
+    n[3] = t3;
+}
+
+// floor((s + D/2) / D), D = 3 * 2^25, for |s| <= D * 2^26: the arithmetic shift floors, what it leaves is below 2^28 in magnitude, so
+// the floor division by 3 is an unsigned 32-bit one behind an offset of 3 * 2^28
+__device__ __forceinline__ int32_t aug_div_d(int64_t s) {
+    const int32_t v = (int32_t)((s + (3ll << 24)) >> 25);
+    return (int32_t)((uint32_t)(v + (3 << 28)) / 3u) - (1 << 28);
+}
+
+// the y pass of one node column: p = &node[cy][cx + j][0], `row` = GW * 2 int32 to the node below
+__device__ __forceinline__ aug_disp aug_ypass(const int32_t* __restrict__ p, int row, const int32_t* ny) {
+    int64_t sx = 0, sy = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        sx += (int64_t)ny[i] * p[(size_t)i * row];
+        sy += (int64_t)ny[i] * p[(size_t)i * row + 1];
+    }
+    return {aug_div_d(sx), aug_div_d(sy)};
+}
+
+// the x pass over four consecutive columns of the y pass
+__device__ __forceinline__ aug_disp aug_xpass(const aug_disp* c, int tx) {
+    int32_t nx[4];
+    aug_bspline(tx, nx);
+    int64_t sx = 0, sy = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        sx += (int64_t)nx[j] * c[j].x;
+        sy += (int64_t)nx[j] * c[j].y;
+    }
+    return {aug_div_d(sx), aug_div_d(sy)};
+}
+
+// one pixel on its own: both passes
+__device__ __forceinline__ aug_disp aug_elastic_pixel(const aug_elastic_args& el, int n, int oy, int ox) {
+    const int cy = oy / el.grid, cx = ox / el.grid;
+    const int ty = ((oy - cy * el.grid) * 256) / el.grid, tx = ((ox - cx * el.grid) * 256) / el.grid;
+    int32_t ny[4];
+    aug_bspline(ty, ny);
+    const int row = el.GW * 2;
+    const int32_t* p = el.nodes + (((size_t)n * el.GH + cy) * el.GW + cx) * 2;
+    aug_disp c[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c[j] = aug_ypass(p + j * 2, row, ny);
+    return aug_xpass(c, tx);
+}
+
+// The same as a call, for the rare pixels of the apply pass that take it (groups that straddle a row or a sample, the scalar tail):
+// inlined four times beside the row path it costs the kernel 194 VGPRs and 1700 instructions; as a call the kernel has 80 to 100
+// VGPRs, as the affine ones (no difference in time was measured between the two: profiles/augment_elastic.txt).  Arguments by
+// value: they travel in registers, the kernel needs no stack.
+__device__ __noinline__ aug_disp aug_elastic_pixel_call(aug_elastic_args el, int n, int oy, int ox) { return aug_elastic_pixel(el, n, oy, ox); }
+
+// four consecutive pixels of one row, (oy, ox) .. (oy, ox + 3) with ox + 3 < OW: at grid >= 4 they lie in at most two cells, so the y
+// pass runs once per node column - four, or five when the group crosses into the next cell (only then does the fifth exist)
+__device__ __forceinline__ void aug_elastic_row4(const aug_elastic_args& el, int n, int oy, int ox, aug_disp* d) {
+    const int cy = oy / el.grid, cx = ox / el.grid;
+    const int ty = ((oy - cy * el.grid) * 256) / el.grid;
+    const int rem = ox - cx * el.grid;
+    int32_t ny[4];
+    aug_bspline(ty, ny);
+    const int row = el.GW * 2;
+    const int32_t* p = el.nodes + (((size_t)n * el.GH + cy) * el.GW + cx) * 2;
+    aug_disp c[5];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c[j] = aug_ypass(p + j * 2, row, ny);
+    c[4] = {0, 0};
+    if (rem + 3 >= el.grid) c[4] = aug_ypass(p + 8, row, ny);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bool next = rem + e >= el.grid;
+        const int r = next ? rem + e - el.grid : rem + e;
+        aug_disp w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = next ? c[j + 1] : c[j];
+        d[e] = aug_xpass(w, (r * 256) / el.grid);
+    }
+}
+
+// the argument of type T among the trailing ones of a launch, or an empty one
+template <typename T>
+__device__ __forceinline__ T aug_pick() { return T{}; }
+template <typename T, typename A0, typename... A>
+__device__ __forceinline__ T aug_pick(A0 a0, A... a) {
+    if constexpr (std::is_same_v<T, A0>) return a0;
+    else return aug_pick<T>(a...);
+}
+
 // one output pixel (n, oy, ox): C normalised channels into out[], the raw source label id as the return value (LABEL only)
-template <int C, bool LABEL, bool COLOUR>
+template <int C, bool LABEL, bool COLOUR, bool ELASTIC>
 __device__ __forceinline__ int aug_pixel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ gt, const aug_mat& a, const aug_col<C>& k,
-                                         const aug_geom& g, int n, int oy, int ox, const float* mean, const float* stdev, float* out) {
-    const int64_t sx = (int64_t)a.m[0] * ox + (int64_t)a.m[1] * oy + a.m[2];
-    const int64_t sy = (int64_t)a.m[3] * ox + (int64_t)a.m[4] * oy + a.m[5];
+                                         const aug_geom& g, int n, int oy, int ox, aug_disp d, const float* mean, const float* stdev,
+                                         float* out) {
+    int64_t sx = (int64_t)a.m[0] * ox + (int64_t)a.m[1] * oy + a.m[2];
+    int64_t sy = (int64_t)a.m[3] * ox + (int64_t)a.m[4] * oy + a.m[5];
+    if constexpr (ELASTIC) { sx += d.x; sy += d.y; }
     const size_t plane = (size_t)n * g.H * g.W;
     // ---- image
     const aug_taps<C> taps(img, g, plane, sx, sy);
@@ -138,21 +248,20 @@ struct aug_colour_args {
 // as 16-byte vectors: 4 * C floats = C stores, four labels = two stores.  `groups` = 0 sends every pixel down the scalar tail.
 // The colour flag is the argument pack: COL is empty - the plain launch, whose arguments and with them whose instruction stream are
 // those it had before the colour instantiations existed - or aug_colour_args, and then the sample's colour table travels with its
-// matrix and is reloaded wherever the matrix is.
+// matrix and is reloaded wherever the matrix is - and / or aug_elastic_args, and then every pixel's source coordinate takes the
+// displacement of the sample's lattice: one y pass per group where its four pixels share a row, pixel by pixel elsewhere.
 template <int C, bool LABEL, typename... COL>
 __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ gt,
                                                                  const int32_t* __restrict__ mats, float* __restrict__ out_img,
                                                                  int64_t* __restrict__ out_gt, const float* __restrict__ mean,
                                                                  const float* __restrict__ stdev, const int64_t* __restrict__ lut,
                                                                  aug_geom g, uint32_t total, uint32_t groups, COL... col) {
-    constexpr bool COLOUR = sizeof...(COL) != 0;
-    const float* colour = nullptr;
-    const int64_t* sums = nullptr;
-    if constexpr (COLOUR) {
-        const aug_colour_args ca[] = {col...};
-        colour = ca[0].table;
-        sums = ca[0].sums;
-    }
+    constexpr bool COLOUR = (std::is_same_v<COL, aug_colour_args> || ...);
+    constexpr bool ELASTIC = (std::is_same_v<COL, aug_elastic_args> || ...);
+    const aug_colour_args ca = aug_pick<aug_colour_args>(col...);
+    const float* colour = ca.table;
+    const int64_t* sums = ca.sums;
+    const aug_elastic_args el = aug_pick<aug_elastic_args>(col...);
     __shared__ int64_t t[256];
     if constexpr (LABEL) {
         t[threadIdx.x] = lut[threadIdx.x];
@@ -176,9 +285,25 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
         if constexpr (COLOUR) k = aug_load_col<C>(colour, sums, n, denom);
         float v[4 * C];
         int64_t lab[4];
+        aug_disp d[4] = {};
+        if constexpr (ELASTIC) {
+            if (ox + 3 < g.OW) {
+                aug_elastic_row4(el, n, oy, ox, d);
+            } else {                                // the group straddles a row or a sample: pixel by pixel, walking as the loop below
+                int dn = n, dy = oy, dx = ox;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    d[e] = aug_elastic_pixel_call(el, dn, dy, dx);
+                    if (e < 3 && ++dx == g.OW) {
+                        dx = 0;
+                        if (++dy == g.OH) { dy = 0; ++dn; }
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int id = aug_pixel<C, LABEL, COLOUR>(img, gt, a, k, g, n, oy, ox, mu, sd, v + e * C);
+            const int id = aug_pixel<C, LABEL, COLOUR, ELASTIC>(img, gt, a, k, g, n, oy, ox, d[e], mu, sd, v + e * C);
             if constexpr (LABEL) lab[e] = t[id];
             if (e < 3 && ++ox == g.OW) {
                 ox = 0;
@@ -208,7 +333,9 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
         aug_col<C> k;
         if constexpr (COLOUR) k = aug_load_col<C>(colour, sums, n, denom);
         float v[C];
-        const int id = aug_pixel<C, LABEL, COLOUR>(img, gt, a, k, g, n, oy, ox, mu, sd, v);
+        aug_disp d = {};
+        if constexpr (ELASTIC) d = aug_elastic_pixel_call(el, n, oy, ox);
+        const int id = aug_pixel<C, LABEL, COLOUR, ELASTIC>(img, gt, a, k, g, n, oy, ox, d, mu, sd, v);
 #pragma unroll
         for (int c = 0; c < C; ++c) out_img[(size_t)p * C + c] = v[c];
         if constexpr (LABEL) out_gt[p] = t[id];
@@ -226,9 +353,11 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_zero_kernel(int64_t* __re
     for (int i = blockIdx.x * AUG_THREADS + threadIdx.x; i < n; i += gridDim.x * AUG_THREADS) sums[i] = 0;
 }
 
-template <int C>
+// EL is empty - the affine pass, with the arguments it had before the elastic one existed - or aug_elastic_args
+template <int C, typename... EL>
 __global__ __launch_bounds__(AUG_THREADS) void augment_sum_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ mats, aug_geom g,
-                                                                  int64_t* __restrict__ sums) {
+                                                                  int64_t* __restrict__ sums, EL... ela) {
+    constexpr bool ELASTIC = sizeof...(EL) != 0;
     __shared__ int64_t part[AUG_THREADS / 64][C];
     const int n = blockIdx.y;
     const aug_mat a = aug_load_mat(mats, n);
@@ -240,8 +369,13 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_sum_kernel(const uint8_t*
     for (uint32_t p = blockIdx.x * AUG_THREADS + threadIdx.x; p < hw; p += gridDim.x * AUG_THREADS) {
         const int oy = (int)(p / (uint32_t)g.OW);
         const int ox = (int)(p - (uint32_t)oy * (uint32_t)g.OW);
-        const int64_t sx = (int64_t)a.m[0] * ox + (int64_t)a.m[1] * oy + a.m[2];
-        const int64_t sy = (int64_t)a.m[3] * ox + (int64_t)a.m[4] * oy + a.m[5];
+        int64_t sx = (int64_t)a.m[0] * ox + (int64_t)a.m[1] * oy + a.m[2];
+        int64_t sy = (int64_t)a.m[3] * ox + (int64_t)a.m[4] * oy + a.m[5];
+        if constexpr (ELASTIC) {
+            const aug_disp d = aug_elastic_pixel(aug_pick<aug_elastic_args>(ela...), n, oy, ox);
+            sx += d.x;
+            sy += d.y;
+        }
         const aug_taps<C> taps(img, g, plane, sx, sy);
 #pragma unroll
         for (int c = 0; c < C; ++c) s[c] += taps.value(c, g.image_fill);
@@ -264,37 +398,38 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_sum_kernel(const uint8_t*
     }
 }
 
-template <int C>
+// `el`: nothing, or the aug_elastic_args of an elastic launch (here and in aug_launch_colour)
+template <int C, typename... EL>
 void aug_launch(bool label, dim3 grid, hipStream_t st, const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img,
                 int64_t* out_gt, const float* mean, const float* stdev, const int64_t* lut, const aug_geom& g, uint32_t total,
-                uint32_t groups) {
+                uint32_t groups, EL... el) {
     if (label)
-        hipLaunchKernelGGL((augment_u8_kernel<C, true>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g,
-                           total, groups);
+        hipLaunchKernelGGL((augment_u8_kernel<C, true, EL...>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g,
+                           total, groups, el...);
     else
-        hipLaunchKernelGGL((augment_u8_kernel<C, false>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g,
-                           total, groups);
+        hipLaunchKernelGGL((augment_u8_kernel<C, false, EL...>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g,
+                           total, groups, el...);
 }
 
-template <int C>
+template <int C, typename... EL>
 void aug_launch_colour(bool label, dim3 grid, hipStream_t st, const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img,
                        int64_t* out_gt, const float* mean, const float* stdev, const int64_t* lut, const aug_geom& g, uint32_t total,
-                       uint32_t groups, const float* colour, int64_t* sums, int N) {
+                       uint32_t groups, const float* colour, int64_t* sums, int N, EL... el) {
     if (sums) {
         const uint32_t hw = (uint32_t)g.OH * (uint32_t)g.OW;
         const int cap = AUG_SUM_MAX_BLOCKS / N > 0 ? AUG_SUM_MAX_BLOCKS / N : 1;
         int bx = cdiv((long)hw, (long)AUG_THREADS * AUG_SUM_ROUNDS);
         if (bx > cap) bx = cap;
         hipLaunchKernelGGL(augment_zero_kernel, dim3(ew_blocks((size_t)N * 3, 64)), dim3(AUG_THREADS), 0, st, sums, N * 3);
-        hipLaunchKernelGGL(augment_sum_kernel<C>, dim3(bx, N), dim3(AUG_THREADS), 0, st, img, mats, g, sums);
+        hipLaunchKernelGGL((augment_sum_kernel<C, EL...>), dim3(bx, N), dim3(AUG_THREADS), 0, st, img, mats, g, sums, el...);
     }
     const aug_colour_args ca = {colour, sums};
     if (label)
-        hipLaunchKernelGGL((augment_u8_kernel<C, true, aug_colour_args>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean, stdev, lut,
-                           g, total, groups, ca);
+        hipLaunchKernelGGL((augment_u8_kernel<C, true, aug_colour_args, EL...>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean,
+                           stdev, lut, g, total, groups, ca, el...);
     else
-        hipLaunchKernelGGL((augment_u8_kernel<C, false, aug_colour_args>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean, stdev,
-                           lut, g, total, groups, ca);
+        hipLaunchKernelGGL((augment_u8_kernel<C, false, aug_colour_args, EL...>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean,
+                           stdev, lut, g, total, groups, ca, el...);
 }
 
 // the argument rules both entries share; 0 = go on
@@ -364,6 +499,42 @@ extern "C" int sscg_augment_colour_u8(const uint8_t* img, const uint8_t* gt, con
         aug_launch_colour<1>(label, dim3(blocks), st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, (uint32_t)total, groups, colour, sums, N);
     else
         aug_launch_colour<3>(label, dim3(blocks), st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, (uint32_t)total, groups, colour, sums, N);
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
+extern "C" int sscg_augment_elastic_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N,
+                                       int H, int W, int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256,
+                                       int image_fill, int label_fill, const float* colour, int need_mean, void* ws, const int32_t* nodes,
+                                       int grid, int GH, int GW, void* stream) {
+    const int bad = aug_check(img, gt, mats, out_img, out_gt, N, H, W, C, OH, OW, mean, stdev, lut256, image_fill, label_fill);
+    if (bad == SSCG_ERR_BAD_ARG) return bad;
+    if (!nodes || grid < 4 || GH != (OH - 1) / grid + 4 || GW != (OW - 1) / grid + 4) return SSCG_ERR_BAD_ARG;
+    if (!colour) need_mean = 0;
+    if (need_mean && (!ws || ((size_t)ws & 7) != 0)) return SSCG_ERR_BAD_ARG;
+    if (bad) return bad;
+    // (the position inside a cell) * 256 stays an int
+    if (grid > (1 << 22) || (colour && (C == 2 || C == 4 || (need_mean && N > 65535)))) return SSCG_ERR_UNSUPPORTED;
+    const int64_t total = (int64_t)N * OH * OW;
+    uint32_t groups;
+    const dim3 blocks(aug_plan(out_img, out_gt, total, &groups));
+    const aug_geom g = {H, W, OH, OW, image_fill, label_fill};
+    const hipStream_t st = (hipStream_t)stream;
+    const bool label = gt != nullptr;
+    const aug_elastic_args el = {nodes, grid, GH, GW};
+    const uint32_t tot = (uint32_t)total;
+    if (colour) {
+        int64_t* sums = need_mean ? reinterpret_cast<int64_t*>(ws) : nullptr;
+        if (C == 1) aug_launch_colour<1>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, tot, groups, colour, sums, N, el);
+        else aug_launch_colour<3>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, tot, groups, colour, sums, N, el);
+    } else {
+        switch (C) {
+            case 1: aug_launch<1>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, tot, groups, el); break;
+            case 2: aug_launch<2>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, tot, groups, el); break;
+            case 3: aug_launch<3>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, tot, groups, el); break;
+            default: aug_launch<4>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, tot, groups, el); break;
+        }
+    }
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

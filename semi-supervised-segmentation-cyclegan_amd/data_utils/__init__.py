@@ -16,8 +16,10 @@ code: in `device_finish` mode `DeviceLoader(..., augmentation=)` draws one map p
 matrices with the batch and finishes the batch with ONE `sscg_augment_u8` launch (warp + ToTensor + Normalize + label table)
 instead of the two passes above; in host mode the same maps go through PIL as the datasets' `augmentation=`.  Colour items
 (brightness, contrast, saturation, hue, gray) compose into one small table per sample that the same launch applies
-(`sscg_augment_colour_u8`; a contrast item adds a sum pass for the image mean).  Without an augmentation nothing changes: the same
-two launches as before."""
+(`sscg_augment_colour_u8`; a contrast item adds a sum pass for the image mean).  An `elastic=` item adds a non-rigid warp to the same
+launch (`sscg_augment_elastic_u8`): a coarse lattice of control nodes per sample, drawn on the host, interpolated per output pixel on
+the device; in host mode the same integer definition runs in numpy instead of PIL.  Without an augmentation nothing changes: the
+same two launches as before."""
 import numpy as np
 import torch
 from PIL import Image
@@ -183,7 +185,9 @@ class DeviceLoader:
     inside the finish - the maps of a batch are drawn on the host from `RandomState(seed)`, in batch order, uploaded with the batch
     and applied by one `functional.augment_batch` launch that replaces the two passes.  When the augmentation has colour ops, their
     per-sample table is drawn from a second generator, `RandomState(seed + augmentations.COLOUR_SEED_OFFSET)`, and travels with the
-    maps; the geometric draws of a seed do not depend on it."""
+    maps; the geometric draws of a seed do not depend on it.  An elastic op likewise: the control lattices of a batch are drawn from a
+    third generator, `RandomState(seed + augmentations.ELASTIC_SEED_OFFSET)`, uploaded with the maps and interpolated inside the same
+    launch (`sscg_augment_elastic_u8`); without one there is no further upload and no other launch than before."""
 
     def __init__(self, loader, transformation, device, augmentation=None, seed=0):
         if not transformation.get('device_finish'):
@@ -191,6 +195,7 @@ class DeviceLoader:
         self.loader, self.device = loader, device
         self.augmentation, self.rng = augmentation, np.random.RandomState(seed)
         self.colour_rng = np.random.RandomState(seed + augmentations.COLOUR_SEED_OFFSET)
+        self.elastic_rng = np.random.RandomState(seed + augmentations.ELASTIC_SEED_OFFSET)
         self.lut = transformation['lut'].to(device)
         self.mean = torch.tensor(transformation['mean'], dtype=torch.float32, device=device)
         self.std = torch.tensor(transformation['std'], dtype=torch.float32, device=device)
@@ -218,14 +223,18 @@ class DeviceLoader:
     def _augmented(self, F, batch):
         aug = self.augmentation
         b, h, w, c = batch[0].shape
-        mats = self._up(torch.from_numpy(aug.matrices(self.rng, b, w, h)))
+        drawn = aug.matrices(self.rng, b, w, h)
+        mats = self._up(torch.from_numpy(drawn))
         gt = self._up(batch[1]) if len(batch) == 3 else None
-        colour = {}
+        extra = {}
         if aug.colour_ops:
             table, need_mean = aug.colours(self.colour_rng, b, c)
-            colour = {"colour": self._up(torch.from_numpy(table)), "need_mean": need_mean}
+            extra = {"colour": self._up(torch.from_numpy(table)), "need_mean": need_mean}
+        if aug.elastic_ops:
+            nodes, grid = aug.fields(self.elastic_rng, b, w, h, drawn)
+            extra["elastic"] = (self._up(torch.from_numpy(nodes)), grid)
         img, gt = F.augment_batch(self._up(batch[0]), gt, mats, aug.out_size or (h, w), self.mean, self.std, self.lut,
-                                  image_fill=aug.image_fill, label_fill=aug.label_fill, **colour)
+                                  image_fill=aug.image_fill, label_fill=aug.label_fill, **extra)
         return (img, batch[1]) if gt is None else (img, gt, batch[2])
 
 

@@ -34,7 +34,22 @@ the same launch that warps; `Compose.__call__` applies the same float32 formula 
 torchvision's ColorJitter, by design: values are clamped to [0, 1] once, at the end, not after every op, and the ops apply in the
 order written, not in a random one.  Colour draws come from a generator of their own (`seed + COLOUR_SEED_OFFSET`), so the geometric
 maps of a seed are the same with and without colour items.  One-channel images: the state is scalar (luma = the channel);
-saturation, hue and grey are the identity."""
+saturation, hue and grey are the identity.
+
+Elastic deformation is the one geometric op that is not an affine map, and it keeps the rule all the same: `RandomElastic` touches no
+pixel, it only answers
+
+    field(rng, gh, gw) -> float64 [gh, gw, 2]   node offsets (x, y) in OUTPUT pixels, uniform in [-alpha, alpha]
+
+on a coarse control lattice laid over the FINAL output view (wherever the item stands in the list), one node every `grid` output
+pixels.  `Compose.fields(rng, n, w, h, mats)` draws a batch of lattices, multiplies each sample's 2x2 linear part into its lattice
+(a displacement of the output coordinate is one of L times as much in the source) and rounds to the int32 Q16 nodes that
+sscg_augment_elastic_u8 (include/sscg.h) interpolates with a cubic B-spline per output pixel and adds to the affine source
+coordinate - still one resampling, in the same launch.  The spline is a convex combination of the nodes, so no pixel moves by more
+than alpha.  The definition is integers throughout, so with an elastic op the host path (`Compose.__call__`) does not go through PIL
+either: it evaluates the same integer definition in numpy (`elastic_displacement`, `warp_u8`), affine and elastic part together,
+and returns the integer pixel value rounded to uint8 - the device's pixels and labels.  Elastic draws come from a third generator
+(`seed + ELASTIC_SEED_OFFSET`): the maps and colour tables of a seed are the same with and without the item."""
 import math
 
 import numpy as np
@@ -45,6 +60,10 @@ LUMA = (0.299, 0.587, 0.114)
 YIQ = np.array([[.299, .587, .114], [.596, -.274, -.322], [.211, -.523, .312]], dtype=np.float64)   # NTSC; row 0 is LUMA, rows 1, 2 sum to 0
 YIQ_INV = np.linalg.inv(YIQ)
 COLOUR_SEED_OFFSET = 500
+ELASTIC_SEED_OFFSET = 900
+ELASTIC_DEFAULT_GRID = 32          # output pixels between control nodes; an untuned default
+ELASTIC_NODE_LIMIT = 2 ** 26       # |node| in Q16 source pixels (include/sscg.h)
+BSPLINE_DENOM = 6 * 2 ** 24        # the common denominator of the B-spline numerators at t in 0..255
 
 
 def _pair(size):
@@ -185,6 +204,75 @@ class RandomSized:
         return m.dot(m2).dot(m3), out
 
 
+class RandomElastic:
+    """Free-form deformation: control nodes every `grid` output pixels (>= 4), each moved by an offset uniform in [-alpha, alpha]
+    output pixels per component, interpolated by a uniform cubic B-spline (sscg_augment_elastic_u8).  alpha <= 0.4 * grid is the
+    control-point bound below which such a deformation cannot fold (Choi and Lee 2000); `from_spec` enforces it."""
+
+    def __init__(self, alpha, grid=ELASTIC_DEFAULT_GRID):
+        self.alpha, self.grid = float(alpha), int(grid)
+        if not self.alpha >= 0.0 or self.grid < 4:            # (a NaN fails the first)
+            raise ValueError("RandomElastic needs alpha >= 0 and grid >= 4, given %r, %r" % (alpha, grid))
+
+    def field(self, rng, gh, gw):
+        return rng.uniform(-self.alpha, self.alpha, (gh, gw, 2))
+
+
+def lattice_shape(grid, oh, ow):
+    """(GH, GW) of the control lattice over an (oh, ow) output: the cells the pixels lie in plus the three further nodes of a cubic."""
+    return (oh - 1) // grid + 4, (ow - 1) // grid + 4
+
+
+def bspline_numerators(t):
+    """The four uniform cubic B-spline weights at t / 256, t an int64 array in 0..255, as integers over BSPLINE_DENOM: [4, ...]."""
+    t = np.asarray(t, dtype=np.int64)
+    u = 256 - t
+    return np.stack([u * u * u, 3 * t ** 3 - 1536 * t * t + 4 * 256 ** 3, -3 * t ** 3 + 768 * t * t + 196608 * t + 256 ** 3, t ** 3])
+
+
+def elastic_displacement(nodes, grid, oh, ow):
+    """The displacement field of sscg_augment_elastic_u8 for one sample: nodes int [GH, GW, 2] (Q16 source pixels) -> int64
+    [oh, ow, 2].  The y pass first, once per output row and node column, then the x pass; both round with floor((s + D/2) / D)."""
+    nodes = np.asarray(nodes).astype(np.int64)
+    assert nodes.shape == lattice_shape(grid, oh, ow) + (2,)
+    D = BSPLINE_DENOM
+    oy, ox = np.arange(oh, dtype=np.int64), np.arange(ow, dtype=np.int64)
+    cy, cx = oy // grid, ox // grid
+    ny, nx = bspline_numerators(((oy - cy * grid) * 256) // grid), bspline_numerators(((ox - cx * grid) * 256) // grid)
+    rows = sum(ny[i][:, None, None] * nodes[cy + i] for i in range(4))           # [oh, GW, 2]
+    rows = (rows + D // 2) // D                                                  # numpy's // floors, negative values too
+    d = sum(nx[j][None, :, None] * rows[:, cx + j] for j in range(4))            # [oh, ow, 2]
+    return (d + D // 2) // D
+
+
+def warp_u8(img, mask, q, d, out, image_fill=0, label_fill=0):
+    """The integer definition of sscg_augment_u8 / sscg_augment_elastic_u8 on one sample, in numpy: img uint8 [h, w, c], mask uint8
+    [h, w] or None, q the six Q16 coefficients, d int64 [oh, ow, 2] (elastic_displacement) or None, out = (oh, ow) ->
+    (uint8 [oh, ow, c], uint8 [oh, ow] or None): the pixel is the integer value v of the definition rounded to 8 bits,
+    (v + 0x8000) >> 16, the label the raw id at the nearest source index (no table)."""
+    h, w, _ = img.shape
+    oh, ow = out
+    q = [int(v) for v in q]
+    oy, ox = np.meshgrid(np.arange(oh, dtype=np.int64), np.arange(ow, dtype=np.int64), indexing="ij")
+    sx, sy = q[0] * ox + q[1] * oy + q[2], q[3] * ox + q[4] * oy + q[5]
+    if d is not None:
+        sx, sy = sx + d[..., 0], sy + d[..., 1]
+    x0, y0 = sx >> 16, sy >> 16
+    fx, fy = ((sx & 0xFFFF) >> 8)[..., None], ((sy & 0xFFFF) >> 8)[..., None]
+
+    def tap(y, x):
+        inside = (x >= 0) & (x < w) & (y >= 0) & (y < h)
+        return np.where(inside[..., None], img[np.clip(y, 0, h - 1), np.clip(x, 0, w - 1)].astype(np.int64), image_fill)
+    top = tap(y0, x0) * (256 - fx) + tap(y0, x0 + 1) * fx
+    bot = tap(y0 + 1, x0) * (256 - fx) + tap(y0 + 1, x0 + 1) * fx
+    px = ((top * (256 - fy) + bot * fy + 0x8000) >> 16).astype(np.uint8)
+    if mask is None:
+        return px, None
+    ix, iy = (sx + 0x8000) >> 16, (sy + 0x8000) >> 16
+    inside = (ix >= 0) & (ix < w) & (iy >= 0) & (iy < h)
+    return px, np.where(inside, mask[np.clip(iy, 0, h - 1), np.clip(ix, 0, w - 1)], label_fill).astype(np.uint8)
+
+
 def _luma(channels):
     return np.array(LUMA if channels == 3 else (1.0,), dtype=np.float64)
 
@@ -288,12 +376,17 @@ class Compose:
     so every sample of a batch leaves with the same shape.  `image_fill` / `label_fill` (0..255) colour what lies outside the
     source; the label fill is a raw id (the label transforms behind it see it like any pixel).  `seed` seeds the generators of the
     host path (`__call__`); the device path is handed its generators by the caller.  Geometric ops (those with `.matrix`) and
-    colour ops (those with `.colour`) may be mixed in `ops`: each kind keeps its order, the colour runs after the geometry."""
+    colour ops (those with `.colour`) may be mixed in `ops`: each kind keeps its order, the colour runs after the geometry.  At most
+    one op may be an elastic one (with `.field`): it deforms the final output view, wherever it stands."""
 
     def __init__(self, ops, out_size=None, image_fill=0, label_fill=0, seed=None):
         self.ops = list(ops)
         self.geometric_ops = [op for op in self.ops if hasattr(op, "matrix")]
         self.colour_ops = [op for op in self.ops if hasattr(op, "colour")]
+        self.elastic_ops = [op for op in self.ops if hasattr(op, "field")]
+        if len(self.elastic_ops) > 1:
+            raise ValueError("at most one elastic op in a pipeline, given %d" % len(self.elastic_ops))
+        self.elastic_rng = np.random.RandomState(seed + ELASTIC_SEED_OFFSET if seed is not None else None)
         self.out_size = _pair(out_size) if out_size is not None else None
         self.image_fill, self.label_fill = int(image_fill), int(label_fill)
         self.rng = np.random.RandomState(seed)
@@ -334,14 +427,57 @@ class Compose:
         iff an op is a contrast."""
         return np.stack([colour_table_row(*self.colour_state(rng, channels)) for _ in range(n)]), self.need_mean
 
+    def lattice(self, rng, q, ow, oh):
+        """int32 [GH, GW, 2]: one drawn lattice over an (ow, oh) output view for the sample whose Q16 coefficients are `q` - the
+        op's offsets (output pixels) times the map's 2x2 linear part (q0 q1; q3 q4, already Q16), in float64, rounded to nearest."""
+        op = self.elastic_ops[0]
+        u = op.field(rng, *lattice_shape(op.grid, oh, ow))
+        q = [float(v) for v in q]
+        nodes = np.rint(np.stack([q[0] * u[..., 0] + q[1] * u[..., 1], q[3] * u[..., 0] + q[4] * u[..., 1]], axis=-1))
+        if nodes.size and np.abs(nodes).max() >= ELASTIC_NODE_LIMIT:
+            raise ValueError("elastic node out of the Q16 range of the lattice (|node| < 2^26 = 1024 source pixels): %g" % np.abs(nodes).max())
+        return nodes.astype(np.int32)
+
+    def fields(self, rng, n, w, h, mats):
+        """(int32 [n, GH, GW, 2], grid): one drawn lattice per sample of a batch of (w, h) images whose maps are `mats` (int [n, 6],
+        what `matrices` drew for them), as sscg_augment_elastic_u8 reads them; None without an elastic op.  The lattice lies over the
+        output view: `out_size`, or the input's size without one."""
+        if not self.elastic_ops:
+            return None
+        oh, ow = self.out_size if self.out_size is not None else (h, w)
+        assert len(mats) == n
+        return np.stack([self.lattice(rng, mats[i], ow, oh) for i in range(n)]), self.elastic_ops[0].grid
+
+    def _integer_call(self, img, mask, M, out):
+        """The host path with an elastic op: the integer definition in numpy, affine and elastic part in one resampling."""
+        bands = len(img.getbands())
+        if img.mode not in ("L", "RGB") or (mask is not None and mask.mode not in ("L", "P")):
+            raise ValueError("elastic augmentation takes 8-bit images of one or three channels and 8-bit masks, given modes %r, %r"
+                             % (img.mode, mask.mode if mask is not None else None))
+        q = to_q16(M)
+        ow, oh = out
+        d = elastic_displacement(self.lattice(self.elastic_rng, q, ow, oh), self.elastic_ops[0].grid, oh, ow)
+        src = np.asarray(img).reshape(img.size[1], img.size[0], bands)
+        px, lab = warp_u8(src, np.asarray(mask) if mask is not None else None, q, d, (oh, ow), self.image_fill, self.label_fill)
+        warped = Image.fromarray(px if bands == 3 else px[:, :, 0])
+        if mask is None:
+            return warped, None
+        warped_mask = Image.fromarray(lab)
+        if mask.mode == "P":                                  # (an "L" image that is given a palette becomes a "P" one)
+            warped_mask.putpalette(mask.getpalette())
+        return warped, warped_mask
+
     def __call__(self, img, mask=None):
         w, h = img.size
         assert mask is None or mask.size == img.size
         M, out = self.matrix(self.rng, w, h)
-        coef = tuple(float(v) for v in M[:2].reshape(-1))
         bands = len(img.getbands())
-        fill = self.image_fill if bands == 1 else (self.image_fill,) * bands
-        img = img.transform(out, Image.AFFINE, coef, Image.BILINEAR, fillcolor=fill)
+        if self.elastic_ops:
+            img, mask = self._integer_call(img, mask, M, out)
+        else:
+            coef = tuple(float(v) for v in M[:2].reshape(-1))
+            fill = self.image_fill if bands == 1 else (self.image_fill,) * bands
+            img = img.transform(out, Image.AFFINE, coef, Image.BILINEAR, fillcolor=fill)
         if self.colour_ops:
             if bands not in (1, 3) or img.mode not in ("L", "RGB"):
                 raise ValueError("colour augmentation takes 8-bit images of one or three channels, given mode %r" % img.mode)
@@ -350,7 +486,7 @@ class Compose:
             img = Image.fromarray(px if bands == 3 else px[:, :, 0])
         if mask is None:
             return img
-        return img, mask.transform(out, Image.AFFINE, coef, Image.NEAREST, fillcolor=self.label_fill)
+        return img, (mask if self.elastic_ops else mask.transform(out, Image.AFFINE, coef, Image.NEAREST, fillcolor=self.label_fill))
 
 
 COLOUR_ITEMS = {"brightness": RandomBrightness, "contrast": RandomContrast, "saturation": RandomSaturation, "hue": RandomHue,
@@ -361,7 +497,9 @@ def from_spec(spec, size, image_fill=0, label_fill=0, out_size=None, seed=None):
     """The augmentation a `--augment` value names, or None for an empty one: a comma list of `hflip`, `rotate=<deg>`,
     `scale=<lo>:<hi>` and `sizedcrop` (RandomSizedCrop to `size` = (height, width)), and of the colour items `brightness=<x>`,
     `contrast=<x>`, `saturation=<x>` (factor in max(0, 1-x)..1+x), `hue=<x>` (0..0.5 of a turn) and `gray=<p>` (a probability) -
-    geometry and colour each applied in the order written, colour behind geometry."""
+    geometry and colour each applied in the order written, colour behind geometry - and at most one `elastic=<alpha>[:<grid>]`
+    (RandomElastic: node offsets up to alpha output pixels on a lattice of `grid` output pixels, default 32, an untuned default;
+    grid >= 4 and 0 <= alpha <= 0.4 * grid), which deforms the final output view wherever it stands in the list."""
     ops = []
     for item in (s.strip() for s in (spec or "").split(",")):
         if not item:
@@ -384,7 +522,16 @@ def from_spec(spec, size, image_fill=0, label_fill=0, out_size=None, seed=None):
             if not 0.0 <= x <= top:                       # (false for a NaN)
                 raise ValueError("--augment %s=<x> needs 0 <= x%s, given %r" % (key, " <= %g" % top if top < float("inf") else "", item))
             ops.append(COLOUR_ITEMS[key](x))
+        elif key == "elastic" and val and val.count(":") <= 1:
+            alpha, _, grid = val.partition(":")
+            alpha, grid = float(alpha), int(grid) if grid else ELASTIC_DEFAULT_GRID
+            if any(hasattr(op, "field") for op in ops):
+                raise ValueError("--augment: one elastic item at the most, given a second: %r" % item)
+            if not 0.0 <= alpha <= 0.4 * grid or grid < 4:        # (false for a NaN)
+                raise ValueError("--augment elastic=<alpha>[:<grid>] needs grid >= 4 and 0 <= alpha <= 0.4 * grid (beyond it the "
+                                 "deformation can fold), given %r" % item)
+            ops.append(RandomElastic(alpha, grid))
         else:
-            raise ValueError("--augment: unknown item %r (hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop, brightness=<x>, "
-                             "contrast=<x>, saturation=<x>, hue=<x>, gray=<p>)" % item)
+            raise ValueError("--augment: unknown item %r (hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop, elastic=<alpha>[:<grid>], "
+                             "brightness=<x>, contrast=<x>, saturation=<x>, hue=<x>, gray=<p>)" % item)
     return Compose(ops, out_size=out_size, image_fill=image_fill, label_fill=label_fill, seed=seed) if ops else None
