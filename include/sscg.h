@@ -854,6 +854,48 @@ int sscg_components_filter(const uint8_t* label_pred, const int64_t* label_true 
                            int conn, int largest, int min_area, int fill, uint64_t exempt_mask,
                            uint8_t* label_out, int64_t* hist /*nullable, accumulated*/, int64_t* stats /*nullable, overwritten*/,
                            void* ws, size_t ws_bytes, void* stream);
+/* ------------------------------------------------------------------ calibration scores of the evaluation: the counts behind the
+ * expected / maximum calibration error (ECE / MCE) over a reliability diagram, the per-class confidence gap, the negative log-likelihood
+ * (NLL), the Brier score and the NLL-optimal temperature of the probabilities the heads above take their labels from - the softmax
+ * output --unl_pseudo_thresh, --ohem_thresh, --crf and --tta trust as a probability (the reference scores label maps only,
+ * utils.py:357-412).  Opt-in (`--calibration`), forward only, never launched by the training step; the N x C x OH x OW probability map
+ * never reaches memory.  (An addition: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.)
+ *
+ * sscg_calib_stats: x is, by `kind`,
+ *   0  fp32 [N][H][W][C] logits, C <= 64, resized to [OH][OW] by sscg_upsample_bilinear_fwd's arithmetic (OH == H && OW == W: the
+ *      identity resize, no interpolation arithmetic) - what sscg_predict_head takes; `scale` is not used;
+ *   1  fp32 [N][OH][OW][C] non-negative scores, H == OH && W == OW, NT == 1 and inv_temps[0] == 1.f required: the probability is
+ *      x[c] * scale, one fp32 multiply and no softmax (prob_sum of sscg_predict_head_ms with scale = 1.f / S; q_out of sscg_crf_head
+ *      with scale = 1.f); scale finite and >= 0.
+ * inv_temps is a HOST array of NT floats (1 <= NT <= 8, each finite and > 0), read during the call and copied into the kernel's
+ * arguments (no table on the device, no host sync).  B = the number of equal-width confidence bins, 2 <= B <= 32.  label_true is int64
+ * [N][OH][OW]; a pixel is COUNTED when its label is in [0, C) (sscg_confusion_hist's rule), every other pixel adds to nothing.
+ * Per counted output pixel and per temperature t = 0 .. NT-1, in that order:
+ *   v[c] = z[c] * inv_temps[t] with z the resized logits - one fp32 multiply per class AFTER the resize, rounded on its own (it never
+ *          contracts into the softmax), so inv_temps[t] == 1.f gives sscg_predict_head's bits; p[c] = sscg_softmax_fwd's value of v;
+ *   pred = the first maximum of p (sscg_argmax_onehot's rule), conf = p[pred], hit = (pred == label);
+ *   b    = min(B - 1, (int)(conf * (float)B)): one fp32 multiply and a truncation, so conf = k / B exactly opens bin k;
+ *   q    = (int64)(conf * 16777216.f): the confidence in Q24 (the multiply is exact, the conversion truncates) - confidence sums are
+ *          integers, independent of the order and identical from call to call;
+ *   bins[t][b] += (1, hit, q)    int64 [NT][B][3]          cls[t][pred] += (1, hit, q)    int64 [NT][C][3]
+ *   sums[t]    += (-log(max((double)p[label], 0x1p-126)), sum_c ((double)p[c] - [c == label])^2)    double [NT][2], in fp64 from the
+ *          fp32 probabilities: a true class whose probability underflowed to 0 costs 126 ln 2, not infinity.
+ * All three outputs are ACCUMULATED into: a caller zeroes them once per evaluation, as it does hist.  From them the host forms
+ *   ECE = sum_b n_b / n |hit_b / n_b - qsum_b / (2^24 n_b)|, MCE = the largest such gap, NLL = sums[.][0] / n, Brier = sums[.][1] / n,
+ *   the gap conf_c - acc_c of every predicted class and the temperature that minimises the NLL (utils.calibration_scores).
+ * Two launches: one thread per output pixel, grid-stride over at most 512 workgroups of 256 threads (a thread owns
+ * ceil(N OH OW / 131072) pixels); the integers through 64-bit per-workgroup LDS bins (256 pixels of confidence 1 carry a Q24 sum past 32
+ * bits) and one 64-bit integer atomic per value of a bin that was hit; the fp64 sums through one record per workgroup in ws, reduced in
+ * a fixed order by a one-block finish that adds the call's total to sums - no float atomics: the same call twice gives the same bits.
+ * ws: sscg_calib_workspace(N, OH, OW, NT) = min(ceil(N OH OW / 256), 512) * NT * 2 * 8 bytes (0 for sizes sscg_calib_stats refuses),
+ * 8-byte aligned, fully written before it is read.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (a null pointer; non-positive sizes; C outside 1..64; B outside 2..32; NT outside 1..8;
+ * an inv_temps[t] that is not finite and > 0; kind outside {0, 1}; kind 1 with H != OH, W != OW, NT != 1, inv_temps[0] != 1 or a scale
+ * that is negative or not finite), SSCG_ERR_UNSUPPORTED (N*OH*OW or N*H*W >= 2^31), SSCG_ERR_WORKSPACE. */
+size_t sscg_calib_workspace(int N, int OH, int OW, int NT);
+int sscg_calib_stats(const float* x, int kind, float scale, int N, int H, int W, int C, int OH, int OW,
+                     const int64_t* label_true, const float* inv_temps, int NT, int B,
+                     int64_t* bins, int64_t* cls, double* sums, void* ws, size_t ws_bytes, void* stream);
 /* ------------------------------------------------------------------ per-epoch image panels: the image grids the reference sends to
  * TensorBoard at the end of every epoch (model.py:576-638; supervised_model: model.py:164-186), without the host round trip of
  * full-resolution maps, the per-pixel Python loop of utils.PIL_to_tensor (utils.py:59-94) and make_grid on the host.  Forward only;

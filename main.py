@@ -3,7 +3,7 @@
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
---boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp,
+--calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp,
 --lovasz_weight, --lovasz_per_image, --lovasz_classes, --lovasz_skip.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL)."""
 import importlib
@@ -53,6 +53,7 @@ class _Args(Namespace):
     boundary = ""
     surface = ""
     components = ""
+    calibration = ""
     boundary_loss = 0.0
     boundary_loss_skip = ""
     boundary_loss_ramp = 0
@@ -173,6 +174,15 @@ def get_args(argv=None):
                              "'conn=4|8' (default 8), 'skip=a:b:c' for classes never filtered; 'on' for min_area=64 (an untuned "
                              "default); e.g. largest,min_area=16,skip=3; combines with --tta, --crf, --boundary, --surface and "
                              "--ema_decay (default: off, the maps are scored as predicted)")
+    parser.add_argument("--calibration", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="also score the per-epoch evaluation's (and --validation's) probabilities by their calibration: the "
+                             "expected and maximum calibration error over a reliability diagram, the negative log-likelihood, the "
+                             "Brier score, the per-class confidence gap and the accuracy / coverage above every confidence threshold "
+                             "(what --unl_pseudo_thresh would keep), printed beside the mIoU; 'on' for bins=15 at temperature 1, "
+                             "'fit' for bins=15,temps=0.5:3.0:7, which also fits the NLL-optimal temperature (both untuned defaults), "
+                             "or a comma list over bins=N (2..32) and temps=lo:hi:n (log-spaced) or temps=a/b/c; temperature 1 is "
+                             "always scored, at most 8 with it; a temperature list does not combine with --tta or --crf; it scores "
+                             "the prediction before --components; --testing has no ground truth and ignores it (default: off)")
     parser.add_argument("--boundary_loss", type=float, default=SUPPRESS, metavar="F",
                         help="add F times the boundary loss of Kervadec et al. (MIDL 2019) to every ground-truth cross entropy "
                              "(lab_loss_CE, gt_cycle_loss, the supervised loss), inside that term's own weight: the softmax "
@@ -247,6 +257,14 @@ def get_args(argv=None):
                 {"voc2012": 21, "cityscapes": 20, "acdc": 4}[args.dataset])
         except ValueError as e:
             parser.error("--components: %s" % e if not str(e).startswith("--components") else str(e))
+    if args.calibration.strip():
+        try:
+            cal = importlib.import_module(PKG + ".utils").parse_calibration(args.calibration)
+        except ValueError as e:
+            parser.error(str(e))
+        if len(cal.temps) > 1 and (getattr(args, "tta", "").strip() or args.crf.strip()):
+            parser.error("--calibration: a temperature list rescales the logits of the single fused head and does not combine with "
+                         "--tta or --crf")
     if args.ohem_thresh is not None and not 0.0 < args.ohem_thresh <= 1.0:
         parser.error("--ohem_thresh must lie in (0, 1]")
     if args.ohem_min_kept < 0:

@@ -164,6 +164,8 @@ SIGNATURES = {
     "sscg_surface_stats": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "sscg_components_workspace": (_sz, [_i, _i, _i, _i]),
     "sscg_components_filter": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
+    "sscg_calib_workspace": (_sz, [_i, _i, _i, _i]),
+    "sscg_calib_stats": (_i, [_p, _i, _f, _i, _i, _i, _i, _i, _i, _p, C.POINTER(_f), _i, _i, _p, _p, _p, _p, _sz, _p]),
     "sscg_panel_labels": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_panel_range_workspace": (_sz, [_i64, _i]),
     "sscg_panel_range": (_i, [_p, _i, _i64, _i, _f, _f, _p, _p, _p, _sz, _p]),

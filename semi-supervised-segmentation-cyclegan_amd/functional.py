@@ -1618,6 +1618,117 @@ def surface_stats(label_true, label_pred, num_classes, options, *, stats=None, s
     return stats, sums
 
 
+# Calibration scores of the evaluation (sscg_calib_stats, include/sscg.h holds the definitions): opt-in (`--calibration`).
+CALIBRATION_MAX_BINS = 32
+CALIBRATION_MAX_TEMPS = 8
+
+
+class CalibrationOptions(object):
+    """The two parameters of the calibration scores: `bins`, the number of equal-width confidence bins of the reliability diagram (an
+    integer in 2..32; 15 is the customary count), and `temps`, the temperatures T the softmax is also evaluated at (logits / T) - finite
+    numbers > 0, at most 8 with the leading 1.0.  temps[0] is always 1.0, the network as it is: a list that does not start with it gets
+    it put in front, and a second 1.0 is dropped.  More than one temperature asks for the fit of the NLL-optimal one."""
+    __slots__ = ("bins", "temps")
+
+    def __init__(self, bins=15, temps=(1.0,)):
+        if isinstance(bins, bool) or not isinstance(bins, int) or not 2 <= bins <= CALIBRATION_MAX_BINS:
+            raise ValueError("calibration bins %r is not an integer in 2..%d" % (bins, CALIBRATION_MAX_BINS))
+        if isinstance(temps, (int, float)) and not isinstance(temps, bool):
+            temps = (temps,)
+        try:
+            given = tuple(temps)
+        except TypeError:
+            raise ValueError("calibration temps %r is not a list of numbers" % (temps,))
+        out = [1.0]
+        for t in given:
+            if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0.0 < float(t) < float("inf"):
+                raise ValueError("calibration temperature %r is not a finite number > 0" % (t,))
+            t = float(t)
+            inv = _inv_temp(t)
+            if not 0.0 < inv < float("inf"):
+                raise ValueError("calibration temperature %r: 1 / T is not a finite fp32 number > 0" % (t,))
+            if t == 1.0:
+                continue
+            if t in out:
+                raise ValueError("calibration temperature %r is given twice" % (t,))
+            out.append(t)
+        if len(out) > CALIBRATION_MAX_TEMPS:
+            raise ValueError("calibration: %d temperatures with the leading 1.0, at most %d" % (len(out), CALIBRATION_MAX_TEMPS))
+        self.bins, self.temps = bins, tuple(out)
+
+    @property
+    def inv_temps(self):
+        """numpy.float32(1) / numpy.float32(T) per temperature: the factors the kernel multiplies the resized logits by."""
+        return [_inv_temp(t) for t in self.temps]
+
+    def __eq__(self, other):
+        return isinstance(other, CalibrationOptions) and (self.bins, self.temps) == (other.bins, other.temps)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((self.bins, self.temps))
+
+    def __repr__(self):
+        return "CalibrationOptions(bins=%r, temps=%r)" % (self.bins, self.temps)
+
+
+def _inv_temp(t):
+    import numpy as np
+    with np.errstate(over="ignore", under="ignore", divide="ignore"):
+        return float(np.float32(1) / np.float32(t))
+
+
+_CALIB_WS_BYTES = {}
+
+
+def calibration_stats(x, size, label_true, options, *, probs=False, scale=1.0, state=None):
+    """The counts behind the calibration scores of a batch (sscg_calib_stats), accumulated into `state` = (bins int64 [NT,B,3], cls int64
+    [NT,C,3], sums float64 [NT,2]) on the device (None = new zeroed ones), which is returned.  `x`: fp32 [N,C,H,W] logits, resized to
+    `size` like predict_labels' - their softmax at every temperature of `options` is scored; or, with probs=True, non-negative scores
+    already at `size` whose probability is x * scale (prob_sum of predict_labels_ms with scale = 1 / views; q of crf_labels or a
+    softmax map with scale = 1) - one temperature only.  `label_true`: N*OH*OW integer labels; values outside [0, C) are not counted."""
+    if not isinstance(options, CalibrationOptions):
+        raise TypeError("options must be a functional.CalibrationOptions, not %r" % (options,))
+    _need_hip(x, f32_only=True)
+    if not label_true.is_cuda:
+        raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % label_true.device)
+    if x.dim() != 4:
+        raise _lib.SscgError("calibration_stats: 4-D logits or scores expected")
+    _no_grad_input(x, "calibration_stats")
+    xs = to_nhwc(x.detach())
+    n, c, h, w = xs.shape
+    oh, ow = int(size[0]), int(size[1])
+    nt, b = len(options.temps), options.bins
+    if probs and (h, w) != (oh, ow):
+        raise _lib.SscgError("calibration_stats: scores (probs=True) must already have the output size")
+    if probs and nt != 1:
+        raise ValueError("calibration_stats: scores (probs=True) have no logits to rescale: one temperature only, got %r" % (options.temps,))
+    lt = label_true.to(torch.int64).contiguous()
+    if lt.numel() != n * oh * ow:
+        raise _lib.SscgError("calibration_stats: label_true must have N*OH*OW elements")
+    if state is None:
+        flat = torch.empty((nt * (b + c) * 3 + nt * 2,), dtype=torch.int64, device=xs.device)
+        check(lib.sscg_fill(flat.data_ptr(), 2 * flat.numel(), 0.0, _stream()), "sscg_fill")   # 2 fp32 zeros per 8-byte zero
+        state = (flat[:nt * b * 3].view(nt, b, 3), flat[nt * b * 3:nt * (b + c) * 3].view(nt, c, 3),
+                 flat[nt * (b + c) * 3:].view(torch.float64).view(nt, 2))
+    bins, cls, sums = state
+    for t, dt, shape, what in ((bins, torch.int64, (nt, b, 3), "bins must be a contiguous int64 [NT, B, 3]"),
+                               (cls, torch.int64, (nt, c, 3), "cls must be a contiguous int64 [NT, C, 3]"),
+                               (sums, torch.float64, (nt, 2), "sums must be a contiguous float64 [NT, 2]")):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+            raise _lib.SscgError("calibration_stats: %s tensor on the device" % what)
+    key = (n, oh, ow, nt)
+    if key not in _CALIB_WS_BYTES:
+        _CALIB_WS_BYTES[key] = lib.sscg_calib_workspace(*key)
+    ws = _WS.get(_CALIB_WS_BYTES[key], xs.device)
+    its = (C.c_float * nt)(*options.inv_temps)
+    check(lib.sscg_calib_stats(xs.data_ptr(), 1 if probs else 0, float(scale), n, h, w, c, oh, ow, lt.data_ptr(), its, nt, b,
+                               bins.data_ptr(), cls.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sscg_calib_stats")
+    return state
+
+
 # Connected-component filtering of predicted label maps (sscg_components_filter, include/sscg.h holds the definitions): opt-in
 # (`--components`).
 class ComponentOptions(object):

@@ -307,6 +307,30 @@ class _WeightedCE(object):
         elif hasattr(self, "eval_components"):
             del self.eval_components
 
+    def set_calibration(self, opts, tta=None, crf=None):
+        """--calibration: a F.CalibrationOptions (utils.parse_calibration), or None = off, handed to the score keeper
+        (runningScore.set_calibration): evaluate()'s parameter list stays as it is, the option is state like the surface option.  A
+        temperature grid together with `tta` / `crf` (what evaluate() will be called with) or SSCG_FUSE_PREDICT=0 is refused here."""
+        self.running_metrics_val.set_calibration(opts, tta=tta, crf=crf)
+
+    def _calibration_scores(self, running):
+        """--calibration: the calibration scores of the evaluation that has just run (runningScore.get_calibration_scores), kept in
+        `self.eval_calibration` = {"ece", "mce", "nll", "brier", "accuracy", "confidence", "counted", "class_gap", "bins", "above"} and,
+        with a temperature grid, {"temperature", "temperature_at_edge", "temperature_grid"}.  They score the prediction as the network
+        makes it: --components changes label maps, not probabilities.  Off: the attribute is absent."""
+        scores = running.get_calibration_scores()
+        if scores is not None:
+            self.eval_calibration = scores
+        elif hasattr(self, "eval_calibration"):
+            del self.eval_calibration
+
+    def _print_calibration(self):
+        if hasattr(self, "eval_calibration"):
+            s = self.eval_calibration
+            print("The ECE / MCE / NLL / Brier score for the epoch are: ", s["ece"], s["mce"], s["nll"], s["brier"],
+                  *(("| NLL-optimal temperature: ", s["temperature"], "(at the end of the grid)" if s["temperature_at_edge"] else "")
+                    if "temperature" in s else ()))
+
     def _ce_device(self):
         ids = getattr(self.args, "gpu_ids", None)
         return torch.device("cuda", int(ids[0])) if ids else torch.device("cpu")
@@ -867,6 +891,8 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         self.Gis.eval()
         self.running_metrics_val.reset()
         self.running_metrics_val.set_boundary(boundary)
+        self.running_metrics_val.check_calibration(tta, crf)      # --calibration: a temperature grid needs the single fused head
+        calibrated = self.running_metrics_val.get_calibration() is not None
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
@@ -884,12 +910,15 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
                 self.running_metrics_val.update_logits(val_gt.squeeze(1), logits, self.crop)
                 continue
             outputs = F.softmax2d(self.interp(logits))
+            if calibrated:                   # --calibration on the chain of separate passes: the softmax map itself is scored
+                self.running_metrics_val.update_probs(val_gt.squeeze(1), outputs)
             self.running_metrics_val.update_device(val_gt.squeeze(1), F.argmax_index(outputs))   # :566-569 without the host round trip
         score, class_iou = self.running_metrics_val.get_scores()
         self._dice_scores(self.running_metrics_val)
         self._boundary_scores(self.running_metrics_val)
         self._surface_scores(self.running_metrics_val)
         self._component_scores(self.running_metrics_val)
+        self._calibration_scores(self.running_metrics_val)
         self.Gsi.train()
         self.Gis.train()
         return score["Mean IoU : \t"], class_iou
@@ -934,6 +963,8 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         history = []
         self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
         self.set_components(utils.parse_components(getattr(args, 'components', '')))
+        self.set_calibration(utils.parse_calibration(getattr(args, 'calibration', '')), tta=utils.parse_tta(getattr(args, 'tta', '')),
+                             crf=utils.parse_crf(getattr(args, 'crf', '')))
         for epoch in range(self.start_epoch, args.epochs):
             self.set_boundary_epoch(epoch)
             self.set_unl_epoch(epoch)
@@ -986,6 +1017,7 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
                         if hasattr(self, "eval_surface"):
                             print("The HD / HD%d / ASSD / NSD for the epoch are: " % self.running_metrics_val.get_surface().pct,
                                   self.eval_surface["hd"], self.eval_surface["hd95"], self.eval_surface["assd"], self.eval_surface["nsd"])
+                        self._print_calibration()
                         if hasattr(self, "eval_components"):
                             print("The components found / kept and the pixels relabelled for the epoch are: ", self.eval_components["components"],
                                   self.eval_components["kept_components"], self.eval_components["removed_pixels"])
@@ -1091,6 +1123,8 @@ class supervised_model(_WeightedCE):
         self.Gsi.eval()
         self.running_metrics_val.reset()
         self.running_metrics_val.set_boundary(boundary)
+        self.running_metrics_val.check_calibration(tta, crf)      # --calibration: a temperature grid needs the single fused head
+        calibrated = self.running_metrics_val.get_calibration() is not None
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
@@ -1108,12 +1142,15 @@ class supervised_model(_WeightedCE):
                 self.running_metrics_val.update_logits(val_gt.squeeze(1), logits, self.crop)
                 continue
             outputs = F.softmax2d(F.upsample_bilinear(logits, self.crop))
+            if calibrated:                   # --calibration on the chain of separate passes: the softmax map itself is scored
+                self.running_metrics_val.update_probs(val_gt.squeeze(1), outputs)
             self.running_metrics_val.update_device(val_gt.squeeze(1), F.argmax_index(outputs))
         score, class_iou = self.running_metrics_val.get_scores()
         self._dice_scores(self.running_metrics_val)
         self._boundary_scores(self.running_metrics_val)
         self._surface_scores(self.running_metrics_val)
         self._component_scores(self.running_metrics_val)
+        self._calibration_scores(self.running_metrics_val)
         self.running_metrics_val.reset()
         self.Gsi.train()
         return score["Mean IoU : \t"], class_iou
@@ -1142,6 +1179,8 @@ class supervised_model(_WeightedCE):
         history, done = [], 0
         self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
         self.set_components(utils.parse_components(getattr(args, 'components', '')))
+        self.set_calibration(utils.parse_calibration(getattr(args, 'calibration', '')), tta=utils.parse_tta(getattr(args, 'tta', '')),
+                             crf=utils.parse_crf(getattr(args, 'crf', '')))
         for epoch in range(self.start_epoch, args.epochs):
             self.set_boundary_epoch(epoch)
             self.Gsi.train()
@@ -1181,6 +1220,7 @@ class supervised_model(_WeightedCE):
                         if hasattr(self, "eval_surface"):
                             print("The HD / HD%d / ASSD / NSD for the epoch are: " % self.running_metrics_val.get_surface().pct,
                                   self.eval_surface["hd"], self.eval_surface["hd95"], self.eval_surface["assd"], self.eval_surface["nsd"])
+                        self._print_calibration()
                         if hasattr(self, "eval_components"):
                             print("The components found / kept and the pixels relabelled for the epoch are: ", self.eval_components["components"],
                                   self.eval_components["kept_components"], self.eval_components["removed_pixels"])

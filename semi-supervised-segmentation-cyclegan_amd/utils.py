@@ -170,6 +170,8 @@ class runningScore(object):
         self._surface_records = []   # per update_* call (stats int64 [2, N, C, 5], sums float64 [2, N, C]) on the device
         self._components = None      # set_components(): a F.ComponentOptions, or None = the label maps are scored as predicted
         self._component_stats = []   # per update_* call F.component_filter's stats int64 [N, C, 4] on the device
+        self._calibration = None     # set_calibration(): a F.CalibrationOptions, or None = no calibration scores, no launch for them
+        self._calibration_state = None  # (bins, cls, sums) accumulated by sscg_calib_stats while the option is set
 
     def set_boundary(self, boundary):
         """The contour scores (Boundary IoU, trimap mIoU) as STATE of the score keeper: a F.BoundaryOptions (utils.parse_boundary), or an
@@ -196,6 +198,58 @@ class runningScore(object):
 
     def get_surface(self):
         return self._surface
+
+    def set_calibration(self, calibration, tta=None, crf=None):
+        """The calibration scores (ECE, MCE, NLL, Brier, the per-class gap, the fitted temperature) as STATE of the score keeper: a
+        F.CalibrationOptions (utils.parse_calibration), or None = off.  While set, every update_* on logits also hands what its head
+        takes the labels from to F.calibration_stats: the logits themselves (update_logits), the views' summed probabilities
+        (update_logits_ms, scale 1 / views), the CRF's Q (update_logits_crf), a softmax map (update_probs).  The scores are those of
+        the prediction AS THE NETWORK MAKES IT: the component filter changes label maps, not probabilities, and is not seen here.
+        A temperature grid rescales logits, which only update_logits has: together with `tta` (a view list), `crf` (a F.CrfOptions) or
+        SSCG_FUSE_PREDICT=0 it is refused here (check_calibration), not at the first batch.  While off, every method launches exactly
+        what it launches without the option."""
+        if calibration is not None and not isinstance(calibration, F.CalibrationOptions):
+            raise TypeError("set_calibration: a functional.CalibrationOptions or None expected, not %r" % (calibration,))
+        self.check_calibration(tta, crf, calibration)
+        if calibration != self._calibration:
+            self._calibration_state = None
+        self._calibration = calibration
+
+    def get_calibration(self):
+        return self._calibration
+
+    def check_calibration(self, tta=None, crf=None, calibration=False):
+        """Refuse a temperature grid (more than one temperature) where there are no logits to rescale: under multi-scale / mirrored
+        inference, behind the CRF and on the chain of separate passes (SSCG_FUSE_PREDICT=0); and, at any temperature, a CRF of 0
+        iterations behind several views (it has no Q, and its scores' number of views is not known to update_logits_crf).  evaluate()
+        calls it before the first batch.  `calibration`: the option to check instead of the one that is set."""
+        opts = self._calibration if calibration is False else calibration
+        if opts is None:
+            return
+        if tta and crf is not None and crf.iterations == 0:
+            raise ValueError("calibration: a CRF of 0 iterations behind several views has no Q to score and is those views alone: "
+                             "drop the CRF")
+        if len(opts.temps) == 1:
+            return
+        why = "--tta" if tta else ("--crf" if crf is not None else ("SSCG_FUSE_PREDICT=0" if not F.FUSE_PREDICT[0] else None))
+        if why is not None:
+            raise ValueError("calibration: a temperature grid %r rescales the logits of the single fused head and does not combine with "
+                             "%s (the probabilities there are not one softmax of logits): ask for temperature 1 only" % (opts.temps, why))
+
+    def update_calibration(self, label_trues, x, size, probs=False, scale=1.0):
+        """F.calibration_stats of one batch into the kept counts: `x` = logits to be resized to `size`, or (probs=True) scores at
+        `size` whose probability is x * scale.  What the update_* methods call while the option is set."""
+        if self._calibration is None:
+            raise ValueError("update_calibration: no calibration option is set (set_calibration)")
+        self._calibration_state = F.calibration_stats(x, size, label_trues, self._calibration, probs=probs, scale=scale,
+                                                      state=self._calibration_state)
+
+    def update_probs(self, label_trues, probs):
+        """What the calibration option asks of a batch whose softmax map [N,C,OH,OW] already exists (the chain of separate passes,
+        SSCG_FUSE_PREDICT=0): F.calibration_stats on the map.  The label map of the same batch goes to update_device().  Nothing is
+        launched while the option is off."""
+        if self._calibration is not None:
+            self.update_calibration(label_trues, probs, probs.shape[2:], probs=True)
 
     def set_components(self, components):
         """The component filter (F.component_filter) as STATE of the score keeper: a F.ComponentOptions (utils.parse_components), or
@@ -248,7 +302,9 @@ class runningScore(object):
     def update_logits(self, label_trues, logits, size):
         """update_device() from the network's low-resolution logits: resize -> softmax -> argmax -> counts in one launch
         (F.predict_labels); neither the resized logits nor a predicted label map reach memory (with set_boundary(): the uint8 map
-        does, for F.boundary_counts)."""
+        does, for F.boundary_counts).  With set_calibration(): one more launch pair on the same logits (F.calibration_stats)."""
+        if self._calibration is not None:
+            self.update_calibration(label_trues, logits, size)
         if self._components is not None:
             self._filter_components(label_trues, F.predict_labels(logits, size, want_u8=True, num_classes=self.n_classes)[0])
             return
@@ -260,27 +316,51 @@ class runningScore(object):
 
     def update_logits_ms(self, label_trues, logits_list, flips, size):
         """update_logits() over several views of the batch (multi-scale / mirrored inference): the views' probabilities are summed
-        and the counts taken in one launch (F.predict_labels_ms)."""
+        and the counts taken in one launch (F.predict_labels_ms).  With set_calibration() the head also writes the summed
+        probabilities, which F.calibration_stats scores with scale 1 / views."""
+        cal = self._calibration is not None
+        if cal:
+            self.check_calibration(tta=True)
         if self._components is not None:
-            self._filter_components(label_trues, F.predict_labels_ms(logits_list, flips, size, want_u8=True,
-                                                                     num_classes=self.n_classes)[0])
+            out = F.predict_labels_ms(logits_list, flips, size, want_u8=True, num_classes=self.n_classes, **({"want_prob": True} if cal else {}))
+            if cal:
+                self.update_calibration(label_trues, out[3], size, probs=True, scale=inv_views(len(logits_list)))
+            self._filter_components(label_trues, out[0])
             return
         want = self._boundary is not None or self._surface is not None
-        u8, _, self._device_hist = F.predict_labels_ms(logits_list, flips, size, want_u8=want, label_true=label_trues,
-                                                       hist=self._device_hist, num_classes=self.n_classes)[:3]
+        out = F.predict_labels_ms(logits_list, flips, size, want_u8=want, label_true=label_trues, hist=self._device_hist,
+                                  num_classes=self.n_classes, **({"want_prob": True} if cal else {}))
+        u8, self._device_hist = out[0], out[2]
+        if cal:
+            self.update_calibration(label_trues, out[3], size, probs=True, scale=inv_views(len(logits_list)))
         if want:
             self._count_boundary(label_trues, u8)
 
     def update_logits_crf(self, label_trues, logits_or_probs, image, size, crf, probs=False):
         """update_logits() with the windowed dense CRF (F.crf_labels) between the softmax and the first maximum: `image` guides it;
-        probs=True: the scores are the summed probabilities of several views (F.predict_labels_ms(want_prob=True)) at `size`."""
+        probs=True: the scores are the summed probabilities of several views (F.predict_labels_ms(want_prob=True)) at `size`.
+        With set_calibration() the head also writes Q after its last step, which F.calibration_stats scores with scale 1; a CRF of 0
+        iterations has no Q: on logits it is update_logits() and is scored as such, on summed probabilities it is refused (the number
+        of views is not known here: check_calibration)."""
+        cal = self._calibration is not None
+        want_q = cal and crf.iterations > 0
+        if cal:
+            self.check_calibration(tta=probs, crf=crf)
+            if not want_q:
+                self.update_calibration(label_trues, logits_or_probs, size)
         if self._components is not None:
-            self._filter_components(label_trues, F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=True,
-                                                              num_classes=self.n_classes)[0])
+            out = F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=True, num_classes=self.n_classes,
+                               **({"want_q": True} if want_q else {}))
+            if want_q:
+                self.update_calibration(label_trues, out[3], size, probs=True)
+            self._filter_components(label_trues, out[0])
             return
         want = self._boundary is not None or self._surface is not None
-        u8, _, self._device_hist = F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=want, label_true=label_trues,
-                                                hist=self._device_hist, num_classes=self.n_classes)[:3]
+        out = F.crf_labels(logits_or_probs, image, size, crf, probs=probs, want_u8=want, label_true=label_trues, hist=self._device_hist,
+                           num_classes=self.n_classes, **({"want_q": True} if want_q else {}))
+        u8, self._device_hist = out[0], out[2]
+        if want_q:
+            self.update_calibration(label_trues, out[3], size, probs=True)
         if want:
             self._count_boundary(label_trues, u8)
 
@@ -308,6 +388,23 @@ class runningScore(object):
         else:
             stats, sums = np.zeros((2, 0, c, 5), dtype=np.int64), np.zeros((2, 0, c), dtype=np.float64)
         return surface_scores(stats, sums, c, self.dataset, self._surface.pct)
+
+    def get_calibration_scores(self):
+        """calibration_scores() of the counts accumulated since the last reset(); None while the option is off.  One device -> host copy
+        of NT (3 B + 3 C + 2) eight-byte values."""
+        if self._calibration is None:
+            return None
+        c, opts = self.n_classes, self._calibration
+        nt, b = len(opts.temps), opts.bins
+        if self._calibration_state is None:
+            bins, cls = np.zeros((nt, b, 3), dtype=np.int64), np.zeros((nt, c, 3), dtype=np.int64)
+            sums = np.zeros((nt, 2), dtype=np.float64)
+        else:
+            sb, sc, ss = self._calibration_state
+            packed = torch.cat([sb.reshape(-1), sc.reshape(-1), ss.reshape(-1).view(torch.int64)]).cpu().numpy()
+            bins, cls = packed[:sb.numel()].reshape(nt, b, 3), packed[sb.numel():sb.numel() + sc.numel()].reshape(nt, c, 3)
+            sums = packed[sb.numel() + sc.numel():].view(np.float64).reshape(nt, 2)
+        return calibration_scores(bins, cls, sums, opts.temps, c, self.dataset)
 
     def get_component_scores(self):
         """What the component filter did since the last reset(), summed over the evaluated samples; None while the option is off.
@@ -366,6 +463,12 @@ class runningScore(object):
         self._boundary_counts = None
         self._surface_records = []
         self._component_stats = []
+        self._calibration_state = None
+
+
+def inv_views(views):
+    """1 / views as the fp32 value the calibration kernel multiplies summed probabilities by."""
+    return float(np.float32(1) / np.float32(int(views)))
 
 
 def kept_classes(n_classes, dataset):
@@ -487,6 +590,119 @@ def parse_surface(spec):
         except ValueError as e:
             raise ValueError("--surface: %r: %s" % (tok, e))
     return F.SurfaceOptions(**kw)
+
+
+def calibration_scores(bins, cls, sums, temps, n_classes, dataset):
+    """The calibration scores of F.calibration_stats' counts (include/sscg.h: sscg_calib_stats): bins int64 [NT, B, 3] and cls int64
+    [NT, C, 3] = (pixels, hits, the sum of the confidences in Q24) per confidence bin / per PREDICTED class, sums float64 [NT, 2] = (the
+    sum of -log p[label], the sum of the squared distances to the one-hot label), temps the NT temperatures, temps[0] == 1.  In fp64,
+    at T = 1, with n = the counted pixels:
+    ece = sum_b n_b / n |hit_b / n_b - qsum_b / (2^24 n_b)|;  mce = the largest of those gaps over the non-empty bins;  nll, brier = the
+    sums / n;  accuracy = hits / n;  confidence = the mean confidence;  counted = n;  class_gap[c] = conf_c - acc_c of the pixels PREDICTED
+    as c, over the classes runningScore.get_scores() keeps for the dataset, NaN where a class is never predicted;  bins = the
+    reliability diagram, a list of (lo, hi, n_b, accuracy, mean confidence);  above = for every bin edge e a tuple (e, coverage,
+    accuracy) of the pixels in the bins at or above it - what a confidence threshold e (`--unl_pseudo_thresh e`) would keep, and how
+    right it would be.  With NT > 1 also temperature_grid = [(T, nll, ece)] in ascending T and temperature = the grid's NLL argmin,
+    refined by the vertex of the parabola through it and its two neighbours in log T; at an end of the grid it is the grid point and
+    temperature_at_edge is True.  Without a counted pixel every score is NaN and counted is 0."""
+    c = int(n_classes)
+    bn, cl, sm = np.asarray(bins, dtype=np.int64), np.asarray(cls, dtype=np.int64), np.asarray(sums, dtype=np.float64)
+    temps = [float(t) for t in temps]
+    nt = len(temps)
+    if bn.ndim != 3 or bn.shape[0] != nt or bn.shape[2] != 3 or cl.shape != (nt, c, 3) or sm.shape != (nt, 2):
+        raise ValueError("calibration_scores: bins [%d, B, 3], cls [%d, %d, 3] and sums [%d, 2] expected, got %s, %s and %s" % (
+            nt, nt, c, nt, bn.shape, cl.shape, sm.shape))
+    nb = bn.shape[1]
+    q24 = float(1 << 24)
+
+    def at(t):
+        n_b, h_b, q_b = (bn[t, :, k].astype(np.float64) for k in range(3))
+        n = n_b.sum()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            acc_b, conf_b = h_b / n_b, q_b / (q24 * n_b)
+            gap = np.where(n_b > 0, np.abs(acc_b - conf_b), 0.0)
+            if n > 0:
+                ece, mce = float((n_b / n * gap).sum()), float(gap.max())
+            else:
+                ece = mce = float("nan")
+            return {"n": n, "ece": ece, "mce": mce, "nll": float(sm[t, 0] / n) if n > 0 else float("nan"),
+                    "brier": float(sm[t, 1] / n) if n > 0 else float("nan"), "acc_b": acc_b, "conf_b": conf_b, "n_b": n_b, "h_b": h_b,
+                    "q_b": q_b}
+
+    one = at(0)
+    n, n_b, h_b = one["n"], one["n_b"], one["h_b"]
+    out = {"ece": one["ece"], "mce": one["mce"], "nll": one["nll"], "brier": one["brier"], "counted": int(n)}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["accuracy"] = float(h_b.sum() / n) if n > 0 else float("nan")
+        out["confidence"] = float(one["q_b"].sum() / (q24 * n)) if n > 0 else float("nan")
+        cn, ch, cq = (cl[0, :, k].astype(np.float64) for k in range(3))
+        gap_c = np.where(cn > 0, cq / (q24 * cn) - ch / cn, np.nan)[kept_classes(c, dataset)]
+        out["class_gap"] = dict(zip(range(len(gap_c)), gap_c))
+        out["bins"] = [(b / nb, (b + 1) / nb, int(n_b[b]), float(one["acc_b"][b]), float(one["conf_b"][b])) for b in range(nb)]
+        tail_n, tail_h = np.cumsum(n_b[::-1])[::-1], np.cumsum(h_b[::-1])[::-1]
+        out["above"] = [(b / nb, float(tail_n[b] / n) if n > 0 else float("nan"),
+                         float(tail_h[b] / tail_n[b]) if tail_n[b] > 0 else float("nan")) for b in range(nb)]
+    if nt > 1:
+        order = sorted(range(nt), key=lambda t: temps[t])
+        rows = [at(t) for t in order]
+        grid = [(temps[t], r["nll"], r["ece"]) for t, r in zip(order, rows)]
+        out["temperature_grid"] = grid
+        nll = np.array([g[1] for g in grid])
+        if not np.isfinite(nll).all():
+            out["temperature"], out["temperature_at_edge"] = float("nan"), False
+        else:
+            i = int(np.argmin(nll))
+            out["temperature"], out["temperature_at_edge"] = grid[i][0], i in (0, nt - 1)
+            if not out["temperature_at_edge"]:
+                x0, x1, x2 = (float(np.log(grid[k][0])) for k in (i - 1, i, i + 1))
+                y0, y1, y2 = (float(nll[k]) for k in (i - 1, i, i + 1))
+                den = (x1 - x0) * (y1 - y2) - (x1 - x2) * (y1 - y0)
+                if den != 0.0:
+                    xv = x1 - 0.5 * ((x1 - x0) ** 2 * (y1 - y2) - (x1 - x2) ** 2 * (y1 - y0)) / den
+                    out["temperature"] = float(np.exp(min(max(xv, x0), x2)))
+    return out
+
+
+def parse_calibration(spec):
+    """`--calibration`: the calibration scores of the evaluation.  "on" = F.CalibrationOptions(): 15 confidence bins, temperature 1
+    only; "fit" = bins=15,temps=0.5:3.0:7: also seven log-spaced temperatures from 0.5 to 3.0, from which the NLL-optimal one is fitted
+    (both are untuned defaults, not published ones); else a comma list over bins=N (2..32) and temps=lo:hi:n (n log-spaced
+    temperatures from lo to hi) or temps=a/b/c (the temperatures themselves) - temperature 1 is always put in front, at most 8 with it;
+    keys left out keep their defaults.  Returns a F.CalibrationOptions, None for "" / None.  Raises ValueError naming the bad token."""
+    import math
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    if spec == "on":
+        return F.CalibrationOptions()
+    if spec == "fit":
+        spec = "bins=15,temps=0.5:3.0:7"
+    kw = {}
+    for tok in spec.split(","):
+        key, sep, val = tok.strip().partition("=")
+        if not sep or key not in ("bins", "temps") or key in kw:
+            raise ValueError("--calibration: %r is not 'on', 'fit' or one key=value over bins, temps" % tok)
+        try:
+            if key == "bins":
+                kw[key] = int(val)
+            elif ":" in val:
+                lo, hi, cnt = val.split(":")
+                lo, hi, cnt = float(lo), float(hi), int(cnt)
+                if not (0.0 < lo < hi < float("inf")) or not 2 <= cnt <= F.CALIBRATION_MAX_TEMPS:
+                    raise ValueError("--calibration: %r: lo:hi:n needs 0 < lo < hi and n in 2..%d" % (tok, F.CALIBRATION_MAX_TEMPS))
+                step = (math.log(hi) - math.log(lo)) / (cnt - 1)
+                kw[key] = tuple([lo] + [math.exp(math.log(lo) + k * step) for k in range(1, cnt - 1)] + [hi])
+            else:
+                kw[key] = tuple(float(v) for v in val.split("/"))
+        except ValueError as e:
+            if str(e).startswith("--calibration"):
+                raise
+            raise ValueError("--calibration: %r is not %s" % (tok, "an integer" if key == "bins" else "lo:hi:n or a list a/b/c of numbers"))
+        try:
+            F.CalibrationOptions(**{key: kw[key]})
+        except ValueError as e:
+            raise ValueError("--calibration: %r: %s" % (tok, e))
+    return F.CalibrationOptions(**kw)
 
 
 def parse_components(spec):

@@ -63,13 +63,42 @@ def validation(args, val_loader=None):
     crf = utils.parse_crf(getattr(args, 'crf', ''))
     # --crf: the windowed dense CRF, guided by the images, on Gsi's logits (with --tta: on the views' summed probabilities)
     labels_crf = lambda x, scores, probs: filt(F.crf_labels(scores, utils.crf_guide(x, size), size, crf, probs=probs)[0]).cpu().numpy()
-    img = lambda x: F.act_fwd(F.to_nhwc(F.upsample_bilinear(Gis(x), size)), F.ACT_TANH)   # Gis -> interp -> Tanh
+    cal = utils.parse_calibration(getattr(args, 'calibration', ''))
+    keeper = None
+    if cal is not None:
+        # --calibration: the counts behind ECE / MCE / NLL / Brier of what the saved prediction is taken from (before --components), against
+        # the split's ground truth; a temperature grid with --tta, --crf or SSCG_FUSE_PREDICT=0 is refused here
+        keeper = utils.runningScore(n_channels, args.dataset)
+        keeper.set_calibration(cal, tta=tta, crf=crf)
+
+    def scored(x, logits, gt):
+        """The prediction of one batch as below, its probabilities scored against `gt` on the way."""
+        if crf is not None:
+            scores, probs = utils.crf_scores(Gsi, x, size, tta) if tta else (logits, False)
+            if crf.iterations == 0:         # no mean-field step, no Q: the logits' own softmax (with --tta this was refused above)
+                keeper.update_calibration(gt, scores, size)
+                return labels_crf(x, scores, probs)
+            out = F.crf_labels(scores, utils.crf_guide(x, size), size, crf, probs=probs, want_q=True)
+            keeper.update_calibration(gt, out[3], size, probs=True)
+        elif tta:
+            out = F.predict_labels_ms(*utils.tta_logits(Gsi, x, tta), size, want_prob=True)
+            keeper.update_calibration(gt, out[3], size, probs=True, scale=utils.inv_views(len(tta)))
+        else:
+            if fused:
+                keeper.update_calibration(gt, logits, size)
+            else:
+                keeper.update_probs(gt, soft(logits))
+            return labels(logits)
+        return filt(out[0]).cpu().numpy()
+    img =lambda x: F.act_fwd(F.to_nhwc(F.upsample_bilinear(Gis(x), size)), F.ACT_TANH)   # Gis -> interp -> Tanh
     Gsi.eval()
     with torch.no_grad():
         for i, (image_test, real_segmentation, image_name) in enumerate(val_loader):
             image_test, real_segmentation = utils.cuda([image_test, real_segmentation], args.gpu_ids)
             logits = Gsi(image_test) if semi or not tta else None     # the image-regeneration branches stay single-view
-            if crf is not None:
+            if keeper is not None:
+                prediction = scored(image_test, logits, real_segmentation.squeeze(1))
+            elif crf is not None:
                 prediction = labels_crf(image_test, *(utils.crf_scores(Gsi, image_test, size, tta) if tta else (logits, False)))
             else:
                 prediction = labels_ms(image_test) if tta else labels(logits)
@@ -101,5 +130,11 @@ def validation(args, val_loader=None):
                     save(fake_img[j], os.path.join(_mk(base, 'regenerated_image'), image_name[j] + '.jpg'))
                     save(fake_img_from_labels[j], os.path.join(_mk(base, 'image_from_labels'), image_name[j] + '.jpg'))
             print('Epoch-', str(i + 1), ' Done!')
+    if keeper is not None:
+        s = keeper.get_calibration_scores()
+        print('The calibration of the resulting segment maps: ECE %s MCE %s NLL %s Brier %s accuracy %s confidence %s over %d pixels%s' % (
+            s["ece"], s["mce"], s["nll"], s["brier"], s["accuracy"], s["confidence"], s["counted"],
+            ' | NLL-optimal temperature %s%s' % (s["temperature"], ' (at the end of the grid)' if s["temperature_at_edge"] else '')
+            if "temperature" in s else ''))
     print('The iou of the resulting segment maps: ', str(best_iou))
     return best_iou
