@@ -489,8 +489,16 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
 
         if not os.path.isdir(args.checkpoint_dir):
             os.makedirs(args.checkpoint_dir, exist_ok=True)
-        try:                                                        # model.py:298-311
+        # model.py:298-311.  Only a MISSING file starts from scratch: the reference's bare `except` also swallows a file that exists and
+        # cannot be restored (unreadable, a key missing, a shape mismatch) and then trains over it - here that stops the run
+        try:
             ck = utils.load_checkpoint('%s/latest_semisuper_cycleGAN.ckpt' % (args.checkpoint_dir))
+        except FileNotFoundError:
+            ck = None
+            print(' [*] No checkpoint!')
+            self.start_epoch = 0
+            self.best_iou = -100
+        if ck is not None:
             self.start_epoch = ck['epoch']
             for k in ('Di', 'Ds', 'Gis', 'Gsi'):
                 getattr(self, k).load_state_dict(ck[k])
@@ -499,11 +507,7 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
             if self.g_optimizer.ema_decay is not None and 'Gsi_ema' in ck and 'Gis_ema' in ck:    # (else: the EMA restarts from the weights)
                 self.g_optimizer.load_ema_state_dict(self.Gsi, ck['Gsi_ema'])
                 self.g_optimizer.load_ema_state_dict(self.Gis, ck['Gis_ema'])
-            self.best_iou = ck['best_iou']
-        except Exception:
-            print(' [*] No checkpoint!')
-            self.start_epoch = 0
-            self.best_iou = -100
+            self.best_iou = float(ck['best_iou'])
 
     # --ssim_weight / --ssim_window / --ssim_sigma (opt-in; the reference's image terms are plain L1): every image L1 term gains
     # ssim_w * (1 - mean SSIM) inside its own weight, from the L1's own forward and backward launch (functional.l1_ssim_loss)
@@ -1024,7 +1028,7 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
                     if first:       # model.py:576-638, on the batch evaluate() has just consumed: no second iterator on the loader
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank0:                                 # model.py:641-655
-                    self.best_iou = miou
+                    self.best_iou, class_iou = utils.checkpoint_scores(miou, class_iou)     # plain numbers: the file loads weights-only
                     ck = {'epoch': epoch + 1, 'Di': self.Di.state_dict(), 'Ds': self.Ds.state_dict(),
                           'Gis': self.Gis.state_dict(), 'Gsi': self.Gsi.state_dict(),
                           'd_optimizer': self.d_optimizer.state_dict(), 'g_optimizer': self.g_optimizer.state_dict(),
@@ -1062,18 +1066,20 @@ class supervised_model(_WeightedCE):
         self.running_metrics_val = utils.runningScore(self.n_channels, args.dataset)
         if not os.path.isdir(args.checkpoint_dir):
             os.makedirs(args.checkpoint_dir, exist_ok=True)
-        try:
+        try:                # (only a missing file starts from scratch, as in semisuper_cycleGAN)
             ck = utils.load_checkpoint('%s/latest_supervised_model.ckpt' % (args.checkpoint_dir))
+        except FileNotFoundError:
+            ck = None
+            print(' [*] No checkpoint!')
+            self.start_epoch = 0
+            self.best_iou = -100
+        if ck is not None:
             self.start_epoch = ck['epoch']
             self.Gsi.load_state_dict(ck['Gsi'])
             self.gsi_optimizer.load_state_dict(ck['gsi_optimizer'])
             if self.gsi_optimizer.ema_decay is not None and 'Gsi_ema' in ck:      # (else: the EMA restarts from the weights)
                 self.gsi_optimizer.load_ema_state_dict(self.Gsi, ck['Gsi_ema'])
-            self.best_iou = ck['best_iou']
-        except Exception:
-            print(' [*] No checkpoint!')
-            self.start_epoch = 0
-            self.best_iou = -100
+            self.best_iou = float(ck['best_iou'])
 
     def step(self, l_img, l_gt):
         """model.py:120-143."""
@@ -1227,7 +1233,7 @@ class supervised_model(_WeightedCE):
                     if first:                                                       # model.py:164-186
                         write_panels(self.panels(*first), epoch, writer, panel_dir)
                 if miou >= self.best_iou and rank == 0:
-                    self.best_iou = miou
+                    self.best_iou, class_iou = utils.checkpoint_scores(miou, class_iou)     # plain numbers: the file loads weights-only
                     ck = {'epoch': epoch + 1, 'Gsi': self.Gsi.state_dict(), 'gsi_optimizer': self.gsi_optimizer.state_dict(),
                           'best_iou': self.best_iou, 'class_iou': class_iou}
                     if self.gsi_optimizer.ema_decay is not None:

@@ -292,3 +292,6 @@ class FusedAdam(torch.optim.Optimizer):
                 p._sscg_touched = True
                 steps = max(steps, int(float(st["step"])))
         self._steps = steps
+        # super().load_state_dict left a second device copy of both moments in self.state (2 x 343 MB for the generators); the arenas
+        # hold the values now, and state_dict() rebuilds self.state from views of them
+        self.state.clear()

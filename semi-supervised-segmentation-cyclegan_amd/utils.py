@@ -947,12 +947,44 @@ def ce_weights_from_counts(rule, counts):
     raise ValueError("unknown class-weight rule %r" % (rule,))
 
 
+def checkpoint_scores(miou, class_iou):
+    """The two score entries of a checkpoint as plain Python numbers: ('best_iou': float, 'class_iou': {int: float}) of what
+    runningScore.get_scores() returns (numpy.float64 scalars; an empty class stays NaN).  A file that holds only tensors, containers
+    and Python numbers is read back by torch's default (weights-only) loading; numpy scalars are not."""
+    return float(miou), {int(k): float(v) for k, v in class_iou.items()}
+
+
 def save_checkpoint(state, save_path):
     torch.save(state, save_path)
 
 
+def _numpy_scalar_globals():
+    """The globals a pickled numpy scalar names: the reconstructor (written as numpy._core.multiarray.scalar by numpy 2.x, as
+    numpy.core.multiarray.scalar by numpy 1.x), numpy.dtype and the dtype classes of float64 / int64.  Nothing else."""
+    import importlib
+    out = [np.dtype, type(np.dtype(np.float64)), type(np.dtype(np.int64))]
+    paths = ("numpy._core.multiarray", "numpy.core.multiarray")
+    for mod in paths:               # (the first that exists: numpy 2.x only keeps the old path as a deprecated alias of the new one)
+        try:
+            fn = importlib.import_module(mod).scalar
+        except (ImportError, AttributeError):
+            continue
+        # the unpickler matches the name the FILE uses, whichever numpy wrote it: both names stand for this numpy's function
+        out.extend((fn, m + ".scalar") for m in paths)
+        break
+    return out
+
+
 def load_checkpoint(ckpt_path, map_location="cpu"):
-    ckpt = torch.load(ckpt_path, map_location=map_location)
+    """torch.load with torch's safe (weights-only) unpickler.  Files written before checkpoint_scores() existed, and the reference's,
+    hold numpy.float64 scalars ('best_iou', 'class_iou'): for those the load is repeated with exactly the numpy scalar globals
+    allow-listed.  A file that holds any other pickled class raises (pickle.UnpicklingError), a missing file FileNotFoundError."""
+    import pickle
+    try:
+        ckpt = torch.load(ckpt_path, map_location=map_location, weights_only=True)
+    except pickle.UnpicklingError:
+        with torch.serialization.safe_globals(_numpy_scalar_globals()):
+            ckpt = torch.load(ckpt_path, map_location=map_location, weights_only=True)
     print(" [*] Loading checkpoint from %s succeed!" % ckpt_path)
     return ckpt
 

@@ -1,8 +1,10 @@
 """`python main.py --testing ...`: the reference's testing.py (:17-100) on the MI355X backend: paletted
 predictions of Gsi over the test split under `--results_dir/{supervised,unsupervised}`.
 As written there, Gsi is built as `resnet_9blocks_softmax` (testing.py:40) although training saves a DeepLab
-`Gsi`: loading then fails, ' [*] No checkpoint!' is printed and the run continues on the initial weights.  The
-behaviour is kept; `--testing_gen deeplab` builds the network the checkpoint actually holds."""
+`Gsi`: loading then fails, and the reference prints ' [*] No checkpoint!' and goes on with the initial weights.
+Here only a missing file does that; a file that exists and does not fit the network stops the run with torch's
+error (its predictions would be those of a random network).  `--testing_gen deeplab` builds the network the
+checkpoint actually holds."""
 import importlib
 import os
 
@@ -31,11 +33,13 @@ def test(args, test_loader=None):
     semi = args.model == 'semisupervised_cycleGAN'
     try:
         ckpt = utils.load_checkpoint('%s/latest_%s.ckpt' % (args.checkpoint_dir, 'semisuper_cycleGAN' if semi else 'supervised_model'))
+    except FileNotFoundError:
+        ckpt = None
+        print(' [*] No checkpoint!')
+    if ckpt is not None:
         Gsi.load_state_dict(ckpt['Gsi'])
         if getattr(args, 'ema_decay', None) is not None and 'Gsi_ema' in ckpt:      # --ema_decay: the averaged parameters (buffers stay)
             Gsi.load_state_dict(ckpt['Gsi_ema'], strict=False)
-    except Exception:
-        print(' [*] No checkpoint!')
     out = os.path.join(args.results_dir, 'unsupervised' if semi else 'supervised')
     os.makedirs(out, exist_ok=True)
     tta = utils.parse_tta(getattr(args, 'tta', ''))

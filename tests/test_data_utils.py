@@ -159,9 +159,11 @@ def test_validation_and_testing_drivers_write_the_reference_outputs(tmp_path, de
 
 
 @pytest.mark.gpu
-def test_main_trains_from_the_real_pipeline_and_checkpoints(tmp_path, dev, monkeypatch):
+def test_main_trains_from_the_real_pipeline_and_checkpoints(tmp_path, dev, monkeypatch, capsys):
     """`python main.py --training True --model semisupervised_cycleGAN` end to end on a small VOC-layout tree:
-    datasets -> uint8 batches -> device finishing -> G+D steps -> device-side mIoU -> checkpoint (model.py:314-660)."""
+    datasets -> uint8 batches -> device finishing -> G+D steps -> device-side mIoU -> checkpoint (model.py:314-660).  The file
+    train() wrote is read back by the project's own utils.load_checkpoint, and `--validation` on the same checkpoint_dir loads it
+    (it does not score freshly initialised networks behind a "No checkpoint!")."""
     import importlib
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,9 +174,19 @@ def test_main_trains_from_the_real_pipeline_and_checkpoints(tmp_path, dev, monke
     main.main(["--training", "True", "--model", "semisupervised_cycleGAN", "--dataset", "voc2012", "--crop_height", "64",
                "--crop_width", "64", "--batch_size", "2", "--gpu_ids", "0", "--epochs", "1", "--decay_epoch", "0", "--no_dropout",
                "--checkpoint_dir", str(tmp_path / "ckpt"), "--data", "real"])
-    ck = torch.load(str(tmp_path / "ckpt" / "latest_semisuper_cycleGAN.ckpt"), map_location="cpu", weights_only=False)
+    ck = load_sub("utils").load_checkpoint(str(tmp_path / "ckpt" / "latest_semisuper_cycleGAN.ckpt"))
     assert set(ck) == {'epoch', 'Di', 'Ds', 'Gis', 'Gsi', 'd_optimizer', 'g_optimizer', 'best_iou', 'class_iou'} and ck['epoch'] == 1
+    assert type(ck['best_iou']) is float
     assert np.isfinite(ck['best_iou'])
+    assert all(type(k) is int and type(v) is float for k, v in ck['class_iou'].items()) and len(ck['class_iou']) == 20
+    capsys.readouterr()
+    main.main(["--validation", "True", "--model", "semisupervised_cycleGAN", "--dataset", "voc2012", "--crop_height", "64",
+               "--crop_width", "64", "--batch_size", "2", "--gpu_ids", "0", "--no_dropout", "--checkpoint_dir", str(tmp_path / "ckpt"),
+               "--validation_dir", str(tmp_path / "val")])
+    printed = capsys.readouterr().out
+    assert "latest_semisuper_cycleGAN.ckpt succeed!" in printed and "No checkpoint!" not in printed
+    assert "The iou of the resulting segment maps:  %s" % ck['best_iou'] in printed
+    assert len(os.listdir(tmp_path / "val" / "unsupervised" / "generated_labels")) > 0
 
 
 def _cityscapes_tree(root, n_train=8, n_val=3):

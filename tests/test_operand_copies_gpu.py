@@ -436,9 +436,12 @@ class Rig:
     """Two small nets of arch.ops layers in which every kind of copy occurs.
     G (optim.FusedAdam): 7x7 21->64 stem (padded-stem path) -> 3x3 64->64 -> a FROZEN 3x3 64->64 (no optimiser) -> a 3x3 64->64
     under a stock torch.optim.Adam -> ConvTranspose2d 64->64 -> 3x3 64->21 head (padded-head data gradient) -> 1x1 21->5 (ragged
-    channel counts: the exact fp32 kernels in every mode).  D (a second FusedAdam): 3x3 21->64 -> 3x3 64->64 -> 1x1 64->1."""
+    channel counts: the exact fp32 kernels in every mode).  D (a second FusedAdam): 3x3 21->64 -> 3x3 64->64 -> 1x1 64->1.
+    g_kw / d_kw: keyword options of the two FusedAdams (lr, weight_decay, decoupled, max_grad_norm, ema_decay).  inputs: a list of
+    [2,21,16,16] CPU tensors the phases consume in order (two per step: G, then D) in place of draws from the rig's own generator -
+    `replay(k)` points at the inputs of step k, so that a second rig can continue where a first one stopped."""
 
-    def __init__(self, F, dev, seed=0):
+    def __init__(self, F, dev, seed=0, g_kw=None, d_kw=None, inputs=None):
         ops, optim = load_sub("arch.ops"), load_sub("optim")
         self.F, self.dev = F, dev
         torch.manual_seed(seed)
@@ -452,10 +455,11 @@ class Rig:
         for m in (self.g["head"], self.g["ragged"], self.d["head"]):
             m.head = True                   # fp32 output in bf16 mode, as the networks' last convs
         self.frozen.weight.requires_grad_(False)
-        self.g_opt = optim.FusedAdam(self.g.parameters(), lr=2e-4)
-        self.d_opt = optim.FusedAdam(self.d.parameters(), lr=2e-4)
+        self.g_opt = optim.FusedAdam(self.g.parameters(), **dict(dict(lr=2e-4), **(g_kw or {})))
+        self.d_opt = optim.FusedAdam(self.d.parameters(), **dict(dict(lr=2e-4), **(d_kw or {})))
         self.s_opt = torch.optim.Adam(self.stock.parameters(), lr=2e-4, betas=(0.5, 0.999))
         self.gen = torch.Generator().manual_seed(seed + 1)
+        self.inputs, self.next_input = inputs, 0
         self.steps = 0
         self.ptrs = []          # after every refresh: {(weight, attribute): data_ptr of the transposed copy}
         self.checks = collections.Counter()
@@ -476,8 +480,16 @@ class Rig:
         w.update(frozen=self.frozen.weight, stock=self.stock.weight)
         return w
 
+    def replay(self, step):
+        """The next phases read the fixed inputs of step `step` (0-based) onwards."""
+        self.next_input = 2 * step
+
     def _input(self):
-        x = torch.randn(2, 21, 16, 16, generator=self.gen).to(self.dev).contiguous(memory_format=CL)
+        if self.inputs is not None:
+            x, self.next_input = self.inputs[self.next_input], self.next_input + 1
+        else:
+            x = torch.randn(2, 21, 16, 16, generator=self.gen)
+        x = x.to(self.dev).contiguous(memory_format=CL)
         return x.requires_grad_(True)       # (the stems' data gradients run too: Gis(fake_gt) in the real step)
 
     def check(self, getters=True, weights=None):

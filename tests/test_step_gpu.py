@@ -127,6 +127,26 @@ def test_checkpoint_roundtrip_and_stock_adam_format(dev, tmp_path):
     l2 = {k: float(v) for k, v in m2.step(*b1).items()}
     for k in l1:
         assert abs(l1[k] - l2[k]) <= 1e-6 * abs(l1[k]), (k, l1[k], l2[k])
+    # the losses of that step were computed from the weights BEFORE its update: they do not depend on the restored moments or step
+    # counter.  The updated weights and both moment arenas do - equal bits, as everywhere two instances of one process are compared
+    m.sync_losses()
+    m2.sync_losses()
+    torch.cuda.synchronize()
+    n_w = 0
+    for k in ("Gis", "Gsi", "Di", "Ds"):
+        sd1, sd2 = getattr(m, k).state_dict(), getattr(m2, k).state_dict()
+        assert list(sd1) == list(sd2)
+        for name in sd1:
+            assert torch.equal(sd1[name], sd2[name]), (k, name)
+            n_w += 1
+    for name in ("g_optimizer", "d_optimizer"):
+        o1, o2 = getattr(m, name), getattr(m2, name)
+        assert o1._steps == o2._steps == 2, (name, o1._steps, o2._steps)
+        for arena in ("arena", "exp_avg", "exp_avg_sq"):
+            a, b = getattr(o1, arena), getattr(o2, arena)
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (name, arena)
+        assert bool(o2.exp_avg.abs().max() > 0)
+    print("checkpoint round trip: after the step behind the load %d network tensors and 2 x 3 arenas equal the saving model's bit for bit" % n_w)
     assert m.Gsi.bn1.batches_tracked() == 6 and int(m.Gsi.state_dict()["bn1.num_batches_tracked"]) == 6
 
 

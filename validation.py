@@ -37,8 +37,14 @@ def validation(args, val_loader=None):
     size = (args.crop_height, args.crop_width)
     best_iou = 0
     semi = args.model == 'semisupervised_cycleGAN'
+    # only a MISSING file leaves the initial weights (the reference's behaviour); a file that exists and cannot be restored stops the
+    # run: its predictions would be those of random networks
     try:
         ckpt = utils.load_checkpoint('%s/latest_%s.ckpt' % (args.checkpoint_dir, 'semisuper_cycleGAN' if semi else 'supervised_model'))
+    except FileNotFoundError:
+        ckpt = None
+        print(' [*] No checkpoint!')
+    if ckpt is not None:
         Gsi.load_state_dict(ckpt['Gsi'])
         if semi:
             Gis.load_state_dict(ckpt['Gis'])
@@ -46,9 +52,7 @@ def validation(args, val_loader=None):
             for net, key in ((Gsi, 'Gsi_ema'), (Gis, 'Gis_ema')):
                 if key in ckpt:
                     net.load_state_dict(ckpt[key], strict=False)
-        best_iou = ckpt['best_iou']
-    except Exception:
-        print(' [*] No checkpoint!')
+        best_iou = float(ckpt['best_iou'])
 
     comp = utils.parse_components(getattr(args, 'components', ''))
     # --components: every predicted label map goes through the connected-component filter on the device before it is copied and saved
