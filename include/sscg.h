@@ -384,6 +384,33 @@ int sscg_augment_elastic_u8(const uint8_t* img, const uint8_t* gt, const int32_t
                             int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill,
                             int label_fill, const float* colour, int need_mean, void* ws, const int32_t* nodes, int grid, int GH, int GW,
                             void* stream);
+/* sscg_augment_elastic_u8 with mixed-sample augmentation (CutMix, ClassMix): every output pixel shows its own sample or, pasted, the
+ * sample's partner, image and label alike, decided inside the same launch.  colour may be NULL as there; nodes may be NULL too = no
+ * lattice (grid, GH and GW are then ignored); the other arguments of sscg_augment_elastic_u8 mean what they mean there.
+ *   table:   mix int32 [N][8] on the device = (partner, x0, y0, x1, y1, mask_lo, mask_hi, 0) per sample.  p = mix[n][0] outside
+ *            [0, N), or p == n: sample n is not mixed.  No table content is an error and none is unsafe: only a valid p indexes
+ *            memory, the other fields are compared and shifted.
+ *   pasted:  output pixel (n, oy, ox) of a mixed sample is pasted if
+ *              (box)   x0 <= ox < x1 and y0 <= oy < y1 - a half-open rectangle of OUTPUT pixels, which may be empty or reach beyond
+ *                      the output: the comparisons alone decide - or
+ *              (class) classes != 0, the pixel is not in the box, and with id_p the raw label id of sample p at (oy, ox) - p's own
+ *                      matrix, p's own lattice, the nearest index, label_fill outside the source: sscg_augment_u8's label rule -
+ *                      cls = lut256[id_p] satisfies 0 <= cls < 64 and bit cls of (mask_hi << 32) | (uint32)mask_lo is set.
+ *   pixel:   a pasted pixel's C channels and its label are those of sample p at (oy, ox): p's matrix, p's lattice, p's colour table
+ *            with p's mean; an unpasted pixel is sample n's own.  The partner's pixel is always p's UNMIXED pixel: chains (n takes
+ *            from p while p takes from q) do not propagate.  The sum pass of need_mean is unchanged: every sample's mean is that of
+ *            its own unmixed warped pixels.
+ * So out[n] = where(pasted, plain[p], plain[n]) bit for bit, image and label, plain being what sscg_augment_u8, _colour_u8 or
+ * _elastic_u8 (whichever fits the other arguments) returns for the batch; an all-unmixed table gives plain.  Same taps per output
+ * pixel (the source sample is decided first), at most one more label gather, nothing more written.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (sscg_augment_u8's cases, a NULL mix, classes != 0 without gt, with nodes grid < 4 or
+ * GH or GW other than the formula's, with a colour table need_mean with a NULL or misaligned ws), SSCG_ERR_UNSUPPORTED
+ * (sscg_augment_u8's size limits, C of 2 or 4, with nodes grid above 2^22, need_mean with N above 65535).
+ * (An addition: no existing entry changes meaning or bits, so SSCG_ABI_VERSION stays 18.) */
+int sscg_augment_mix_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H, int W,
+                        int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill, int label_fill,
+                        const float* colour, int need_mean, void* ws, const int32_t* nodes, int grid, int GH, int GW, const int32_t* mix,
+                        int classes, void* stream);
 
 /* ------------------------------------------------------------------ losses (K10, K11), mean reduction
  * Each forward writes one fp32 scalar to `loss` (device).  Each backward takes the upstream gradient as

@@ -5,7 +5,8 @@ dispatch on --training / --model.  Extra flags (never change a reference default
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
 --calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp,
 --lovasz_weight, --lovasz_per_image, --lovasz_classes, --lovasz_skip.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
-(one process per MI355X; gradients all-reduced with RCCL)."""
+(one process per MI355X; gradients all-reduced with RCCL).  --augment's items `cutmix=` / `classmix=` mix two samples of a
+labelled batch, labels with pixels, inside the device-side batch finish; their class ids are checked against --dataset here."""
 import importlib
 import os
 import sys
@@ -102,7 +103,11 @@ def get_args(argv=None):
                              "default 32, untuned, each moved by up to <alpha> pixels; alpha <= 0.4 * grid, at most one such item); "
                              "brightness=<x>, contrast=<x>, saturation=<x> (factor in max(0,1-x)..1+x), hue=<x> (0..0.5 of a turn), "
                              "gray=<p> - colour behind geometry, each in the order written, clamped to [0,1] once at the end; "
-                             "contrast adds a sum pass for the image mean (default: none)")
+                             "contrast adds a sum pass for the image mean; cutmix=<p>[:<lo>:<hi>] (with probability p a box of lo..hi of "
+                             "the area, default 0.25:0.5, untuned, is pasted from another sample of the batch) and "
+                             "classmix=<p>[:<id>[:<id>...]] (with probability p every pixel of a random half of another sample's classes "
+                             "is pasted; the listed class ids never are, e.g. classmix=0.5:0 for VOC's background) mix the LABELLED "
+                             "batches only, labels with pixels, inside the same launch, at most one item of each (default: none)")
     parser.add_argument("--panels", type=str, default=None, metavar="DIR",
                         help="write the reference's per-epoch image panels (model.py:576-638) to DIR/epoch%%03d_<n>.png, and to a "
                              "tensorboardX.SummaryWriter(DIR) when that module is installed (default: off)")
@@ -265,6 +270,11 @@ def get_args(argv=None):
         if len(cal.temps) > 1 and (getattr(args, "tta", "").strip() or args.crf.strip()):
             parser.error("--calibration: a temperature list rescales the logits of the single fused head and does not combine with "
                          "--tta or --crf")
+    for item in (s.strip() for s in args.augment.split(",")):
+        if item.partition("=")[0] == "classmix":
+            n_cls = {"voc2012": 21, "cityscapes": 20, "acdc": 4}[args.dataset]
+            if not all(t.isdigit() and int(t) < n_cls for t in item.partition("=")[2].split(":")[1:]):
+                parser.error("--augment classmix=<p>[:<id>...] skips class ids in [0, %d), given %r" % (n_cls, item))
     if args.ohem_thresh is not None and not 0.0 < args.ohem_thresh <= 1.0:
         parser.error("--ohem_thresh must lie in (0, 1]")
     if args.ohem_min_kept < 0:

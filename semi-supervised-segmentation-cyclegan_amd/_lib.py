@@ -120,6 +120,7 @@ SIGNATURES = {
     "sscg_augment_colour_workspace": (_sz, [_i]),
     "sscg_augment_colour_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p]),
     "sscg_augment_elastic_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _p]),
+    "sscg_augment_mix_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p]),
     "sscg_loss_workspace": (_sz, [_i64]),
     "sscg_ce_fwd": (_i, [_p, _p, _i64, _i, _p, _p, _p, _sz, _p]),
     "sscg_ce_bwd": (_i, [_p, _p, _i64, _i, _p, _f, _p, _p, _p]),

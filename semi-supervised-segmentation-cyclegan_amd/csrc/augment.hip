@@ -7,6 +7,8 @@
 // integer pixels of every sample.
 // sscg_augment_elastic_u8 adds a free-form deformation to the affine source coordinate (ELASTIC instantiations of the same three
 // kernels): a cubic B-spline over a coarse lattice of int32 control nodes per sample, integers throughout.
+// sscg_augment_mix_u8 composes two samples (CutMix, ClassMix) inside the same launch (MIX instantiations of the apply kernel): a
+// table row per sample names a partner, a box and a class mask, and every output pixel is its own sample's or the partner's.
 #include <type_traits>
 
 #include "common.h"
@@ -168,8 +170,10 @@ __device__ __forceinline__ aug_disp aug_elastic_pixel(const aug_elastic_args& el
 __device__ __noinline__ aug_disp aug_elastic_pixel_call(aug_elastic_args el, int n, int oy, int ox) { return aug_elastic_pixel(el, n, oy, ox); }
 
 // four consecutive pixels of one row, (oy, ox) .. (oy, ox + 3) with ox + 3 < OW: at grid >= 4 they lie in at most two cells, so the y
-// pass runs once per node column - four, or five when the group crosses into the next cell (only then does the fifth exist)
-__device__ __forceinline__ void aug_elastic_row4(const aug_elastic_args& el, int n, int oy, int ox, aug_disp* d) {
+// pass runs once per node column - four, or five when the group crosses into the next cell (only then does the fifth exist).
+// MASKED (a mix launch, where a pixel has one source sample): a pixel whose bit of `need` is clear takes no x pass, d[e] stays
+template <bool MASKED = false>
+__device__ __forceinline__ void aug_elastic_row4(const aug_elastic_args& el, int n, int oy, int ox, aug_disp* d, unsigned need = 0xF) {
     const int cy = oy / el.grid, cx = ox / el.grid;
     const int ty = ((oy - cy * el.grid) * 256) / el.grid;
     const int rem = ox - cx * el.grid;
@@ -189,7 +193,9 @@ __device__ __forceinline__ void aug_elastic_row4(const aug_elastic_args& el, int
         aug_disp w[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) w[j] = next ? c[j + 1] : c[j];
-        d[e] = aug_xpass(w, (r * 256) / el.grid);
+        if constexpr (MASKED) {
+            if (need >> e & 1) d[e] = aug_xpass(w, (r * 256) / el.grid);
+        } else d[e] = aug_xpass(w, (r * 256) / el.grid);
     }
 }
 
@@ -244,12 +250,82 @@ struct aug_colour_args {
     const int64_t* sums;     // [N][3] from the sum pass, or null = no mean
 };
 
+// ---- mixing (include/sscg.h, sscg_augment_mix_u8): what a mix launch adds to the arguments, and the decision per pixel
+struct aug_mix_args {
+    const int32_t* table;    // [N][8] = (partner, x0, y0, x1, y1, mask_lo, mask_hi, 0)
+    int N, classes;
+};
+
+// one sample's row of the table beside what a pasted pixel is made from: the partner's matrix and colour table.  They travel with
+// the sample's own and are reloaded wherever those are.
+template <int C>
+struct aug_mix {
+    int p;                   // the partner, or -1: the sample is not mixed (whatever the table holds, nothing else indexes memory)
+    int x0, y0, x1, y1;
+    uint64_t mask;
+    aug_mat a;
+    aug_col<C> k;
+
+    __device__ __forceinline__ bool in_box(int oy, int ox) const { return p >= 0 && ox >= x0 && ox < x1 && oy >= y0 && oy < y1; }
+};
+
+template <int C, bool COLOUR>
+__device__ __forceinline__ aug_mix<C> aug_load_mix(const aug_mix_args& mx, const int32_t* __restrict__ mats, const float* __restrict__ colour,
+                                                   const int64_t* __restrict__ sums, int n, double denom) {
+    const int32_t* r = mx.table + (size_t)n * 8;
+    aug_mix<C> m = {};
+    m.p = r[0];
+    if ((uint32_t)m.p >= (uint32_t)mx.N || m.p == n) m.p = -1;
+    m.x0 = r[1], m.y0 = r[2], m.x1 = r[3], m.y1 = r[4];
+    m.mask = ((uint64_t)(uint32_t)r[6] << 32) | (uint32_t)r[5];
+    if (m.p >= 0) {
+        m.a = aug_load_mat(mats, m.p);
+        if constexpr (COLOUR) m.k = aug_load_col<C>(colour, sums, m.p, denom);
+    }
+    return m;
+}
+
+// the class rule at (oy, ox) of a mixed sample: the partner's raw id there - its own map, its own displacement d, the label rule of
+// aug_pixel - through the table `t`; a class outside 0..63 never pastes
+template <int C>
+__device__ __forceinline__ bool aug_mix_class(const aug_mix<C>& m, const uint8_t* __restrict__ gt, const aug_geom& g, int oy, int ox, aug_disp d,
+                                              const int64_t* t) {
+    const int64_t sx = (int64_t)m.a.m[0] * ox + (int64_t)m.a.m[1] * oy + m.a.m[2] + d.x;
+    const int64_t sy = (int64_t)m.a.m[3] * ox + (int64_t)m.a.m[4] * oy + m.a.m[5] + d.y;
+    const int64_t ix = (sx + 0x8000) >> 16, iy = (sy + 0x8000) >> 16;
+    int id = g.label_fill;
+    if ((uint64_t)ix < (uint64_t)g.W && (uint64_t)iy < (uint64_t)g.H) id = gt[(size_t)m.p * g.H * g.W + (size_t)(iy * g.W + ix)];
+    const int64_t cls = t[id];
+    return (uint64_t)cls < 64u && (m.mask >> cls & 1) != 0;
+}
+
+// One pixel of sample n on its own: is it pasted - and, with a lattice, the displacement `d` of the sample it then comes from.  The
+// partner's is evaluated only where the partner's coordinate is needed (in the box, or anywhere under the class rule), the own only
+// for an unpasted pixel.
+template <int C, bool LABEL, bool ELASTIC>
+__device__ __forceinline__ bool aug_mix_pixel(const aug_mix<C>& m, int classes, const aug_elastic_args& el, const uint8_t* __restrict__ gt,
+                                              const aug_geom& g, int n, int oy, int ox, const int64_t* t, aug_disp& d) {
+    bool paste = m.in_box(oy, ox);
+    const bool partner = paste || (LABEL && classes != 0 && m.p >= 0);
+    aug_disp dp = {};
+    if constexpr (ELASTIC) {
+        if (partner) dp = aug_elastic_pixel_call(el, m.p, oy, ox);
+    }
+    if constexpr (LABEL) {
+        if (partner && !paste) paste = aug_mix_class<C>(m, gt, g, oy, ox, dp, t);
+    }
+    if constexpr (ELASTIC) d = paste ? dp : aug_elastic_pixel_call(el, n, oy, ox);
+    return paste;
+}
+
 // Every thread owns four consecutive pixels of the flat [N * OH * OW] range (a group may straddle a row or a sample) and stores them
 // as 16-byte vectors: 4 * C floats = C stores, four labels = two stores.  `groups` = 0 sends every pixel down the scalar tail.
 // The colour flag is the argument pack: COL is empty - the plain launch, whose arguments and with them whose instruction stream are
 // those it had before the colour instantiations existed - or aug_colour_args, and then the sample's colour table travels with its
 // matrix and is reloaded wherever the matrix is - and / or aug_elastic_args, and then every pixel's source coordinate takes the
-// displacement of the sample's lattice: one y pass per group where its four pixels share a row, pixel by pixel elsewhere.
+// displacement of the sample's lattice: one y pass per group where its four pixels share a row, pixel by pixel elsewhere - and / or
+// aug_mix_args, and then every pixel first decides which sample it shows, its own or (pasted) the sample's partner, and aug_pixel
+// runs once, for that one: same taps, same stores.
 template <int C, bool LABEL, typename... COL>
 __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ gt,
                                                                  const int32_t* __restrict__ mats, float* __restrict__ out_img,
@@ -258,6 +334,8 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
                                                                  aug_geom g, uint32_t total, uint32_t groups, COL... col) {
     constexpr bool COLOUR = (std::is_same_v<COL, aug_colour_args> || ...);
     constexpr bool ELASTIC = (std::is_same_v<COL, aug_elastic_args> || ...);
+    constexpr bool MIX = (std::is_same_v<COL, aug_mix_args> || ...);
+    const aug_mix_args mx = aug_pick<aug_mix_args>(col...);
     const aug_colour_args ca = aug_pick<aug_colour_args>(col...);
     const float* colour = ca.table;
     const int64_t* sums = ca.sums;
@@ -286,7 +364,33 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
         float v[4 * C];
         int64_t lab[4];
         aug_disp d[4] = {};
-        if constexpr (ELASTIC) {
+        aug_mix<C> m;
+        unsigned pasted = 0;                        // MIX with a lattice, four pixels of one row: decided here, with the shared y pass
+        bool row = false;
+        if constexpr (MIX) {
+            m = aug_load_mix<C, COLOUR>(mx, mats, colour, sums, n, denom);
+            if constexpr (ELASTIC) {
+                if ((row = ox + 3 < g.OW)) {
+                    unsigned box = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) box |= (unsigned)m.in_box(oy, ox + e) << e;
+                    const unsigned partner = m.p < 0 ? 0u : (LABEL && mx.classes != 0) ? 0xFu : box;
+                    aug_disp dp[4] = {};
+                    if (partner) aug_elastic_row4<true>(el, m.p, oy, ox, dp, partner);
+                    pasted = box;
+                    if constexpr (LABEL) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if ((partner & ~box) >> e & 1) pasted |= (unsigned)aug_mix_class<C>(m, gt, g, oy, ox + e, dp[e], t) << e;
+                    }
+                    if (pasted != 0xF) aug_elastic_row4<true>(el, n, oy, ox, d, ~pasted & 0xF);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (pasted >> e & 1) d[e] = dp[e];
+                }
+            }
+        }
+        if constexpr (ELASTIC && !MIX) {
             if (ox + 3 < g.OW) {
                 aug_elastic_row4(el, n, oy, ox, d);
             } else {                                // the group straddles a row or a sample: pixel by pixel, walking as the loop below
@@ -303,7 +407,10 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int id = aug_pixel<C, LABEL, COLOUR, ELASTIC>(img, gt, a, k, g, n, oy, ox, d[e], mu, sd, v + e * C);
+            bool paste = false;
+            if constexpr (MIX) paste = row ? (pasted >> e & 1) != 0 : aug_mix_pixel<C, LABEL, ELASTIC>(m, mx.classes, el, gt, g, n, oy, ox, t, d[e]);
+            const int id = aug_pixel<C, LABEL, COLOUR, ELASTIC>(img, gt, paste ? m.a : a, paste ? m.k : k, g, paste ? m.p : n, oy, ox, d[e], mu, sd,
+                                                                v + e * C);
             if constexpr (LABEL) lab[e] = t[id];
             if (e < 3 && ++ox == g.OW) {
                 ox = 0;
@@ -311,6 +418,7 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
                     oy = 0;
                     a = aug_load_mat(mats, ++n);
                     if constexpr (COLOUR) k = aug_load_col<C>(colour, sums, n, denom);
+                    if constexpr (MIX) m = aug_load_mix<C, COLOUR>(mx, mats, colour, sums, n, denom);
                 }
             }
         }
@@ -334,8 +442,13 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const uint8_t* 
         if constexpr (COLOUR) k = aug_load_col<C>(colour, sums, n, denom);
         float v[C];
         aug_disp d = {};
-        if constexpr (ELASTIC) d = aug_elastic_pixel_call(el, n, oy, ox);
-        const int id = aug_pixel<C, LABEL, COLOUR, ELASTIC>(img, gt, a, k, g, n, oy, ox, d, mu, sd, v);
+        aug_mix<C> m;
+        bool paste = false;
+        if constexpr (MIX) {
+            m = aug_load_mix<C, COLOUR>(mx, mats, colour, sums, n, denom);
+            paste = aug_mix_pixel<C, LABEL, ELASTIC>(m, mx.classes, el, gt, g, n, oy, ox, t, d);
+        } else if constexpr (ELASTIC) d = aug_elastic_pixel_call(el, n, oy, ox);
+        const int id = aug_pixel<C, LABEL, COLOUR, ELASTIC>(img, gt, paste ? m.a : a, paste ? m.k : k, g, paste ? m.p : n, oy, ox, d, mu, sd, v);
 #pragma unroll
         for (int c = 0; c < C; ++c) out_img[(size_t)p * C + c] = v[c];
         if constexpr (LABEL) out_gt[p] = t[id];
@@ -398,7 +511,7 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_sum_kernel(const uint8_t*
     }
 }
 
-// `el`: nothing, or the aug_elastic_args of an elastic launch (here and in aug_launch_colour)
+// `el`: the trailing arguments of the apply kernel - nothing, or any of aug_colour_args, aug_elastic_args, aug_mix_args, in that order
 template <int C, typename... EL>
 void aug_launch(bool label, dim3 grid, hipStream_t st, const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img,
                 int64_t* out_gt, const float* mean, const float* stdev, const int64_t* lut, const aug_geom& g, uint32_t total,
@@ -411,25 +524,40 @@ void aug_launch(bool label, dim3 grid, hipStream_t st, const uint8_t* img, const
                            total, groups, el...);
 }
 
+// the two launches in front of a colour launch whose table uses the image mean
+template <int C, typename... EL>
+void aug_launch_sums(hipStream_t st, const uint8_t* img, const int32_t* mats, const aug_geom& g, int64_t* sums, int N, EL... el) {
+    const uint32_t hw = (uint32_t)g.OH * (uint32_t)g.OW;
+    const int cap = AUG_SUM_MAX_BLOCKS / N > 0 ? AUG_SUM_MAX_BLOCKS / N : 1;
+    int bx = cdiv((long)hw, (long)AUG_THREADS * AUG_SUM_ROUNDS);
+    if (bx > cap) bx = cap;
+    hipLaunchKernelGGL(augment_zero_kernel, dim3(ew_blocks((size_t)N * 3, 64)), dim3(AUG_THREADS), 0, st, sums, N * 3);
+    hipLaunchKernelGGL((augment_sum_kernel<C, EL...>), dim3(bx, N), dim3(AUG_THREADS), 0, st, img, mats, g, sums, el...);
+}
+
 template <int C, typename... EL>
 void aug_launch_colour(bool label, dim3 grid, hipStream_t st, const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img,
                        int64_t* out_gt, const float* mean, const float* stdev, const int64_t* lut, const aug_geom& g, uint32_t total,
                        uint32_t groups, const float* colour, int64_t* sums, int N, EL... el) {
+    if (sums) aug_launch_sums<C>(st, img, mats, g, sums, N, el...);
+    aug_launch<C>(label, grid, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g, total, groups, aug_colour_args{colour, sums}, el...);
+}
+
+// a mix launch: the sum pass is that of the launch without the table (every sample's mean is that of its own unmixed pixels), the
+// apply pass takes the table behind whatever of the colour table and the lattice there is.  colour / el: null = none
+template <int C>
+void aug_launch_mix(bool label, dim3 grid, hipStream_t st, const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img,
+                    int64_t* out_gt, const float* mean, const float* stdev, const int64_t* lut, const aug_geom& g, uint32_t total, uint32_t groups,
+                    const float* colour, int64_t* sums, int N, const aug_elastic_args* el, const aug_mix_args& mx) {
     if (sums) {
-        const uint32_t hw = (uint32_t)g.OH * (uint32_t)g.OW;
-        const int cap = AUG_SUM_MAX_BLOCKS / N > 0 ? AUG_SUM_MAX_BLOCKS / N : 1;
-        int bx = cdiv((long)hw, (long)AUG_THREADS * AUG_SUM_ROUNDS);
-        if (bx > cap) bx = cap;
-        hipLaunchKernelGGL(augment_zero_kernel, dim3(ew_blocks((size_t)N * 3, 64)), dim3(AUG_THREADS), 0, st, sums, N * 3);
-        hipLaunchKernelGGL((augment_sum_kernel<C, EL...>), dim3(bx, N), dim3(AUG_THREADS), 0, st, img, mats, g, sums, el...);
+        if (el) aug_launch_sums<C>(st, img, mats, g, sums, N, *el);
+        else aug_launch_sums<C>(st, img, mats, g, sums, N);
     }
     const aug_colour_args ca = {colour, sums};
-    if (label)
-        hipLaunchKernelGGL((augment_u8_kernel<C, true, aug_colour_args, EL...>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean,
-                           stdev, lut, g, total, groups, ca, el...);
-    else
-        hipLaunchKernelGGL((augment_u8_kernel<C, false, aug_colour_args, EL...>), grid, dim3(AUG_THREADS), 0, st, img, gt, mats, out_img, out_gt, mean,
-                           stdev, lut, g, total, groups, ca, el...);
+    if (colour && el) aug_launch<C>(label, grid, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g, total, groups, ca, *el, mx);
+    else if (colour) aug_launch<C>(label, grid, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g, total, groups, ca, mx);
+    else if (el) aug_launch<C>(label, grid, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g, total, groups, *el, mx);
+    else aug_launch<C>(label, grid, st, img, gt, mats, out_img, out_gt, mean, stdev, lut, g, total, groups, mx);
 }
 
 // the argument rules both entries share; 0 = go on
@@ -535,6 +663,34 @@ extern "C" int sscg_augment_elastic_u8(const uint8_t* img, const uint8_t* gt, co
             default: aug_launch<4>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, tot, groups, el); break;
         }
     }
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
+}
+
+extern "C" int sscg_augment_mix_u8(const uint8_t* img, const uint8_t* gt, const int32_t* mats, float* out_img, int64_t* out_gt, int N, int H,
+                                   int W, int C, int OH, int OW, const float* mean, const float* stdev, const int64_t* lut256, int image_fill,
+                                   int label_fill, const float* colour, int need_mean, void* ws, const int32_t* nodes, int grid, int GH, int GW,
+                                   const int32_t* mix, int classes, void* stream) {
+    const int bad = aug_check(img, gt, mats, out_img, out_gt, N, H, W, C, OH, OW, mean, stdev, lut256, image_fill, label_fill);
+    if (bad == SSCG_ERR_BAD_ARG) return bad;
+    if (!mix || (classes != 0 && !gt)) return SSCG_ERR_BAD_ARG;
+    if (nodes && (grid < 4 || GH != (OH - 1) / grid + 4 || GW != (OW - 1) / grid + 4)) return SSCG_ERR_BAD_ARG;
+    if (!colour) need_mean = 0;
+    if (need_mean && (!ws || ((size_t)ws & 7) != 0)) return SSCG_ERR_BAD_ARG;
+    if (bad) return bad;
+    if (C == 2 || C == 4 || (nodes && grid > (1 << 22)) || (need_mean && N > 65535)) return SSCG_ERR_UNSUPPORTED;
+    const int64_t total = (int64_t)N * OH * OW;
+    uint32_t groups;
+    const dim3 blocks(aug_plan(out_img, out_gt, total, &groups));
+    const aug_geom g = {H, W, OH, OW, image_fill, label_fill};
+    const hipStream_t st = (hipStream_t)stream;
+    const bool label = gt != nullptr;
+    const aug_elastic_args ela = {nodes, grid, GH, GW};
+    const aug_elastic_args* el = nodes ? &ela : nullptr;
+    const aug_mix_args mx = {mix, N, classes != 0};
+    int64_t* sums = need_mean ? reinterpret_cast<int64_t*>(ws) : nullptr;
+    if (C == 1) aug_launch_mix<1>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, (uint32_t)total, groups, colour, sums, N, el, mx);
+    else aug_launch_mix<3>(label, blocks, st, img, gt, mats, out_img, out_gt, mean, stdev, lut256, g, (uint32_t)total, groups, colour, sums, N, el, mx);
     SSCG_LAUNCH_CHECK();
     return SSCG_OK;
 }

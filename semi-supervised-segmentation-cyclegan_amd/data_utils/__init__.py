@@ -18,7 +18,9 @@ instead of the two passes above; in host mode the same maps go through PIL as th
 (brightness, contrast, saturation, hue, gray) compose into one small table per sample that the same launch applies
 (`sscg_augment_colour_u8`; a contrast item adds a sum pass for the image mean).  An `elastic=` item adds a non-rigid warp to the same
 launch (`sscg_augment_elastic_u8`): a coarse lattice of control nodes per sample, drawn on the host, interpolated per output pixel on
-the device; in host mode the same integer definition runs in numpy instead of PIL.  Without an augmentation nothing changes: the
+the device; in host mode the same integer definition runs in numpy instead of PIL.  `cutmix=` / `classmix=` items combine two
+samples of a batch, labels with pixels, inside that launch too (`sscg_augment_mix_u8`) - for the 'label' set only and in
+`device_finish` mode only: there is no per-sample host path for a batch operation.  Without an augmentation nothing changes: the
 same two launches as before."""
 import numpy as np
 import torch
@@ -187,7 +189,10 @@ class DeviceLoader:
     per-sample table is drawn from a second generator, `RandomState(seed + augmentations.COLOUR_SEED_OFFSET)`, and travels with the
     maps; the geometric draws of a seed do not depend on it.  An elastic op likewise: the control lattices of a batch are drawn from a
     third generator, `RandomState(seed + augmentations.ELASTIC_SEED_OFFSET)`, uploaded with the maps and interpolated inside the same
-    launch (`sscg_augment_elastic_u8`); without one there is no further upload and no other launch than before."""
+    launch (`sscg_augment_elastic_u8`); without one there is no further upload and no other launch than before.  Mix ops likewise:
+    the table of a batch (partner, box, class mask per sample) is drawn from a fourth generator, `RandomState(seed +
+    augmentations.MIX_SEED_OFFSET)`, uploaded with the maps and applied per output pixel inside the same launch
+    (`sscg_augment_mix_u8`); without one nothing is drawn, uploaded or launched that was not before."""
 
     def __init__(self, loader, transformation, device, augmentation=None, seed=0):
         if not transformation.get('device_finish'):
@@ -196,6 +201,7 @@ class DeviceLoader:
         self.augmentation, self.rng = augmentation, np.random.RandomState(seed)
         self.colour_rng = np.random.RandomState(seed + augmentations.COLOUR_SEED_OFFSET)
         self.elastic_rng = np.random.RandomState(seed + augmentations.ELASTIC_SEED_OFFSET)
+        self.mix_rng = np.random.RandomState(seed + augmentations.MIX_SEED_OFFSET)
         self.lut = transformation['lut'].to(device)
         self.mean = torch.tensor(transformation['mean'], dtype=torch.float32, device=device)
         self.std = torch.tensor(transformation['std'], dtype=torch.float32, device=device)
@@ -233,6 +239,10 @@ class DeviceLoader:
         if aug.elastic_ops:
             nodes, grid = aug.fields(self.elastic_rng, b, w, h, drawn)
             extra["elastic"] = (self._up(torch.from_numpy(nodes)), grid)
+        if aug.mix_ops:
+            oh, ow = aug.out_size or (h, w)
+            table, classes = aug.mixes(self.mix_rng, b, ow, oh)
+            extra["mix"] = (self._up(torch.from_numpy(table)), classes and gt is not None)
         img, gt = F.augment_batch(self._up(batch[0]), gt, mats, aug.out_size or (h, w), self.mean, self.std, self.lut,
                                   image_fill=aug.image_fill, label_fill=aug.label_fill, **extra)
         return (img, batch[1]) if gt is None else (img, gt, batch[2])
@@ -247,17 +257,25 @@ def build_loaders(args, roots=None, device=None, sets=('label', 'unlabel', 'val'
     drop_last on all three, as written there), finished on `device` when one is given.  `args.augment` (absent or "" = none; the
     comma list of augmentations.from_spec) augments the 'label' and 'unlabel' sets, never 'val' or 'test': inside the device finish
     when there is a device, through the datasets' `augmentation=` (PIL, before Resize / CenterCrop) otherwise; rank r draws from
-    `RandomState(AUGMENT_SEED + 1000 * r + <index of the set>)`."""
+    `RandomState(AUGMENT_SEED + 1000 * r + <index of the set>)`.  The mix items (`cutmix=`, `classmix=`) go to the 'label' set
+    only - the 'unlabel' set is built from the spec without them, its draws unchanged - and need the device finish: in host mode a spec
+    with one raises ValueError."""
     roots = roots or {'voc2012': './data/VOC2012', 'cityscapes': './data/Cityscape', 'acdc': './data/ACDC'}
     from torch.utils.data import DataLoader
     tr = get_transformation((args.crop_height, args.crop_width), resize=True, dataset=args.dataset, device_finish=device is not None)
     cls = {'voc2012': VOCDataset, 'cityscapes': CityscapesDataset, 'acdc': ACDCDataset}[args.dataset]
     out = []
     size = (args.crop_height, args.crop_width)
+    spec = getattr(args, 'augment', '') or ''
+    is_mix = lambda item: item.strip().partition('=')[0] in ('cutmix', 'classmix')
+    unmixed = ','.join(item for item in spec.split(',') if not is_mix(item))
+    if device is None and any(is_mix(item) for item in spec.split(',')):
+        raise ValueError("--augment: cutmix / classmix combine the samples of a batch inside the device finish; there is no host path "
+                         "for them (given %r without a device)" % spec)
     for name in sets:
         ratio = 0.5 if (args.dataset != 'voc2012' or name in ('val', 'test')) else 0.1
         seed = AUGMENT_SEED + 1000 * rank + len(out)
-        aug = augmentations.from_spec(getattr(args, 'augment', ''), size, label_fill=LABEL_FILL[args.dataset], seed=seed,
+        aug = augmentations.from_spec(spec if name == 'label' else unmixed, size, label_fill=LABEL_FILL[args.dataset], seed=seed,
                                       out_size=size if device is not None else None) if name in ('label', 'unlabel') else None
         ds = cls(root_path=roots[args.dataset], name=name, ratio=ratio, transformation=tr, augmentation=aug if device is None else None)
         gen = torch.Generator().manual_seed(20260928 + 1000 * rank + len(out)) if rank else None   # ranks draw different batches

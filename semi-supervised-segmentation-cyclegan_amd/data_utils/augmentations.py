@@ -49,7 +49,18 @@ coordinate - still one resampling, in the same launch.  The spline is a convex c
 than alpha.  The definition is integers throughout, so with an elastic op the host path (`Compose.__call__`) does not go through PIL
 either: it evaluates the same integer definition in numpy (`elastic_displacement`, `warp_u8`), affine and elastic part together,
 and returns the integer pixel value rounded to uint8 - the device's pixels and labels.  Elastic draws come from a third generator
-(`seed + ELASTIC_SEED_OFFSET`): the maps and colour tables of a seed are the same with and without the item."""
+(`seed + ELASTIC_SEED_OFFSET`): the maps and colour tables of a seed are the same with and without the item.
+
+Mixed-sample augmentation (`RandomCutMix`, `RandomClassMix`) combines two samples of a BATCH, labels with pixels, and touches no
+pixel either: a mix op only answers
+
+    mix(rng, ow, oh) -> (fires, box or None, mask or None)
+
+and `Compose.mixes(rng, n, ow, oh)` draws the int32 [n, 8] table (partner, x0, y0, x1, y1, mask_lo, mask_hi, 0) that
+sscg_augment_mix_u8 (include/sscg.h) reads: inside the one launch every output pixel is decided to be its own sample's or, pasted,
+its partner's - in the box, or where the partner shows a class whose bit is set in the mask.  `mix_batch` states the same rule in
+numpy on a finished batch.  There is no per-sample host path: `Compose.__call__` raises with a mix op.  Mix draws come from a fourth
+generator (`seed + MIX_SEED_OFFSET`): the maps, colour tables and lattices of a seed are the same with and without a mix item."""
 import math
 
 import numpy as np
@@ -61,6 +72,7 @@ YIQ = np.array([[.299, .587, .114], [.596, -.274, -.322], [.211, -.523, .312]], 
 YIQ_INV = np.linalg.inv(YIQ)
 COLOUR_SEED_OFFSET = 500
 ELASTIC_SEED_OFFSET = 900
+MIX_SEED_OFFSET = 1300
 ELASTIC_DEFAULT_GRID = 32          # output pixels between control nodes; an untuned default
 ELASTIC_NODE_LIMIT = 2 ** 26       # |node| in Q16 source pixels (include/sscg.h)
 BSPLINE_DENOM = 6 * 2 ** 24        # the common denominator of the B-spline numerators at t in 0..255
@@ -218,6 +230,11 @@ class RandomElastic:
         return rng.uniform(-self.alpha, self.alpha, (gh, gw, 2))
 
 
+def _wrap_i32(a):
+    """int64 values in [0, 2^32) or [-2^31, 2^31) as the int32 with the same low 32 bits."""
+    return (np.asarray(a, dtype=np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
 def lattice_shape(grid, oh, ow):
     """(GH, GW) of the control lattice over an (oh, ow) output: the cells the pixels lie in plus the three further nodes of a cubic."""
     return (oh - 1) // grid + 4, (ow - 1) // grid + 4
@@ -271,6 +288,79 @@ def warp_u8(img, mask, q, d, out, image_fill=0, label_fill=0):
     ix, iy = (sx + 0x8000) >> 16, (sy + 0x8000) >> 16
     inside = (ix >= 0) & (ix < w) & (iy >= 0) & (iy < h)
     return px, np.where(inside, mask[np.clip(iy, 0, h - 1), np.clip(ix, 0, w - 1)], label_fill).astype(np.uint8)
+
+
+class RandomCutMix:
+    """With probability p a rectangle of the partner is pasted (CutMix, Yun et al. 2019): area share a uniform in [lo, hi] of the
+    output, aspect rho = exp(U[-ln 2, ln 2]), bw = clamp(round(sqrt(a.ow.oh.rho)), 1, ow), bh = clamp(round(a.ow.oh / bw), 1, oh)
+    (round = half up; a box too tall for its aspect is cut to the output's height), the corner uniform over the positions that
+    keep the box inside.  lo = 0.25, hi = 0.5 are untuned defaults.  Five draws per call, whether or not it fires."""
+    classes = False
+
+    def __init__(self, p, lo=0.25, hi=0.5):
+        self.p, self.lo, self.hi = float(p), float(lo), float(hi)
+        if not 0.0 <= self.p <= 1.0 or not 0.0 < self.lo <= self.hi <= 1.0:        # (false for a NaN)
+            raise ValueError("RandomCutMix needs 0 <= p <= 1 and 0 < lo <= hi <= 1, given %r, %r, %r" % (p, lo, hi))
+
+    def mix(self, rng, ow, oh):
+        u = rng.random_sample(5)
+        area = (self.lo + (self.hi - self.lo) * u[1]) * ow * oh
+        rho = math.exp((2.0 * u[2] - 1.0) * math.log(2.0))
+        bw = min(max(int(math.floor(math.sqrt(area * rho) + 0.5)), 1), ow)
+        bh = min(max(int(math.floor(area / bw + 0.5)), 1), oh)
+        x0, y0 = min(int(u[3] * (ow - bw + 1)), ow - bw), min(int(u[4] * (oh - bh + 1)), oh - bh)
+        return bool(u[0] < self.p), (x0, y0, x0 + bw, y0 + bh), None
+
+
+class RandomClassMix:
+    """With probability p every pixel of a random half of the partner's classes is pasted (ClassMix, Olsson et al. 2021; copy-paste
+    by class): 64 independent fair bits, one per class id, with the bits of `skip` (ids in [0, 64) that are never pasted) cleared.
+    Which classes the partner shows is not consulted - that would be a host sync - so a mask may paste nothing.  65 draws per call,
+    whether or not it fires."""
+    classes = True
+
+    def __init__(self, p, skip=()):
+        self.p = float(p)
+        if not 0.0 <= self.p <= 1.0:
+            raise ValueError("RandomClassMix needs 0 <= p <= 1, given %r" % (p,))
+        self.skip = tuple(skip)
+        if any(int(c) != c or not 0 <= c < 64 for c in self.skip):
+            raise ValueError("RandomClassMix skips class ids in [0, 64), given %r" % (self.skip,))
+        self.keep = (1 << 64) - 1 - sum(1 << int(c) for c in set(self.skip))
+
+    def mix(self, rng, ow, oh):
+        u = rng.random_sample(65)
+        bits = sum(1 << c for c in range(64) if u[1 + c] < 0.5)
+        return bool(u[0] < self.p), None, bits & self.keep
+
+
+def mix_batch(img, gt, table, classes):
+    """The rule of sscg_augment_mix_u8 on a FINISHED batch, in numpy: img [n, c, oh, ow], gt integer class maps [n, 1, oh, ow] or
+    [n, oh, ow] (or None), table int [n, 8] (`Compose.mixes`), classes a flag -> (img, gt) with out[i] = where(pasted, in[p], in[i]),
+    p = table[i][0] (outside [0, n) or i itself: not mixed).  Pasted: inside the half-open box x0 <= x < x1, y0 <= y < y1, or - with
+    `classes`, which needs gt - where sample p's class is in [0, 64) and its bit of (mask_hi << 32) | mask_lo is set.  Every partner
+    pixel is the partner's pixel before mixing."""
+    img, table = np.asarray(img), np.asarray(table).astype(np.int64)
+    lab = np.asarray(gt) if gt is not None else None
+    n, _, oh, ow = img.shape
+    if table.shape != (n, 8) or (classes and lab is None) or (lab is not None and lab.shape not in ((n, 1, oh, ow), (n, oh, ow))):
+        raise ValueError("mix_batch: a table [n, 8], and labels [n, 1, oh, ow] or [n, oh, ow] with `classes`, expected")
+    ys, xs = np.meshgrid(np.arange(oh), np.arange(ow), indexing="ij")
+    out_img, out_lab = img.copy(), (lab.copy() if lab is not None else None)
+    for i in range(n):
+        p, x0, y0, x1, y1, lo, hi = (int(v) for v in table[i, :7])
+        if not 0 <= p < n or p == i:
+            continue
+        pasted = (xs >= x0) & (xs < x1) & (ys >= y0) & (ys < y1)
+        if classes:
+            cls = lab[p].reshape(oh, ow).astype(np.int64)
+            mask = ((hi & 0xFFFFFFFF) << 32) | (lo & 0xFFFFFFFF)
+            bit = np.array([mask >> c & 1 for c in range(64)], dtype=bool)
+            pasted |= (cls >= 0) & (cls < 64) & bit[np.clip(cls, 0, 63)]
+        out_img[i] = np.where(pasted[None], img[p], img[i])
+        if lab is not None:
+            out_lab[i] = np.where(pasted.reshape(lab[i].shape[-2:]), lab[p], lab[i])
+    return out_img, out_lab
 
 
 def _luma(channels):
@@ -377,7 +467,8 @@ class Compose:
     source; the label fill is a raw id (the label transforms behind it see it like any pixel).  `seed` seeds the generators of the
     host path (`__call__`); the device path is handed its generators by the caller.  Geometric ops (those with `.matrix`) and
     colour ops (those with `.colour`) may be mixed in `ops`: each kind keeps its order, the colour runs after the geometry.  At most
-    one op may be an elastic one (with `.field`): it deforms the final output view, wherever it stands."""
+    one op may be an elastic one (with `.field`): it deforms the final output view, wherever it stands.  Mix ops (with `.mix`; one
+    RandomCutMix and one RandomClassMix at the most) act on a batch behind all of that: the device finish only (`mixes`)."""
 
     def __init__(self, ops, out_size=None, image_fill=0, label_fill=0, seed=None):
         self.ops = list(ops)
@@ -387,6 +478,9 @@ class Compose:
         if len(self.elastic_ops) > 1:
             raise ValueError("at most one elastic op in a pipeline, given %d" % len(self.elastic_ops))
         self.elastic_rng = np.random.RandomState(seed + ELASTIC_SEED_OFFSET if seed is not None else None)
+        self.mix_ops = [op for op in self.ops if hasattr(op, "mix")]
+        if len(self.mix_ops) > len({bool(op.classes) for op in self.mix_ops}):
+            raise ValueError("at most one box op and one class op among the mix ops of a pipeline, given %d ops" % len(self.mix_ops))
         self.out_size = _pair(out_size) if out_size is not None else None
         self.image_fill, self.label_fill = int(image_fill), int(label_fill)
         self.rng = np.random.RandomState(seed)
@@ -448,6 +542,29 @@ class Compose:
         assert len(mats) == n
         return np.stack([self.lattice(rng, mats[i], ow, oh) for i in range(n)]), self.elastic_ops[0].grid
 
+    def mixes(self, rng, n, ow, oh):
+        """(int32 [n, 8], classes): one drawn row (partner, x0, y0, x1, y1, mask_lo, mask_hi, 0) per sample of a batch of n whose
+        output view is (ow, oh), as sscg_augment_mix_u8 reads them; classes is true iff an op is a class op.  Per sample, in batch
+        order: one draw for the partner - uniform over the other n - 1 samples - then every op's own draws in the order written.
+        Each op fires with its own probability, independently; the number of draws does not depend on what fires, so a seed's
+        sequence does not depend on outcomes.  A sample with no firing op - and every sample of a batch of one - keeps its own index
+        as the partner: not mixed.  A box op that did not fire leaves the empty box, a class op that did not the zero mask."""
+        table = np.zeros((n, 8), dtype=np.int64)
+        for i in range(n):
+            j = min(int(rng.random_sample() * (n - 1)), max(n - 2, 0))
+            partner, fired = j + (j >= i), False
+            for op in self.mix_ops:
+                fires, box, mask = op.mix(rng, ow, oh)
+                if not fires or n == 1:
+                    continue
+                fired = True
+                if box is not None:
+                    table[i, 1:5] = box
+                if mask is not None:
+                    table[i, 5:7] = mask & 0xFFFFFFFF, mask >> 32
+            table[i, 0] = partner if fired else i
+        return _wrap_i32(table), any(op.classes for op in self.mix_ops)
+
     def _integer_call(self, img, mask, M, out):
         """The host path with an elastic op: the integer definition in numpy, affine and elastic part in one resampling."""
         bands = len(img.getbands())
@@ -468,6 +585,9 @@ class Compose:
         return warped, warped_mask
 
     def __call__(self, img, mask=None):
+        if self.mix_ops:
+            raise ValueError("mix ops (cutmix, classmix) combine the samples of a batch: they run in the device finish only "
+                             "(DeviceLoader(..., augmentation=) -> functional.augment_batch(mix=)), not sample by sample on the host")
         w, h = img.size
         assert mask is None or mask.size == img.size
         M, out = self.matrix(self.rng, w, h)
@@ -499,7 +619,11 @@ def from_spec(spec, size, image_fill=0, label_fill=0, out_size=None, seed=None):
     `contrast=<x>`, `saturation=<x>` (factor in max(0, 1-x)..1+x), `hue=<x>` (0..0.5 of a turn) and `gray=<p>` (a probability) -
     geometry and colour each applied in the order written, colour behind geometry - and at most one `elastic=<alpha>[:<grid>]`
     (RandomElastic: node offsets up to alpha output pixels on a lattice of `grid` output pixels, default 32, an untuned default;
-    grid >= 4 and 0 <= alpha <= 0.4 * grid), which deforms the final output view wherever it stands in the list."""
+    grid >= 4 and 0 <= alpha <= 0.4 * grid), which deforms the final output view wherever it stands in the list.  Two items mix the
+    samples of a batch (device finish only), at most one of each: `cutmix=<p>[:<lo>:<hi>]` (RandomCutMix: with probability p a box of
+    lo..hi of the area, default 0.25:0.5, untuned) and `classmix=<p>[:<id>[:<id>...]]` (RandomClassMix: with probability p a random half
+    of the classes; the ids, each in [0, 64), are never pasted - `classmix=0.5:0` keeps VOC's background, `classmix=0.5:19` Cityscapes'
+    void where it is)."""
     ops = []
     for item in (s.strip() for s in (spec or "").split(",")):
         if not item:
@@ -531,7 +655,17 @@ def from_spec(spec, size, image_fill=0, label_fill=0, out_size=None, seed=None):
                 raise ValueError("--augment elastic=<alpha>[:<grid>] needs grid >= 4 and 0 <= alpha <= 0.4 * grid (beyond it the "
                                  "deformation can fold), given %r" % item)
             ops.append(RandomElastic(alpha, grid))
+        elif key == "cutmix" and val and val.count(":") in (0, 2):
+            if any(isinstance(op, RandomCutMix) for op in ops):
+                raise ValueError("--augment: one cutmix item at the most, given a second: %r" % item)
+            ops.append(RandomCutMix(*(float(v) for v in val.split(":"))))
+        elif key == "classmix" and val:
+            if any(isinstance(op, RandomClassMix) for op in ops):
+                raise ValueError("--augment: one classmix item at the most, given a second: %r" % item)
+            p, *ids = val.split(":")
+            ops.append(RandomClassMix(float(p), tuple(int(v) for v in ids)))
         else:
             raise ValueError("--augment: unknown item %r (hflip, rotate=<deg>, scale=<lo>:<hi>, sizedcrop, elastic=<alpha>[:<grid>], "
-                             "brightness=<x>, contrast=<x>, saturation=<x>, hue=<x>, gray=<p>)" % item)
+                             "brightness=<x>, contrast=<x>, saturation=<x>, hue=<x>, gray=<p>, cutmix=<p>[:<lo>:<hi>], "
+                             "classmix=<p>[:<id>...])" % item)
     return Compose(ops, out_size=out_size, image_fill=image_fill, label_fill=label_fill, seed=seed) if ops else None

@@ -1948,7 +1948,8 @@ def label_lut(gt_u8, lut):
     return dst.unsqueeze(1)
 
 
-def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, label_fill=0, colour=None, need_mean=False, elastic=None):
+def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, label_fill=0, colour=None, need_mean=False, elastic=None,
+                  mix=None):
     """Batched affine augmentation fused into the batch finish (sscg_augment_u8, one launch): uint8 [N,H,W,C] pixels, uint8 [N,H,W]
     label ids (or None) and one int32 Q16 map per sample (`mats` [N,6], data_utils.augmentations.to_q16) -> what image_u8_to_f32 and
     label_lut return for the warped batch: fp32 logical [N,C,OH,OW] channels-last, int64 [N,1,OH,OW] (or None).  Outside the source:
@@ -1958,7 +1959,11 @@ def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, l
     costs a sum pass in front of the launch.  None = the plain entry, as before.
     `elastic` = (nodes, grid): int32 [N,GH,GW,2] control nodes on the device (data_utils.augmentations.Compose.fields) and their
     spacing in output pixels, GH = (OH-1)//grid + 4, GW likewise - a cubic B-spline displacement added to every pixel's source
-    coordinate inside the same launch (sscg_augment_elastic_u8), with or without `colour`.  None = the affine entries, as before."""
+    coordinate inside the same launch (sscg_augment_elastic_u8), with or without `colour`.  None = the affine entries, as before.
+    `mix` = (table, classes): int32 [N,8] on the device (data_utils.augmentations.Compose.mixes: partner, box, class mask per sample)
+    and whether the class rule applies (it needs labels) - mixed-sample augmentation, CutMix and ClassMix, decided per output pixel
+    inside the same launch (sscg_augment_mix_u8; C of 1 or 3), with whatever of `colour` and `elastic` is given.  None = the entries
+    above, as before."""
     if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or img_u8.dim() != 4:
         raise _lib.SscgError("augment_batch: uint8 [N,H,W,C] tensor on the MI355X expected")
     n, h, w, c = img_u8.shape
@@ -1977,6 +1982,10 @@ def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, l
         gh, gw = (oh - 1) // grid + 4, (ow - 1) // grid + 4
         if not torch.is_tensor(nodes) or not nodes.is_cuda or nodes.dtype != torch.int32 or tuple(nodes.shape) != (n, gh, gw, 2):
             raise _lib.SscgError("augment_batch: int32 [N,%d,%d,2] elastic nodes on the MI355X expected" % (gh, gw))
+    if mix is not None:
+        mix_table, classes = mix[0], int(bool(mix[1]))
+        if not torch.is_tensor(mix_table) or not mix_table.is_cuda or mix_table.dtype != torch.int32 or tuple(mix_table.shape) != (n, 8):
+            raise _lib.SscgError("augment_batch: int32 [N,8] mix table on the MI355X expected")
     src, m = img_u8.contiguous(), mats.contiguous()
     dst = torch.empty((n, oh, ow, c), dtype=torch.float32, device=src.device)
     gsrc = gt_u8.contiguous() if gt_u8 is not None else None
@@ -1984,7 +1993,14 @@ def augment_batch(img_u8, gt_u8, mats, out_size, mean, std, lut, image_fill=0, l
     args = (src.data_ptr(), gsrc.data_ptr() if gsrc is not None else None, m.data_ptr(), dst.data_ptr(),
             gdst.data_ptr() if gdst is not None else None, n, h, w, c, oh, ow, mean.data_ptr(), std.data_ptr(),
             lut.data_ptr() if gsrc is not None else None, int(image_fill), int(label_fill))
-    if elastic is not None:
+    if mix is not None:
+        table = colour.contiguous() if colour is not None else None
+        ws = _WS.get(lib.sscg_augment_colour_workspace(n), src.device) if colour is not None and need_mean else None
+        lattice, geom = (nodes.contiguous(), (grid, gh, gw)) if elastic is not None else (None, (0, 0, 0))
+        rows = mix_table.contiguous()
+        check(lib.sscg_augment_mix_u8(*args, _ptr(table), int(bool(need_mean)), _ptr(ws), _ptr(lattice), *geom, rows.data_ptr(), classes,
+                                      _stream()), "sscg_augment_mix_u8")
+    elif elastic is not None:
         table = colour.contiguous() if colour is not None else None
         ws = _WS.get(lib.sscg_augment_colour_workspace(n), src.device) if colour is not None and need_mean else None
         lattice = nodes.contiguous()
