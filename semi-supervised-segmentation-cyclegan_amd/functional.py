@@ -2225,9 +2225,11 @@ def _transpose_batch(jobs):
 
 def _note_batch(tab):
     """racecheck.py sees pointers in argument lists; the batch's buffers sit in a device table - announce them."""
-    note = getattr(lib, "note_batch", None)
-    if note is not None:
-        note(tab[0].data_ptr(), [(row[0], row[1]) for row in tab[1]])
+    if _NOTE_BATCH is not None:
+        _NOTE_BATCH(tab[0].data_ptr(), [(row[0], row[1]) for row in tab[1]])
+
+
+_NOTE_BATCH = getattr(lib, "note_batch", None)      # only racecheck.py's handle has it
 
 
 def _wtag(w):
@@ -4022,17 +4024,47 @@ def mse_loss(a, b):
     return MseFn.apply(a, b)
 
 
+WSUM_MAX_TERMS = 16        # sscg_weighted_sum's cap (include/sscg.h): the terms travel in the kernel's argument block
+
+
+def weighted_sum_launches(n):
+    """Forward launches of `weighted_sum` over n terms: one up to the entry's cap; beyond it every further launch takes the running
+    partial sum (weight 1) and the next WSUM_MAX_TERMS - 1 terms.  Any n >= 1 is served: nothing on the host path counts terms."""
+    if n < 1:
+        raise ValueError("weighted_sum needs at least one term (given %d)" % n)
+    return 1 if n <= WSUM_MAX_TERMS else 1 + -(-(n - WSUM_MAX_TERMS) // (WSUM_MAX_TERMS - 1))
+
+
+def _weighted_sum_launch(ptrs, weights, out):
+    """One sscg_weighted_sum launch over the device scalars at `ptrs`.  The entry reads them through a host table, which
+    racecheck.py cannot follow from the argument list: they are announced like the buffers of a batched transpose."""
+    n = len(ptrs)
+    tab = (C.c_void_p * n)(*ptrs)
+    ws = (C.c_float * n)(*weights)
+    if _NOTE_BATCH is not None:
+        _NOTE_BATCH(C.addressof(tab), [(p, None) for p in ptrs])
+    check(lib.sscg_weighted_sum(tab, ws, n, out.data_ptr(), _stream()), "sscg_weighted_sum")
+
+
 class WeightedSumFn(torch.autograd.Function):
-    """sum_i w_i * term_i over 0-dim device scalars (gen_loss, discriminator_loss)."""
+    """sum_i w_i * term_i over 0-dim device scalars (gen_loss, discriminator_loss), any number of them: up to WSUM_MAX_TERMS in one
+    launch; more are folded in index order (weighted_sum_launches), so the value is the left-to-right fp32 sum either way."""
 
     @staticmethod
     def forward(ctx, weights, *terms):
         n = len(terms)
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in terms])
-        ws = (C.c_float * n)(*[float(w) for w in weights])
+        weighted_sum_launches(n)
+        ptrs = [t.data_ptr() for t in terms]
+        ws = [float(w) for w in weights]
+        if len(ws) != n:
+            raise ValueError("weighted_sum: %d terms but %d weights" % (n, len(ws)))
         out = _scalar(terms[0].device)
-        check(lib.sscg_weighted_sum(ptrs, ws, n, out.data_ptr(), _stream()), "sscg_weighted_sum")
-        ctx.weights = [float(w) for w in weights]
+        _weighted_sum_launch(ptrs[:WSUM_MAX_TERMS], ws[:WSUM_MAX_TERMS], out)
+        for i in range(WSUM_MAX_TERMS, n, WSUM_MAX_TERMS - 1):
+            part, out = out, _scalar(terms[0].device)
+            j = i + WSUM_MAX_TERMS - 1
+            _weighted_sum_launch([part.data_ptr()] + ptrs[i:j], [1.0] + ws[i:j], out)
+        ctx.weights = ws
         return out
 
     @staticmethod
@@ -4040,9 +4072,7 @@ class WeightedSumFn(torch.autograd.Function):
         grads = []
         for w in ctx.weights:
             gi = _scalar(g.device)
-            ptrs = (C.c_void_p * 1)(g.data_ptr())
-            ws = (C.c_float * 1)(w)
-            check(lib.sscg_weighted_sum(ptrs, ws, 1, gi.data_ptr(), _stream()), "sscg_weighted_sum")
+            _weighted_sum_launch([g.data_ptr()], [w], gi)
             grads.append(gi)
         return (None, *grads)
 

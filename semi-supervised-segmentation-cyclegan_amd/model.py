@@ -115,6 +115,33 @@ def write_panels(panels, epoch, writer=None, panel_dir=None):
             utils.save_panel_png(arr, os.path.join(panel_dir, "epoch%03d_%d.png" % (epoch, i + 1)))
 
 
+GEN_LOSS_BASE_TERMS = 6     # lab_loss_CE, lab_loss_MSE, img_gen_loss, gt_gen_loss, img_cycle_loss, gt_cycle_loss (model.py:464-468)
+
+
+def gen_loss_terms(variants=(), dice=False, boundary=False, lovasz=False, ssim=False, unl=0):
+    """How many terms semisuper_cycleGAN.step hands to F.weighted_sum as gen_loss: the reference's six, one per enabled region loss
+    (Dice, boundary, Lovasz) on each of the two ground-truth heads, `unl` unlabelled-head losses (0..3), an SSIM term beside every
+    image L1 (lab_loss_MSE; img_cycle_l1 under l1_cycle), and the variants' own terms.  Pure: the step checks its assembled list
+    against it, tests/test_step_options_host.py walks every flag combination main.py accepts."""
+    variants = set(variants)
+    n = GEN_LOSS_BASE_TERMS + 2 * (bool(dice) + bool(boundary) + bool(lovasz)) + int(unl) + bool(ssim)
+    if "l1_cycle" in variants:
+        n += 1 + bool(ssim)
+    if "perceptual" in variants:
+        n += 2
+    if "lab_gt_dis" in variants:
+        n += 1
+    return n
+
+
+def gen_loss_terms_of(args):
+    """gen_loss_terms for a parsed command line (main.get_args) or its twin: a loss flag counts when its weight is > 0."""
+    on = lambda key: float(getattr(args, key, 0.0) or 0.0) > 0.0
+    return gen_loss_terms((v for v in str(getattr(args, "variants", "") or "").split(",") if v), dice=on("dice_weight"),
+                          boundary=on("boundary_loss"), lovasz=on("lovasz_weight"), ssim=on("ssim_weight"),
+                          unl=sum(on(k) for k in ("unl_entropy", "unl_maxsq", "unl_pseudo")))
+
+
 def _optim_options(args, ema):
     """--clip_grad_norm / --weight_decay / --adamw / --ema_decay (opt-in; the reference has none of them) -> FusedAdam's keyword
     arguments.  `ema`: this optimiser keeps the EMA copy (the generators' and the supervised Gsi's do, the discriminators' does not)."""
@@ -474,6 +501,8 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         self._init_ce(args, C)
         self._init_ssim(args)
         self._init_unl(args)
+        self.gen_terms = gen_loss_terms_of(args)
+        F.weighted_sum_launches(self.gen_terms)      # (any count is served; a refusal would come here, not at the first step)
 
         self.g_optimizer = FusedAdam(itertools.chain(self.Gis.parameters(), self.Gsi.parameters()), lr=args.lr, betas=(0.5, 0.999),
                                      **_optim_options(args, ema=True))
@@ -727,6 +756,8 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
             extra_weights.append(a.lamda_gt * self.lovasz_w)
         lab_loss_MSE = self._image_l1(fake_img_l1, l_img, extras, "lab_loss_ssim", a.lab_MSE_weight, extra_terms, extra_weights)   # :461
         # :464-468  gen_loss = CE_w*CE + MSE_w*L1 + adv_w*(img_gen + gt_gen) + img_cycle + lamda_gt*gt_cycle
+        if GEN_LOSS_BASE_TERMS + len(extra_terms) != self.gen_terms:      # a term added here must be added to gen_loss_terms too
+            raise RuntimeError("gen_loss has %d terms, gen_loss_terms counted %d" % (GEN_LOSS_BASE_TERMS + len(extra_terms), self.gen_terms))
         gen_loss = F.weighted_sum(
             [lab_loss_CE, lab_loss_MSE, img_gen_loss, gt_gen_loss, img_cycle_loss, gt_cycle_loss] + extra_terms,
             [a.lab_CE_weight, a.lab_MSE_weight, a.adversarial_weight, a.adversarial_weight, 1.0, a.lamda_gt] + extra_weights)

@@ -795,7 +795,8 @@ def test_scalar_losses_and_weighted_sum(n, F, dev):
 
 def test_weighted_sum_of_16_terms_and_refusal_of_17(F, dev):
     """sscg_weighted_sum at its limit of 16 terms (terms and weights positive: a sum that cancels has no scale to be relative to),
-    gradients w_i * g, and the refusal of 17."""
+    gradients w_i * g, and the RAW entry's refusal of 17 (functional.weighted_sum folds beyond 16: the test below)."""
+    import ctypes as C
     fig = _Figures("weighted_sum")
     vals = [1.0 + 0.37 * k for k in range(17)]
     ws = [0.25 + 0.11 * ((7 * k) % 17) for k in range(17)]
@@ -807,8 +808,60 @@ def test_weighted_sum_of_16_terms_and_refusal_of_17(F, dev):
     w32 = [float(torch.tensor(w)) for w in ws]
     fig.add("sum16", abs(float(out) - sum(a * b for a, b in zip(v32[:16], w32[:16]))) / sum(a * b for a, b in zip(v32[:16], w32[:16])), 1e-6)
     fig.add("grads16", max(abs(float(t.grad) - w * float(torch.tensor(LOSS_G))) / (w * LOSS_G) for t, w in zip(terms[:16], w32)), 1e-6)
-    with pytest.raises(F._lib.SscgError):
-        F.weighted_sum(terms, ws)
+    raw = torch.full((), 7.0, device=dev)
+    rc = F.lib.sscg_weighted_sum((C.c_void_p * 17)(*[t.data_ptr() for t in terms]), (C.c_float * 17)(*ws), 17, raw.data_ptr(), F._stream())
+    torch.cuda.synchronize()
+    fig.true("raw_entry_refuses_17", rc != 0 and float(raw) == 7.0, "rc %d" % rc)
+    fig.check()
+
+
+def _wsum_case(n):
+    """n terms of mixed sign over seven decades, weights of mixed sign: (terms, weights) as python floats that are fp32 values."""
+    vals = [(-1.0) ** (k // 2) * (1.0 + 0.37 * k) * 10.0 ** ((5 * k) % 7 - 3) for k in range(n)]
+    ws = [(-1.0) ** (k % 3 == 1) * (0.25 + 0.11 * ((7 * k) % 17)) for k in range(n)]
+    return [float(torch.tensor(v)) for v in vals], [float(torch.tensor(w)) for w in ws]
+
+
+@pytest.mark.parametrize("n", [16, 17, 31, 32, 40])
+def test_weighted_sum_of_any_number_of_terms(n, F, dev, monkeypatch):
+    """functional.weighted_sum beyond the raw entry's 16 terms (every loss flag plus --variants l1_cycle is 18): up to 16 it is ONE
+    launch with the raw entry's own bits; beyond, the first launch sums terms 0..15 and each later one takes the running partial
+    sum with weight 1 plus the next 15 terms, in index order (17 and 32: a last launch of the partial and ONE term; 31: exactly full).
+    Value against the fp64 sum of the same fp32 terms and weights within n * 2^-24 * sum_i |w_i t_i| - each product and each add
+    rounds once in fp32, the partial never exceeds sum |w_i t_i|; a fused multiply-add only rounds less - and every term's gradient
+    is fl(w_i * g), bit for bit."""
+    import ctypes as C
+    fig = _Figures("weighted_sum n=%d" % n)
+    vals, ws = _wsum_case(n)
+    terms = [torch.tensor(v, device=dev, requires_grad=True) for v in vals]
+    calls = []
+    real = F.lib.sscg_weighted_sum
+
+    def counted(tab, w, k, out, stream):
+        calls.append((k, tab[0], w[0], out))
+        return real(tab, w, k, out, stream)
+    monkeypatch.setattr(F.lib, "sscg_weighted_sum", counted)
+    with _nan_outputs():
+        out = F.weighted_sum(terms, ws)
+        fwd = list(calls)
+        out.backward(torch.tensor(LOSS_G, device=dev))
+    monkeypatch.undo()
+    want = F.weighted_sum_launches(n)
+    fig.true("forward_launches", len(fwd) == want == (1 if n <= 16 else 1 + -(-(n - 16) // 15)), "%d launches, %d expected" % (len(fwd), want))
+    sizes = [16] + [min(16, n - i + 1) for i in range(16, n, 15)] if n > 16 else [n]
+    chained = all(c[0] == k and (j == 0 or (c[1] == fwd[j - 1][3] and c[2] == 1.0)) for j, (c, k) in enumerate(zip(fwd, sizes)))
+    fig.true("fold_in_index_order", chained and fwd[0][1] == terms[0].data_ptr() and fwd[-1][3] == out.data_ptr(), "sizes %s" % [c[0] for c in fwd])
+    fig.true("backward_one_launch_per_term", len(calls) - len(fwd) == n, "%d launches" % (len(calls) - len(fwd)))
+    ref = sum(np.float64(a) * np.float64(b) for a, b in zip(vals, ws))
+    scale = sum(abs(np.float64(a) * np.float64(b)) for a, b in zip(vals, ws))
+    fig.add("value_vs_fp64", abs(float(out) - ref), n * 2.0 ** -24 * scale)
+    g32 = torch.tensor(LOSS_G, dtype=F32)
+    wrong = [i for i, (t, w) in enumerate(zip(terms, ws)) if t.grad is None or not torch.equal(t.grad.cpu(), torch.tensor(w, dtype=F32) * g32)]
+    fig.true("grads_exactly_w_times_g", not wrong, "terms %s differ" % wrong)
+    if n <= 16:     # today's path is one raw launch: the same bits
+        raw = torch.zeros((), device=dev)
+        rc = real((C.c_void_p * n)(*[t.data_ptr() for t in terms]), (C.c_float * n)(*ws), n, raw.data_ptr(), F._stream())
+        fig.true("one_launch_bits", rc == 0 and torch.equal(raw.cpu().view(torch.int32), out.detach().cpu().view(torch.int32)))
     fig.check()
 
 

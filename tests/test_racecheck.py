@@ -124,6 +124,63 @@ def test_engine_handover_merges_the_producers_clock():
     assert not c.reports
 
 
+class _FakeLib(object):
+    """Stands in for the ctypes handle: the checker logs a launch before it forwards it."""
+
+    def __init__(self):
+        self.calls = []
+
+    def sscg_weighted_sum(self, *a):
+        self.calls.append(a)
+        return 0
+
+
+def _checked(rc):
+    """A checked handle over a fake library with a fresh core; returns (handle, core, restore)."""
+    saved = (rc.CORE, rc._STATE["table"])
+    rc._STATE["table"] = rc.parse_header(os.path.join(ROOT, "include", "sscg.h"))
+    rc.CORE = rc.RaceCore()
+
+    def restore():
+        rc.CORE, rc._STATE["table"] = saved
+    return rc._Checked(_FakeLib()), rc.CORE, restore
+
+
+def test_weighted_sum_reads_the_scalars_behind_its_host_table():
+    """sscg_weighted_sum's argument list shows a host table; the loss scalars it names are announced with note_batch (as the batched
+    transpose's buffers are).  A term written on stream a and summed on stream b without an edge is a read-after-write; with a wait
+    it is not; the output is a write like any other; and the note is consumed by its launch."""
+    import ctypes
+    rc = load_sub("_lib").dev_tool("racecheck")
+    term, other, out = 0x7000, 0x7100, 0x7200
+    for wait in (False, True):
+        lib, c, restore = _checked(rc)
+        try:
+            _launch(c, "a", writes=[(term, 4)], what="head writes its loss scalar")
+            _launch(c, "b", writes=[(other, 4)], what="a term of the summing stream")
+            if wait:
+                c.wait_stream("b", "a")
+            tab = (ctypes.c_void_p * 2)(term, other)
+            lib.note_batch(ctypes.addressof(tab), [(term, None), (other, None)])
+            assert lib.sscg_weighted_sum(tab, (ctypes.c_float * 2)(1.0, 0.5), 2, out, "b") == 0
+            assert len(lib._lib.calls) == 1 and lib.counts == {"sscg_weighted_sum": 1} and not lib._batches
+            kinds = [(r["kind"], r["old"][2]) for r in c.reports.values()]
+            assert kinds == ([] if wait else [("read-after-write", "head writes its loss scalar")]), kinds
+            # the sum's output is shadowed as a write on b: a reader on a needs an edge of its own
+            _launch(c, "a", reads=[(out, 4)], what="reader of the sum")
+            assert len(c.reports) == (1 if wait else 2)
+        finally:
+            restore()
+    # a caller that announces nothing (the raw entry): the table's own entries are read
+    lib, c, restore = _checked(rc)
+    try:
+        _launch(c, "a", writes=[(term, 4)])
+        lib.sscg_weighted_sum((ctypes.c_void_p * 1)(term), (ctypes.c_float * 1)(1.0), 1, out, "b")
+        assert [r["kind"] for r in c.reports.values()] == ["read-after-write"]
+    finally:
+        restore()
+
+
 def test_read_write_table_covers_the_abi():
     rc, lib = load_sub("_lib").dev_tool("racecheck"), load_sub("_lib")
     table = rc.parse_header(os.path.join(ROOT, "include", "sscg.h"))
@@ -135,3 +192,17 @@ def test_read_write_table_covers_the_abi():
     kinds = dict(table["sscg_adam_step"])
     assert kinds["param"] == "w" and kinds["grad"] == "r" and kinds["shadow"] == "w"
     assert dict(table["sscg_norm_apply"])["residual"] == "r"
+    # the opt-in heads and optimiser entries the every-option schedule scenarios depend on (tests/aids/step_options.py)
+    def kinds_of(name, reads=(), writes=()):
+        kinds = dict(table[name])
+        assert [a for a in reads if kinds[a] != "r"] == [] and [a for a in writes if kinds[a] != "w"] == [], (name, kinds)
+        assert kinds["stream"] == "stream"
+    kinds_of("sscg_ohem_fwd", reads=("x", "labels", "class_w"), writes=("keys", "loss", "valid", "thr", "counts", "ws"))
+    kinds_of("sscg_upsample_head_bwd_b", reads=("x", "labels", "keys", "thr", "valid", "coef", "sdm", "bnd_coef", "g_ce", "g_dice", "g_bnd"),
+             writes=("dx",))
+    kinds_of("sscg_lovasz_fwd", reads=("x", "labels"), writes=("keys", "coef", "loss", "ws"))
+    kinds_of("sscg_unl_fwd", reads=("x",), writes=("losses", "sums", "pseudo", "ws"))
+    kinds_of("sscg_upsample_head_bwd_u", reads=("x", "pseudo", "sums"), writes=("dx",))
+    kinds_of("sscg_grad_norm", reads=("grad",), writes=("norm", "clip", "ws"))
+    kinds_of("sscg_adam_step_ex", reads=("grad", "clip"), writes=("param", "exp_avg", "exp_avg_sq", "shadow", "ema"))
+    kinds_of("sscg_weighted_sum", reads=("terms", "w"), writes=("out",))

@@ -11,6 +11,7 @@ racecheck.py names the launches; both are clean on the fixed tree, which is what
 (`python tests/aids/flake_pool.py 20` - 64 overlapped steps from twenty fresh models, the run that flaked ~1 in 10 in round 3 - is
 20 of 20 finite on this tree, profiles/r04_fuzz.txt; it is not part of the suite: 5 s per model.)"""
 import os
+import re
 import subprocess
 import sys
 
@@ -68,3 +69,50 @@ def test_full_size_config_2_step_overlapped_low_priority_equals_serial():
     r = _run("fuzz_step.py", [1, 2, 256, 8])
     assert r.returncode == 0 and "0 of 2 schedules differ" in r.stdout, (r.stdout[-3000:], r.stderr[-2000:])
     assert "finite=False" not in r.stdout and "side lanes: priority 1" in r.stdout
+
+
+# ------------------------------------------------------------------------------------------------ every opt-in option on
+# The tests above run the step as it was when the schedule was last audited.  Since then it has gained opt-in work with the
+# properties that bit before (state saved per call for the backward, lazily grown per-stream workspaces, clipping and the EMA update on
+# the D stream, an augmenting loader issuing while the previous D step runs): tests/aids/step_options.py names one set with all of
+# it on, and the aids assert that none of it was a no-op before their verdict counts (exit status 2 otherwise).
+ALL_ON = "options=all"
+
+
+def _not_vacuous(r):
+    assert "options all: not vacuous" in r.stdout and "ran vacuously" not in r.stdout, (r.stdout[-4000:], r.stderr[-2000:])
+
+
+def test_ordering_checker_finds_nothing_with_every_option_on():
+    """Three overlapped semi-supervised steps with every loss and optimiser option on, batches from augmenting DeviceLoaders (affine,
+    contrast, elastic, CutMix: their batch finish is in the checked log), an evaluation of two batches under the EMA weights between
+    the second and the third step with train()'s synchronisation only, then two supervised steps with the same flags in the same
+    process: no unordered cross-stream access and no unordered allocator reuse in either phase."""
+    r = _run("racecheck_step.py", [3, 64, 2, 1, "f32", ALL_ON])
+    print(r.stdout[-6000:])
+    assert len(re.findall(r"(?<![0-9])0 distinct reports", r.stdout)) == 2, (r.stdout[-4000:], r.stderr[-2000:])
+    assert r.returncode == 0 and "losses finite: True" in r.stdout and "supervised losses finite: True" in r.stdout
+    assert "evaluated 2 batches under the EMA weights" in r.stdout
+    _not_vacuous(r)
+
+
+def _every_option_bits(env):
+    r = _run("fuzz_step.py", [1, 3, 64, 2, "f32", ALL_ON], env)
+    print(r.stdout[-6000:])
+    assert r.returncode == 0 and "0 of 2 schedules differ" in r.stdout, (r.stdout[-4000:], r.stderr[-2000:])
+    assert "finite=False" not in r.stdout and "DIFFER" not in r.stdout and r.stdout.count("further records") == 2
+    _not_vacuous(r)
+
+
+def test_fuzzed_schedules_with_every_option_on_compute_the_serial_bits():
+    """Three steps (the first sizes the lazily built workspaces, the second regrows or reuses them while the first D step is in
+    flight, the third is the first with steady-state allocator reuse), plain and fuzzed, low-priority side lanes: the nine losses,
+    every extra loss key, both optimisers' gradient norms - of every step - both parameter arenas, the EMA arena and the BatchNorm
+    state equal the serial one-stream run bit for bit."""
+    _every_option_bits({"SSCG_SIDE_PRIORITY": "1"})
+
+
+def test_options_through_rccl_equal_the_serial_non_dp_bits():
+    """The same record through the RCCL path: the generator update - and with it the clipping, the decay and the EMA update - is
+    deferred past the all-reduce, so it runs at another place in the schedule; a sum over one rank is the identity."""
+    _every_option_bits({"SSCG_FORCE_DP": "1", "MASTER_PORT": "29733"})

@@ -21,6 +21,7 @@ the stream of their neighbours - and RCCL's internal stream, which is modelled a
 The core (`RaceCore`) is plain Python and is unit-tested on the CPU (tests/test_racecheck.py); the torch layer patches
 `torch.cuda.Stream/Event`, `Tensor.data_ptr/record_stream` and wraps the library handle.
 """
+import ctypes
 import os
 import re
 import sys
@@ -327,6 +328,7 @@ class _Checked(object):
         self._lib = lib
         self._cache = {}
         self._batches = {}
+        self.counts = {}            # entry point -> launches logged (the census of a run)
 
     def __getattr__(self, name):
         fn = self._cache.get(name)
@@ -335,7 +337,9 @@ class _Checked(object):
         return fn
 
     def note_batch(self, table_ptr, pairs):
-        """functional._transpose_batch: the (source, destination) pointers behind a job table in device memory."""
+        """The pointers an entry reaches through a table, which the argument list does not show: (source, destination) per job of
+        functional._transpose_batch's table in device memory; (term, None) per term of sscg_weighted_sum's host table (keyed by the
+        table's address; the note is consumed by the launch, the table does not outlive it)."""
         self._batches[table_ptr] = pairs
 
     def _wrap(self, name, fn):
@@ -345,6 +349,7 @@ class _Checked(object):
 
         def call(*a):
             core = CORE
+            self.counts[name] = self.counts.get(name, 0) + 1
             if core is not None:
                 s = a[-1] or 0
                 v = core.tick(s)
@@ -355,17 +360,20 @@ class _Checked(object):
                     for src, dst in self._batches.get(a[0], ()):
                         core.access(v, s, src, ext.get(src, 4), False, where + ".w")
                         core.access(v, s, dst, ext.get(dst, 4), True, where + ".wt")
+                if name == "sscg_weighted_sum":
+                    # the loss scalars behind the host table: the ones functional.weighted_sum announced, else the table's own entries
+                    where = "%s(%s)" % (name, _where())
+                    key = ctypes.addressof(a[0]) if isinstance(a[0], ctypes.Array) else a[0]
+                    pairs = self._batches.pop(key, None)
+                    if pairs is None:
+                        pairs = [(int(p), None) for p in a[0] if p]
+                    for src, _ in pairs:
+                        core.access(v, s, src, ext.get(src, 4), False, where + ".terms")
                 for (arg, kind), val in zip(row, a):
                     if kind not in ("r", "w") or val is None:
                         continue
-                    if name == "sscg_weighted_sum":
-                        if arg == "terms":
-                            for p in val:
-                                if where is None:
-                                    where = "%s(%s)" % (name, _where())
-                                core.access(v, s, int(p), 4, False, where + ".terms")
-                        if arg in ("terms", "w"):
-                            continue
+                    if name == "sscg_weighted_sum" and arg in ("terms", "w"):       # host arrays (the terms: above)
+                        continue
                     if name == "sscg_predict_head_ms" and arg == "xs":     # a host array of device pointers: the views' logits
                         for p in val:
                             if where is None:
@@ -413,6 +421,7 @@ class _Fuzzed(object):
     def __init__(self, lib):
         self._lib = lib
         self._cache = {}
+        self.counts = {}            # entry point -> launches (the census of a run)
 
     def __getattr__(self, name):
         fn = self._cache.get(name)
@@ -421,7 +430,8 @@ class _Fuzzed(object):
             if name.endswith(("_workspace", "_bytes", "_applies", "_version")):
                 fn = real
             else:
-                def fn(*a, _real=real):
+                def fn(*a, _real=real, _name=name):
+                    self.counts[_name] = self.counts.get(_name, 0) + 1
                     if FUZZ["on"]:
                         import torch
                         r = FUZZ["rng"]
