@@ -749,6 +749,42 @@ int sscg_image_head(const float* x, int N, int H, int W, int C, int OH, int OW, 
 int sscg_predict_head_ms(const float* const* xs, const int* Hs, const int* Ws, int S, uint32_t flip_mask, int N, int C, int OH, int OW,
                          float* prob_sum, int64_t* index, uint8_t* label_u8, const int64_t* label_true, int64_t* hist, void* stream);
 int sscg_resize_flip(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, int flip, void* stream);
+/* ------------------------------------------------------------------ sliding-window inference: the network run on overlapping windows
+ * of its training size over a larger image, the windows' probabilities blended with a separable importance map (nnU-Net / MONAI
+ * sliding-window inference, mmseg mode='slide').  The reference resizes every image to the crop, so there is no call site to name;
+ * opt-in (`--sliding`), forward only, never launched by the training step.  (Additions: no existing entry changes meaning, so
+ * SSCG_ABI_VERSION stays 18.)
+ *
+ * Geometry, per axis (y: image rows OH, window rows wh, stride sy, ky windows; x alike): window i sits at pos_i = min(i * s, L - w),
+ * the last one flush with the edge; (k - 1) * s >= L - w is required, so the windows cover the axis.  Window index
+ * ((n * ky + iy) * kx + ix) * F + f with F = flip ? 2 : 1; f = 1 is the horizontally mirrored twin of f = 0.
+ *
+ * sscg_window_gather: x [N][H][W][C] fp32 -> y [(N ky kx F)][wh][ww][C], y[widx][ly][lx] = x[n][pos_iy + ly][pos_ix + (f ? ww-1-lx : lx)]:
+ * a pure copy, one launch - the network input of every window.  Errors before any HIP call: SSCG_ERR_BAD_ARG (null pointers,
+ * non-positive sizes, wh > H, ww > W, (ky-1)*sy < H - wh, (kx-1)*sx < W - ww), SSCG_ERR_UNSUPPORTED (2^31 windows or more).
+ *
+ * sscg_predict_head_sw: x holds the windows' low-resolution logits [(N ky kx F)][h][w][C] fp32 (C <= 64) in the gather's order; wy[wh],
+ * wx[ww] are the window's weight tables, ry[OH], rx[OW] the reciprocals of the summed weights per row / column (the blend is separable,
+ * so ry[oy] * rx[ox] normalises pixel (oy, ox); with flip, ry carries the factor 0.5) - all four fp32 in device memory.
+ * Per output pixel (n, oy, ox): the windows that cover it, found by arithmetic on (oy, sy, ky, OH - wh) and (ox, sx, kx, OW - ww), in
+ * ascending (iy, ix) order, f = 0 before f = 1; with (ly, lx) = (oy - pos_iy, ox - pos_ix): the bilinear resize of the window's map to
+ * [wh][ww] at (ly, f ? ww-1-lx : lx) with align_corners=True (sscg_upsample_bilinear_fwd's arithmetic; h == wh && w == ww is the
+ * identity resize), the softmax over C (sscg_softmax_fwd's), then t = p[c], g = wy[ly] * wx[lx], acc[c] = first ? g * t : acc[c] + g * t,
+ * every product rounded to fp32 before the add.  Then the first maximum of acc[] (sscg_argmax_onehot's rule), unnormalised.
+ * Every output equals the separate passes' bit for bit - per window sscg_upsample_bilinear_fwd, sscg_softmax_fwd, a mirror of the W
+ * axis for f = 1, an fp32 multiply by the outer product of wy and wx, an fp32 add into the window's place of a zeroed accumulator; then
+ * sscg_argmax_onehot's index, sscg_confusion_hist and an fp32 multiply by the outer product of ry and rx.  No window's resized logits
+ * or probabilities reach memory.
+ *   prob       (nullable) fp32 [N][OH][OW][C]: acc[c] * (ry[oy] * rx[ox]), two roundings - the blended probabilities;
+ *   index / label_u8 / label_true + hist: exactly as in sscg_predict_head (hist accumulated into, t outside [0, C) ignored).
+ * At least one output is required.  Errors before any HIP call: SSCG_ERR_BAD_ARG (a null x or table; non-positive sizes or strides;
+ * C outside 1..64; wh > OH, ww > OW, (ky-1)*sy < OH - wh, (kx-1)*sx < OW - ww; no output; label_true without hist or the reverse),
+ * SSCG_ERR_UNSUPPORTED (N*OH*OW, or N*OH*OW*C with prob, or the number of windows >= 2^31). */
+int sscg_window_gather(const float* x, float* y, int N, int H, int W, int C, int wh, int ww, int sy, int sx, int ky, int kx, int flip,
+                       void* stream);
+int sscg_predict_head_sw(const float* x, int N, int h, int w, int C, int wh, int ww, int sy, int sx, int ky, int kx, int flip, int OH,
+                         int OW, const float* wy, const float* wx, const float* ry, const float* rx, float* prob, int64_t* index,
+                         uint8_t* label_u8, const int64_t* label_true, int64_t* hist, void* stream);
 /* ------------------------------------------------------------------ windowed dense-CRF refinement of a predicted class map: the
  * mean-field update of the fully connected CRF that conventionally follows a DeepLab-v2 net, with the pairwise sum truncated to a
  * dilated (2r+1)^2 window.  The reference has no CRF, so there is no call site to name; opt-in (`--crf`), forward only, never launched

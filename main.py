@@ -4,7 +4,7 @@ dispatch on --training / --model.  Extra flags (never change a reference default
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
 --calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp,
---lovasz_weight, --lovasz_per_image, --lovasz_classes, --lovasz_skip.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
+--lovasz_weight, --lovasz_per_image, --lovasz_classes, --lovasz_skip, --sliding.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL).  --augment's items `cutmix=` / `classmix=` mix two samples of a
 labelled batch, labels with pixels, inside the device-side batch finish; their class ids are checked against --dataset here."""
 import importlib
@@ -70,6 +70,7 @@ class _Args(Namespace):
     lovasz_per_image = False
     lovasz_classes = "present"
     lovasz_skip = ""
+    sliding = ""
 
 
 def get_args(argv=None):
@@ -240,6 +241,15 @@ def get_args(argv=None):
                         help="average the Lovasz loss over the classes present in the segment, or over all (default: present)")
     parser.add_argument("--lovasz_skip", type=str, default=SUPPRESS, metavar="LIST",
                         help="comma list of class ids the Lovasz loss leaves out, as --dice_skip (default: none)")
+    parser.add_argument("--sliding", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="sliding-window inference in the per-epoch evaluation, --validation and --testing: the val / test images "
+                             "are kept at a larger evaluation size instead of being resized to the crop, the network runs on "
+                             "overlapping crop-sized windows and the windows' probabilities are blended with a centre-weighted map; "
+                             "'on' for scale=2,overlap=0.5,blend=gauss (an untuned default), or a comma list over size=HxW or scale=F "
+                             "(exactly one: the evaluation size, at least the crop), overlap=F (0..0.75, default 0.5), "
+                             "blend=gauss|const, sigma=F (of the window, default 0.125, untuned) and flip (every window also mirrored); "
+                             "at most 16 windows per axis; combines with --crf, --components, --boundary, --surface, --calibration "
+                             "(temperature 1) and --ema_decay, not with --tta or --panels (default: off, the images are the crop)")
     args = parser.parse_args(argv, namespace=_Args())
     if args.crf.strip():
         try:
@@ -335,6 +345,22 @@ def get_args(argv=None):
     return args
 
 
+def check_sliding(args):
+    """--sliding against the crop (known once the dataset's default is in) and the options it does not combine with: ValueError."""
+    if not args.sliding.strip():
+        return None
+    utils = importlib.import_module(PKG + ".utils")
+    opts = utils.parse_sliding(args.sliding, (args.crop_height, args.crop_width))
+    if getattr(args, "tta", "").strip():
+        raise ValueError("--sliding does not combine with --tta: multi-scale windows are not built; 'flip' is --sliding's own key")
+    if args.panels:
+        raise ValueError("--sliding does not combine with --panels: the panels are drawn at the crop size")
+    if args.calibration.strip() and len(utils.parse_calibration(args.calibration).temps) > 1:
+        raise ValueError("--sliding does not combine with a --calibration temperature list: the blended probabilities are not one "
+                         "softmax of logits that could be rescaled; ask for temperature 1 only")
+    return opts
+
+
 def main(argv=None):
     args = get_args(argv)
     args.gpu_ids = [int(s) for s in args.gpu_ids.split(",") if int(s) >= 0]
@@ -342,6 +368,7 @@ def main(argv=None):
     args.overlap_d = True                # train() reads the losses after sync_losses()
     if args.crop_height is None and args.crop_width is None:
         args.crop_height, args.crop_width = DEFAULT_CROP[args.dataset]
+    check_sliding(args)
     if args.gpu_ids:
         import torch
         torch.cuda.set_device(args.gpu_ids[0])          # arch/ops.py:31-34: everything lives on gpu_ids[0]

@@ -158,6 +158,8 @@ SIGNATURES = {
     "sscg_image_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "sscg_predict_head_ms": (_i, [C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, C.c_uint32, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sscg_resize_flip": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "sscg_window_gather": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "sscg_predict_head_sw": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "sscg_crf_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "sscg_crf_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _cp, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "sscg_boundary_counts": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),

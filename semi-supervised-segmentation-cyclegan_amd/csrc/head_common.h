@@ -151,6 +151,21 @@ __device__ __forceinline__ void sscg_prob_accumulate(float* acc, const float* v,
         }
 }
 
+// acc[c] <- (first ? 0 : acc[c]) + g * (v[c] * inv): one window's probabilities times its blend weight g (sliding.hip).  The separate
+// passes store the probability, then the weighted probability, each as an fp32 value, and add the latter in place: three roundings,
+// none of which may contract.
+template <int CT>
+__device__ __forceinline__ void sscg_prob_accumulate_weighted(float* acc, const float* v, float inv, float g, int C, bool first) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
+        if (CT || c < C) {
+            const float t = v[c] * inv;
+            const float p = g * t;
+            acc[c] = first ? p : acc[c] + p;
+        }
+}
+
 // argmax over c of a[c], first maximum wins (argmax_onehot_kernel's strict > from class 0 up)
 template <int CT>
 __device__ __forceinline__ int sscg_first_max(const float* a, int C) {

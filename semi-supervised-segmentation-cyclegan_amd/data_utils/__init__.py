@@ -259,13 +259,19 @@ def build_loaders(args, roots=None, device=None, sets=('label', 'unlabel', 'val'
     when there is a device, through the datasets' `augmentation=` (PIL, before Resize / CenterCrop) otherwise; rank r draws from
     `RandomState(AUGMENT_SEED + 1000 * r + <index of the set>)`.  The mix items (`cutmix=`, `classmix=`) go to the 'label' set
     only - the 'unlabel' set is built from the spec without them, its draws unchanged - and need the device finish: in host mode a spec
-    with one raises ValueError."""
+    with one raises ValueError.  `args.sliding` (absent or "" = off; utils.parse_sliding's grammar): the 'val' and 'test' sets get a
+    transformation of their own at the evaluation size (images bilinear, ground truth nearest neighbour); the 'label' / 'unlabel' sets
+    keep the crop and their draws."""
     roots = roots or {'voc2012': './data/VOC2012', 'cityscapes': './data/Cityscape', 'acdc': './data/ACDC'}
     from torch.utils.data import DataLoader
     tr = get_transformation((args.crop_height, args.crop_width), resize=True, dataset=args.dataset, device_finish=device is not None)
     cls = {'voc2012': VOCDataset, 'cityscapes': CityscapesDataset, 'acdc': ACDCDataset}[args.dataset]
     out = []
     size = (args.crop_height, args.crop_width)
+    tr_eval = tr
+    if (getattr(args, 'sliding', '') or '').strip():
+        from ..utils import parse_sliding
+        tr_eval = get_transformation(parse_sliding(args.sliding, size).size, resize=True, dataset=args.dataset, device_finish=device is not None)
     spec = getattr(args, 'augment', '') or ''
     is_mix = lambda item: item.strip().partition('=')[0] in ('cutmix', 'classmix')
     unmixed = ','.join(item for item in spec.split(',') if not is_mix(item))
@@ -277,8 +283,9 @@ def build_loaders(args, roots=None, device=None, sets=('label', 'unlabel', 'val'
         seed = AUGMENT_SEED + 1000 * rank + len(out)
         aug = augmentations.from_spec(spec if name == 'label' else unmixed, size, label_fill=LABEL_FILL[args.dataset], seed=seed,
                                       out_size=size if device is not None else None) if name in ('label', 'unlabel') else None
-        ds = cls(root_path=roots[args.dataset], name=name, ratio=ratio, transformation=tr, augmentation=aug if device is None else None)
+        trn = tr if name in ('label', 'unlabel') else tr_eval
+        ds = cls(root_path=roots[args.dataset], name=name, ratio=ratio, transformation=trn, augmentation=aug if device is None else None)
         gen = torch.Generator().manual_seed(20260928 + 1000 * rank + len(out)) if rank else None   # ranks draw different batches
         ld = DataLoader(ds, batch_size=args.batch_size, shuffle=True, drop_last=True, generator=gen)
-        out.append(DeviceLoader(ld, tr, device, augmentation=aug, seed=seed) if device is not None else ld)
+        out.append(DeviceLoader(ld, trn, device, augmentation=aug, seed=seed) if device is not None else ld)
     return out

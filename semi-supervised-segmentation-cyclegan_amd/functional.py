@@ -1388,6 +1388,235 @@ def predict_labels_ms(logits_list, flips, size, *, want_prob=False, want_index=F
     return u8, idx, hist, prob
 
 
+# Sliding-window inference (sscg_window_gather / sscg_predict_head_sw, include/sscg.h holds the definition): the network on overlapping
+# windows of its training size over a larger image, the windows' probabilities blended into one label map in one launch.  Opt-in
+# (`--sliding`).  SSCG_FUSE_SLIDING=0 keeps window_gather / predict_labels_sw on the chains of separate passes (an A/B aid: the bits are
+# the same).
+FUSE_SLIDING = [os.environ.get("SSCG_FUSE_SLIDING", "1") != "0"]
+SLIDING_MAX_WINDOWS = 16        # per axis
+
+
+class SlidingOptions(object):
+    """`window` = (wh, ww), the size the network was trained at; `size` = (H, W) >= window, the evaluation size the images are kept at;
+    `overlap` in [0, 0.75] of the window shared by neighbours; `blend` = "gauss" (weights exp(-d^2 / (2 (sigma w)^2)) around the
+    window's centre, `sigma` in (0, 1] of the window; 0.125 is MONAI's / nnU-Net's value, untuned here) or "const"; `flip`: every window
+    also runs mirrored along W."""
+    __slots__ = ("window", "size", "overlap", "blend", "sigma", "flip")
+
+    def __init__(self, window, size, overlap=0.5, blend="gauss", sigma=0.125, flip=False):
+        try:
+            window, size = (int(window[0]), int(window[1])), (int(size[0]), int(size[1]))
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("sliding: window and size are (height, width) pairs, got %r and %r" % (window, size))
+        if window[0] < 1 or window[1] < 1:
+            raise ValueError("sliding window %r is not positive" % (window,))
+        if size[0] < window[0] or size[1] < window[1]:
+            raise ValueError("sliding size %dx%d is below the %dx%d window (the crop)" % (size + window))
+        overlap, sigma = float(overlap), float(sigma)
+        if not 0.0 <= overlap <= 0.75:
+            raise ValueError("sliding overlap %r is outside [0, 0.75]" % (overlap,))
+        if blend not in ("gauss", "const"):
+            raise ValueError("sliding blend %r is neither gauss nor const" % (blend,))
+        if not 0.0 < sigma <= 1.0:
+            raise ValueError("sliding sigma %r is outside (0, 1]" % (sigma,))
+        self.window, self.size, self.overlap, self.blend, self.sigma, self.flip = window, size, overlap, blend, sigma, bool(flip)
+        for L, w in zip(size, window):
+            if len(sliding_positions(L, w, overlap)) > SLIDING_MAX_WINDOWS:
+                raise ValueError("sliding: %d windows of %d along an axis of %d at overlap %r, at most %d" % (
+                    len(sliding_positions(L, w, overlap)), w, L, overlap, SLIDING_MAX_WINDOWS))
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, SlidingOptions) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "SlidingOptions(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+
+def sliding_stride(w, overlap):
+    return max(1, int(w * (1.0 - overlap) + 0.5))
+
+
+def sliding_positions(L, w, overlap):
+    """The window positions along an axis of length L: stride s = max(1, int(w (1 - overlap) + 0.5)), k = 1 if L == w else
+    ceil((L - w) / s) + 1 windows at min(i s, L - w) - the last one pushed back flush with the edge."""
+    L, w = int(L), int(w)
+    if w > L:
+        raise ValueError("sliding: a window of %d does not fit an axis of %d" % (w, L))
+    s = sliding_stride(w, overlap)
+    k = 1 if L == w else -(-(L - w) // s) + 1
+    return [min(i * s, L - w) for i in range(k)]
+
+
+def _sliding_tables(L, w, pos, blend, sigma):
+    """(weights fp32 [w], reciprocal coverage fp32 [L]) of one axis: the weights computed in float64 and rounded once; the coverage
+    summed in fp32 in ascending window order."""
+    import numpy as np
+    if blend == "gauss":
+        d = np.arange(w, dtype=np.float64) - (w - 1) / 2.0
+        wt = np.exp(-(d * d) / (2.0 * (sigma * w) ** 2)).astype(np.float32)
+    else:
+        wt = np.ones(w, dtype=np.float32)
+    cov = np.zeros(L, dtype=np.float32)
+    for p in pos:
+        cov[p:p + w] += wt
+    return wt, (np.float32(1) / cov).astype(np.float32)
+
+
+class SlidingPlan(object):
+    """The geometry of one (H, W, options): per axis the stride, the window count and positions, the weight table and the normaliser;
+    `views` = windows per sample x (2 with flip).  With a device: the four tables as fp32 tensors there (uploaded once)."""
+    __slots__ = ("options", "OH", "OW", "wh", "ww", "sy", "sx", "ky", "kx", "pos_y", "pos_x", "flip", "views", "wy", "wx", "ry", "rx",
+                 "device", "wy_dev", "wx_dev", "ry_dev", "rx_dev")
+
+    def single(self):
+        """One unmirrored window: the image is the window."""
+        return self.views == 1
+
+
+_SLIDING_PLANS = {}
+
+
+def sliding_plan(H, W, options, device=None):
+    """The SlidingPlan of images [H, W] under `options`, cached per (H, W, options, device).  `device` None: host tables only."""
+    import numpy as np
+    if not isinstance(options, SlidingOptions):
+        raise TypeError("sliding_plan: a functional.SlidingOptions expected, not %r" % (options,))
+    H, W = int(H), int(W)
+    key = (H, W, options, None if device is None else str(device))
+    plan = _SLIDING_PLANS.get(key)
+    if plan is not None:
+        return plan
+    wh, ww = options.window
+    if H < wh or W < ww:
+        raise ValueError("sliding: images of %dx%d are below the %dx%d window" % (H, W, wh, ww))
+    plan = SlidingPlan()
+    plan.options, plan.OH, plan.OW, plan.wh, plan.ww, plan.flip = options, H, W, wh, ww, options.flip
+    plan.sy, plan.sx = sliding_stride(wh, options.overlap), sliding_stride(ww, options.overlap)
+    plan.pos_y, plan.pos_x = sliding_positions(H, wh, options.overlap), sliding_positions(W, ww, options.overlap)
+    plan.ky, plan.kx = len(plan.pos_y), len(plan.pos_x)
+    if max(plan.ky, plan.kx) > SLIDING_MAX_WINDOWS:
+        raise ValueError("sliding: %d x %d windows over %dx%d, at most %d per axis" % (plan.ky, plan.kx, H, W, SLIDING_MAX_WINDOWS))
+    plan.views = plan.ky * plan.kx * (2 if plan.flip else 1)
+    plan.wy, plan.ry = _sliding_tables(H, wh, plan.pos_y, options.blend, options.sigma)
+    plan.wx, plan.rx = _sliding_tables(W, ww, plan.pos_x, options.blend, options.sigma)
+    if plan.flip:
+        plan.ry = plan.ry * np.float32(0.5)         # the two views of a window carry the same weight
+    plan.device = device
+    plan.wy_dev = plan.wx_dev = plan.ry_dev = plan.rx_dev = None
+    if device is not None:
+        plan.wy_dev, plan.wx_dev, plan.ry_dev, plan.rx_dev = (torch.from_numpy(np.ascontiguousarray(t)).to(device)
+                                                              for t in (plan.wy, plan.wx, plan.ry, plan.rx))
+    _SLIDING_PLANS[key] = plan
+    return plan
+
+
+def _plan_on(plan, t, what):
+    if not isinstance(plan, SlidingPlan):
+        raise TypeError("%s: a plan of functional.sliding_plan expected, not %r" % (what, plan))
+    if plan.wy_dev is None or plan.wy_dev.device != t.device:
+        raise _lib.SscgError("%s: the plan's tables are not on %s (sliding_plan(..., device=))" % (what, t.device))
+
+
+def window_gather(images, plan):
+    """The network input of every window of `plan`: fp32 [N,C,H,W] -> channels-last [N * views, C, wh, ww], window
+    ((n ky + iy) kx + ix) F + f, the f = 1 twin with its columns mirrored - a pure copy in one launch; the batch itself when there is
+    one unmirrored window."""
+    _need_hip(images, f32_only=True)
+    if images.dim() != 4:
+        raise _lib.SscgError("window_gather: 4-D tensor expected")
+    _no_grad_input(images, "window_gather")
+    if not isinstance(plan, SlidingPlan):
+        raise TypeError("window_gather: a plan of functional.sliding_plan expected, not %r" % (plan,))
+    n, c, h, w = images.shape
+    if (h, w) != (plan.OH, plan.OW):
+        raise _lib.SscgError("window_gather: images of %dx%d, the plan is for %dx%d" % (h, w, plan.OH, plan.OW))
+    if plan.single():
+        return images
+    if not FUSE_SLIDING[0]:
+        x = images.detach()
+        wins = []
+        for i in range(n):
+            for py in plan.pos_y:
+                for px in plan.pos_x:
+                    t = x[i, :, py:py + plan.wh, px:px + plan.ww]
+                    wins.append(t)
+                    if plan.flip:
+                        wins.append(torch.flip(t, dims=(2,)))
+        return torch.stack(wins).contiguous(memory_format=CL)
+    x = to_nhwc(images.detach())
+    y = empty_nhwc(n * plan.views, c, plan.wh, plan.ww, x.device)
+    check(lib.sscg_window_gather(x.data_ptr(), y.data_ptr(), n, h, w, c, plan.wh, plan.ww, plan.sy, plan.sx, plan.ky, plan.kx,
+                                 1 if plan.flip else 0, _stream()), "sscg_window_gather")
+    return y
+
+
+def predict_labels_sw(logits, plan, *, want_prob=False, want_index=False, want_u8=True, label_true=None, hist=None, num_classes=None):
+    """Label maps at the plan's evaluation size from the logits of its windows, fp32 [N * views, C, h, w] in window_gather's order: per
+    output pixel, over the windows that cover it in ascending order (the unmirrored view before the mirrored one), interp(window,
+    bilinear, align_corners=True) -> mirror -> Softmax2d, times the window's blend weight, summed in fp32; then .max(1)[1] - one
+    launch, bit for bit what the separate passes give.  Returns (label_u8 uint8 [N,OH,OW] or None, index int64 [N,OH,OW] or None,
+    hist or None, prob fp32 [N,C,OH,OW] channels-last or None = the blended, NORMALISED probabilities); `label_true` / `hist` as in
+    predict_labels."""
+    _need_hip(logits, f32_only=True)
+    if logits.dim() != 4:
+        raise _lib.SscgError("predict_labels_sw: 4-D logits expected")
+    _no_grad_input(logits, "predict_labels_sw")
+    _plan_on(plan, logits, "predict_labels_sw")
+    x = to_nhwc(logits.detach())
+    nv, c, h, w = x.shape
+    if nv % plan.views:
+        raise _lib.SscgError("predict_labels_sw: %d logit maps are no multiple of the plan's %d windows per sample" % (nv, plan.views))
+    n, oh, ow = nv // plan.views, plan.OH, plan.OW
+    if num_classes is not None and int(num_classes) != c:
+        raise _lib.SscgError("predict_labels_sw: %d classes asked for, the logits have %d channels" % (num_classes, c))
+    if hist is not None and label_true is None:
+        raise _lib.SscgError("predict_labels_sw: a confusion matrix needs label_true")
+    if not (want_prob or want_index or want_u8 or label_true is not None):
+        raise _lib.SscgError("predict_labels_sw: no output asked for")
+    lt = None
+    if label_true is not None:
+        if not label_true.is_cuda:
+            raise _lib.SscgError("sscg kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % label_true.device)
+        lt = label_true.to(torch.int64).contiguous()
+        if lt.numel() != n * oh * ow:
+            raise _lib.SscgError("predict_labels_sw: label_true must have N*OH*OW elements")
+        if hist is None:
+            hist = torch.empty((c, c), dtype=torch.int64, device=x.device)
+            check(lib.sscg_fill(hist.data_ptr(), 2 * hist.numel(), 0.0, _stream()), "sscg_fill")   # 2 fp32 zeros per int64 zero
+        elif not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == c * c):
+            raise _lib.SscgError("predict_labels_sw: hist must be a contiguous int64 [C, C] tensor on the device")
+    if not FUSE_SLIDING[0]:
+        acc = torch.zeros((n, c, oh, ow), dtype=torch.float32, device=x.device).contiguous(memory_format=CL)
+        blend = plan.wy_dev[:, None] * plan.wx_dev[None, :]
+        F_ = 2 if plan.flip else 1
+        for iy, py in enumerate(plan.pos_y):
+            for ix, px in enumerate(plan.pos_x):
+                for f in range(F_):
+                    xk = to_nhwc(x[(iy * plan.kx + ix) * F_ + f::plan.views])           # the window's map of every sample
+                    p = softmax_fwd(xk if (h, w) == (plan.wh, plan.ww) else upsample_fwd(xk, plan.wh, plan.ww))
+                    if f:
+                        p = torch.flip(p, dims=(3,))
+                    acc[:, :, py:py + plan.wh, px:px + plan.ww].add_(torch.mul(p, blend))
+        idx = argmax_index(acc) if (want_index or want_u8 or lt is not None) else None
+        if lt is not None:
+            confusion_hist(lt, idx, c, hist)
+        prob = (acc * (plan.ry_dev[:, None] * plan.rx_dev[None, :])).contiguous(memory_format=CL) if want_prob else None
+        return idx.to(torch.uint8) if want_u8 else None, idx if want_index else None, hist, prob
+    u8 = torch.empty((n, oh, ow), dtype=torch.uint8, device=x.device) if want_u8 else None
+    idx = torch.empty((n, oh, ow), dtype=torch.int64, device=x.device) if want_index else None
+    prob = empty_nhwc(n, c, oh, ow, x.device) if want_prob else None
+    check(lib.sscg_predict_head_sw(x.data_ptr(), n, h, w, c, plan.wh, plan.ww, plan.sy, plan.sx, plan.ky, plan.kx, 1 if plan.flip else 0,
+                                   oh, ow, plan.wy_dev.data_ptr(), plan.wx_dev.data_ptr(), plan.ry_dev.data_ptr(), plan.rx_dev.data_ptr(),
+                                   _ptr(prob), _ptr(idx), _ptr(u8), _ptr(lt), _ptr(hist), _stream()), "sscg_predict_head_sw")
+    return u8, idx, hist, prob
+
+
 # Windowed dense-CRF refinement of a predicted class map (sscg_crf_head, include/sscg.h holds the definition): opt-in (`--crf`), an
 # inference call.  The defaults below are UNTUNED - no dataset was on hand to tune them; theta_beta is in the units of the guide image
 # the drivers pass, the normalised batch.

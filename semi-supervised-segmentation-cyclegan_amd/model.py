@@ -334,11 +334,37 @@ class _WeightedCE(object):
         elif hasattr(self, "eval_components"):
             del self.eval_components
 
-    def set_calibration(self, opts, tta=None, crf=None):
+    def set_sliding(self, opts):
+        """--sliding: a F.SlidingOptions (utils.parse_sliding), or None = off, kept as state of the model: evaluate()'s parameter list
+        stays as it is, like for the surface option.  While set, evaluate() takes the label maps from overlapping crop-sized windows
+        of the loader's (larger) images; while off it launches exactly what it launches without the option."""
+        if opts is not None and not isinstance(opts, F.SlidingOptions):
+            raise TypeError("set_sliding: a functional.SlidingOptions or None expected, not %r" % (opts,))
+        if opts is not None and opts.window != tuple(self.crop):
+            raise ValueError("set_sliding: the window %r is not the crop %r the network was trained at" % (opts.window, tuple(self.crop)))
+        self._sliding = opts
+
+    def get_sliding(self):
+        return getattr(self, "_sliding", None)
+
+    def _evaluate_sliding(self, val_img, val_gt, sliding, crf):
+        """One batch of evaluate() under set_sliding(): Gsi on the windows of the batch, `batch_size` windows per forward; the blended label map is
+        scored at the batch's own size.  With `crf`: the CRF runs on the blended, normalised probabilities, guided by the batch."""
+        size = tuple(val_img.shape[2:])
+        chunk = max(1, int(getattr(self.args, "batch_size", 0) or val_img.shape[0]))
+        if crf is not None:
+            scores, probs = utils.crf_scores(self.Gsi, val_img, size, sliding=sliding, chunk=chunk)
+            self.running_metrics_val.update_logits_crf(val_gt.squeeze(1), scores, val_img, size, crf, probs=probs)
+            return
+        plan = F.sliding_plan(size[0], size[1], sliding, val_img.device)
+        self.running_metrics_val.update_logits_sw(val_gt.squeeze(1), utils.sliding_logits(self.Gsi, val_img, plan, chunk), plan)
+
+    def set_calibration(self, opts, tta=None, crf=None, sliding=None):
         """--calibration: a F.CalibrationOptions (utils.parse_calibration), or None = off, handed to the score keeper
         (runningScore.set_calibration): evaluate()'s parameter list stays as it is, the option is state like the surface option.  A
-        temperature grid together with `tta` / `crf` (what evaluate() will be called with) or SSCG_FUSE_PREDICT=0 is refused here."""
-        self.running_metrics_val.set_calibration(opts, tta=tta, crf=crf)
+        temperature grid together with `tta` / `crf` / `sliding` (what evaluate() will be called with) or SSCG_FUSE_PREDICT=0 is refused
+        here."""
+        self.running_metrics_val.set_calibration(opts, tta=tta, crf=crf, sliding=sliding)
 
     def _calibration_scores(self, running):
         """--calibration: the calibration scores of the evaluation that has just run (runningScore.get_calibration_scores), kept in
@@ -921,17 +947,27 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         reference evaluates one view only).  None = the single forward of the reference.  `crf`: a F.CrfOptions (utils.parse_crf) - the
         label is taken after its mean-field steps on the (summed) probabilities (the reference has no CRF); None = the plain first maximum.
         `boundary`: a F.BoundaryOptions (utils.parse_boundary) - the Boundary IoU and the trimap mIoU of the same label maps are kept in
-        `self.eval_boundary` (utils.boundary_scores); None = neither is computed, nothing more is launched.  The return value is the same."""
+        `self.eval_boundary` (utils.boundary_scores); None = neither is computed, nothing more is launched.  The return value is the same.
+        With set_sliding() (a F.SlidingOptions, utils.parse_sliding; the option is state like the surface option) the loader's images
+        keep their own (larger) size, Gsi runs on overlapping crop-sized windows and the windows' probabilities are blended
+        (utils.sliding_logits, runningScore.update_logits_sw); the label maps have the batch's size, not the crop.  Off: the images
+        are the crop, nothing more is launched."""
+        sliding = self.get_sliding()
+        if sliding is not None and tta:
+            raise ValueError("evaluate: sliding-window inference does not combine with tta (its own key 'flip' mirrors the windows)")
         self.Gsi.eval()
         self.Gis.eval()
         self.running_metrics_val.reset()
         self.running_metrics_val.set_boundary(boundary)
-        self.running_metrics_val.check_calibration(tta, crf)      # --calibration: a temperature grid needs the single fused head
+        self.running_metrics_val.check_calibration(tta, crf, sliding=sliding)      # --calibration: a temperature grid needs the single fused head
         calibrated = self.running_metrics_val.get_calibration() is not None
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
                 first_batch.extend((val_img, val_gt))
+            if sliding is not None:         # overlapping crop-sized windows over the batch's own size, blended into one label map
+                self._evaluate_sliding(val_img, val_gt, sliding, crf)
+                continue
             if crf is not None:             # the windowed dense CRF between the softmax and the first maximum, guided by the batch
                 scores, probs = utils.crf_scores(self.Gsi, val_img, self.crop, tta)
                 self.running_metrics_val.update_logits_crf(val_gt.squeeze(1), scores, utils.crf_guide(val_img, self.crop), self.crop, crf,
@@ -998,8 +1034,10 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         history = []
         self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
         self.set_components(utils.parse_components(getattr(args, 'components', '')))
+        sliding = utils.parse_sliding(getattr(args, 'sliding', ''), self.crop)
+        self.set_sliding(sliding)
         self.set_calibration(utils.parse_calibration(getattr(args, 'calibration', '')), tta=utils.parse_tta(getattr(args, 'tta', '')),
-                             crf=utils.parse_crf(getattr(args, 'crf', '')))
+                             crf=utils.parse_crf(getattr(args, 'crf', '')), sliding=sliding)
         for epoch in range(self.start_epoch, args.epochs):
             self.set_boundary_epoch(epoch)
             self.set_unl_epoch(epoch)
@@ -1156,16 +1194,22 @@ class supervised_model(_WeightedCE):
         `first_batch`: a list that receives the first batch's (val_img, val_gt) on the device (the batch of the panels).
         `tta`: a view list of utils.parse_tta, `crf`: a F.CrfOptions, both as in semisuper_cycleGAN.evaluate; None = the reference's
         single forward and plain first maximum.  `boundary`: a F.BoundaryOptions, as in semisuper_cycleGAN.evaluate (the scores are
-        kept in `self.eval_boundary`); None = off."""
+        kept in `self.eval_boundary`); None = off.  set_sliding(): sliding-window inference, as in semisuper_cycleGAN.evaluate."""
+        sliding = self.get_sliding()
+        if sliding is not None and tta:
+            raise ValueError("evaluate: sliding-window inference does not combine with tta (its own key 'flip' mirrors the windows)")
         self.Gsi.eval()
         self.running_metrics_val.reset()
         self.running_metrics_val.set_boundary(boundary)
-        self.running_metrics_val.check_calibration(tta, crf)      # --calibration: a temperature grid needs the single fused head
+        self.running_metrics_val.check_calibration(tta, crf, sliding=sliding)      # --calibration: a temperature grid needs the single fused head
         calibrated = self.running_metrics_val.get_calibration() is not None
         for val_img, val_gt, _ in val_loader:
             val_img, val_gt = utils.cuda([val_img, val_gt], self.args.gpu_ids)
             if first_batch is not None and not first_batch:
                 first_batch.extend((val_img, val_gt))
+            if sliding is not None:         # overlapping crop-sized windows over the batch's own size, blended into one label map
+                self._evaluate_sliding(val_img, val_gt, sliding, crf)
+                continue
             if crf is not None:             # the windowed dense CRF between the softmax and the first maximum, guided by the batch
                 scores, probs = utils.crf_scores(self.Gsi, val_img, self.crop, tta)
                 self.running_metrics_val.update_logits_crf(val_gt.squeeze(1), scores, utils.crf_guide(val_img, self.crop), self.crop, crf,
@@ -1216,8 +1260,10 @@ class supervised_model(_WeightedCE):
         history, done = [], 0
         self.set_surface(utils.parse_surface(getattr(args, 'surface', '')))
         self.set_components(utils.parse_components(getattr(args, 'components', '')))
+        sliding = utils.parse_sliding(getattr(args, 'sliding', ''), self.crop)
+        self.set_sliding(sliding)
         self.set_calibration(utils.parse_calibration(getattr(args, 'calibration', '')), tta=utils.parse_tta(getattr(args, 'tta', '')),
-                             crf=utils.parse_crf(getattr(args, 'crf', '')))
+                             crf=utils.parse_crf(getattr(args, 'crf', '')), sliding=sliding)
         for epoch in range(self.start_epoch, args.epochs):
             self.set_boundary_epoch(epoch)
             self.Gsi.train()

@@ -199,7 +199,7 @@ class runningScore(object):
     def get_surface(self):
         return self._surface
 
-    def set_calibration(self, calibration, tta=None, crf=None):
+    def set_calibration(self, calibration, tta=None, crf=None, sliding=None):
         """The calibration scores (ECE, MCE, NLL, Brier, the per-class gap, the fitted temperature) as STATE of the score keeper: a
         F.CalibrationOptions (utils.parse_calibration), or None = off.  While set, every update_* on logits also hands what its head
         takes the labels from to F.calibration_stats: the logits themselves (update_logits), the views' summed probabilities
@@ -210,7 +210,7 @@ class runningScore(object):
         what it launches without the option."""
         if calibration is not None and not isinstance(calibration, F.CalibrationOptions):
             raise TypeError("set_calibration: a functional.CalibrationOptions or None expected, not %r" % (calibration,))
-        self.check_calibration(tta, crf, calibration)
+        self.check_calibration(tta, crf, calibration, sliding=sliding)
         if calibration != self._calibration:
             self._calibration_state = None
         self._calibration = calibration
@@ -218,20 +218,21 @@ class runningScore(object):
     def get_calibration(self):
         return self._calibration
 
-    def check_calibration(self, tta=None, crf=None, calibration=False):
+    def check_calibration(self, tta=None, crf=None, calibration=False, sliding=None):
         """Refuse a temperature grid (more than one temperature) where there are no logits to rescale: under multi-scale / mirrored
         inference, behind the CRF and on the chain of separate passes (SSCG_FUSE_PREDICT=0); and, at any temperature, a CRF of 0
         iterations behind several views (it has no Q, and its scores' number of views is not known to update_logits_crf).  evaluate()
-        calls it before the first batch.  `calibration`: the option to check instead of the one that is set."""
+        calls it before the first batch.  `calibration`: the option to check instead of the one that is set.  `sliding` (a
+        F.SlidingOptions, or True): sliding-window inference blends several softmaxes too, so it is refused like `tta`."""
         opts = self._calibration if calibration is False else calibration
         if opts is None:
             return
-        if tta and crf is not None and crf.iterations == 0:
+        if (tta or sliding) and crf is not None and crf.iterations == 0:
             raise ValueError("calibration: a CRF of 0 iterations behind several views has no Q to score and is those views alone: "
                              "drop the CRF")
         if len(opts.temps) == 1:
             return
-        why = "--tta" if tta else ("--crf" if crf is not None else ("SSCG_FUSE_PREDICT=0" if not F.FUSE_PREDICT[0] else None))
+        why = "--tta" if tta else "--sliding" if sliding else ("--crf" if crf is not None else ("SSCG_FUSE_PREDICT=0" if not F.FUSE_PREDICT[0] else None))
         if why is not None:
             raise ValueError("calibration: a temperature grid %r rescales the logits of the single fused head and does not combine with "
                              "%s (the probabilities there are not one softmax of logits): ask for temperature 1 only" % (opts.temps, why))
@@ -333,6 +334,30 @@ class runningScore(object):
         u8, self._device_hist = out[0], out[2]
         if cal:
             self.update_calibration(label_trues, out[3], size, probs=True, scale=inv_views(len(logits_list)))
+        if want:
+            self._count_boundary(label_trues, u8)
+
+    def update_logits_sw(self, label_trues, logits, plan):
+        """update_logits() under sliding-window inference: `logits` are the maps of every window of the batch in F.window_gather's
+        order (utils.sliding_logits), `plan` the F.sliding_plan of the batch's size; the windows' probabilities are blended and the
+        counts taken in one launch (F.predict_labels_sw).  With set_calibration() the head also writes the blended, normalised
+        probabilities, which F.calibration_stats scores with scale 1."""
+        cal = self._calibration is not None
+        size = (plan.OH, plan.OW)
+        if cal:
+            self.check_calibration(sliding=True)
+        if self._components is not None:
+            out = F.predict_labels_sw(logits, plan, want_u8=True, num_classes=self.n_classes, **({"want_prob": True} if cal else {}))
+            if cal:
+                self.update_calibration(label_trues, out[3], size, probs=True, scale=1.0)
+            self._filter_components(label_trues, out[0])
+            return
+        want = self._boundary is not None or self._surface is not None
+        out = F.predict_labels_sw(logits, plan, want_u8=want, label_true=label_trues, hist=self._device_hist,
+                                  num_classes=self.n_classes, **({"want_prob": True} if cal else {}))
+        u8, self._device_hist = out[0], out[2]
+        if cal:
+            self.update_calibration(label_trues, out[3], size, probs=True, scale=1.0)
         if want:
             self._count_boundary(label_trues, u8)
 
@@ -845,6 +870,72 @@ def tta_logits(net, images, views):
     return [net(F.resize_flip(images, tta_size(h, w, scale), flip)) for scale, flip in views], [flip for _, flip in views]
 
 
+_SLIDING_KEYS = ("size", "scale", "overlap", "blend", "sigma", "flip")
+
+
+def parse_sliding(spec, crop):
+    """`--sliding`: sliding-window inference of the evaluation, --validation and --testing.  The window is the crop (`crop` = (height,
+    width), the size the network was trained at).  "on" = scale=2,overlap=0.5,blend=gauss (an untuned default); else a comma list over
+    size=HxW or scale=F (exactly one: the evaluation size the images are kept at - scale multiplies the crop, rounded half up; never
+    below the crop), overlap=F (0..0.75, default 0.5), blend=gauss|const (default gauss), sigma=F (in (0, 1] of the window, default
+    0.125: MONAI's / nnU-Net's value, untuned here) and flip (every window also runs mirrored along W).  At most 16 windows per axis.
+    Returns a F.SlidingOptions, None for "" / None.  Raises ValueError naming the bad token."""
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    crop = (int(crop[0]), int(crop[1]))
+    if spec == "on":
+        spec = "scale=2,overlap=0.5,blend=gauss"
+    kw, seen = {}, set()
+    for tok in spec.split(","):
+        key, sep, val = tok.strip().partition("=")
+        if key not in _SLIDING_KEYS or key in seen or (key == "flip") == bool(sep):
+            raise ValueError("--sliding: %r is not 'on', flip or one key=value over size, scale, overlap, blend, sigma (each once)" % tok)
+        seen.add(key)
+        try:
+            if key == "flip":
+                kw["flip"] = True
+            elif key == "size":
+                hh, x, ww = val.partition("x")
+                if not x:
+                    raise ValueError
+                kw["size"] = (int(hh), int(ww))
+            elif key == "scale":
+                f = float(val)
+                if not (f > 0 and f < float("inf")):
+                    raise ValueError
+                kw["size"] = (int(crop[0] * f + 0.5), int(crop[1] * f + 0.5))
+            elif key == "blend":
+                kw["blend"] = val
+            else:
+                kw[key] = float(val)
+        except ValueError:
+            raise ValueError("--sliding: %r is not %s" % (tok, {"size": "size=<height>x<width>", "scale": "a positive scale"}.get(key, "a number")))
+    if ("size" in seen) == ("scale" in seen):
+        raise ValueError("--sliding: %r must name the evaluation size once, as size=HxW or as scale=F" % spec)
+    try:
+        return F.SlidingOptions(crop, **kw)
+    except ValueError as e:
+        raise ValueError("--sliding: %r: %s" % (spec, e))
+
+
+def sliding_logits(net, images, plan, chunk):
+    """`net` on every window of the batch (F.window_gather), `chunk` consecutive windows per forward - the loader's batch size, so the
+    network sees the batch size it was sized for; eval-mode BatchNorm and InstanceNorm do not depend on the chunking.  Returns the
+    logits of all windows in one buffer [N * views, C, h, w], the input of F.predict_labels_sw."""
+    wins = F.window_gather(images, plan)
+    total, chunk = wins.shape[0], max(1, int(chunk))
+    if total <= chunk:
+        return net(wins)
+    out = None
+    for i in range(0, total, chunk):
+        lg = net(wins[i:i + chunk])
+        if out is None:
+            out = F.empty_nhwc(total, lg.shape[1], lg.shape[2], lg.shape[3], lg.device)
+        out[i:i + lg.shape[0]].copy_(lg)
+    return out
+
+
 _CRF_KEYS = {"iters": "iterations", "radius": "radius", "dilation": "dilation", "wb": "w_bilateral", "ws": "w_spatial",
              "alpha": "theta_alpha", "beta": "theta_beta", "gamma": "theta_gamma"}
 
@@ -882,9 +973,19 @@ def crf_guide(images, size):
     return images if tuple(images.shape[2:]) == (int(size[0]), int(size[1])) else F.upsample_bilinear(images, size)
 
 
-def crf_scores(net, images, size, tta=None):
+def crf_scores(net, images, size, tta=None, sliding=None, chunk=None):
     """What F.crf_labels starts from, as (scores, probs): the logits of `net`'s single forward (probs=False), or with `tta` (a view list
-    of parse_tta) the summed probabilities of the views at `size` - F.predict_labels_ms asked for nothing else (probs=True)."""
+    of parse_tta) the summed probabilities of the views at `size` - F.predict_labels_ms asked for nothing else (probs=True) - or with
+    `sliding` (a F.SlidingOptions) the blended, normalised probabilities of the windows at the images' own size (probs=True; the
+    guide is then the batch itself), `net` run on `chunk` windows at a time (default: the batch size)."""
+    if sliding is not None:
+        if tta:
+            raise ValueError("sliding-window inference does not combine with --tta (its own key 'flip' mirrors the windows)")
+        plan = F.sliding_plan(images.shape[2], images.shape[3], sliding, images.device)
+        if (plan.OH, plan.OW) != (int(size[0]), int(size[1])):
+            raise ValueError("crf_scores: sliding-window scores have the images' size %dx%d, not %r" % (plan.OH, plan.OW, tuple(size)))
+        logits = sliding_logits(net, images, plan, chunk or images.shape[0])
+        return F.predict_labels_sw(logits, plan, want_prob=True, want_u8=False)[3], True
     if tta:
         return F.predict_labels_ms(*tta_logits(net, images, tta), size, want_prob=True, want_u8=False)[3], True
     return net(images), False

@@ -19,10 +19,13 @@ def test(args, test_loader=None):
     utils = importlib.import_module(PKG + ".utils")
     n_channels = {'voc2012': 21, 'cityscapes': 20, 'acdc': 4}[args.dataset]
     dev = torch.device("cuda", args.gpu_ids[0])
+    # --sliding: the images keep the evaluation size, Gsi runs on overlapping crop-sized windows, the label maps have that size
+    sliding = utils.parse_sliding(getattr(args, 'sliding', ''), (args.crop_height, args.crop_width))
     if test_loader is None:
         du = importlib.import_module(PKG + ".data_utils")
         from torch.utils.data import DataLoader
-        tr = du.get_transformation((args.crop_height, args.crop_width), resize=True, dataset=args.dataset, device_finish=True)
+        tr = du.get_transformation(sliding.size if sliding is not None else (args.crop_height, args.crop_width), resize=True,
+                                   dataset=args.dataset, device_finish=True)
         cls = {'voc2012': du.VOCDataset, 'cityscapes': du.CityscapesDataset, 'acdc': du.ACDCDataset}[args.dataset]
         root = {'voc2012': './data/VOC2012', 'cityscapes': './data/Cityscape', 'acdc': './data/ACDC'}[args.dataset]
         test_set = cls(root_path=root, name='test', ratio=0.5, transformation=tr, augmentation=None)
@@ -43,6 +46,8 @@ def test(args, test_loader=None):
     out = os.path.join(args.results_dir, 'unsupervised' if semi else 'supervised')
     os.makedirs(out, exist_ok=True)
     tta = utils.parse_tta(getattr(args, 'tta', ''))
+    if sliding is not None and tta:
+        raise ValueError("--sliding does not combine with --tta: 'flip' is --sliding's own key")
     crf = utils.parse_crf(getattr(args, 'crf', ''))
     comp = utils.parse_components(getattr(args, 'components', ''))
     # --components: the predicted label maps go through the connected-component filter on the device before they are copied and saved
@@ -51,6 +56,18 @@ def test(args, test_loader=None):
     with torch.no_grad():
         for i, (image_test, image_name) in enumerate(test_loader):
             image_test = utils.cuda(image_test, args.gpu_ids)
+            if sliding is not None:     # --sliding: Gsi on the windows of the batch, blended into one uint8 map at the images' size
+                size = image_test.shape[2:]
+                if crf is not None:
+                    scores, probs = utils.crf_scores(Gsi, image_test, size, sliding=sliding, chunk=args.batch_size)
+                    prediction = filt(F.crf_labels(scores, image_test, size, crf, probs=probs)[0]).cpu().numpy()
+                else:
+                    plan = F.sliding_plan(size[0], size[1], sliding, image_test.device)
+                    prediction = filt(F.predict_labels_sw(utils.sliding_logits(Gsi, image_test, plan, args.batch_size), plan)[0]).cpu().numpy()
+                for j in range(prediction.shape[0]):
+                    utils.colorize_mask(prediction[j], args.dataset).save(os.path.join(out, image_name[j] + '.png'))
+                print('Epoch-', str(i + 1), ' Done!')
+                continue
             logits = None if tta else Gsi(image_test)
             if crf is not None:     # --crf: the windowed dense CRF, guided by the images, at the size the plain path predicts at
                 size = image_test.shape[2:] if tta else logits.shape[2:]
