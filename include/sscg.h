@@ -824,6 +824,37 @@ size_t sscg_crf_workspace(int N, int C, int OH, int OW, int iterations);
 int sscg_crf_head(const float* x, int kind, int N, int H, int W, int C, int OH, int OW, const float* img, int IC,
                   const sscg_crf_params* p, float* q_out, int64_t* index, uint8_t* label_u8, const int64_t* label_true, int64_t* hist,
                   void* ws, size_t ws_bytes, void* stream);
+/* ------------------------------------------------------------------ gated (relaxed dense) CRF loss of a softmax map: the regulariser
+ * of Tang et al. (ECCV 2018) / Obukhov et al. (2019) - two nearby pixels of similar colour that disagree are penalised - with the
+ * pairwise weight of sscg_crf_head.  The reference has no such term, so there is no call site to name; opt-in (`--unl_crf`), the
+ * training-side counterpart of `--crf`.  (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.)
+ *
+ * sscg_crf_loss_fwd: p fp32 [N][OH][OW][C], the channels-last softmax map (rows need not sum to exactly 1), 1 <= C <= 64; img the guide
+ * image fp32 [N][OH][OW][IC], 1 <= IC <= 4; prm as for sscg_crf_head, its `iterations` member ignored.  k(i, j) is sscg_crf_head's
+ * pairwise weight exactly - the formula, the three 1 / (2 theta^2) constants formed in double and rounded to fp32 once, the same
+ * operations - over the taps in row-major (dy, dx) order, centre excluded; a tap outside the map is skipped, nothing is renormalised.
+ * Per pixel i:
+ *   msg_c(i) = sum over the taps of k(i, j) * p_c(j): one fp32 accumulator per class, filled with fmaf in tap order - the bits of the
+ *              message of a mean-field step of sscg_crf_head on Q = p;
+ *   ksum(i)  = sum over the taps of k(i, j), in the same tap order with plain fp32 adds;
+ *   e(i)     = ksum(i) - sum_c p_c(i) * msg_c(i): the product sum over c ascending with fmaf from 0, then one subtraction.
+ * loss = (sum_i e(i)) / M, M = N * OH * OW: e(i) and ksum(i) widened to fp64, one record (sum e, sum ksum) per 16 x 16 tile in a fixed
+ * order, the records summed in a fixed order by one block; no float atomics - the same bits from call to call, whatever ws held.
+ *   loss  fp32 [1] = (float)(sums[0] / M);      sums fp64 [2] = (sum e, sum ksum);
+ *   coef  (nullable: the value only) fp32 [N][OH][OW][C]: coef[i][c] = s * msg_c(i), s = (float)(-2.0 / (double)M), one fp32 multiply.
+ *         It is d loss / d p_c(i) exactly: k(i, j) == k(j, i) bit for bit and the tap sets are symmetric, so the scatter half of the
+ *         derivative equals the gather half.  No gradient reaches the guide image.
+ * For rows that sum to 1, e(i) = sum over the taps of k(i, j) (1 - p(i) . p(j)) >= 0.  The VALUE of e cancels where the prediction is
+ * already smooth (ksum and the product sum agree in their leading digits), so its absolute error is a few ulp of ksum, not of e; the
+ * gradient is a plain sum of non-negative products and does not cancel.
+ * ws: sscg_crf_loss_workspace(N, OH, OW) bytes (one record of two doubles per tile), fully written before it is read.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (null p / img / prm / loss / sums; non-positive sizes; C outside 1..64; IC outside 1..4;
+ * radius outside 1..5; dilation < 1; a weight that is negative or not finite; a theta that is not > 0, or so small that 1 / (2 theta^2)
+ * is not a finite fp32 number), SSCG_ERR_UNSUPPORTED (radius * dilation > 16; N*OH*OW*C >= 2^31), SSCG_ERR_WORKSPACE.
+ * The backward of a node built on it is sscg_lovasz_scale_add(coef, g, NULL, out, n): out = g * coef. */
+size_t sscg_crf_loss_workspace(int N, int OH, int OW);
+int sscg_crf_loss_fwd(const float* p, int N, int OH, int OW, int C, const float* img, int IC, const sscg_crf_params* prm, float* loss,
+                      double* sums, float* coef, void* ws, size_t ws_bytes, void* stream);
 /* ------------------------------------------------------------------ contour scores of the evaluation: the counts behind the Boundary
  * IoU (Cheng et al., CVPR 2021) and the trimap mIoU of the DeepLab papers, beside the confusion matrix of runningScore (utils.py:357-412,
  * the call site whose evaluation this extends; the reference has neither score).  Opt-in (`--boundary`), forward only, never launched by

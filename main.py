@@ -3,7 +3,7 @@
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
---calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp,
+--calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp, --unl_crf, --unl_crf_kernel,
 --lovasz_weight, --lovasz_per_image, --lovasz_classes, --lovasz_skip, --sliding.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL).  --augment's items `cutmix=` / `classmix=` mix two samples of a
 labelled batch, labels with pixels, inside the device-side batch finish; their class ids are checked against --dataset here."""
@@ -66,6 +66,8 @@ class _Args(Namespace):
     unl_pseudo = 0.0
     unl_pseudo_thresh = None        # 0.9 once --unl_pseudo is given
     unl_ramp = 0
+    unl_crf = 0.0
+    unl_crf_kernel = ""
     lovasz_weight = 0.0
     lovasz_per_image = False
     lovasz_classes = "present"
@@ -227,6 +229,16 @@ def get_args(argv=None):
     parser.add_argument("--unl_ramp", type=int, default=SUPPRESS, metavar="N",
                         help="raise the three --unl_* weights linearly over the first N epochs, F * min(1, epoch / N); N >= 0, "
                              "0 = constant (default: 0)")
+    parser.add_argument("--unl_crf", type=float, default=SUPPRESS, metavar="F",
+                        help="add F times the gated CRF loss (Tang et al., ECCV 2018; Obukhov et al., 2019) of the UNLABELLED batch's "
+                             "prediction to the generator loss: nearby pixels of similar colour in the unlabelled image that are "
+                             "predicted differently are penalised, the mean over the pixels of sum_j k(i, j) (1 - p(i) . p(j)) with "
+                             "--crf's pairwise kernel; the training-side counterpart of --crf; reported as unl_crf; --unl_ramp "
+                             "applies; the supervised model ignores it; F >= 0, 0 = off (default: off)")
+    parser.add_argument("--unl_crf_kernel", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="with --unl_crf: the pairwise kernel in --crf's grammar, a comma list of key=value over radius, dilation, "
+                             "wb, ws, alpha, beta, gamma ('iters' is accepted and ignored), or 'on' (default: --crf's defaults, "
+                             "untuned for training)")
     parser.add_argument("--lovasz_weight", type=float, default=SUPPRESS, metavar="F",
                         help="add F times the Lovasz-softmax loss (Berman et al., CVPR 2018), the mIoU surrogate, to every "
                              "ground-truth cross entropy (lab_loss_CE, gt_cycle_loss, the supervised loss), inside that term's own "
@@ -327,6 +339,15 @@ def get_args(argv=None):
             parser.error("--unl_pseudo_thresh must lie in [0, 1]")
     if args.unl_ramp < 0:
         parser.error("--unl_ramp must be an integer >= 0")
+    if not args.unl_crf >= 0.0 or args.unl_crf == float("inf"):
+        parser.error("--unl_crf must be a finite number >= 0")
+    if args.unl_crf_kernel.strip():
+        if not args.unl_crf > 0.0:
+            parser.error("--unl_crf_kernel needs --unl_crf F with F > 0")
+        try:
+            importlib.import_module(PKG + ".utils").parse_unl_crf_kernel(args.unl_crf_kernel)
+        except ValueError as e:
+            parser.error(str(e))
     if not args.lovasz_weight >= 0.0 or args.lovasz_weight == float("inf"):
         parser.error("--lovasz_weight must be a finite number >= 0")
     if args.lovasz_skip.strip():

@@ -162,6 +162,8 @@ SIGNATURES = {
     "sscg_predict_head_sw": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "sscg_crf_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "sscg_crf_head": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _cp, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "sscg_crf_loss_workspace": (_sz, [_i, _i, _i]),
+    "sscg_crf_loss_fwd": (_i, [_p, _i, _i, _i, _i, _p, _i, _cp, _p, _p, _p, _p, _sz, _p]),
     "sscg_boundary_counts": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "sscg_surface_workspace": (_sz, [_i, _i, _i, _i]),
     "sscg_surface_stats": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),

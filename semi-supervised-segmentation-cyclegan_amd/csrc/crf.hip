@@ -8,6 +8,7 @@
 // thread owns its pixel from the first tap to the label, and nothing is summed across threads - so the result depends neither on the
 // tiling nor on N.
 #include "common.h"
+#include "crf_common.h"
 #include "head_common.h"
 #include "sscg_internal.h"
 #include <cfloat>
@@ -16,28 +17,8 @@
 namespace {
 
 constexpr int MAX_BLOCKS = 2048;                      // crf_init / crf_first_max: 8 workgroups per CU, grid-stride beyond
-constexpr int TILE = 16;                              // a workgroup of 256 threads owns TILE x TILE output pixels
-constexpr int RMAX = 5;                               // radius <= 5: at most 11 x 11 - 1 = 120 taps
-constexpr int SIDE = 2 * RMAX + 1;
-constexpr int TAPS = SIDE * SIDE;                     // the full grid, centre included (its slot is never read)
-constexpr int STAGE = 4;                             // global loads a thread has in flight while a Q quad is staged
-constexpr int REACH_MAX = 16;                         // radius * dilation: the halo is at most 48 x 48 pixels
+constexpr int TILE = CRF_TILE, RMAX = CRF_RMAX, SIDE = CRF_SIDE, STAGE = CRF_STAGE, REACH_MAX = CRF_REACH_MAX;      // crf_common.h
 constexpr int KIND_LOGITS_RESIZE = 0, KIND_LOGITS_IDENT = 1, KIND_PROBS = 2;
-
-// The per-tap constants, made on the host, in the kernel's argument block (uniform loads): slot (dy + RMAX) * SIDE + (dx + RMAX).
-struct CrfTaps {
-    float spatial[TAPS];      // w_spatial * expf(-d2 * ig)
-    float d2a[TAPS];          // d2 * ia
-};
-
-struct CrfGeom {
-    int C, OH, OW, IC;
-    int r, d, reach;          // radius, dilation, radius * dilation
-    int side, pitch;          // halo side TILE + 2 * reach; its row pitch in LDS (pixels, a multiple of 16)
-    int tiles_x, tiles_y;
-    FastDiv dtx, dty, dside;
-    float wb, ib;
-};
 
 // u and Q0 of one output pixel.  LOGITS: u_c = (z_c - m) - logf(s), m = max z, s = sum expf(z_c - m) over c ascending; PROBS:
 // u_c = logf(max(x_c, FLT_MIN)).  Q0 = softmax(u) by sscg_softmax_exp's operations.
@@ -81,13 +62,6 @@ __global__ __launch_bounds__(256) void crf_init_kernel(const float* __restrict__
         for (int c = 0; c < (CT ? CT : SSCG_MAXC); ++c)
             if (CT || c < C) qp[c] = v[c] * inv;
     }
-}
-
-// k(i, j) = w_bilateral * expf(-(d2 * ia + c2 * ib)) + w_spatial * expf(-d2 * ig); c2 over the (zero-padded) four guide channels
-__device__ __forceinline__ float crf_weight(const float4& a, const float4& b, float d2a, float spatial, float wb, float ib) {
-    const float e0 = a.x - b.x, e1 = a.y - b.y, e2 = a.z - b.z, e3 = a.w - b.w;
-    const float c2 = e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-    return wb * expf(-(d2a + c2 * ib)) + spatial;
 }
 
 // One mean-field step.  Workgroup = one TILE x TILE tile of one sample, thread = one pixel of it; the tile's halo (side x side
@@ -265,16 +239,6 @@ void launch_iter(bool last, dim3 grid, size_t stage_lds, size_t bins_lds, hipStr
                            (uint8_t*)nullptr, (const int64_t*)nullptr, (unsigned long long*)nullptr, g, tp);
 }
 
-bool finite_nonneg(float w) { return w >= 0.f && w < INFINITY; }
-
-// 1 / (2 theta^2) formed in double and rounded to fp32 once; false unless theta > 0 and the result is a finite fp32 number
-bool inv_two_theta_sq(float theta, float* out) {
-    if (!(theta > 0.f)) return false;
-    const float v = (float)(1.0 / (2.0 * (double)theta * (double)theta));
-    *out = v;
-    return v < INFINITY;
-}
-
 }  // namespace
 
 extern "C" size_t sscg_crf_workspace(int N, int C, int OH, int OW, int iterations) {
@@ -288,9 +252,9 @@ extern "C" int sscg_crf_head(const float* x, int kind, int N, int H, int W, int 
     if (!x || !img || !p || (kind != SSCG_CRF_LOGITS && kind != SSCG_CRF_PROBS)) return SSCG_ERR_BAD_ARG;
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C > SSCG_MAXC || OH <= 0 || OW <= 0 || IC < 1 || IC > 4) return SSCG_ERR_BAD_ARG;
     if (p->radius < 1 || p->radius > RMAX || p->dilation < 1 || p->iterations < 0) return SSCG_ERR_BAD_ARG;
-    if (!finite_nonneg(p->w_bilateral) || !finite_nonneg(p->w_spatial)) return SSCG_ERR_BAD_ARG;             // (false for a NaN)
+    if (!crf_finite_nonneg(p->w_bilateral) || !crf_finite_nonneg(p->w_spatial)) return SSCG_ERR_BAD_ARG;             // (false for a NaN)
     float ia, ib, ig;
-    if (!inv_two_theta_sq(p->theta_alpha, &ia) || !inv_two_theta_sq(p->theta_beta, &ib) || !inv_two_theta_sq(p->theta_gamma, &ig))
+    if (!crf_inv_two_theta_sq(p->theta_alpha, &ia) || !crf_inv_two_theta_sq(p->theta_beta, &ib) || !crf_inv_two_theta_sq(p->theta_gamma, &ig))
         return SSCG_ERR_BAD_ARG;
     if ((!q_out && !index && !label_u8 && !hist) || (label_true == nullptr) != (hist == nullptr)) return SSCG_ERR_BAD_ARG;
     if (p->iterations == 0 && q_out) return SSCG_ERR_BAD_ARG;                    // no mean-field step, no Q
@@ -331,21 +295,8 @@ extern "C" int sscg_crf_head(const float* x, int kind, int N, int H, int W, int 
     }
 
     CrfGeom g;
-    g.C = C; g.OH = OH; g.OW = OW; g.IC = IC;
-    g.r = p->radius; g.d = p->dilation; g.reach = p->radius * p->dilation;
-    g.side = TILE + 2 * g.reach;
-    g.pitch = (g.side + 15) / 16 * 16;
-    g.tiles_x = (OW + TILE - 1) / TILE; g.tiles_y = (OH + TILE - 1) / TILE;
-    g.dtx = make_fastdiv(g.tiles_x); g.dty = make_fastdiv(g.tiles_y); g.dside = make_fastdiv(g.side);
-    g.wb = p->w_bilateral; g.ib = ib;
     CrfTaps tp;
-    for (int dy = -RMAX; dy <= RMAX; ++dy)
-        for (int dx = -RMAX; dx <= RMAX; ++dx) {
-            const float d2 = (float)((dy * g.d) * (dy * g.d) + (dx * g.d) * (dx * g.d));       // <= 2 * 16^2 inside the radius: exact
-            const int t = (dy + RMAX) * SIDE + dx + RMAX;
-            tp.spatial[t] = p->w_spatial * expf(-d2 * ig);
-            tp.d2a[t] = d2 * ia;
-        }
+    crf_setup(C, OH, OW, IC, p->radius, p->dilation, p->w_bilateral, p->w_spatial, ia, ib, ig, &g, &tp);
     const size_t stage_lds = (size_t)g.side * g.pitch * sizeof(float4);             // <= 36 KB
     const dim3 grid((unsigned)((size_t)N * g.tiles_x * g.tiles_y));
     for (int it = 0; it < p->iterations; ++it) {

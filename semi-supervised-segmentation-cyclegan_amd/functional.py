@@ -4092,6 +4092,66 @@ def upsample_softmax_unl(x, size, unl=None, want_soft=True, want_pseudo=False):
     return soft, l_ent, l_msq, l_pl, {"sums": sums, "pseudo": pseudo if want_pseudo else None}
 
 
+# ----------------------------------------------------------------------------- the gated CRF loss (opt-in; include/sscg.h: sscg_crf_loss_fwd)
+def _crf_loss_options(crf):
+    """None = CrfOptions(): the UNTUNED defaults of the inference CRF, which nobody has tuned for training either."""
+    if crf is None:
+        return CrfOptions()
+    if isinstance(crf, dict):
+        crf = CrfOptions(**crf)
+    if not isinstance(crf, CrfOptions):
+        raise TypeError("crf must be a functional.CrfOptions (or a dict of its arguments), not %r" % (crf,))
+    return crf
+
+
+def crf_loss_fwd(p, image, crf, want_coef=True):
+    """sscg_crf_loss_fwd on a channels-last fp32 softmax map p [N,C,OH,OW] and a channels-last guide image [N,IC,OH,OW]: (loss, sums fp64
+    [2] = (sum e, sum ksum), coef fp32 [N,OH,OW,C] = d loss / d p or None).  No autograd: crf_loss wraps it."""
+    n, c, oh, ow = p.shape
+    loss = _scalar(p.device)
+    sums = torch.empty((2,), dtype=torch.float64, device=p.device)
+    coef = torch.empty((n, oh, ow, c), dtype=torch.float32, device=p.device) if want_coef else None
+    ws = torch.empty(lib.sscg_crf_loss_workspace(n, oh, ow), dtype=torch.uint8, device=p.device)
+    check(lib.sscg_crf_loss_fwd(p.data_ptr(), n, oh, ow, c, image.data_ptr(), int(image.shape[1]), C.byref(crf.params()), loss.data_ptr(),
+                                sums.data_ptr(), _ptr(coef), ws.data_ptr(), ws.numel(), _stream()), "sscg_crf_loss_fwd")
+    return loss, sums, coef
+
+
+class CrfLossFn(torch.autograd.Function):
+    """The gated CRF loss of a softmax map [N,C,OH,OW] under a guide image [N,IC,OH,OW] (include/sscg.h: sscg_crf_loss_fwd).  The loss
+    is quadratic in the map and the pairwise weight symmetric, so the forward leaves d loss / d p - kept only when the map needs a
+    gradient - and the backward is one sscg_lovasz_scale_add launch on it.  The image gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, probs, image, crf):
+        _need_hip(probs, f32_only=True)
+        _need_hip(image, f32_only=True)
+        loss, _, coef = crf_loss_fwd(to_nhwc(probs), to_nhwc(image), crf, ctx.needs_input_grad[0])
+        ctx.save_for_backward(coef)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (coef,) = ctx.saved_tensors
+        return _lovasz_upstream(coef, g.contiguous(), None), None, None
+
+
+def crf_loss(probs, image, crf=None):
+    """The gated (relaxed dense) CRF loss (Tang et al., ECCV 2018; Obukhov et al., 2019) of the softmax map `probs` fp32 [N,C,OH,OW]
+    guided by `image` fp32 [N,IC,OH,OW] (IC <= 4, the map's size): the mean over the pixels of sum_j k(i, j) (1 - p(i) . p(j)) over the
+    dilated window of `crf` - a CrfOptions, a dict of its arguments, or None for CrfOptions(), whose defaults are UNTUNED for training
+    as they are for inference; its `iterations` is not used.  Differentiable in `probs` only."""
+    crf = _crf_loss_options(crf)
+    _need_hip(probs, f32_only=True)
+    _need_hip(image, f32_only=True)
+    if probs.dim() != 4 or image.dim() != 4:
+        raise _lib.SscgError("crf_loss: a 4-D softmax map and a 4-D guide image expected")
+    n, c, oh, ow = probs.shape
+    if tuple(image.shape) != (n, image.shape[1], oh, ow) or not 1 <= image.shape[1] <= 4:
+        raise _lib.SscgError("crf_loss: the guide image must be [N, 1..4, OH, OW] at the map's size, got %s" % (tuple(image.shape),))
+    return CrfLossFn.apply(probs, image.detach(), crf)
+
+
 class MSEConstFn(torch.autograd.Function):
     """nn.MSELoss()(x, full_like(x, target)) - the LSGAN terms."""
 

@@ -120,8 +120,9 @@ GEN_LOSS_BASE_TERMS = 6     # lab_loss_CE, lab_loss_MSE, img_gen_loss, gt_gen_lo
 
 def gen_loss_terms(variants=(), dice=False, boundary=False, lovasz=False, ssim=False, unl=0):
     """How many terms semisuper_cycleGAN.step hands to F.weighted_sum as gen_loss: the reference's six, one per enabled region loss
-    (Dice, boundary, Lovasz) on each of the two ground-truth heads, `unl` unlabelled-head losses (0..3), an SSIM term beside every
-    image L1 (lab_loss_MSE; img_cycle_l1 under l1_cycle), and the variants' own terms.  Pure: the step checks its assembled list
+    (Dice, boundary, Lovasz) on each of the two ground-truth heads, `unl` losses of the unlabelled prediction (0..4: the unlabelled
+    head's three and the gated CRF loss), an SSIM term beside every image L1 (lab_loss_MSE; img_cycle_l1 under l1_cycle), and the
+    variants' own terms.  Pure: the step checks its assembled list
     against it, tests/test_step_options_host.py walks every flag combination main.py accepts."""
     variants = set(variants)
     n = GEN_LOSS_BASE_TERMS + 2 * (bool(dice) + bool(boundary) + bool(lovasz)) + int(unl) + bool(ssim)
@@ -139,7 +140,7 @@ def gen_loss_terms_of(args):
     on = lambda key: float(getattr(args, key, 0.0) or 0.0) > 0.0
     return gen_loss_terms((v for v in str(getattr(args, "variants", "") or "").split(",") if v), dice=on("dice_weight"),
                           boundary=on("boundary_loss"), lovasz=on("lovasz_weight"), ssim=on("ssim_weight"),
-                          unl=sum(on(k) for k in ("unl_entropy", "unl_maxsq", "unl_pseudo")))
+                          unl=sum(on(k) for k in ("unl_entropy", "unl_maxsq", "unl_pseudo", "unl_crf")))
 
 
 def _optim_options(args, ema):
@@ -428,8 +429,23 @@ class _UnlabelledLosses(object):
     unl_options = None              # functional.UnlabelledOptions when a weight is > 0: no launch, loss key or checkpoint key otherwise
     unl_ramp = 0                    # epochs over which the three weights rise linearly from 0; 0 = constant
     _unl_scale = 1.0                # min(1, epoch / ramp) of the current epoch (set_unl_epoch)
+    # --unl_crf / --unl_crf_kernel (opt-in): the gated CRF loss of the same prediction under the unlabelled image (functional.crf_loss:
+    # one stencil launch on the softmax map the head returns, one scale launch backward), a term of its own under the same ramp
+    unl_crf = 0.0                   # its weight; 0 = no launch, loss key or checkpoint key
+    unl_crf_options = None          # functional.CrfOptions of the pairwise kernel when the weight is > 0
+
+    def _init_unl_crf(self, args):
+        w = float(getattr(args, "unl_crf", 0.0) or 0.0)
+        if not (w >= 0.0 and w < float("inf")):
+            raise ValueError("--unl_crf %r must be a finite number >= 0" % (getattr(args, "unl_crf", None),))
+        spec = str(getattr(args, "unl_crf_kernel", "") or "").strip()
+        if spec and not w > 0.0:
+            raise ValueError("--unl_crf_kernel needs --unl_crf F with F > 0")
+        if w > 0.0:
+            self.unl_crf, self.unl_crf_options = w, utils.parse_unl_crf_kernel(spec)
 
     def _init_unl(self, args):
+        self._init_unl_crf(args)
         w = {}
         for key in ("unl_entropy", "unl_maxsq", "unl_pseudo"):
             w[key] = float(getattr(args, key, 0.0) or 0.0)
@@ -444,23 +460,35 @@ class _UnlabelledLosses(object):
         ramp = getattr(args, "unl_ramp", 0) or 0
         if isinstance(ramp, bool) or ramp != int(ramp) or int(ramp) < 0:
             raise ValueError("--unl_ramp %r must be an integer >= 0" % (ramp,))
-        if not any(v > 0.0 for v in w.values()):
+        if not any(v > 0.0 for v in w.values()) and not self.unl_crf > 0.0:
             return
         self.unl_ramp = int(ramp)
-        self.unl_options = F.UnlabelledOptions(entropy=w["unl_entropy"], maxsq=w["unl_maxsq"], pseudo=w["unl_pseudo"], thresh=thresh)
+        if any(v > 0.0 for v in w.values()):
+            self.unl_options = F.UnlabelledOptions(entropy=w["unl_entropy"], maxsq=w["unl_maxsq"], pseudo=w["unl_pseudo"], thresh=thresh)
         self.set_unl_epoch(0)
 
     def set_unl_epoch(self, epoch):
-        """--unl_ramp: the factor on the three unlabelled weights for `epoch` (utils.boundary_loss_schedule's arithmetic); train() calls
+        """--unl_ramp: the factor on the unlabelled weights for `epoch` (utils.boundary_loss_schedule's arithmetic); train() calls
         it once per epoch.  Off: nothing changes."""
-        if self.unl_options is not None:
+        if self.unl_options is not None or self.unl_crf > 0.0:
             self._unl_scale = utils.boundary_loss_schedule(1.0, self.unl_ramp, epoch)
         return self._unl_scale
 
-    def _unl_head(self, fake_logits, extras, extra_terms, extra_weights):
+    def _unl_head(self, fake_logits, extras, extra_terms, extra_weights, unl_img=None):
         """The softmax map of the unlabelled prediction (:401-402): the plain fused head by default.  With an --unl_* weight the head
         also returns the enabled losses: each joins the extras under its own key with its own ramped weight, and --unl_pseudo reports
-        the kept share K / V - a device scalar from the sums the forward left, no sync."""
+        the kept share K / V - a device scalar from the sums the forward left, no sync.  --unl_crf: the gated CRF loss of the map under
+        `unl_img`, a node of its own beside the head - autograd adds its gradient to the map's."""
+        fake_gt = self._unl_head_losses(fake_logits, extras, extra_terms, extra_weights)
+        if self.unl_crf > 0.0:
+            if unl_img is None:
+                raise ValueError("--unl_crf: _unl_head needs the unlabelled image batch, the guide of the CRF loss")
+            extras["unl_crf"] = F.crf_loss(fake_gt, utils.crf_guide(unl_img, self.crop), self.unl_crf_options)
+            extra_terms.append(extras["unl_crf"])
+            extra_weights.append(self.unl_crf * self._unl_scale)
+        return fake_gt
+
+    def _unl_head_losses(self, fake_logits, extras, extra_terms, extra_weights):
         o = self.unl_options
         if o is None:
             return F.upsample_softmax_ce(fake_logits, self.crop)[0]
@@ -684,7 +712,7 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         ohem_kept = {}
         lab_gt, lab_loss_CE, lab_loss_dice = self._head(lab_logits, labels, True, ohem_kept)   # (plain nn.CrossEntropyLoss() by default)
         extra_terms, extra_weights, extras = [], [], {}
-        fake_gt = self._unl_head(fake_logits, extras, extra_terms, extra_weights)    # (--unl_*: plus the enabled losses)
+        fake_gt = self._unl_head(fake_logits, extras, extra_terms, extra_weights, unl_img)    # (--unl_*: plus the enabled losses)
         if fork:
             main.wait_event(gis_first)
         # (Gis(onehot_gt) and Gis(fake_gt) as ONE grouped-BatchNorm pass on the main lane was built in round 4 and measured slower than
@@ -1132,6 +1160,8 @@ class supervised_model(_WeightedCE):
             print("--ssim_weight is ignored: the supervised model has no image term")
         if any(float(getattr(args, k, 0.0) or 0.0) != 0.0 for k in ("unl_entropy", "unl_maxsq", "unl_pseudo")):
             print("--unl_entropy / --unl_maxsq / --unl_pseudo are ignored: the supervised model has no unlabelled batch")
+        if float(getattr(args, "unl_crf", 0.0) or 0.0) != 0.0:
+            print("--unl_crf is ignored: the supervised model has no unlabelled batch")
         self.running_metrics_val = utils.runningScore(self.n_channels, args.dataset)
         if not os.path.isdir(args.checkpoint_dir):
             os.makedirs(args.checkpoint_dir, exist_ok=True)

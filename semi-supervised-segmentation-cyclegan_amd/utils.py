@@ -968,6 +968,15 @@ def parse_crf(spec):
         raise ValueError("--crf: %r: %s" % (spec, e))
 
 
+def parse_unl_crf_kernel(spec):
+    """`--unl_crf_kernel`: the pairwise kernel of the gated CRF loss, in parse_crf's grammar (`iters` is accepted and ignored: the loss
+    has no mean-field step).  "" / None / "on" = F.CrfOptions(), the UNTUNED defaults.  Raises ValueError naming the flag."""
+    try:
+        return parse_crf(spec) or F.CrfOptions()
+    except ValueError as e:
+        raise ValueError(str(e).replace("--crf:", "--unl_crf_kernel:", 1))
+
+
 def crf_guide(images, size):
     """The CRF's guide image: the batch as the network sees it (normalised), resized to `size` when it has another."""
     return images if tuple(images.shape[2:]) == (int(size[0]), int(size[1])) else F.upsample_bilinear(images, size)
