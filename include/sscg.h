@@ -648,6 +648,41 @@ int sscg_unl_bwd(const float* x, const uint8_t* pseudo, int N, int H, int W, int
                  const float* g_pl, const double* sums, float* dx, void* stream);
 int sscg_upsample_head_bwd_u(const float* x, const uint8_t* pseudo, const float* dy_soft, const float* g_ent, const float* g_msq,
                              const float* g_pl, const double* sums, float* dx, int N, int H, int W, int C, int OH, int OW, void* stream);
+/* Mean-teacher consistency of the UNLABELLED head (opt-in, `--unl_teacher`; the reference has none): the student's prediction against
+ * the prediction of the same network under the exponential moving average of its weights (Tarvainen & Valpola 2017; French et al. 2020
+ * for segmentation), as a squared distance of the probability maps and as a cross entropy against the teacher's confidence-masked hard
+ * labels (FixMatch, Sohn et al. 2020).  x = the student's logits [N][H][W][C], t = the teacher's, same shape, 1 <= C <= 64; flip
+ * (nullable) uint8 [N]: non-zero = that sample's teacher saw the image mirrored on W.  Per output pixel (n, oy, ox), V = N * OH * OW:
+ *     z  = x resized to [OH][OW] (bilinear, align_corners=True, the pinned arithmetic of sscg_upsample_bilinear_fwd as in sscg_unl_fwd;
+ *          OH == H && OW == W: the flat form, no interpolation arithmetic), u_c = z_c - max z, s = sum_c exp(u_c), p_c = exp(u_c) / s -
+ *          the bits of the head's softmax map;
+ *     zt = t resized the same way, read at column ox' = flip[n] ? OW - 1 - ox : ox - sscg_upsample_bilinear_fwd followed by a mirror
+ *          on W; v_c = zt_c * inv_temp, ONE fp32 multiply after the resize (sscg_calibration's temperature); q = softmax(v);
+ *     y* = the first maximum of q (sscg_argmax_onehot's rule), conf = q[y*];  KEPT <=> conf >= thresh;
+ *     d  = sum_c (p_c - q_c)^2: the fp32 difference of the two rounded probabilities, then fmaf from 0 with c ascending;
+ *     ce = ln s - u[y*]: sscg_unl_fwd's kept term, from the student's logit difference, never from log p;
+ *     agree <=> kept and the first maximum of p is y*.
+ * The teacher, y* and the keep decision are constants: no gradient flows through them.
+ *   sums   fp64 [4] = (sum over the kept pixels of d, A = the agreeing kept pixels, sum over the kept pixels of ce, K = the kept pixels):
+ *          index 3 is K, what the pseudo-label slot of sscg_upsample_head_bwd_u / sscg_unl_bwd divides by;
+ *   losses fp32 [2] = (L_mse = sums[0] / (C V), L_ce = sums[2] / max(K, 1)) - the squared distance is averaged over every class of every
+ *          pixel (French et al.): a dropped pixel lowers it, and its scale is known at launch;
+ *   pseudo (nullable) uint8 [N][OH][OW] = y* of a kept pixel, 255 of a dropped one: sscg_unl_fwd's map, from the teacher;
+ *   coef   (nullable) fp32 [N][OH][OW][C] = s (p_c - q_c) at a kept pixel, s = (float)(2.0 / ((double)C V)), one multiply; exactly +0 at
+ *          a dropped pixel.  It is d L_mse / d p_c, the dy_soft operand of the head's backward entries: the backward of a node built on
+ *          this entry is sscg_lovasz_scale_add(coef, g_mse, dy_soft, out, n) and ONE sscg_upsample_head_bwd_u launch whose pseudo-label
+ *          slot takes (pseudo, g_ce, sums).  No backward entry of its own.
+ * sscg_unl_fwd's frame: one thread per output pixel, no block straddles a sample, K and A per wave by ballot, one fp64 record per block
+ * in the workspace, a reduce step in index order and a one-block finish; no float atomics - the same call twice gives the same bits,
+ * whatever ws held - and the resized form gives the bits of the identity form on sscg_upsample_bilinear_fwd's output (mirrored where
+ * flip is set).  With t == x, flip NULL and inv_temp == 1: pseudo, sums[3] and sums[2] are sscg_unl_fwd's at the same thresh, sums[0]
+ * is 0, A == K and coef is all zeros.  ws: sscg_teacher_workspace(N, OH, OW) bytes, contents irrelevant.
+ * Errors before any HIP call: SSCG_ERR_BAD_ARG (a null x, t, losses or sums; non-positive sizes; C outside 1..64; thresh outside [0, 1]
+ * or NaN; inv_temp not finite or <= 0), SSCG_ERR_UNSUPPORTED (N*OH*OW or N*H*W >= 2^31), SSCG_ERR_WORKSPACE; the workspace query returns
+ * 0 for sizes the entry refuses.  (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+size_t sscg_teacher_workspace(int N, int OH, int OW);
+int sscg_teacher_fwd(const float* x, const float* t, const uint8_t* flip, int N, int H, int W, int C, int OH, int OW, float inv_temp,
+                     float thresh, float* losses, double* sums, uint8_t* pseudo, float* coef, void* ws, size_t ws_bytes, void* stream);
 /* Segmented stable radix sort (no reference counterpart): S segments of L uint32 keys each, [S][L].  out_keys: every segment in
  * DESCENDING order; out_index: the position (0 .. L-1, int32) each key had in its segment; equal keys keep ascending index.  upper:
  * every key is below it (0: no bound) - a pass over eight-bit digits that are zero in every key is skipped; keys at or above a

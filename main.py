@@ -3,7 +3,7 @@
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
---calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp, --unl_crf, --unl_crf_kernel,
+--calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp, --unl_crf, --unl_crf_kernel, --unl_teacher,
 --lovasz_weight, --lovasz_per_image, --lovasz_classes, --lovasz_skip, --sliding.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL).  --augment's items `cutmix=` / `classmix=` mix two samples of a
 labelled batch, labels with pixels, inside the device-side batch finish; their class ids are checked against --dataset here."""
@@ -68,6 +68,7 @@ class _Args(Namespace):
     unl_ramp = 0
     unl_crf = 0.0
     unl_crf_kernel = ""
+    unl_teacher = ""
     lovasz_weight = 0.0
     lovasz_per_image = False
     lovasz_classes = "present"
@@ -239,6 +240,16 @@ def get_args(argv=None):
                         help="with --unl_crf: the pairwise kernel in --crf's grammar, a comma list of key=value over radius, dilation, "
                              "wb, ws, alpha, beta, gamma ('iters' is accepted and ignored), or 'on' (default: --crf's defaults, "
                              "untuned for training)")
+    parser.add_argument("--unl_teacher", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="mean-teacher consistency on the UNLABELLED batch (Tarvainen & Valpola 2017; French et al. 2020): a "
+                             "teacher - the same Gsi under --ema_decay's averaged weights, in evaluation mode - predicts the same "
+                             "images and the student is pulled towards it where the teacher's confidence is at least thresh; a comma "
+                             "list over mse=F (weight of the squared distance of the two probability maps), ce=F (weight of the cross "
+                             "entropy against the teacher's hard labels, FixMatch's form; not with --unl_pseudo), thresh=T in [0, 1] "
+                             "(default 0), temp=T > 0 (the teacher's softmax temperature, default 1) and flip (the teacher sees each "
+                             "sample mirrored with probability 1/2), or 'on' for mse=1 (an untuned default); needs --ema_decay; "
+                             "reported as unl_teacher_mse / unl_teacher_ce with the kept share unl_teacher_kept and the agreement "
+                             "unl_teacher_agree; --unl_ramp applies; the supervised model ignores it (default: off)")
     parser.add_argument("--lovasz_weight", type=float, default=SUPPRESS, metavar="F",
                         help="add F times the Lovasz-softmax loss (Berman et al., CVPR 2018), the mIoU surrogate, to every "
                              "ground-truth cross entropy (lab_loss_CE, gt_cycle_loss, the supervised loss), inside that term's own "
@@ -348,6 +359,15 @@ def get_args(argv=None):
             importlib.import_module(PKG + ".utils").parse_unl_crf_kernel(args.unl_crf_kernel)
         except ValueError as e:
             parser.error(str(e))
+    if args.unl_teacher.strip():
+        try:
+            teacher = importlib.import_module(PKG + ".utils").parse_unl_teacher(args.unl_teacher)
+        except ValueError as e:
+            parser.error(str(e))
+        if args.ema_decay is None:
+            parser.error("--unl_teacher needs --ema_decay: the teacher is the averaged weights")
+        if teacher.ce > 0.0 and args.unl_pseudo > 0.0:
+            parser.error("--unl_teacher ce= and --unl_pseudo are the same term from two label sources: give one")
     if not args.lovasz_weight >= 0.0 or args.lovasz_weight == float("inf"):
         parser.error("--lovasz_weight must be a finite number >= 0")
     if args.lovasz_skip.strip():

@@ -14,7 +14,7 @@
 //                          dropped one.  The backward READS its labels and keep decisions there: it recomputes the logits with
 //                          head_logits (head_geom.h), whose last bit may differ from the pinned arithmetic used here, and a decision
 //                          re-derived from them could differ from the one K counted.
-//   2. unl_reduce_kernel   one block per sample: its records in index order;
+//   2. unl_reduce_kernel   (unl_rows.h) one block per sample: its records in index order;
 //      unl_finish_kernel   one block: the samples in index order -> sums[4] (fp64) and the three losses (fp32).
 //   3. the backward        flat (unl_bwd_kernel: one thread per pixel) or through the adjoint of the resize: the UNL term of the head's
 //                          one backward kernel (head_bwd_kernel, head_bwd.hip), in the same launch as the softmax map's gradient.
@@ -23,10 +23,9 @@
 #include "head_common.h"
 #include "head_geom.h"
 #include "sscg_internal.h"
+#include "unl_rows.h"
 
 namespace {
-
-constexpr int UNL_BLOCKS = 256;    // statistics blocks per sample, grid-stride beyond (dice.hip's DICE_BLOCKS)
 
 struct UnlGeom {
     sscg_resize_geom r;
@@ -96,26 +95,6 @@ __global__ __launch_bounds__(256) void unl_stats_kernel(const float* __restrict_
     }
 }
 
-// `cnt` rows of four doubles -> one row: 64 row lanes of four threads (lane r takes rows r, r + 64, ... in order), the lanes in order by
-// the column's first thread.  unl_reduce_kernel: block n sums sample n's records; unl_finish_kernel: one block sums the samples.
-__device__ __forceinline__ double unl_sum_rows(const double* __restrict__ rows, int cnt, double (&sm)[256]) {
-    const int k = threadIdx.x & 3, rl = threadIdx.x >> 2;
-    double s = 0.0;
-    for (int r = rl; r < cnt; r += 64) s += rows[(size_t)r * 4 + k];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x < 4)
-        for (int r = 0; r < 64; ++r) t += sm[r * 4 + k];
-    return t;       // threads 0..3: column k
-}
-
-__global__ __launch_bounds__(256) void unl_reduce_kernel(const double* __restrict__ part, int bps, double* __restrict__ ssum) {
-    __shared__ double sm[256];
-    const double t = unl_sum_rows(part + (size_t)blockIdx.x * bps * 4, bps, sm);
-    if (threadIdx.x < 4) ssum[(size_t)blockIdx.x * 4 + threadIdx.x] = t;
-}
-
 __global__ __launch_bounds__(256) void unl_finish_kernel(const double* __restrict__ ssum, int N, double V, int C,
                                                          double* __restrict__ sums, float* __restrict__ losses) {
     __shared__ double sm[256];
@@ -165,13 +144,6 @@ __global__ __launch_bounds__(256) void unl_bwd_kernel(const float* __restrict__ 
             if (CT || c < C) dr[c] = v[c] * (unl_upstream(k, u[c], v[c]) - dot) + kp * (v[c] - (c == ys ? 1.f : 0.f));
     }
 }
-
-int unl_bps(int OH, int OW) {
-    const long b = ((long)OH * OW + 255) / 256;
-    return (int)(b > UNL_BLOCKS ? UNL_BLOCKS : b);
-}
-
-bool thresh_ok(float t) { return t >= 0.f && t <= 1.f; }      // (false for a NaN)
 
 template <bool RESIZE>
 void launch_stats(const UnlGeom& g, int N, hipStream_t st, const float* x, double* part, uint8_t* pmap) {

@@ -1325,6 +1325,36 @@ def resize_flip(x, size, flip):
     return y
 
 
+def mirror_samples(x, flags):
+    """The batch x [N,C,H,W] (fp32, no gradient) with sample n mirrored on W where flags[n] (a host sequence of N booleans) is set, as a
+    new channels-last tensor: per run of equal flags one sscg_resize_flip launch at the samples' own size (mirrored runs) or one copy
+    (plain runs), straight into the run's slice of the result - every sample is read and written once.  The batch itself when no flag
+    is set."""
+    _need_hip(x, f32_only=True)
+    if x.dim() != 4:
+        raise _lib.SscgError("mirror_samples: 4-D tensor expected")
+    _no_grad_input(x, "mirror_samples")
+    flags = [bool(f) for f in flags]
+    n, c, h, w = x.shape
+    if len(flags) != n:
+        raise ValueError("mirror_samples: %d flags for a batch of %d" % (len(flags), n))
+    if not any(flags):
+        return x
+    x = to_nhwc(x.detach())
+    y = empty_nhwc(n, c, h, w, x.device)
+    n0 = 0
+    while n0 < n:
+        n1 = n0 + 1
+        while n1 < n and flags[n1] == flags[n0]:
+            n1 += 1
+        if flags[n0]:
+            check(lib.sscg_resize_flip(x[n0:n1].data_ptr(), y[n0:n1].data_ptr(), n1 - n0, h, w, c, h, w, 1, _stream()), "sscg_resize_flip")
+        else:
+            y[n0:n1].copy_(x[n0:n1])
+        n0 = n1
+    return y
+
+
 def predict_labels_ms(logits_list, flips, size, *, want_prob=False, want_index=False, want_u8=True, label_true=None, hist=None,
                       num_classes=None):
     """Label maps from the logits of up to 8 views of one batch: per view, in order, interp(size, bilinear, align_corners=True) ->
@@ -4090,6 +4120,203 @@ def upsample_softmax_unl(x, size, unl=None, want_soft=True, want_pseudo=False):
         soft = softmax2d(up) if want_soft else None
         l_ent, l_msq, l_pl, sums, pseudo = UnlabelledLossFn.apply(up, unl.thresh, keep)
     return soft, l_ent, l_msq, l_pl, {"sums": sums, "pseudo": pseudo if want_pseudo else None}
+
+
+# ----------------------------------------------------------------------------- mean-teacher consistency (opt-in; include/sscg.h: sscg_teacher_fwd)
+class TeacherOptions(object):
+    """Mean-teacher consistency of the unlabelled head: the weights of the squared distance of the two probability maps (`mse`) and of
+    the cross entropy against the teacher's hard labels (`ce`), each finite and >= 0 (0 = that term is not used); the confidence
+    threshold of the teacher's labels in [0, 1] - it gates BOTH terms; the softmax temperature of the teacher, > 0 (below 1 sharpens);
+    `flip`: the teacher sees each sample mirrored with probability 1/2 (model.step draws; the functions below take the bytes).  The
+    functions return the two losses unweighted: the weights are the caller's."""
+    __slots__ = ("mse", "ce", "thresh", "temp", "flip")
+
+    def __init__(self, mse=0.0, ce=0.0, thresh=0.0, temp=1.0, flip=False):
+        import math
+        vals = []
+        for name, v in (("mse", mse), ("ce", ce)):
+            f = float(v)
+            if not (math.isfinite(f) and f >= 0.0):
+                raise ValueError("teacher %s weight %r is not a finite number >= 0" % (name, v))
+            vals.append(f)
+        t = float(thresh)
+        if not 0.0 <= t <= 1.0:
+            raise ValueError("teacher thresh %r is outside [0, 1]" % (thresh,))
+        temp = float(temp)
+        if not (math.isfinite(temp) and temp > 0.0):
+            raise ValueError("teacher temp %r is not a finite number > 0" % (temp,))
+        self.mse, self.ce = vals
+        self.thresh, self.temp, self.flip = t, temp, bool(flip)
+
+    @property
+    def any(self):
+        return self.mse > 0.0 or self.ce > 0.0
+
+    @property
+    def inv_temp(self):
+        """1 / temp rounded to fp32 once: the factor the kernel multiplies the teacher's resized logits by."""
+        return float(torch.tensor(1.0 / self.temp, dtype=torch.float32))
+
+
+def _teacher_options(teacher):
+    if isinstance(teacher, dict):
+        teacher = TeacherOptions(**teacher)
+    if not isinstance(teacher, TeacherOptions):
+        raise TypeError("teacher must be a functional.TeacherOptions (or a dict of its arguments), not %r" % (teacher,))
+    return teacher
+
+
+def teacher_fwd(x, t, flip, size, inv_temp, thresh, want_pseudo=True, want_coef=True):
+    """sscg_teacher_fwd on channels-last fp32 student logits x and teacher logits t [N,C,H,W] (size = (OH, OW); (H, W): the flat form);
+    flip: uint8 [N] on the device or None.  (losses fp32 [2] = (L_mse, L_ce), sums fp64 [4] = (sum_kept d, A, sum_kept ce, K), the
+    teacher's label map uint8 [N,OH,OW] - 255 = dropped - or None, coef fp32 [N,OH,OW,C] = d L_mse / d p or None).  No autograd:
+    upsample_softmax_teacher wraps it."""
+    n, c, h, w = x.shape
+    if tuple(t.shape) != (n, c, h, w) or t.dtype != torch.float32 or t.device != x.device:
+        raise _lib.SscgError("teacher_fwd: the teacher's logits must match the student's %s fp32 on %s, got %s %s on %s"
+                             % (tuple(x.shape), x.device, tuple(t.shape), t.dtype, t.device))
+    if flip is not None and (flip.dtype != torch.uint8 or tuple(flip.shape) != (n,) or flip.device != x.device or not flip.is_contiguous()):
+        raise _lib.SscgError("teacher_fwd: flip must be a contiguous uint8 [%d] tensor on %s" % (n, x.device))
+    oh, ow = int(size[0]), int(size[1])
+    losses = torch.empty((2,), dtype=torch.float32, device=x.device)
+    sums = torch.empty((4,), dtype=torch.float64, device=x.device)
+    pseudo = torch.empty((n, oh, ow), dtype=torch.uint8, device=x.device) if want_pseudo else None
+    coef = torch.empty((n, oh, ow, c), dtype=torch.float32, device=x.device) if want_coef else None
+    ws = torch.empty(lib.sscg_teacher_workspace(n, oh, ow), dtype=torch.uint8, device=x.device)
+    check(lib.sscg_teacher_fwd(x.data_ptr(), t.data_ptr(), _ptr(flip), n, h, w, c, oh, ow, float(inv_temp), float(thresh), losses.data_ptr(),
+                               sums.data_ptr(), _ptr(pseudo), _ptr(coef), ws.data_ptr(), ws.numel(), _stream()), "sscg_teacher_fwd")
+    return losses, sums, pseudo, coef
+
+
+def _teacher_forward(ctx, x, t, flip, size, inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep):
+    """What both teacher nodes run behind the softmax map: sscg_teacher_fwd, and sscg_unl_fwd when an --unl_* weight asks for its three
+    losses.  Saves (x, coef, the teacher's sums and map, sscg_unl_fwd's sums and map) and returns the node's outputs after the map:
+    (L_mse, L_ce, L_ent, L_msq, L_pl, the teacher's sums and map, sscg_unl_fwd's sums) - None for what did not run."""
+    t_losses, t_sums, t_map, coef = teacher_fwd(x, t, flip, size, inv_temp, thresh, True, want_coef)
+    l_mse, l_ce = t_losses.unbind(0)
+    l_ent = l_msq = l_pl = u_sums = u_map = None
+    if unl_thresh is not None:
+        u_losses, u_sums, u_map = unl_fwd(x, size, unl_thresh, unl_keep and not use_ce)
+        l_ent, l_msq, l_pl = u_losses.unbind(0)
+    ctx.use_ce = use_ce
+    ctx.save_for_backward(x, coef, t_sums, t_map, u_sums, u_map)
+    # the constants, and the losses whose backward has nothing to read: the squared distance without its coefficient map, the teacher's
+    # cross entropy unless it owns the pseudo-label slot, sscg_unl_fwd's without its own map
+    dead = [v for v, live in ((l_mse, coef is not None), (l_ce, use_ce), (l_pl, u_map is not None)) if v is not None and not live]
+    ctx.mark_non_differentiable(t_sums, t_map, *((u_sums,) if u_sums is not None else ()), *dead)
+    ctx.set_materialize_grads(False)
+    return l_mse, l_ce, l_ent, l_msq, l_pl, t_sums, t_map, u_sums
+
+
+def _teacher_slot(ctx, g_ce, g_pl):
+    """(pseudo, g, sums) of the ONE pseudo-label slot of the backward entries: the teacher's when its cross entropy is on, else
+    sscg_unl_fwd's own; (None, None, some sums) when neither received a gradient."""
+    _, _, t_sums, t_map, u_sums, u_map = ctx.saved_tensors
+    if ctx.use_ce:
+        return (t_map, g_ce, t_sums) if g_ce is not None else (None, None, t_sums)
+    if u_map is not None and g_pl is not None:
+        return u_map, g_pl, u_sums
+    return None, None, t_sums
+
+
+class TeacherHeadFn(torch.autograd.Function):
+    """interp (bilinear, align_corners=True) -> softmax2d of the UNLABELLED prediction plus its consistency with a teacher's logits of
+    the same shape, from the LOW-resolution logits of both: (softmax map or None, L_mse, L_ce, L_ent, L_msq, L_pl, the teacher's sums
+    and label map, sscg_unl_fwd's sums or None).  Forward: the label head's own launch for the map (the bits of upsample_softmax_ce's),
+    sscg_teacher_fwd, and sscg_unl_fwd when `unl_thresh` is given.  Backward: the squared distance's coefficient map joins the map's
+    upstream gradient (one sscg_lovasz_scale_add), then ONE sscg_upsample_head_bwd_u launch whose pseudo-label slot is the teacher's
+    (use_ce) or sscg_unl_fwd's own.  The teacher's logits and `flip` are constants."""
+
+    @staticmethod
+    def forward(ctx, x, oh, ow, t, flip, want_soft, inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep):
+        _need_hip(x, f32_only=True)
+        x, t = to_nhwc(x), to_nhwc(t)
+        y = _label_head_forward(x, oh, ow, None, True, False, None, 0.0)[0] if want_soft else None
+        ctx.size = (oh, ow)
+        return (y,) + _teacher_forward(ctx, x, t, flip, (oh, ow), inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep)
+
+    @staticmethod
+    def backward(ctx, dy, g_mse, g_ce, g_ent, g_msq, g_pl, *_consts):
+        x, coef = ctx.saved_tensors[:2]
+        pseudo, g_slot, sums = _teacher_slot(ctx, g_ce, g_pl)
+        if coef is None:
+            g_mse = None
+        if dy is None and g_mse is None and g_ent is None and g_msq is None and g_slot is None:
+            return (None,) * 12
+        if dy is not None:
+            dy = to_nhwc(dy)
+        if g_mse is not None:
+            dy = _lovasz_upstream(coef, g_mse.contiguous(), dy)
+        oh, ow = ctx.size
+        n, c, h, w = x.shape
+        dx = empty_nhwc(n, c, h, w, x.device)
+        check(lib.sscg_upsample_head_bwd_u(x.data_ptr(), _ptr(pseudo), _ptr(dy), _ptr(g_ent), _ptr(g_msq), _ptr(g_slot), sums.data_ptr(),
+                                           dx.data_ptr(), n, h, w, c, oh, ow, _stream()), "sscg_upsample_head_bwd_u")
+        return (dx,) + (None,) * 11
+
+
+class TeacherLossFn(torch.autograd.Function):
+    """The flat form, where the fused head does not apply: the same values from full-resolution logits `up` and teacher logits of the
+    same size, and from `soft` = softmax2d(up) (a node of its own; None when the squared distance is off), which this node does not
+    read - it is where that term's gradient goes: g_mse * coef is `soft`'s gradient (sscg_lovasz_scale_add) and SoftmaxFn's
+    sscg_softmax_bwd carries it on; every other live term is one sscg_unl_bwd launch on `up`."""
+
+    @staticmethod
+    def forward(ctx, up, soft, t, flip, inv_temp, thresh, use_ce, unl_thresh, unl_keep):
+        _need_hip(up, f32_only=True)
+        up, t = to_nhwc(up), to_nhwc(t)
+        return _teacher_forward(ctx, up, t, flip, up.shape[2:], inv_temp, thresh, use_ce, soft is not None, unl_thresh, unl_keep)
+
+    @staticmethod
+    def backward(ctx, g_mse, g_ce, g_ent, g_msq, g_pl, *_consts):
+        up, coef = ctx.saved_tensors[:2]
+        pseudo, g_slot, sums = _teacher_slot(ctx, g_ce, g_pl)
+        d_soft = d_up = None
+        if coef is not None and g_mse is not None:
+            d_soft = _lovasz_upstream(coef, g_mse.contiguous(), None)
+        if g_ent is not None or g_msq is not None or g_slot is not None:
+            n, c, h, w = up.shape
+            d_up = torch.empty_like(up, memory_format=CL)
+            check(lib.sscg_unl_bwd(up.data_ptr(), _ptr(pseudo), n, h, w, c, _ptr(g_ent), _ptr(g_msq), _ptr(g_slot), sums.data_ptr(),
+                                   d_up.data_ptr(), _stream()), "sscg_unl_bwd")
+        return (d_up, d_soft) + (None,) * 7
+
+
+def upsample_softmax_teacher(x, size, teacher_logits, teacher, unl=None, flip=None, want_soft=True):
+    """(softmax2d(interp(x)) or None, L_mse, L_ce, L_ent, L_msq, L_pl, stats): the unlabelled prediction's softmax map (the bits of
+    upsample_softmax_ce's) and its consistency with `teacher_logits` - the low-resolution logits, shaped like x, of a teacher that saw
+    the same batch, sample n mirrored on W where flip[n] (uint8 [N] on the device, or None) is set.  teacher: a TeacherOptions (or a
+    dict); L_mse = the squared distance of the two probability maps over the pixels the teacher is confident on, divided by C V;
+    L_ce = the student's cross entropy against the teacher's first maximum over the same pixels, divided by their number.  Unweighted.
+    unl: an UnlabelledOptions with a weight (or None): L_ent, L_msq and L_pl are upsample_softmax_unl's, else None; both pseudo-label
+    terms at once are refused - the backward has one pseudo-label slot and the teacher's labels are the better source.  stats = {"sums":
+    fp64 [4] = (sum_kept d, A = agreeing kept pixels, sum_kept ce, K), "pseudo": the teacher's uint8 label map, 255 = dropped,
+    "unl_sums": sscg_unl_fwd's sums or None}.  No gradient reaches the teacher.  Fused when the resize grows the map - ONE stencil
+    launch backward - else the separate passes on upsample_bilinear's output."""
+    teacher = _teacher_options(teacher)
+    unl = _unl_options(unl) if unl is not None else None
+    if unl is not None and not unl.any:
+        unl = None
+    use_ce = teacher.ce > 0.0
+    if use_ce and unl is not None and unl.pseudo > 0.0:
+        raise ValueError("teacher ce and unl pseudo are both > 0: the head's backward has one pseudo-label slot, and the teacher's labels "
+                         "are the better source of the same term")
+    if teacher_logits.requires_grad:
+        teacher_logits = teacher_logits.detach()
+    oh, ow = int(size[0]), int(size[1])
+    unl_thresh = unl.thresh if unl is not None else None
+    unl_keep = unl is not None and unl.pseudo > 0.0
+    want_coef = teacher.mse > 0.0
+    if _head_applies(x, oh, ow):
+        out = TeacherHeadFn.apply(x, oh, ow, teacher_logits, flip, bool(want_soft), teacher.inv_temp, teacher.thresh, use_ce, want_coef,
+                                  unl_thresh, unl_keep)
+    else:
+        up = upsample_bilinear(x, size)
+        soft = softmax2d(up) if want_soft or want_coef else None
+        out = (soft if want_soft else None,) + TeacherLossFn.apply(up, soft if want_coef else None, upsample_bilinear(teacher_logits, size),
+                                                                   flip, teacher.inv_temp, teacher.thresh, use_ce, unl_thresh, unl_keep)
+    soft, l_mse, l_ce, l_ent, l_msq, l_pl, t_sums, t_map, u_sums = out
+    return soft, l_mse, l_ce, l_ent, l_msq, l_pl, {"sums": t_sums, "pseudo": t_map, "unl_sums": u_sums}
 
 
 # ----------------------------------------------------------------------------- the gated CRF loss (opt-in; include/sscg.h: sscg_crf_loss_fwd)

@@ -140,7 +140,13 @@ def gen_loss_terms_of(args):
     on = lambda key: float(getattr(args, key, 0.0) or 0.0) > 0.0
     return gen_loss_terms((v for v in str(getattr(args, "variants", "") or "").split(",") if v), dice=on("dice_weight"),
                           boundary=on("boundary_loss"), lovasz=on("lovasz_weight"), ssim=on("ssim_weight"),
-                          unl=sum(on(k) for k in ("unl_entropy", "unl_maxsq", "unl_pseudo", "unl_crf")))
+                          unl=sum(on(k) for k in ("unl_entropy", "unl_maxsq", "unl_pseudo", "unl_crf")) + _teacher_terms_of(args))
+
+
+def _teacher_terms_of(args):
+    """The generator-loss terms --unl_teacher adds: one per weight (mse, ce) that is > 0."""
+    t = utils.parse_unl_teacher(getattr(args, "unl_teacher", "") or "")
+    return 0 if t is None else int(t.mse > 0.0) + int(t.ce > 0.0)
 
 
 def _optim_options(args, ema):
@@ -434,6 +440,49 @@ class _UnlabelledLosses(object):
     unl_crf = 0.0                   # its weight; 0 = no launch, loss key or checkpoint key
     unl_crf_options = None          # functional.CrfOptions of the pairwise kernel when the weight is > 0
 
+    # --unl_teacher (opt-in): mean-teacher consistency - the same Gsi under the EMA weights (--ema_decay), in evaluation mode, predicts
+    # the unlabelled batch first (_teacher_logits); the head then scores the student against it (functional.upsample_softmax_teacher:
+    # one statistics launch more, the same single stencil launch backward), two terms of their own under the same ramp
+    unl_teacher = None              # functional.TeacherOptions when the flag is given: no launch, loss key or checkpoint key otherwise
+    _teacher_rng = None             # the mirror draws' own CPU generator (`flip`): no other draw of a seed moves
+    TEACHER_SEED = 0x7EAC
+
+    def _init_unl_teacher(self, args):
+        opts = utils.parse_unl_teacher(getattr(args, "unl_teacher", "") or "")
+        if opts is None:
+            return
+        if getattr(args, "ema_decay", None) is None:
+            raise ValueError("--unl_teacher needs --ema_decay: the teacher is the averaged weights")
+        if opts.ce > 0.0 and float(getattr(args, "unl_pseudo", 0.0) or 0.0) > 0.0:
+            raise ValueError("--unl_teacher ce= and --unl_pseudo are the same term from two label sources (the head's backward has one "
+                             "pseudo-label slot): give one")
+        self.unl_teacher = opts
+        if opts.flip:
+            self._teacher_rng = torch.Generator().manual_seed(self.TEACHER_SEED)
+
+    def _teacher_view(self, unl_img):
+        """What the teacher sees: the unlabelled batch, each sample mirrored on W with probability 1/2 under `flip` - (view, the flip
+        bytes uint8 [N] on the device or None).  The draws are the host's, so the view is built per run of equal draws
+        (functional.mirror_samples: each sample read and written once) and nothing waits for the device."""
+        if self._teacher_rng is None:
+            return unl_img, None
+        draws = torch.rand(unl_img.shape[0], generator=self._teacher_rng) < 0.5
+        flip = draws.to(torch.uint8).to(unl_img.device)
+        return F.mirror_samples(unl_img, draws.tolist()), flip
+
+    def _teacher_logits(self, view):
+        """The teacher's low-resolution logits of `view` (_teacher_view's batch), detached, fp32: Gsi under the EMA weights
+        (g_optimizer.ema_weights: two arena swaps with their operand copies) in evaluation mode - the folded-BatchNorm inference path,
+        no dropout, no running statistic moves - and back to the mode it had."""
+        was = self.Gsi.training
+        with self.g_optimizer.ema_weights(), torch.no_grad():
+            self.Gsi.eval()
+            try:
+                logits = self.Gsi(view)
+            finally:
+                self.Gsi.train(was)
+        return logits.detach().float()
+
     def _init_unl_crf(self, args):
         w = float(getattr(args, "unl_crf", 0.0) or 0.0)
         if not (w >= 0.0 and w < float("inf")):
@@ -446,6 +495,7 @@ class _UnlabelledLosses(object):
 
     def _init_unl(self, args):
         self._init_unl_crf(args)
+        self._init_unl_teacher(args)
         w = {}
         for key in ("unl_entropy", "unl_maxsq", "unl_pseudo"):
             w[key] = float(getattr(args, key, 0.0) or 0.0)
@@ -460,7 +510,7 @@ class _UnlabelledLosses(object):
         ramp = getattr(args, "unl_ramp", 0) or 0
         if isinstance(ramp, bool) or ramp != int(ramp) or int(ramp) < 0:
             raise ValueError("--unl_ramp %r must be an integer >= 0" % (ramp,))
-        if not any(v > 0.0 for v in w.values()) and not self.unl_crf > 0.0:
+        if not any(v > 0.0 for v in w.values()) and not self.unl_crf > 0.0 and self.unl_teacher is None:
             return
         self.unl_ramp = int(ramp)
         if any(v > 0.0 for v in w.values()):
@@ -470,16 +520,22 @@ class _UnlabelledLosses(object):
     def set_unl_epoch(self, epoch):
         """--unl_ramp: the factor on the unlabelled weights for `epoch` (utils.boundary_loss_schedule's arithmetic); train() calls
         it once per epoch.  Off: nothing changes."""
-        if self.unl_options is not None or self.unl_crf > 0.0:
+        if self.unl_options is not None or self.unl_crf > 0.0 or self.unl_teacher is not None:
             self._unl_scale = utils.boundary_loss_schedule(1.0, self.unl_ramp, epoch)
         return self._unl_scale
 
-    def _unl_head(self, fake_logits, extras, extra_terms, extra_weights, unl_img=None):
+    def _unl_head(self, fake_logits, extras, extra_terms, extra_weights, unl_img=None, teacher=None):
         """The softmax map of the unlabelled prediction (:401-402): the plain fused head by default.  With an --unl_* weight the head
         also returns the enabled losses: each joins the extras under its own key with its own ramped weight, and --unl_pseudo reports
         the kept share K / V - a device scalar from the sums the forward left, no sync.  --unl_crf: the gated CRF loss of the map under
-        `unl_img`, a node of its own beside the head - autograd adds its gradient to the map's."""
-        fake_gt = self._unl_head_losses(fake_logits, extras, extra_terms, extra_weights)
+        `unl_img`, a node of its own beside the head - autograd adds its gradient to the map's.  --unl_teacher: `teacher` = (the
+        teacher's logits, its flip bytes) of this batch, and the head is functional.upsample_softmax_teacher."""
+        if self.unl_teacher is not None:
+            if teacher is None:
+                raise ValueError("--unl_teacher: _unl_head needs the teacher's logits of this batch (_teacher_logits)")
+            fake_gt = self._unl_teacher_losses(fake_logits, teacher, extras, extra_terms, extra_weights)
+        else:
+            fake_gt = self._unl_head_losses(fake_logits, extras, extra_terms, extra_weights)
         if self.unl_crf > 0.0:
             if unl_img is None:
                 raise ValueError("--unl_crf: _unl_head needs the unlabelled image batch, the guide of the CRF loss")
@@ -500,6 +556,26 @@ class _UnlabelledLosses(object):
                 extra_weights.append(w * self._unl_scale)
         if o.pseudo > 0.0:
             extras["unl_pseudo_kept"] = (stats["sums"][3] / float(fake_gt.shape[0] * self.crop[0] * self.crop[1])).float()
+        return fake_gt
+
+
+    def _unl_teacher_losses(self, fake_logits, teacher, extras, extra_terms, extra_weights):
+        """_unl_head_losses with the teacher: the --unl_* terms as they were, then unl_teacher_mse / unl_teacher_ce with their ramped
+        weights, and the diagnostics unl_teacher_kept = K / V and unl_teacher_agree = A / max(K, 1) - device scalars from the sums."""
+        o, t = self.unl_options, self.unl_teacher
+        fake_gt, l_mse, l_ce, l_ent, l_msq, l_pl, stats = F.upsample_softmax_teacher(fake_logits, self.crop, teacher[0], t, o, flip=teacher[1])
+        V = float(fake_gt.shape[0] * self.crop[0] * self.crop[1])
+        for key, term, w in ((("unl_entropy", l_ent, o.entropy), ("unl_maxsq", l_msq, o.maxsq), ("unl_pseudo_ce", l_pl, o.pseudo))
+                             if o is not None else ()) + (("unl_teacher_mse", l_mse, t.mse), ("unl_teacher_ce", l_ce, t.ce)):
+            if w > 0.0:
+                extras[key] = term
+                extra_terms.append(term)
+                extra_weights.append(w * self._unl_scale)
+        if o is not None and o.pseudo > 0.0:
+            extras["unl_pseudo_kept"] = (stats["unl_sums"][3] / V).float()
+        sums = stats["sums"]
+        extras["unl_teacher_kept"] = (sums[3] / V).float()
+        extras["unl_teacher_agree"] = (sums[1] / sums[3].clamp(min=1.0)).float()
         return fake_gt
 
 
@@ -651,6 +727,10 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         # the generators' operand copies (bf16 shadow / split planes) exist and are current before any lane reads them: a no-op
         # after the first step (the Adam kernel rewrites them); the discriminators' follow at :431, behind their own update
         self.g_optimizer.ensure_operand_copies()
+        teacher = None
+        if self.unl_teacher is not None:        # --unl_teacher: the EMA weights predict the unlabelled batch before any lane starts
+            view, flip = self._teacher_view(unl_img)
+            teacher = (self._teacher_logits(view), flip)
         labels = l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3])          # l_gt.squeeze(1)
         onehot_gt = make_one_hot(l_gt, a.dataset, a.gpu_ids)
 
@@ -712,7 +792,7 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         ohem_kept = {}
         lab_gt, lab_loss_CE, lab_loss_dice = self._head(lab_logits, labels, True, ohem_kept)   # (plain nn.CrossEntropyLoss() by default)
         extra_terms, extra_weights, extras = [], [], {}
-        fake_gt = self._unl_head(fake_logits, extras, extra_terms, extra_weights, unl_img)    # (--unl_*: plus the enabled losses)
+        fake_gt = self._unl_head(fake_logits, extras, extra_terms, extra_weights, unl_img, teacher)    # (--unl_*: plus the enabled losses)
         if fork:
             main.wait_event(gis_first)
         # (Gis(onehot_gt) and Gis(fake_gt) as ONE grouped-BatchNorm pass on the main lane was built in round 4 and measured slower than
@@ -1162,6 +1242,8 @@ class supervised_model(_WeightedCE):
             print("--unl_entropy / --unl_maxsq / --unl_pseudo are ignored: the supervised model has no unlabelled batch")
         if float(getattr(args, "unl_crf", 0.0) or 0.0) != 0.0:
             print("--unl_crf is ignored: the supervised model has no unlabelled batch")
+        if str(getattr(args, "unl_teacher", "") or "").strip():
+            print("--unl_teacher is ignored: the supervised model has no unlabelled batch")
         self.running_metrics_val = utils.runningScore(self.n_channels, args.dataset)
         if not os.path.isdir(args.checkpoint_dir):
             os.makedirs(args.checkpoint_dir, exist_ok=True)

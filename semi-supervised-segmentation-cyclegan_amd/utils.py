@@ -977,6 +977,41 @@ def parse_unl_crf_kernel(spec):
         raise ValueError(str(e).replace("--crf:", "--unl_crf_kernel:", 1))
 
 
+_TEACHER_KEYS = ("mse", "ce", "thresh", "temp")
+
+
+def parse_unl_teacher(spec):
+    """`--unl_teacher`: mean-teacher consistency on the unlabelled batch, in parse_crf's comma grammar: key=value over mse, ce, thresh,
+    temp, plus the bare word `flip`, e.g. "mse=1,ce=0.5,thresh=0.6,flip" - keys left out keep F.TeacherOptions' defaults.  "on" =
+    mse=1, an UNTUNED default.  Returns a F.TeacherOptions, None for "" / None.  Raises ValueError naming the bad token; a spec that
+    turns neither term on is refused."""
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    if spec == "on":
+        return F.TeacherOptions(mse=1.0)
+    kw = {}
+    for tok in spec.split(","):
+        key, sep, val = tok.strip().partition("=")
+        if key == "flip" and not sep and "flip" not in kw:
+            kw["flip"] = True
+            continue
+        if not sep or key not in _TEACHER_KEYS or key in kw:
+            raise ValueError("--unl_teacher: %r is not `flip` or one key=value over %s" % (tok, ", ".join(_TEACHER_KEYS)))
+        try:
+            kw[key] = float(val)
+        except ValueError:
+            raise ValueError("--unl_teacher: %r is not a number" % (tok,))
+        try:
+            F.TeacherOptions(**{key: kw[key]})      # the value's own range: the error names the token
+        except ValueError as e:
+            raise ValueError("--unl_teacher: %r: %s" % (tok, e))
+    opts = F.TeacherOptions(**kw)
+    if not opts.any:
+        raise ValueError("--unl_teacher: %r turns on neither mse= nor ce=" % (spec,))
+    return opts
+
+
 def crf_guide(images, size):
     """The CRF's guide image: the batch as the network sees it (normalised), resized to `size` when it has another."""
     return images if tuple(images.shape[2:]) == (int(size[0]), int(size[1])) else F.upsample_bilinear(images, size)
