@@ -683,6 +683,30 @@ int sscg_upsample_head_bwd_u(const float* x, const uint8_t* pseudo, const float*
 size_t sscg_teacher_workspace(int N, int OH, int OW);
 int sscg_teacher_fwd(const float* x, const float* t, const uint8_t* flip, int N, int H, int W, int C, int OH, int OW, float inv_temp,
                      float thresh, float* losses, double* sums, uint8_t* pseudo, float* coef, void* ws, size_t ws_bytes, void* stream);
+/* CutMix consistency for the mean teacher (opt-in, `--unl_cutmix`; French et al. 2020: the student sees a CutMix of two unlabelled
+ * images and is held to the same CutMix of the teacher's predictions of the two UNMIXED images).  Both entries read an int32 [N][8]
+ * `table`, sscg_augment_mix_u8's rows (partner, x0, y0, x1, y1, mask_lo, mask_hi, 0); the mask words are not read.  With p = table[n][0]
+ *     pasted(n, h, w) <=> 0 <= p < N and p != n and x0 <= w < x1 and y0 <= h < y1
+ * - plain integer compares on whatever the row holds: boxes that are empty or reach outside the map are safe and need no clamping,
+ * and the partner is range-checked before anything is indexed by it.
+ * sscg_mix_boxes: the student's input.  x, y fp32 [N][H][W][C]; y[n][h][w][:] = pasted(n, h, w) ? x[p][h][w][:] : x[n][h][w][:].
+ *   Every partner pixel is the partner's pixel before mixing, so y == x is refused.  One launch, a pure copy, every element of y
+ *   written once; four floats per thread where H*W*C is a multiple of 4 and both pointers are 16-byte aligned, one otherwise.
+ *   Errors before any HIP call: SSCG_ERR_BAD_ARG (a null x, y or table; y == x; non-positive sizes), SSCG_ERR_UNSUPPORTED
+ *   (N*H*W*C >= 2^31).
+ * sscg_teacher_fwd_mix: the teacher's side - sscg_teacher_fwd, every word of it, except for the sample the TEACHER's logits of an
+ *   output pixel (n, oy, ox) come from: src = pasted(n, oy, ox) ? p : n with the box in OUTPUT pixels, and zt = sample src of t,
+ *   resized by the pinned arithmetic and read at column flip[src] ? OW - 1 - ox : ox - the partner's flip, not the pixel's own
+ *   sample's.  The teacher's logits are low resolution and the box lives at the output resolution, so they cannot be mixed before the
+ *   resize; here the resized teacher is never written.  The student, q, y*, the keep rule, d, ce, agree, sums, losses, pseudo, coef,
+ *   the workspace (sscg_teacher_workspace) and the finish are sscg_teacher_fwd's: the backward of a node built on this entry is that of
+ *   one built on sscg_teacher_fwd.  table == NULL: sscg_teacher_fwd's own kernels, the same bits - as are a table that mixes nothing.
+ *   The resized form gives the bits of the identity form on sscg_upsample_bilinear_fwd's outputs of x and t.  Errors: sscg_teacher_fwd's.
+ * (Additions: no existing entry changes meaning, so SSCG_ABI_VERSION stays 18.) */
+int sscg_mix_boxes(const float* x, float* y, const int32_t* table, int N, int H, int W, int C, void* stream);
+int sscg_teacher_fwd_mix(const float* x, const float* t, const uint8_t* flip, const int32_t* table, int N, int H, int W, int C,
+                         int OH, int OW, float inv_temp, float thresh, float* losses, double* sums, uint8_t* pseudo, float* coef,
+                         void* ws, size_t ws_bytes, void* stream);
 /* Segmented stable radix sort (no reference counterpart): S segments of L uint32 keys each, [S][L].  out_keys: every segment in
  * DESCENDING order; out_index: the position (0 .. L-1, int32) each key had in its segment; equal keys keep ascending index.  upper:
  * every key is below it (0: no bound) - a pass over eight-bit digits that are zero in every key is skipped; keys at or above a

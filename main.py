@@ -3,7 +3,7 @@
 dispatch on --training / --model.  Extra flags (never change a reference default): --synthetic_steps,
 --as_written, --augment, --panels, --tta, --ce_weights, --label_smoothing, --clip_grad_norm, --weight_decay, --adamw,
 --ema_decay, --dice_weight, --dice_smooth, --dice_skip, --dice_batch, --ohem_thresh, --ohem_min_kept, --ohem_min_frac, --crf, --boundary, --surface, --components,
---calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp, --unl_crf, --unl_crf_kernel, --unl_teacher,
+--calibration, --boundary_loss, --boundary_loss_skip, --boundary_loss_ramp, --ssim_weight, --ssim_window, --ssim_sigma, --unl_entropy, --unl_maxsq, --unl_pseudo, --unl_pseudo_thresh, --unl_ramp, --unl_crf, --unl_crf_kernel, --unl_teacher, --unl_cutmix,
 --lovasz_weight, --lovasz_per_image, --lovasz_classes, --lovasz_skip, --sliding.  Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main.py ...`
 (one process per MI355X; gradients all-reduced with RCCL).  --augment's items `cutmix=` / `classmix=` mix two samples of a
 labelled batch, labels with pixels, inside the device-side batch finish; their class ids are checked against --dataset here."""
@@ -69,6 +69,7 @@ class _Args(Namespace):
     unl_crf = 0.0
     unl_crf_kernel = ""
     unl_teacher = ""
+    unl_cutmix = ""
     lovasz_weight = 0.0
     lovasz_per_image = False
     lovasz_classes = "present"
@@ -250,6 +251,14 @@ def get_args(argv=None):
                              "sample mirrored with probability 1/2), or 'on' for mse=1 (an untuned default); needs --ema_decay; "
                              "reported as unl_teacher_mse / unl_teacher_ce with the kept share unl_teacher_kept and the agreement "
                              "unl_teacher_agree; --unl_ramp applies; the supervised model ignores it (default: off)")
+    parser.add_argument("--unl_cutmix", type=str, default=SUPPRESS, metavar="SPEC",
+                        help="with --unl_teacher: CutMix consistency (French et al. 2020) - the teacher predicts the unlabelled batch "
+                             "as it is, then every sample of it takes, with probability p, a box of a partner sample, and the student, "
+                             "which sees the mixed batch from there on, is held to the same mix of the teacher's two predictions; SPEC "
+                             "= p[:lo:hi] in the grammar of --augment cutmix=: 0 < p <= 1, the box's share of the area in lo..hi "
+                             "(default 0.25:0.5, untuned); the unlabelled images must have the crop's size; a batch of one is never "
+                             "mixed; reported as unl_cutmix_share, the pasted share of the batch's pixels; the supervised model "
+                             "ignores it (default: off)")
     parser.add_argument("--lovasz_weight", type=float, default=SUPPRESS, metavar="F",
                         help="add F times the Lovasz-softmax loss (Berman et al., CVPR 2018), the mIoU surrogate, to every "
                              "ground-truth cross entropy (lab_loss_CE, gt_cycle_loss, the supervised loss), inside that term's own "
@@ -368,6 +377,13 @@ def get_args(argv=None):
             parser.error("--unl_teacher needs --ema_decay: the teacher is the averaged weights")
         if teacher.ce > 0.0 and args.unl_pseudo > 0.0:
             parser.error("--unl_teacher ce= and --unl_pseudo are the same term from two label sources: give one")
+    if args.unl_cutmix.strip():
+        try:
+            importlib.import_module(PKG + ".utils").parse_unl_cutmix(args.unl_cutmix)
+        except ValueError as e:
+            parser.error(str(e))
+        if not args.unl_teacher.strip() or args.ema_decay is None:
+            parser.error("--unl_cutmix needs --unl_teacher (and with it --ema_decay): it mixes what the teacher and the student see")
     if not args.lovasz_weight >= 0.0 or args.lovasz_weight == float("inf"):
         parser.error("--lovasz_weight must be a finite number >= 0")
     if args.lovasz_skip.strip():

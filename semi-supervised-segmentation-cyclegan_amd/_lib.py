@@ -150,6 +150,8 @@ SIGNATURES = {
     "sscg_upsample_head_bwd_u": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "sscg_teacher_workspace": (_sz, [_i, _i, _i]),
     "sscg_teacher_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _sz, _p]),
+    "sscg_mix_boxes": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "sscg_teacher_fwd_mix": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _sz, _p]),
     "sscg_sort_chunk": (_i, []),
     "sscg_sort_ws_bytes": (_sz, [_i64, _i64]),
     "sscg_sort_u32_desc": (_i, [_p, _i, _i, C.c_uint32, _p, _p, _p, _sz, _p]),

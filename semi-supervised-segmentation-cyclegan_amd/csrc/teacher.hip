@@ -10,8 +10,14 @@
 //     y*  = the first maximum of q, conf = q[y*], KEPT <=> conf >= tau
 //     d   = sum_c (p_c - q_c)^2, ce = ln s - u[y*], agree = kept and the first maximum of p is y*
 //     sums = (sum_kept d, A, sum_kept ce, K);  L_mse = sums[0] / (C V);  L_ce = sums[2] / max(K, 1)
-// unl.hip's frame: one thread per output pixel, no block straddles a sample (flip[n] is uniform over a block), K and A per wave by
-// ballot, one fp64 record per block, unl_reduce_kernel and a one-block finish - no float atomics, every sum in a fixed order.
+// unl.hip's frame: one thread per output pixel, no block straddles a sample, K and A per wave by ballot, one fp64 record per block,
+// unl_reduce_kernel and a one-block finish - no float atomics, every sum in a fixed order.  In the plain instances the teacher's
+// sample is the block's own, so its base pointer and flip[n] are uniform over a block.
+// sscg_teacher_fwd_mix (CutMix consistency, French et al. 2020: the student saw a CutMix of the batch, the teacher the unmixed one):
+// the MIX instances read one row (partner, x0, y0, x1, y1, ...) of an int32 [N][8] table per block - still uniform - and then every
+// THREAD decides whether its output pixel lies in the pasted box and takes the teacher's rows of the partner there: the source sample
+// `src`, its base pointer `tn` and its mirror flip[src] are per thread in those instances, nothing else changes, and the resized
+// teacher [N][OH][OW][C] that a select after the resize would need is never written.
 // The thread holds TWO tables of C floats, not three: the teacher is streamed first and leaves q and y*; of the student's logit
 // differences only u[y*] is ever read, so it is picked while the student's logits are still logits and u is never a table.  A class
 // count known only at run time holds NO table (teacher_pixel_stream): two tables of 64 floats fill the register file.
@@ -161,10 +167,22 @@ __device__ __forceinline__ TeacherPixel teacher_pixel_stream(const float* __rest
     return r;
 }
 
-template <int CT, bool RESIZE>
+// Which sample's teacher an output pixel reads.  Plain: its own.  Table: the partner inside the half-open box of the sample's row
+// (partner, x0, y0, x1, y1, mask_lo, mask_hi, 0) - plain integer compares on whatever the row holds; the partner is range-checked
+// before anything is indexed by it, and a partner outside [0, N) or equal to n mixes nothing.
+struct TeacherPlain {
+    static constexpr bool kMix = false;
+};
+struct TeacherTable {
+    static constexpr bool kMix = true;
+    const int32_t* table;
+    int N;
+};
+
+template <int CT, bool RESIZE, class MIX>
 __global__ __launch_bounds__(256) void teacher_stats_kernel(const float* __restrict__ x, const float* __restrict__ t,
                                                             const uint8_t* __restrict__ flip, double* __restrict__ part,
-                                                            uint8_t* __restrict__ pmap, float* __restrict__ coef, TeacherGeom g) {
+                                                            uint8_t* __restrict__ pmap, float* __restrict__ coef, TeacherGeom g, MIX mix) {
     __shared__ float redf[4][2];
     __shared__ int redk[4][2];
     const int C = CT ? CT : g.r.C;
@@ -174,6 +192,18 @@ __global__ __launch_bounds__(256) void teacher_stats_kernel(const float* __restr
     uint8_t* pn = pmap ? pmap + (size_t)n * g.npix : nullptr;
     float* cn = coef ? coef + (size_t)n * g.npix * C : nullptr;
     const bool mirrored = flip && flip[n] != 0;
+    [[maybe_unused]] int bx0 = 0, by0 = 0, bx1 = 0, by1 = 0;          // (the empty box: nothing is pasted)
+    [[maybe_unused]] const float* tp = tn;
+    [[maybe_unused]] bool pmirrored = mirrored;
+    if constexpr (MIX::kMix) {
+        const int32_t* row = mix.table + (size_t)n * 8;
+        const int p = row[0];
+        if (p >= 0 && p < mix.N && p != n) {           // (else the box stays empty and nothing is indexed by p)
+            bx0 = row[1]; by0 = row[2]; bx1 = row[3]; by1 = row[4];
+            tp = t + (size_t)p * g.r.H * g.r.W * C;
+            pmirrored = flip && flip[p] != 0;
+        }
+    }
     float sd = 0.f, sc = 0.f;
     int kw = 0, aw = 0;
     for (long base = (long)blk * 256; base < g.npix; base += (long)g.bps * 256) {      // (long: npix may sit just below 2^31)
@@ -181,11 +211,18 @@ __global__ __launch_bounds__(256) void teacher_stats_kernel(const float* __restr
         const bool in = o_raw < g.npix;
         const int o = in ? (int)o_raw : g.npix - 1;
         const int oy = fd_div(o, g.r.dow), ox = o - oy * g.r.OW;
-        const int oxt = mirrored ? g.r.OW - 1 - ox : ox;
+        const float* ts = tn;
+        bool mir = mirrored;
+        if constexpr (MIX::kMix) {
+            const bool pasted = ox >= bx0 && ox < bx1 && oy >= by0 && oy < by1;
+            ts = pasted ? tp : tn;
+            mir = pasted ? pmirrored : mirrored;        // the PARTNER's flip: its teacher saw its own image mirrored, or not
+        }
+        const int oxt = mir ? g.r.OW - 1 - ox : ox;
         float* cr = cn ? cn + (size_t)o * C : nullptr;
         TeacherPixel r;
-        if constexpr (CT > 0) r = teacher_pixel_tables<CT, RESIZE>(xn, tn, oy, ox, oxt, g, in, cr);
-        else r = teacher_pixel_stream<RESIZE>(xn, tn, oy, ox, oxt, g, in, cr);
+        if constexpr (CT > 0) r = teacher_pixel_tables<CT, RESIZE>(xn, ts, oy, ox, oxt, g, in, cr);
+        else r = teacher_pixel_stream<RESIZE>(xn, ts, oy, ox, oxt, g, in, cr);
         const bool keep = in && r.conf >= g.tau;
         const bool agree = keep && r.ys == r.y;
         sd += keep ? r.d : 0.f;
@@ -219,13 +256,41 @@ __global__ __launch_bounds__(256) void teacher_finish_kernel(const double* __res
     }
 }
 
-template <bool RESIZE>
+template <bool RESIZE, class MIX>
 void launch_stats(const TeacherGeom& g, int N, hipStream_t st, const float* x, const float* t, const uint8_t* flip, double* part,
-                  uint8_t* pmap, float* coef) {
+                  uint8_t* pmap, float* coef, MIX mix) {
     const dim3 grid((unsigned)N * g.bps), blk(256);
     sscg_dispatch_classes(g.r.C, [&](auto ct) {
-        hipLaunchKernelGGL((teacher_stats_kernel<decltype(ct)::value, RESIZE>), grid, blk, 0, st, x, t, flip, part, pmap, coef, g);
+        hipLaunchKernelGGL((teacher_stats_kernel<decltype(ct)::value, RESIZE, MIX>), grid, blk, 0, st, x, t, flip, part, pmap, coef, g, mix);
     });
+}
+
+// Both entries: table == NULL runs the plain instances.
+int teacher_fwd(const float* x, const float* t, const uint8_t* flip, const int32_t* table, int N, int H, int W, int C, int OH, int OW,
+                float inv_temp, float thresh, float* losses, double* sums, uint8_t* pseudo, float* coef, void* ws, size_t ws_bytes,
+                void* stream) {
+    if (!x || !t || !losses || !sums || !sizes_ok(N, H, W, C, OH, OW) || !thresh_ok(thresh)) return SSCG_ERR_BAD_ARG;
+    if (!(inv_temp > 0.f && inv_temp < INFINITY)) return SSCG_ERR_BAD_ARG;      // (false for a NaN)
+    if (too_large(N, H, W, OH, OW)) return SSCG_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < sscg_teacher_workspace(N, OH, OW)) return SSCG_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const double V = (double)N * OH * OW;
+    const TeacherGeom g = {sscg_make_resize_geom(H, W, C, OH, OW), OH * OW, unl_bps(OH, OW), thresh, inv_temp, (float)(2.0 / ((double)C * V))};
+    double* part = reinterpret_cast<double*>(ws);
+    const bool resize = !(OH == H && OW == W);
+    if (table) {
+        const TeacherTable mix = {table, N};
+        if (resize) launch_stats<true>(g, N, st, x, t, flip, part, pseudo, coef, mix);
+        else launch_stats<false>(g, N, st, x, t, flip, part, pseudo, coef, mix);
+    } else {
+        if (resize) launch_stats<true>(g, N, st, x, t, flip, part, pseudo, coef, TeacherPlain{});
+        else launch_stats<false>(g, N, st, x, t, flip, part, pseudo, coef, TeacherPlain{});
+    }
+    double* ssum = part + (size_t)N * g.bps * 4;
+    hipLaunchKernelGGL(unl_reduce_kernel, dim3((unsigned)N), dim3(256), 0, st, part, g.bps, ssum);
+    hipLaunchKernelGGL(teacher_finish_kernel, dim3(1), dim3(256), 0, st, ssum, N, V, C, sums, losses);
+    SSCG_LAUNCH_CHECK();
+    return SSCG_OK;
 }
 
 }  // namespace
@@ -238,19 +303,11 @@ extern "C" size_t sscg_teacher_workspace(int N, int OH, int OW) {
 extern "C" int sscg_teacher_fwd(const float* x, const float* t, const uint8_t* flip, int N, int H, int W, int C, int OH, int OW,
                                 float inv_temp, float thresh, float* losses, double* sums, uint8_t* pseudo, float* coef, void* ws,
                                 size_t ws_bytes, void* stream) {
-    if (!x || !t || !losses || !sums || !sizes_ok(N, H, W, C, OH, OW) || !thresh_ok(thresh)) return SSCG_ERR_BAD_ARG;
-    if (!(inv_temp > 0.f && inv_temp < INFINITY)) return SSCG_ERR_BAD_ARG;      // (false for a NaN)
-    if (too_large(N, H, W, OH, OW)) return SSCG_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < sscg_teacher_workspace(N, OH, OW)) return SSCG_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const double V = (double)N * OH * OW;
-    const TeacherGeom g = {sscg_make_resize_geom(H, W, C, OH, OW), OH * OW, unl_bps(OH, OW), thresh, inv_temp, (float)(2.0 / ((double)C * V))};
-    double* part = reinterpret_cast<double*>(ws);
-    if (OH == H && OW == W) launch_stats<false>(g, N, st, x, t, flip, part, pseudo, coef);
-    else launch_stats<true>(g, N, st, x, t, flip, part, pseudo, coef);
-    double* ssum = part + (size_t)N * g.bps * 4;
-    hipLaunchKernelGGL(unl_reduce_kernel, dim3((unsigned)N), dim3(256), 0, st, part, g.bps, ssum);
-    hipLaunchKernelGGL(teacher_finish_kernel, dim3(1), dim3(256), 0, st, ssum, N, V, C, sums, losses);
-    SSCG_LAUNCH_CHECK();
-    return SSCG_OK;
+    return teacher_fwd(x, t, flip, nullptr, N, H, W, C, OH, OW, inv_temp, thresh, losses, sums, pseudo, coef, ws, ws_bytes, stream);
+}
+
+extern "C" int sscg_teacher_fwd_mix(const float* x, const float* t, const uint8_t* flip, const int32_t* table, int N, int H, int W, int C,
+                                    int OH, int OW, float inv_temp, float thresh, float* losses, double* sums, uint8_t* pseudo,
+                                    float* coef, void* ws, size_t ws_bytes, void* stream) {
+    return teacher_fwd(x, t, flip, table, N, H, W, C, OH, OW, inv_temp, thresh, losses, sums, pseudo, coef, ws, ws_bytes, stream);
 }

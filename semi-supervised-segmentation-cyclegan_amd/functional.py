@@ -1355,6 +1355,51 @@ def mirror_samples(x, flags):
     return y
 
 
+def mix_table_rows(table, n):
+    """A host mix table (numpy or CPU tensor, data_utils.augmentations.Compose.mixes' int32 [N, 8] rows) as a contiguous int32 CPU
+    tensor, checked: the shape, and the class-mask words, which the box entries do not read and therefore refuse when set."""
+    t = torch.as_tensor(table)
+    if t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (n, 8):
+        raise _lib.SscgError("a host int32 [%d, 8] mix table expected, got %s %s on %s" % (n, t.dtype, tuple(t.shape), t.device))
+    if bool((t[:, 5:7] != 0).any()):
+        raise ValueError("the mix table names class masks (words 5 and 6): the box entries mix boxes only - ClassMix is "
+                         "functional.augment_batch(mix=)'s")
+    return t.contiguous()
+
+
+def mix_rows_live(rows):
+    """Which rows of a checked host table can paste anything (bool [N]): a partner in [0, N) other than the sample, a non-empty box"""
+    n = rows.shape[0]
+    idx = torch.arange(n, dtype=torch.int32)
+    p = rows[:, 0]
+    return (p >= 0) & (p < n) & (p != idx) & (rows[:, 1] < rows[:, 3]) & (rows[:, 2] < rows[:, 4])
+
+
+def upload_mix_table(rows, device):
+    """The checked host table on `device`, through pinned memory: nothing waits for the copy"""
+    return (rows.pin_memory() if device.type == "cuda" else rows).to(device, non_blocking=True)
+
+
+def mix_boxes(x, table, device_table=None):
+    """CutMix of a finished batch (sscg_mix_boxes, one launch): x fp32 [N,C,H,W] (no gradient), table a HOST int32 [N, 8] (numpy or CPU
+    tensor; data_utils.augmentations.Compose.mixes' rows, class-mask words 0) -> a new channels-last tensor with sample n's box taken
+    from sample table[n][0] - data_utils.augmentations.mix_batch(x, None, table, False) bit for bit.  The batch itself when no row
+    mixes.  `device_table`: the table already on x's device (upload_mix_table), else it is uploaded here without a sync."""
+    if x.dim() != 4:
+        raise _lib.SscgError("mix_boxes: 4-D tensor expected")
+    n, c, h, w = x.shape
+    rows = mix_table_rows(table, n)         # (the table's own errors first: they need no device)
+    _need_hip(x, f32_only=True)
+    _no_grad_input(x, "mix_boxes")
+    if not bool(mix_rows_live(rows).any()):
+        return x
+    x = to_nhwc(x.detach())
+    y = empty_nhwc(n, c, h, w, x.device)
+    dt = device_table if device_table is not None else upload_mix_table(rows, x.device)
+    check(lib.sscg_mix_boxes(x.data_ptr(), y.data_ptr(), dt.data_ptr(), n, h, w, c, _stream()), "sscg_mix_boxes")
+    return y
+
+
 def predict_labels_ms(logits_list, flips, size, *, want_prob=False, want_index=False, want_u8=True, label_true=None, hist=None,
                       num_classes=None):
     """Label maps from the logits of up to 8 views of one batch: per view, in order, interp(size, bilinear, align_corners=True) ->
@@ -4166,9 +4211,10 @@ def _teacher_options(teacher):
     return teacher
 
 
-def teacher_fwd(x, t, flip, size, inv_temp, thresh, want_pseudo=True, want_coef=True):
+def teacher_fwd(x, t, flip, size, inv_temp, thresh, want_pseudo=True, want_coef=True, table=None):
     """sscg_teacher_fwd on channels-last fp32 student logits x and teacher logits t [N,C,H,W] (size = (OH, OW); (H, W): the flat form);
-    flip: uint8 [N] on the device or None.  (losses fp32 [2] = (L_mse, L_ce), sums fp64 [4] = (sum_kept d, A, sum_kept ce, K), the
+    flip: uint8 [N] on the device or None.  table: an int32 [N, 8] mix table on the device (mix_boxes' rows, the box in OUTPUT pixels)
+    or None - given, the call is sscg_teacher_fwd_mix: inside sample n's box the teacher is sample table[n][0]'s.  (losses fp32 [2] = (L_mse, L_ce), sums fp64 [4] = (sum_kept d, A, sum_kept ce, K), the
     teacher's label map uint8 [N,OH,OW] - 255 = dropped - or None, coef fp32 [N,OH,OW,C] = d L_mse / d p or None).  No autograd:
     upsample_softmax_teacher wraps it."""
     n, c, h, w = x.shape
@@ -4182,17 +4228,23 @@ def teacher_fwd(x, t, flip, size, inv_temp, thresh, want_pseudo=True, want_coef=
     sums = torch.empty((4,), dtype=torch.float64, device=x.device)
     pseudo = torch.empty((n, oh, ow), dtype=torch.uint8, device=x.device) if want_pseudo else None
     coef = torch.empty((n, oh, ow, c), dtype=torch.float32, device=x.device) if want_coef else None
+    if table is not None and (table.dtype != torch.int32 or tuple(table.shape) != (n, 8) or table.device != x.device or not table.is_contiguous()):
+        raise _lib.SscgError("teacher_fwd: table must be a contiguous int32 [%d, 8] tensor on %s" % (n, x.device))
     ws = torch.empty(lib.sscg_teacher_workspace(n, oh, ow), dtype=torch.uint8, device=x.device)
-    check(lib.sscg_teacher_fwd(x.data_ptr(), t.data_ptr(), _ptr(flip), n, h, w, c, oh, ow, float(inv_temp), float(thresh), losses.data_ptr(),
-                               sums.data_ptr(), _ptr(pseudo), _ptr(coef), ws.data_ptr(), ws.numel(), _stream()), "sscg_teacher_fwd")
+    tail = (n, h, w, c, oh, ow, float(inv_temp), float(thresh), losses.data_ptr(), sums.data_ptr(), _ptr(pseudo), _ptr(coef), ws.data_ptr(),
+            ws.numel(), _stream())
+    if table is None:
+        check(lib.sscg_teacher_fwd(x.data_ptr(), t.data_ptr(), _ptr(flip), *tail), "sscg_teacher_fwd")
+    else:
+        check(lib.sscg_teacher_fwd_mix(x.data_ptr(), t.data_ptr(), _ptr(flip), table.data_ptr(), *tail), "sscg_teacher_fwd_mix")
     return losses, sums, pseudo, coef
 
 
-def _teacher_forward(ctx, x, t, flip, size, inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep):
+def _teacher_forward(ctx, x, t, flip, size, inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep, mix=None):
     """What both teacher nodes run behind the softmax map: sscg_teacher_fwd, and sscg_unl_fwd when an --unl_* weight asks for its three
-    losses.  Saves (x, coef, the teacher's sums and map, sscg_unl_fwd's sums and map) and returns the node's outputs after the map:
+    losses; `mix`: teacher_fwd's table.  Saves (x, coef, the teacher's sums and map, sscg_unl_fwd's sums and map) and returns the node's outputs after the map:
     (L_mse, L_ce, L_ent, L_msq, L_pl, the teacher's sums and map, sscg_unl_fwd's sums) - None for what did not run."""
-    t_losses, t_sums, t_map, coef = teacher_fwd(x, t, flip, size, inv_temp, thresh, True, want_coef)
+    t_losses, t_sums, t_map, coef = teacher_fwd(x, t, flip, size, inv_temp, thresh, True, want_coef, mix)
     l_mse, l_ce = t_losses.unbind(0)
     l_ent = l_msq = l_pl = u_sums = u_map = None
     if unl_thresh is not None:
@@ -4225,15 +4277,16 @@ class TeacherHeadFn(torch.autograd.Function):
     and label map, sscg_unl_fwd's sums or None).  Forward: the label head's own launch for the map (the bits of upsample_softmax_ce's),
     sscg_teacher_fwd, and sscg_unl_fwd when `unl_thresh` is given.  Backward: the squared distance's coefficient map joins the map's
     upstream gradient (one sscg_lovasz_scale_add), then ONE sscg_upsample_head_bwd_u launch whose pseudo-label slot is the teacher's
-    (use_ce) or sscg_unl_fwd's own.  The teacher's logits and `flip` are constants."""
+    (use_ce) or sscg_unl_fwd's own.  The teacher's logits, `flip` and `mix` (teacher_fwd's table: sscg_teacher_fwd_mix takes the forward's
+    place, the backward is the same) are constants."""
 
     @staticmethod
-    def forward(ctx, x, oh, ow, t, flip, want_soft, inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep):
+    def forward(ctx, x, oh, ow, t, flip, want_soft, inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep, mix=None):
         _need_hip(x, f32_only=True)
         x, t = to_nhwc(x), to_nhwc(t)
         y = _label_head_forward(x, oh, ow, None, True, False, None, 0.0)[0] if want_soft else None
         ctx.size = (oh, ow)
-        return (y,) + _teacher_forward(ctx, x, t, flip, (oh, ow), inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep)
+        return (y,) + _teacher_forward(ctx, x, t, flip, (oh, ow), inv_temp, thresh, use_ce, want_coef, unl_thresh, unl_keep, mix)
 
     @staticmethod
     def backward(ctx, dy, g_mse, g_ce, g_ent, g_msq, g_pl, *_consts):
@@ -4242,7 +4295,7 @@ class TeacherHeadFn(torch.autograd.Function):
         if coef is None:
             g_mse = None
         if dy is None and g_mse is None and g_ent is None and g_msq is None and g_slot is None:
-            return (None,) * 12
+            return (None,) * 13
         if dy is not None:
             dy = to_nhwc(dy)
         if g_mse is not None:
@@ -4252,7 +4305,7 @@ class TeacherHeadFn(torch.autograd.Function):
         dx = empty_nhwc(n, c, h, w, x.device)
         check(lib.sscg_upsample_head_bwd_u(x.data_ptr(), _ptr(pseudo), _ptr(dy), _ptr(g_ent), _ptr(g_msq), _ptr(g_slot), sums.data_ptr(),
                                            dx.data_ptr(), n, h, w, c, oh, ow, _stream()), "sscg_upsample_head_bwd_u")
-        return (dx,) + (None,) * 11
+        return (dx,) + (None,) * 12
 
 
 class TeacherLossFn(torch.autograd.Function):
@@ -4262,10 +4315,10 @@ class TeacherLossFn(torch.autograd.Function):
     sscg_softmax_bwd carries it on; every other live term is one sscg_unl_bwd launch on `up`."""
 
     @staticmethod
-    def forward(ctx, up, soft, t, flip, inv_temp, thresh, use_ce, unl_thresh, unl_keep):
+    def forward(ctx, up, soft, t, flip, inv_temp, thresh, use_ce, unl_thresh, unl_keep, mix=None):
         _need_hip(up, f32_only=True)
         up, t = to_nhwc(up), to_nhwc(t)
-        return _teacher_forward(ctx, up, t, flip, up.shape[2:], inv_temp, thresh, use_ce, soft is not None, unl_thresh, unl_keep)
+        return _teacher_forward(ctx, up, t, flip, up.shape[2:], inv_temp, thresh, use_ce, soft is not None, unl_thresh, unl_keep, mix)
 
     @staticmethod
     def backward(ctx, g_mse, g_ce, g_ent, g_msq, g_pl, *_consts):
@@ -4279,10 +4332,10 @@ class TeacherLossFn(torch.autograd.Function):
             d_up = torch.empty_like(up, memory_format=CL)
             check(lib.sscg_unl_bwd(up.data_ptr(), _ptr(pseudo), n, h, w, c, _ptr(g_ent), _ptr(g_msq), _ptr(g_slot), sums.data_ptr(),
                                    d_up.data_ptr(), _stream()), "sscg_unl_bwd")
-        return (d_up, d_soft) + (None,) * 7
+        return (d_up, d_soft) + (None,) * 8
 
 
-def upsample_softmax_teacher(x, size, teacher_logits, teacher, unl=None, flip=None, want_soft=True):
+def upsample_softmax_teacher(x, size, teacher_logits, teacher, unl=None, flip=None, want_soft=True, mix=None):
     """(softmax2d(interp(x)) or None, L_mse, L_ce, L_ent, L_msq, L_pl, stats): the unlabelled prediction's softmax map (the bits of
     upsample_softmax_ce's) and its consistency with `teacher_logits` - the low-resolution logits, shaped like x, of a teacher that saw
     the same batch, sample n mirrored on W where flip[n] (uint8 [N] on the device, or None) is set.  teacher: a TeacherOptions (or a
@@ -4292,7 +4345,11 @@ def upsample_softmax_teacher(x, size, teacher_logits, teacher, unl=None, flip=No
     terms at once are refused - the backward has one pseudo-label slot and the teacher's labels are the better source.  stats = {"sums":
     fp64 [4] = (sum_kept d, A = agreeing kept pixels, sum_kept ce, K), "pseudo": the teacher's uint8 label map, 255 = dropped,
     "unl_sums": sscg_unl_fwd's sums or None}.  No gradient reaches the teacher.  Fused when the resize grows the map - ONE stencil
-    launch backward - else the separate passes on upsample_bilinear's output."""
+    launch backward - else the separate passes on upsample_bilinear's output.
+    mix: an int32 [N, 8] table on the device (mix_boxes' rows, drawn at `size`) or None - the CutMix consistency: x is the student's
+    prediction of mix_boxes(batch, table), teacher_logits the teacher's of the UNMIXED batch, and inside sample n's box the student
+    is held to the teacher's prediction of sample table[n][0] (sscg_teacher_fwd_mix: the same mix of the teacher's maps, which are
+    never written at the output size).  A constant, like flip."""
     teacher = _teacher_options(teacher)
     unl = _unl_options(unl) if unl is not None else None
     if unl is not None and not unl.any:
@@ -4309,12 +4366,12 @@ def upsample_softmax_teacher(x, size, teacher_logits, teacher, unl=None, flip=No
     want_coef = teacher.mse > 0.0
     if _head_applies(x, oh, ow):
         out = TeacherHeadFn.apply(x, oh, ow, teacher_logits, flip, bool(want_soft), teacher.inv_temp, teacher.thresh, use_ce, want_coef,
-                                  unl_thresh, unl_keep)
+                                  unl_thresh, unl_keep, mix)
     else:
         up = upsample_bilinear(x, size)
         soft = softmax2d(up) if want_soft or want_coef else None
         out = (soft if want_soft else None,) + TeacherLossFn.apply(up, soft if want_coef else None, upsample_bilinear(teacher_logits, size),
-                                                                   flip, teacher.inv_temp, teacher.thresh, use_ce, unl_thresh, unl_keep)
+                                                                   flip, teacher.inv_temp, teacher.thresh, use_ce, unl_thresh, unl_keep, mix)
     soft, l_mse, l_ce, l_ent, l_msq, l_pl, t_sums, t_map, u_sums = out
     return soft, l_mse, l_ce, l_ent, l_msq, l_pl, {"sums": t_sums, "pseudo": t_map, "unl_sums": u_sums}
 

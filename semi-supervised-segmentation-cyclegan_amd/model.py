@@ -460,6 +460,53 @@ class _UnlabelledLosses(object):
         if opts.flip:
             self._teacher_rng = torch.Generator().manual_seed(self.TEACHER_SEED)
 
+    # --unl_cutmix (opt-in, with --unl_teacher): CutMix consistency (French et al. 2020) - after the teacher predicted the UNMIXED batch,
+    # every sample takes, with probability p, a box of a partner (functional.mix_boxes: one copy launch); the mixed batch is the step's
+    # unlabelled batch from there on, and the head holds the student to the same mix of the teacher's predictions
+    # (functional.upsample_softmax_teacher(mix=): sscg_teacher_fwd_mix in sscg_teacher_fwd's place, the same backward)
+    unl_cutmix = None               # data_utils.augmentations.Compose of one RandomCutMix when the flag is given: nothing changes otherwise
+    _cutmix_rng = None              # the boxes' own numpy generator: the flip draws and every other draw of a seed stay where they were
+    CUTMIX_SEED = 0xC417
+    _cutmix_said = False
+
+    def _init_unl_cutmix(self, args):
+        spec = utils.parse_unl_cutmix(getattr(args, "unl_cutmix", "") or "")
+        if spec is None:
+            return
+        if self.unl_teacher is None:
+            raise ValueError("--unl_cutmix needs --unl_teacher (and with it --ema_decay): it mixes what the teacher and the student see")
+        import numpy as np
+        from .data_utils import augmentations
+        self.unl_cutmix = augmentations.Compose([augmentations.RandomCutMix(*spec)])
+        self._cutmix_rng = np.random.RandomState(self.CUTMIX_SEED)
+
+    def _cutmix_table(self, n):
+        """One step's draw: the host int32 [n, 8] table (partner, x0, y0, x1, y1, 0, 0, 0) of Compose.mixes - its partner rule,
+        RandomCutMix's boxes - at the head's output size."""
+        return self.unl_cutmix.mixes(self._cutmix_rng, n, self.crop[1], self.crop[0])[0]
+
+    def _cutmix_unl(self, unl_img, extras):
+        """(the mixed unlabelled batch, the table on the device - None for a batch of one): the step's draw applied to the batch
+        the teacher has already seen.  extras["unl_cutmix_share"] = the pasted share of the batch's pixels, from the host's table: a
+        CPU scalar, no launch and no sync."""
+        n, _, h, w = unl_img.shape
+        if (h, w) != (int(self.crop[0]), int(self.crop[1])):
+            raise ValueError("--unl_cutmix: the unlabelled images are %dx%d, the head's output %dx%d - the boxes are drawn at the "
+                             "output size and must mean the same pixels of both" % (h, w, self.crop[0], self.crop[1]))
+        if n == 1 and not self._cutmix_said:
+            print("--unl_cutmix: a batch of one has no partner and is never mixed")
+            self._cutmix_said = True
+        rows = F.mix_table_rows(self._cutmix_table(n), n)
+        live = F.mix_rows_live(rows)
+        bw = (rows[:, 3].clamp(max=w) - rows[:, 1].clamp(min=0)).clamp(min=0)
+        bh = (rows[:, 4].clamp(max=h) - rows[:, 2].clamp(min=0)).clamp(min=0)
+        extras["unl_cutmix_share"] = ((bw * bh * live).sum().double() / float(n * h * w)).float()
+        if n == 1:
+            return unl_img, None
+        # (a draw in which no sample fired still takes the table to the head: the mix entry then gives the plain entry's bits)
+        table = F.upload_mix_table(rows, unl_img.device)
+        return F.mix_boxes(unl_img, rows, table), table
+
     def _teacher_view(self, unl_img):
         """What the teacher sees: the unlabelled batch, each sample mirrored on W with probability 1/2 under `flip` - (view, the flip
         bytes uint8 [N] on the device or None).  The draws are the host's, so the view is built per run of equal draws
@@ -496,6 +543,7 @@ class _UnlabelledLosses(object):
     def _init_unl(self, args):
         self._init_unl_crf(args)
         self._init_unl_teacher(args)
+        self._init_unl_cutmix(args)
         w = {}
         for key in ("unl_entropy", "unl_maxsq", "unl_pseudo"):
             w[key] = float(getattr(args, key, 0.0) or 0.0)
@@ -524,16 +572,17 @@ class _UnlabelledLosses(object):
             self._unl_scale = utils.boundary_loss_schedule(1.0, self.unl_ramp, epoch)
         return self._unl_scale
 
-    def _unl_head(self, fake_logits, extras, extra_terms, extra_weights, unl_img=None, teacher=None):
+    def _unl_head(self, fake_logits, extras, extra_terms, extra_weights, unl_img=None, teacher=None, mix=None):
         """The softmax map of the unlabelled prediction (:401-402): the plain fused head by default.  With an --unl_* weight the head
         also returns the enabled losses: each joins the extras under its own key with its own ramped weight, and --unl_pseudo reports
         the kept share K / V - a device scalar from the sums the forward left, no sync.  --unl_crf: the gated CRF loss of the map under
         `unl_img`, a node of its own beside the head - autograd adds its gradient to the map's.  --unl_teacher: `teacher` = (the
-        teacher's logits, its flip bytes) of this batch, and the head is functional.upsample_softmax_teacher."""
+        teacher's logits, its flip bytes) of this batch, and the head is functional.upsample_softmax_teacher; --unl_cutmix: `mix` =
+        the step's table on the device (_cutmix_unl), handed to that head."""
         if self.unl_teacher is not None:
             if teacher is None:
                 raise ValueError("--unl_teacher: _unl_head needs the teacher's logits of this batch (_teacher_logits)")
-            fake_gt = self._unl_teacher_losses(fake_logits, teacher, extras, extra_terms, extra_weights)
+            fake_gt = self._unl_teacher_losses(fake_logits, teacher, extras, extra_terms, extra_weights, mix)
         else:
             fake_gt = self._unl_head_losses(fake_logits, extras, extra_terms, extra_weights)
         if self.unl_crf > 0.0:
@@ -559,11 +608,12 @@ class _UnlabelledLosses(object):
         return fake_gt
 
 
-    def _unl_teacher_losses(self, fake_logits, teacher, extras, extra_terms, extra_weights):
+    def _unl_teacher_losses(self, fake_logits, teacher, extras, extra_terms, extra_weights, mix=None):
         """_unl_head_losses with the teacher: the --unl_* terms as they were, then unl_teacher_mse / unl_teacher_ce with their ramped
         weights, and the diagnostics unl_teacher_kept = K / V and unl_teacher_agree = A / max(K, 1) - device scalars from the sums."""
         o, t = self.unl_options, self.unl_teacher
-        fake_gt, l_mse, l_ce, l_ent, l_msq, l_pl, stats = F.upsample_softmax_teacher(fake_logits, self.crop, teacher[0], t, o, flip=teacher[1])
+        kw = {"mix": mix} if mix is not None else {}
+        fake_gt, l_mse, l_ce, l_ent, l_msq, l_pl, stats = F.upsample_softmax_teacher(fake_logits, self.crop, teacher[0], t, o, flip=teacher[1], **kw)
         V = float(fake_gt.shape[0] * self.crop[0] * self.crop[1])
         for key, term, w in ((("unl_entropy", l_ent, o.entropy), ("unl_maxsq", l_msq, o.maxsq), ("unl_pseudo_ce", l_pl, o.pseudo))
                              if o is not None else ()) + (("unl_teacher_mse", l_mse, t.mse), ("unl_teacher_ce", l_ce, t.ce)):
@@ -727,10 +777,13 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         # the generators' operand copies (bf16 shadow / split planes) exist and are current before any lane reads them: a no-op
         # after the first step (the Adam kernel rewrites them); the discriminators' follow at :431, behind their own update
         self.g_optimizer.ensure_operand_copies()
-        teacher = None
+        teacher = unl_mix = None
+        unl_extras = {}
         if self.unl_teacher is not None:        # --unl_teacher: the EMA weights predict the unlabelled batch before any lane starts
             view, flip = self._teacher_view(unl_img)
             teacher = (self._teacher_logits(view), flip)
+            if self.unl_cutmix is not None:     # --unl_cutmix: the teacher saw the unmixed batch; every reader below sees the mixed one
+                unl_img, unl_mix = self._cutmix_unl(unl_img, unl_extras)
         labels = l_gt.reshape(l_gt.shape[0], l_gt.shape[2], l_gt.shape[3])          # l_gt.squeeze(1)
         onehot_gt = make_one_hot(l_gt, a.dataset, a.gpu_ids)
 
@@ -791,8 +844,8 @@ class semisuper_cycleGAN(_WeightedCE, _UnlabelledLosses):
         # the resized [B, C, crop] logits are never written (functional.UpsampleHeadFn)
         ohem_kept = {}
         lab_gt, lab_loss_CE, lab_loss_dice = self._head(lab_logits, labels, True, ohem_kept)   # (plain nn.CrossEntropyLoss() by default)
-        extra_terms, extra_weights, extras = [], [], {}
-        fake_gt = self._unl_head(fake_logits, extras, extra_terms, extra_weights, unl_img, teacher)    # (--unl_*: plus the enabled losses)
+        extra_terms, extra_weights, extras = [], [], unl_extras
+        fake_gt = self._unl_head(fake_logits, extras, extra_terms, extra_weights, unl_img, teacher, unl_mix)    # (--unl_*: plus the enabled losses)
         if fork:
             main.wait_event(gis_first)
         # (Gis(onehot_gt) and Gis(fake_gt) as ONE grouped-BatchNorm pass on the main lane was built in round 4 and measured slower than
@@ -1244,6 +1297,8 @@ class supervised_model(_WeightedCE):
             print("--unl_crf is ignored: the supervised model has no unlabelled batch")
         if str(getattr(args, "unl_teacher", "") or "").strip():
             print("--unl_teacher is ignored: the supervised model has no unlabelled batch")
+        if str(getattr(args, "unl_cutmix", "") or "").strip():
+            print("--unl_cutmix is ignored: the supervised model has no unlabelled batch")
         self.running_metrics_val = utils.runningScore(self.n_channels, args.dataset)
         if not os.path.isdir(args.checkpoint_dir):
             os.makedirs(args.checkpoint_dir, exist_ok=True)

@@ -1012,6 +1012,32 @@ def parse_unl_teacher(spec):
     return opts
 
 
+def parse_unl_cutmix(spec):
+    """`--unl_cutmix`: CutMix consistency for the mean teacher, in the grammar of `--augment cutmix=`: `p[:lo:hi]` - with probability p
+    (0 < p <= 1) a sample of the unlabelled batch takes a box of lo..hi of the area (0 < lo <= hi <= 1; default 0.25:0.5, UNTUNED)
+    from a partner.  Returns (p, lo, hi), None for "" / None.  Raises ValueError naming the bad token."""
+    import math
+    spec = (spec or "").strip()
+    if not spec:
+        return None
+    toks = spec.split(":")
+    if len(toks) not in (1, 3):
+        raise ValueError("--unl_cutmix: %r is not p or p:lo:hi" % (spec,))
+    vals = []
+    for tok in toks:
+        try:
+            v = float(tok)
+        except ValueError:
+            raise ValueError("--unl_cutmix: %r is not a number" % (tok,))
+        if not (math.isfinite(v) and 0.0 < v <= 1.0):
+            raise ValueError("--unl_cutmix: %r is not in (0, 1]" % (tok,))
+        vals.append(v)
+    p, lo, hi = vals if len(vals) == 3 else (vals[0], 0.25, 0.5)
+    if lo > hi:
+        raise ValueError("--unl_cutmix: %r: lo %r is above hi %r" % (spec, toks[1], toks[2]))
+    return p, lo, hi
+
+
 def crf_guide(images, size):
     """The CRF's guide image: the batch as the network sees it (normalised), resized to `size` when it has another."""
     return images if tuple(images.shape[2:]) == (int(size[0]), int(size[1])) else F.upsample_bilinear(images, size)
